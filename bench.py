@@ -27,8 +27,10 @@ between; they leave the start barrier in lockstep (every worker in the same phas
 assemble PRG strings) and fall out of phase over the first steps, so few steps measure the transient, not the rate
 (3 steps: ~745 ms per step, 12 steps: ~670 ms on the same box, profiles/r02/README.md).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workers P] [--streams S] [--weak]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workers P] [--streams S] [--weak] [--dump-outputs DIR]
     --workers 0 runs the same loop inside this process (profiler runs: nothing forks)
+    --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (write_outputs; under 64 MB): the inputs
+    are the same on every run, so two builds can be compared output for output
 """
 import argparse
 import hashlib
@@ -130,6 +132,46 @@ def source_digest():
         with open(os.path.join(d, name), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()[:16]
+
+
+DUMP_SAMPLE = 256                   # alignments whose PRG text --dump-outputs writes in full (up to DUMP_TEXT_CAP / DUMP_SAMPLE chars)
+DUMP_TEXT_CAP = 12 << 20            # chars of sampled PRG text in all: 48 MB as float32
+
+
+def dump_sample(batch):
+    """The alignments (seeds) whose PRG text --dump-outputs writes: a fixed, seeded sample of the job."""
+    import numpy as np
+    n = min(DUMP_SAMPLE, batch)
+    return set(int(s) for s in np.random.default_rng(20241015).choice(batch, size=n, replace=False))
+
+
+def write_outputs(out_dir, batch, per_seed, sample):
+    """--dump-outputs: what the last timed step computed, as float arrays indexed by seed (0..batch-1):
+      prg_length.npy     (batch,)   float64  bytes of each alignment's PRG string (-1: no PRG)
+      n_nodes.npy        (batch,)   float64  nodes of its recursion tree
+      prg_digest.npy     (batch, 2) float64  sha256(PRG)[:8] as two big-endian uint32 words (0, 0: no PRG)
+      sample_seeds.npy   (n,)       float64  the fixed sample (dump_sample) whose text follows, ascending
+      sample_offsets.npy (n + 1,)   float64  where each sampled PRG starts in sample_text
+      sample_text.npy    (m,)       float32  the sampled PRGs' bytes, each cut at DUMP_TEXT_CAP // n chars"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    length = np.full(batch, -1.0)
+    nodes = np.zeros(batch)
+    digest = np.zeros((batch, 2))
+    for sd, (ln, nn, dg, _) in per_seed.items():
+        length[sd], nodes[sd] = ln, nn
+        if dg:
+            digest[sd] = np.frombuffer(dg, ">u4")
+    seeds = sorted(sample)
+    cap = DUMP_TEXT_CAP // max(len(seeds), 1)
+    texts = [(per_seed[sd][3] or b"")[:cap] for sd in seeds]
+    offsets = np.zeros(len(seeds) + 1)
+    offsets[1:] = np.cumsum([len(t) for t in texts])
+    arrays = dict(prg_length=length, n_nodes=nodes, prg_digest=digest, sample_seeds=np.array(seeds, np.float64),
+                  sample_offsets=offsets, sample_text=np.frombuffer(b"".join(texts), np.uint8).astype(np.float32))
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return dict(dir=out_dir, files=sorted(n + ".npy" for n in arrays), bytes=int(sum(a.nbytes for a in arrays.values())))
 
 
 def _worker(conn, device, seeds, n_streams, gen_procs=1, cli_dir=None, backend_kind=None, first_pass=False):
@@ -273,6 +315,19 @@ def _worker(conn, device, seeds, n_streams, gen_procs=1, cli_dir=None, backend_k
                 bad += mismatches(blob, sub, [None if p is None else bytes(p) for p in last[i]], n_nodes)
             return bad
 
+        def dump(sample):
+            """What the last timed step handed its caller, per alignment: {seed: (PRG length or -1, nodes, sha256(PRG)[:8],
+            PRG text if the seed is in `sample` else None)}."""
+            out = {}
+            for i, e in enumerate(engs):
+                sub = seeds[i::n_streams]
+                n_nodes = np.bincount(e.tab["msa"], minlength=len(sub))
+                for k, sd in enumerate(sub):
+                    p = None if last[i] is None or last[i][k] is None else bytes(last[i][k])
+                    out[sd] = (-1 if p is None else len(p), int(n_nodes[k]), b"" if p is None else hashlib.sha256(p).digest()[:8],
+                               p if sd in sample else None)
+            return out
+
         # the resident batch is ~10^6 long-lived Python containers (ids, descriptions): keep the cyclic collector from walking
         # them every time a step's short-lived lists trigger a full collection (measured: 130-210 ms pauses every third step)
         import gc
@@ -307,6 +362,8 @@ def _worker(conn, device, seeds, n_streams, gen_procs=1, cli_dir=None, backend_k
                 conn.send(("done", (prof, counters, len(seeds))))
             elif cmd == "verify":
                 conn.send(("done", verify()))
+            elif cmd == "dump":
+                conn.send(("done", dump(arg)))
             elif cmd == "e2e":
                 conn.send(("done", end_to_end()))
             else:
@@ -343,7 +400,14 @@ def main():
     ap.add_argument("--profile-timed", action="store_true",
                     help="HIP events around every entry point INSIDE the timed region too (diagnostic; adds event traffic)")
     ap.add_argument("--gen-procs", type=int, default=0, help="processes per worker that generate its alignments (0 = auto)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (per-alignment PRG lengths, node counts and "
+                         "digests, the PRG text of a fixed sample) as DIR/<name>.npy (write_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     # MPRG_DIST_BACKEND=gloo + MPRG_DEVICE_MODULO=1: several ranks on ONE GPU, to exercise the multi-rank control flow
@@ -521,6 +585,21 @@ def main():
         dist.all_reduce(flag, op=dist.ReduceOp.SUM)
         if verified is not None:
             verified["mismatches_all_ranks"] = int(flag.item())
+
+    # ---- outside the timed region, before anything else runs a step: what the last timed step computed, to files
+    dumped = None
+    if args.dump_outputs:
+        sample = dump_sample(args.batch)
+        per_seed = {}
+        for d_ in command("dump", sample):
+            per_seed.update(d_)
+        if grouped:          # strong scaling: every rank holds its shard's answers
+            everything = [None] * world
+            dist.all_gather_object(everything, per_seed)
+            for d_ in everything:
+                per_seed.update(d_)
+        if rank == 0:
+            dumped = write_outputs(args.dump_outputs, args.batch, per_seed, sample)
 
     excl = e2e = None
     if rank == 0:
@@ -761,7 +840,7 @@ def main():
                                                 + counters["kmeans_bytes"]) / args.steps,
                        "whole_step_GBps": round((counters["cells_all"] + counters["cells_clustered"]
                                                  + counters["kmeans_bytes"]) / args.steps / (dt_max / args.steps) * 1e-9, 3),
-                       "verified": verified, "end_to_end": e2e},
+                       "verified": verified, "end_to_end": e2e, "dumped_outputs": dumped},
             "roofline": roof,
             "cpu_baseline": cpu,
         }
