@@ -42,7 +42,8 @@ enum { MPRG_ST_PARTITION_ERROR = 1, MPRG_ST_ALL_N_SLICE = 2,
        MPRG_ST_BAD_LAUNCH = 4 /* a view of fused_list does not satisfy the fused launch shape: a host error, not a property of the data */ };
 /* per-fit status bits written by the KMeans kernels */
 enum { MPRG_KM_RELOCATED = 1 /* an empty cluster was relocated (info) */,
-       MPRG_KM_UNSUPPORTED = 2 /* error: the relocation's selection ran out of frames (more than 5^10 samples) */ };
+       MPRG_KM_UNSUPPORTED = 2 /* error: the relocation's selection ran out of frames (more than 5^10 samples), or
+                                  mprg_kmeans_fit_lds was given a fit its launch's class does not hold (nothing written) */ };
 
 const char *mprg_version(void);
 const char *mprg_last_error(void);
@@ -256,7 +257,8 @@ int mprg_kmeans_fit_small(const int64_t *prob, const int32_t *kinfo, const int32
  * needs another form (more than 64 distinct sequences, more than 10 restarts, a state beyond the largest class, a count matrix beyond
  * workspace prepared WITHOUT the sample-sample tables: the fit reads them — mprg_kmeans_prepare_big with_tables = 0 leaves them out; the
  * forest's control steps look that up in the workspace themselves, a caller of this function must know).  Arguments and
- * results as mprg_kmeans_fit_small; every fit of a launch must be of class <= lds_class.
+ * results as mprg_kmeans_fit_small; every fit of a launch must be of class <= lds_class (a fit that is not: MPRG_KM_UNSUPPORTED in
+ * its km_status, its labels and results untouched).
  * Replaces, for these fits, scikit-learn's KMeans.fit + predict behind cluster_sequences.py:262-266. */
 int mprg_kmeans_lds_class(int64_t D, int64_t V, int k, int n_init);
 int mprg_kmeans_fit_lds(const int64_t *prob, const int32_t *kinfo, const int32_t *fit_list, int n_fits, int lds_class, int n_init,
@@ -501,7 +503,8 @@ int mprg_forest_sizes_fill(const int64_t *F, void *stream);
  *     round k for mprg_kmeans_fit_wave per LDS class, 90 fits for mprg_kmeans_fit, 91 / 92 for mprg_kmeans_fit_small class 0 / 1
  *     (listed in MPRG_F_FIT_LISTS; which forms are used: MPRG_F_KM_MODE — bit 0 the wave form, bit 1 the small workgroup form, bit 2
  *     (round 6, the hosts' default) the LDS form mprg_kmeans_fit_lds: its classes 0-3 take slots 86-89, classes 4 / 5 slots 91 / 92,
- *     and the algorithmic bytes of its fits are added to word 81). */
+ *     and the algorithmic bytes of its fits are added to word 81; with bit 2 set, bits 0 and 1 are ignored: a fit without an LDS
+ *     class goes to slot 90). */
 int mprg_forest_kloop_advance(const int64_t *F, int k, void *stream);
 /* S7  after the loop: hdr: 0 new MultiClusterNodes, 1 their rows, 2 their children.  _fill: tables of mprg_split_children;
  *     _split_children (after it): the nodes become cluster nodes, their children are appended at MPRG_F_N_NODES. */

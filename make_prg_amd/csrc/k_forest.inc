@@ -486,7 +486,8 @@ MPRG_DEV double wave_sum_f64(double v) {
 }
 // mode: bit 0 = small fits take the wave form, bit 1 = small fits take the 128-thread workgroup form (else: the general form),
 // bit 2 (round 6) = the LDS form (k_kmeans_fit_lds) takes every fit it has a class for, before the other two are asked; its four
-// classes use the wave form's list slots (the two are not combined)
+// classes use the wave form's list slots, its last two the small form's (so with bit 2 set, bits 0 and 1 are ignored: a fit
+// without an LDS class takes the general form, never slots 5 / 6, which the hosts launch as LDS classes 4 / 5)
 #define KL_LISTS 7                      // launch lists: wave / LDS classes 0-3, general workgroup form, small workgroup form k <= 6 / any k
 KERNEL(k_kl_advance, long long P, int k, int n_init, int mode, const int64_t *ptab, const int64_t *sub, int32_t *num_clusters,
        int32_t *active, int32_t *kinfo, const double *km_info, int32_t *km_status, const int32_t *further, int uoff,
@@ -505,7 +506,7 @@ KERNEL(k_kl_advance, long long P, int k, int n_init, int mode, const int64_t *pt
     const double kb = 8.0 * (double)D * (double)V * (info[4] + (double)n_init);
     if ((mode & 4) && kml_class_ws(D, V, k - 1, n_init, false, ws) >= 0) kb_wave = kb;
     else if ((mode & 1) && km_wave_class(D, V, k - 1) >= 0) kb_wave = kb;
-    else if ((mode & 2) && km_small_class(D, V, k - 1, n_init) >= 0) kb_small = kb;
+    else if ((mode & 2) && !(mode & 4) && km_small_class(D, V, k - 1, n_init) >= 0) kb_small = kb;
     else kb_wg = kb;
     if (!(info[3] >= (double)(k - 1))) { nc -= 1; act = 0; }       // fewer than k distinct labels: revert and stop (:267-273)
     else if (!further[b]) act = 0;                                 // every cluster is one-reference-like: accepted
@@ -525,7 +526,7 @@ KERNEL(k_kl_advance, long long P, int k, int n_init, int mode, const int64_t *pt
       cls = 4;
       const int wc = (mode & 4) ? kml_class_ws(D, V, k, n_init, false, ws) : ((mode & 1) ? km_wave_class(D, V, k) : -1);
       if (wc >= 0) cls = wc < 4 ? wc : wc + 1;        // (the LDS form's fifth and sixth class take the small form's list slots: the two are not combined)
-      else if (mode & 2) { const int sc = km_small_class(D, V, k, n_init); if (sc >= 0) cls = 5 + sc; }
+      else if ((mode & 2) && !(mode & 4)) { const int sc = km_small_class(D, V, k, n_init); if (sc >= 0) cls = 5 + sc; }
       const int64_t *sv = sub + ptab[b * PF] * VF;
       cf = (double)(sv[5] * sv[7]);
     }
@@ -572,7 +573,7 @@ KERNEL(k_kl_speculate, long long P, int n_init, int mode, const int64_t *ptab, K
   bool general = k < D;                                 // (round k runs only while k < D: cluster_sequences.py:258-261)
   if (general && (mode & 4) && kml_class_ws(D, V, k, n_init, false, ws_all ? ws_all + ptab[b * PF + 9] : nullptr) >= 0) general = false;
   if (general && (mode & 1) && !(mode & 4) && km_wave_class(D, V, k) >= 0) general = false;
-  if (general && (mode & 2) && km_small_class(D, V, k, n_init) >= 0) general = false;
+  if (general && (mode & 2) && !(mode & 4) && km_small_class(D, V, k, n_init) >= 0) general = false;
   int32_t *ki = kinfo_out + 5 * e;
   ki[0] = (int32_t)b; ki[1] = general ? k : 0; ki[2] = (k - 2) * n_init; ki[3] = uoff.v[k]; ki[4] = (int32_t)((k - 2) * labels_per_k);
 }

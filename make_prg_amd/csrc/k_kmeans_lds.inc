@@ -281,6 +281,12 @@ MPRG_DEV void kml_fit_body(const int fit, const int64_t *prob_all, const int32_t
   const int nu = 1 + (k - 1) * T;
   const double *uniforms = uniforms_all + KI[3];
   const KmlLayout L = kml_layout(D, V, k, NR, keep);
+  // a fit outside the class rule, or beyond this launch's pool (a host that filed it in the wrong list): an error, and no LDS touched —
+  // the arrays below are sized for D <= KML_DMAX and the pool for lds_bytes (uniform across the workgroup: the early return is safe)
+  if (kml_class(D, V, k, NR, keep) < 0 || L.need > lds_bytes) {
+    ONE_THREAD { ATOMIC_OR(km_status + fit, (int32_t)MPRG_KM_UNSUPPORTED); }
+    return;
+  }
   const bool tables = L.need_tables <= lds_bytes;         // g1 / g4 of K6 in LDS for the seeding
   const int VP = km_xl_pitch(V), Dk = D * k, kk = k * k;
   KmlDiv dvD, dvK, dvV, dvDk, dvT;

@@ -49,8 +49,7 @@ def test_relocation_matches_oracle_persistent_workgroups():
     check(EmuBackend(), fits, path="fit", n_slots=512)
 
 
-def test_fits_with_many_samples():
-    """Count matrices with more samples than the pan-genome shapes of the golden fits (several 8-wide operand blocks)."""
+def many_sample_fits():
     rng = np.random.default_rng(3)
     fits = []
     for D, V, k in ((70, 9, 3), (90, 5, 2), (130, 7, 10), (66, 30, 6)):
@@ -59,16 +58,23 @@ def test_fits_with_many_samples():
         lab, dbg = orc.kmeans_fit_predict(M, k, want_debug=True)
         fits.append(dict(shape=[D, V], counts_i16_hex=M.astype("<i2").tobytes().hex(), k=k, labels=lab.tolist(),
                          inertia=float(dbg["inertia"]).hex(), n_iter=dbg["n_iter"]))
-    for path, slots in (("global", 0), ("one-launch", 0), ("wave", 0), ("small", 0), ("lds", 0), ("fit", 1), ("fit", 64)):
+    return fits
+
+
+MANY_SAMPLE_PATHS = (("global", 0), ("one-launch", 0), ("wave", 0), ("small", 0), ("lds", 0), ("fit", 1), ("fit", 64))
+
+
+def test_fits_with_many_samples():
+    """Count matrices with more samples than the pan-genome shapes of the golden fits (several 8-wide operand blocks)."""
+    fits = many_sample_fits()
+    for path, slots in MANY_SAMPLE_PATHS:
         got = run_kmeans_fits(EmuBackend(), fits, path=path, n_slots=slots)
         for g, f in zip(got, fits):
             assert not g["status"] & 2
             assert g["labels"] == f["labels"] and g["inertia_hex"] == f["inertia"] and g["n_iter"] == f["n_iter"]
 
 
-def test_relocation_with_wide_matrices():
-    """More than 128 features: the tolerance (np.var(...).mean()) and the relocation distances take NumPy's pairwise-sum
-    recursion, which the kernels run on a stack in LDS."""
+def wide_relocation_fits():
     rng = np.random.default_rng(11)
     fits = []
     for V in (150, 300, 700, 1100):
@@ -81,6 +87,13 @@ def test_relocation_with_wide_matrices():
                 fits.append(dict(shape=[D, V], counts_i16_hex=M.astype("<i2").tobytes().hex(), k=k, labels=lab.tolist(),
                                  inertia=float(dbg["inertia"]).hex(), n_iter=dbg["n_iter"]))
                 break
+    return fits
+
+
+def test_relocation_with_wide_matrices():
+    """More than 128 features: the tolerance (np.var(...).mean()) and the relocation distances take NumPy's pairwise-sum
+    recursion, which the kernels run on a stack in LDS."""
+    fits = wide_relocation_fits()
     assert len(fits) >= 3
     check(EmuBackend(), fits)
     check(EmuBackend(), fits, path="one-launch")
@@ -90,9 +103,7 @@ def test_relocation_with_wide_matrices():
     check(EmuBackend(), fits, path="fit", n_slots=2)
 
 
-def test_fits_outside_the_lds_count_form():
-    """The restart kernel keeps a fit's counts as bytes in LDS when they fit (km_euclid_xl); counts above 255 and matrices
-    beyond the pool take the global-memory form — same answers."""
+def count_form_fits():
     rng = np.random.default_rng(5)
     fits = []
     for D, V, k, top in ((24, 40, 3, 400), (120, 130, 4, 6), (14, 23, 5, 256), (31, 61, 2, 3)):
@@ -101,7 +112,17 @@ def test_fits_outside_the_lds_count_form():
         lab, dbg = orc.kmeans_fit_predict(M, k, want_debug=True)
         fits.append(dict(shape=[D, V], counts_i16_hex=M.astype("<i2").tobytes().hex(), k=k, labels=lab.tolist(),
                          inertia=float(dbg["inertia"]).hex(), n_iter=dbg["n_iter"]))
-    for path, slots in (("global", 0), ("global-nocounts", 0), ("one-launch", 0), ("wave", 0), ("small", 0), ("lds", 0), ("fit", 2)):
+    return fits
+
+
+COUNT_FORM_PATHS = (("global", 0), ("global-nocounts", 0), ("one-launch", 0), ("wave", 0), ("small", 0), ("lds", 0), ("fit", 2))
+
+
+def test_fits_outside_the_lds_count_form():
+    """The restart kernel keeps a fit's counts as bytes in LDS when they fit (km_euclid_xl); counts above 255 and matrices
+    beyond the pool take the global-memory form — same answers."""
+    fits = count_form_fits()
+    for path, slots in COUNT_FORM_PATHS:
         got = run_kmeans_fits(EmuBackend(), fits, path=path, n_slots=slots)
         for g, f in zip(got, fits):
             assert not g["status"] & 2

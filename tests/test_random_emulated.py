@@ -3,6 +3,7 @@ must agree with the oracle on PRG, recursion tree and prg_index, for several (ma
 import pytest
 
 from tests import parity_common as pc
+from tests import view_edges as ve
 from tests.emu.backend import EmuBackend
 from tests.random_msas import random_cases
 
@@ -24,52 +25,18 @@ def test_node_host(emu, N, L, seed, monkeypatch):
     pc.check_vs_oracle(emu, random_cases(seed, 80), N, L)
 
 
-def _wide_fasta(seed, S, C, p_mut, gaps=True):
-    import numpy as np
-    rng = np.random.default_rng(seed)
-    base = rng.integers(0, 4, C)
-    out = []
-    for i in range(S):
-        y = base.copy()
-        m = rng.random(C) < p_mut
-        y[m] = rng.integers(0, 4, int(m.sum()))
-        txt = np.frombuffer(b"ACGT", np.uint8)[y].copy()
-        if gaps:
-            for st in np.nonzero(rng.random(C) < 0.003)[0]:
-                txt[st:st + int(rng.integers(1, 5))] = ord("-")
-        out.append(f">w{i}\n{txt.tobytes().decode()}\n")
-    return "".join(out)
-
-
-@pytest.mark.parametrize("N,L,S,C,p", [(2, 1, 5, 900, 0.02),       # n/(L-1) exceeds the LDS interval stacks: global stacks
-                                       (2, 2, 4, 1400, 0.05),
-                                       (1, 7, 3, 13000, 0.002)])   # wider than the LDS column bytes (PT_COLS): masks read directly
+@pytest.mark.parametrize("N,L,S,C,p", ve.WIDE_VIEWS)
 def test_wide_views_take_the_fallback_paths(emu, N, L, S, C, p, monkeypatch):
     monkeypatch.setattr(pc, "ENGINE", "forest")
-    pc.check_vs_oracle(emu, [_wide_fasta(100 + C, S, C, p)], N, L)
+    pc.check_vs_oracle(emu, *ve.wide_view(N, L, S, C, p))
 
 
 def test_gap_runs_reach_across_column_segments(emu, monkeypatch):
     """k_gap_runs splits a wide view into 512-column segments: a run that begins before a segment (or covers whole segments) is
     counted backwards from the segment's start.  Rows with gap stretches across columns 2 048 and 4 096, variation inside them."""
-    import numpy as np
-    rng = np.random.default_rng(5)
-    C = 4400
-    base = rng.integers(0, 4, C)
-    rows = []
-    for i in range(6):
-        y = np.frombuffer(b"ACGT", np.uint8)[base].copy()
-        for c in (1990, 2040, 2100, 3000, 4090, 4100, 4300):          # variation: non-match columns inside and next to the stretches
-            y[c] = b"ACGT"[(int(base[c]) + 1 + i % 3) % 4]
-        rows.append(y)
-    rows[1][2030:2060] = ord("-")          # across the first boundary
-    rows[2][1985:4200] = ord("-")          # a whole segment and both boundaries
-    rows[4][4096:4110] = ord("-")          # begins exactly at a boundary
-    rows[5][4080:4096] = ord("-")          # ends exactly before one
-    text = "".join(f">g{i}\n{r.tobytes().decode()}\n" for i, r in enumerate(rows))
     monkeypatch.setattr(pc, "ENGINE", "forest")
-    for N, L in ((3, 7), (2, 3)):
-        pc.check_vs_oracle(emu, [text], N, L)
+    for N, L in ve.GAP_RUN_NL:
+        pc.check_vs_oracle(emu, *ve.gap_runs_across_segments(N, L))
 
 
 def test_big_view_row_groups_when_every_hash_collides(monkeypatch):
@@ -92,42 +59,15 @@ def test_big_view_row_groups_when_every_hash_collides(monkeypatch):
 def test_leaf_of_many_alleles_is_laid_out_by_its_wavefront(emu, monkeypatch):
     """k_as_leaf_jobs: a leaf of more than 128 alleles (here the child of a root at the nesting limit, 300 and 90 distinct rows in one
     batch so that big and small leaves share wavefronts) gets its alleles' places from a wavefront prefix sum."""
-    import numpy as np
-    rng = np.random.default_rng(21)
-    texts = []
-    for S in (300, 90, 200):
-        C = 30
-        base = rng.integers(0, 4, C)
-        rows = []
-        for i in range(S):
-            y = base.copy()
-            y[5:25] = rng.integers(0, 4, 20)
-            t = np.frombuffer(b"ACGT", np.uint8)[y].copy()
-            if i % 5 == 0:
-                t[10:10 + i % 7] = ord("-")          # alleles of different lengths
-            rows.append(t.tobytes().decode())
-        texts.append("".join(f">a{i}\n{r}\n" for i, r in enumerate(rows)))
     monkeypatch.setattr(pc, "ENGINE", "forest")
-    eng = pc.check_vs_oracle(emu, texts, 1, 7)
+    eng = pc.check_vs_oracle(emu, *ve.leaf_of_many_alleles())
     assert int(eng.tab["nseq"].max()) > 128
 
 
 def test_tall_view_takes_the_wide_majority_workgroups(emu, monkeypatch):
     """More rows than the LDS member lists of k_cluster_majority hold (CF_ROWS): k_cluster_majority_big's shared counters."""
-    import numpy as np
-    rng = np.random.default_rng(77)
-    C = 48
-    clades = [rng.integers(0, 4, C) for _ in range(3)]
-    variants = []
-    for cl in clades:
-        for _ in range(4):
-            y = cl.copy()
-            y[rng.integers(0, C, 2)] = rng.integers(0, 4, 2)
-            variants.append(y)
-    rows = [variants[int(rng.integers(0, len(variants)))] for _ in range(1100)]
-    text = "".join(f">t{i}\n{np.frombuffer(b'ACGT', np.uint8)[r].tobytes().decode()}\n" for i, r in enumerate(rows))
     monkeypatch.setattr(pc, "ENGINE", "forest")
-    pc.check_vs_oracle(emu, [text], 5, 7)
+    pc.check_vs_oracle(emu, *ve.tall_view())
 
 
 def test_row_grouping_is_exact_when_every_hash_collides(monkeypatch):
@@ -145,17 +85,9 @@ def test_row_grouping_is_exact_when_every_hash_collides(monkeypatch):
 def test_more_clusters_than_the_lds_offsets_of_split_children(emu, monkeypatch):
     """1 100 distinct sequences shorter than the k-mer size next to 40 long ones: every short one is a cluster of its own,
     more ranks than k_split_children keeps offsets for in LDS (SC_RANKS) — the one-lane form."""
-    import itertools
     import numpy as np
     monkeypatch.setattr(pc, "ENGINE", "forest")
-    rng = np.random.default_rng(3)
-    rows = [f"ACGTTGCAAC{''.join(w)}------GGATCCATGA" for w in itertools.islice(itertools.product("ACGT", repeat=6), 1100)]
-    for i in range(40):
-        base = list(("ACGTACGTACGT", "TTGACCTGAATC")[i % 2])
-        base[int(rng.integers(0, 12))] = "ACGT"[int(rng.integers(0, 4))]
-        rows.append("ACGTTGCAAC" + "".join(base) + "GGATCCATGA")
-    text = "".join(f">s{i}\n{r}\n" for i, r in enumerate(rows))
-    eng = pc.check_vs_oracle(emu, [text], 5, 7)
+    eng = pc.check_vs_oracle(emu, *ve.many_short_clusters())
     assert np.bincount(eng.tab["parent"][eng.tab["parent"] >= 0]).max() > 1024      # a cluster node with > 1024 children
 
 
@@ -179,30 +111,17 @@ def test_problems_prepared_without_tables_stay_with_the_wide_fits(emu, monkeypat
     leave such problems to the wide fits even where their restarts' state would fit its largest classes (here: 44 distinct sequences whose
     ~750 k-mers make a 260 KB matrix; five close clades + noise, so that a seeding from garbage tables changes the answer — a build without
     the rule fails this test).  Thresholds of 1 byte: every level counts as big, no big problem gets tables."""
-    import numpy as np
     import make_prg_amd.forest as F
     monkeypatch.setattr(F, "KM_BIG_BYTES", 1)
     monkeypatch.setattr(F, "KM_NO_TABLES_BYTES", 1)
     monkeypatch.setattr(pc, "ENGINE", "forest")
-    texts = []
-    for seed in (92, 97):
-        rng = np.random.default_rng(seed)
-        C = 44
-        base = rng.integers(0, 4, C)
-        clades = []
-        for _ in range(5):
-            y = base.copy(); m = rng.random(C) < 0.3; y[m] = rng.integers(0, 4, int(m.sum())); clades.append(y)
-        rows = []
-        for i in range(44):
-            y = clades[i % 5].copy(); m = rng.random(C) < 0.1; y[m] = rng.integers(0, 4, int(m.sum()))
-            rows.append(np.frombuffer(b"ACGT", np.uint8)[y].tobytes().decode())
-        texts.append("".join(f">w{i}\n{r}\n" for i, r in enumerate(rows)))
-    eng = pc.check_vs_oracle(emu, texts, 2, 7)
+    texts, N, L = ve.clades_without_tables()
+    eng = pc.check_vs_oracle(emu, texts, N, L)
     assert eng._big_seen and int(eng.counters.get("max_problem_bytes", 0)) > 156 * 1024
     assert emu.lib.mprg_kmeans_lds_class(44, 744, 2, 10) >= 0          # (by its shape the top problem HAS a class: the workspace's flag decides)
     # ... and with the tables made (the default threshold) the same problems take the LDS form: same answers
     monkeypatch.setattr(F, "KM_NO_TABLES_BYTES", 4 << 30)
-    pc.check_vs_oracle(emu, texts, 2, 7)
+    pc.check_vs_oracle(emu, texts, N, L)
 
 
 def test_kmeans_forms_of_earlier_rounds_through_the_forest(monkeypatch, golden_integration):
@@ -259,21 +178,11 @@ def test_big_problem_through_the_byte_matrix(emu, monkeypatch, no_tables_from):
     """A clustering problem whose count matrix is beyond the LDS prepare classes (150 distinct sequences x ~250 4-mers: 300 KB) in a level
     that counts as big: mprg_kmeans_prepare_big writes the byte matrix, the wide fits stream it — with the seeding's tables
     (no_tables_from = huge) and without (1: their elements on demand)."""
-    import numpy as np
     import make_prg_amd.forest as F
     monkeypatch.setattr(F, "KM_BIG_BYTES", 200_000)
     monkeypatch.setattr(F, "KM_NO_TABLES_BYTES", no_tables_from)
     monkeypatch.setattr(pc, "ENGINE", "forest")
-    rng = np.random.default_rng(17)
-    clades = [rng.integers(0, 4, 34) for _ in range(3)]
-    rows = []
-    for i in range(150):
-        y = clades[i % 3].copy()
-        m = rng.random(34) < 0.25
-        y[m] = rng.integers(0, 4, int(m.sum()))
-        rows.append("ACGTACGT" + np.frombuffer(b"ACGT", np.uint8)[y].tobytes().decode() + "TTGACCAT")
-    text = "".join(f">q{i}\n{r}\n" for i, r in enumerate(rows))
-    eng = pc.check_vs_oracle(emu, [text], 2, 4)
+    eng = pc.check_vs_oracle(emu, *ve.byte_matrix_problem())
     assert eng._big_seen and eng.counters["max_problem_bytes"] > 156 * 1024
 
 
@@ -293,24 +202,8 @@ def test_wide_and_tall_view_shares_a_rows_candidates_among_threads(emu, monkeypa
     share a row's earlier rows (candidate classes); the view's rows are wide enough for k_cluster_hamming's group-per-row form and
     k_ungap_hash's batched steps.  Four variants (one mutated column in every five, at different phases: the whole alignment is ONE
     non-match interval), 530 rows drawn from them, a few with gaps (gapped twins of rows that are equal without gaps)."""
-    import numpy as np
-    rng = np.random.default_rng(31)
-    C, S = 4200, 530
-    base = rng.integers(0, 4, C)
-    variants = [base.copy()]
-    for v in range(3):
-        y = base.copy()
-        cols = np.arange(C)[np.arange(C) % 5 == v + 1]
-        y[cols] = (y[cols] + 1 + v) % 4
-        variants.append(y)
-    pick = rng.integers(0, len(variants), S)
-    pick[:8] = [3, 1, 3, 0, 2, 1, 0, 2]          # every variant's first row early, repeats in different candidate classes
-    txt = [np.frombuffer(b"ACGT", np.uint8)[variants[int(p)]].copy() for p in pick]
-    for i in range(5, S, 37):
-        txt[i][100 + i % 50:103 + i % 50] = ord("-")
-    text = "".join(f">w{i}\n{t.tobytes().decode()}\n" for i, t in enumerate(txt))
     monkeypatch.setattr(pc, "ENGINE", "forest")
-    pc.check_vs_oracle(emu, [text], 2, 7)
+    pc.check_vs_oracle(emu, *ve.wide_and_tall_view())
 
 
 def test_sample_tables_by_tiles_equal_the_chains_by_threads(emu):
