@@ -532,6 +532,28 @@ int mprg_forest_export_fill(const int64_t *F, void *stream);
 int mprg_export_alignments(const uint8_t *arena, const int64_t *meta, const int64_t *row_base, const int64_t *out_off, long long n_msas,
                            long long total_rows, uint8_t *out, void *stream);
 
+/* `update --aligner builtin`: new sequences added to leaf alignments by a batched profile alignment (the spec:
+ * make_prg_amd/update/profile_align.py; DESIGN.md §Built-in aligner).  Not MAFFT: no reference function is replaced.
+ * leaves: n_leaves x MPRG_AL_LEAF_FIELDS int64 {offset of the leaf's R x C cell codes in `cells` (row-major, no padding),
+ *   R >= 1, C >= 1, offset of its profile in `profile` (int32 elements; 6 * C per leaf)}.
+ * mprg_align_profiles: work: n_work x 2 int32 {leaf, 256-column tile}.  Writes the leaf's profile as 6 rows of C int32, in 1/64
+ *   row (C's truncating division by R): rows 0-3 the score of A C G T against column j, row 4 that of R Y K M S W N, row 5 the
+ *   cost of a gap in the new sequence at j.
+ * mprg_align_pairs: pairs: n_pairs x MPRG_AL_PAIR_FIELDS int64 {leaf, offset of the new sequence's cell codes in `seqs` (no
+ *   gaps), its length n >= 0, workspace offset (int32 words, a multiple of 64), ops offset (bytes)}.  A pair needs
+ *   ceil(2 (C + 1) / 64) * 64 + ceil(n / 64) * ceil((C + 70) / 8) * 64 words of `workspace` (the row between two 64-residue strips
+ *   and the traceback, 4 bits per cell) and n + C bytes of `ops`.  out: n_pairs x 3 int32 {status, score, op count k}; ops[ops
+ *   offset .. + k) receives the alignment's ops ('M' residue in a column, 'I' residue as a new column, 'D' column skipped) in
+ *   REVERSE order (the last op first).  status: MPRG_AL_OK, MPRG_AL_TOO_LONG (n + C >= MPRG_AL_MAX_LEN: the int32 scores could
+ *   overflow; nothing written), MPRG_AL_NO_SPACE (the pair's workspace or ops range lies outside the buffers; nothing written),
+ *   MPRG_AL_BAD_INPUT (leaf index out of range, R or C < 1).  A pair is one wavefront; pairs in order of descending cell count
+ *   keep the launch's tail short. */
+enum { MPRG_AL_LEAF_FIELDS = 4, MPRG_AL_PAIR_FIELDS = 5, MPRG_AL_MAX_LEN = 1000000,
+       MPRG_AL_OK = 0, MPRG_AL_TOO_LONG = 1, MPRG_AL_NO_SPACE = 2, MPRG_AL_BAD_INPUT = 3 };
+int mprg_align_profiles(const uint8_t *cells, const int64_t *leaves, const int32_t *work, int n_work, int32_t *profile, void *stream);
+int mprg_align_pairs(const int32_t *profile, const int64_t *leaves, int n_leaves, const uint8_t *seqs, const int64_t *pairs, int n_pairs,
+                     int32_t *workspace, long long workspace_words, uint8_t *ops, long long ops_bytes, int32_t *out, void *stream);
+
 /* (f)-1 output encoders, HOST functions (host pointers), one pass over a PRG string as PrgBuilder emits it.
  * reference make_prg/utils/prg_encoder.py:44-91 and make_prg/utils/gfa.py:16-109.
  * mprg_prg_encode_host: out[n] receives the uint32 stream (A C G T -> 1 2 3 4, markers as integers, the closing

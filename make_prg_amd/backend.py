@@ -83,6 +83,9 @@ SIGNATURES = {
     "mprg_forest_kloop_advance": (c_int, [c_void_p, c_int, c_void_p]),
     "mprg_forest_export_count": (c_int, [c_void_p, c_void_p]),
     "mprg_forest_export_fill": (c_int, [c_void_p, c_void_p]),
+    "mprg_align_profiles": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "mprg_align_pairs": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p,
+                                 ctypes.c_longlong, c_void_p, c_void_p]),
     "mprg_random_sample_host": (None, [c_uint32, c_int, c_void_p]),
     "mprg_prg_encode_host": (ctypes.c_longlong, [c_void_p, ctypes.c_longlong, c_void_p]),
     "mprg_fasta_scan_host": (ctypes.c_longlong, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),

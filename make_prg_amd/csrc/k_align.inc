@@ -1,0 +1,160 @@
+// ---------------------------------------------------------------------------------------------------------------
+// K-A  built-in profile aligner of `update --aligner builtin` (make_prg_amd/update/profile_align.py holds the spec;
+//      DESIGN.md §Built-in aligner): new sequences aligned one by one against the profile of a leaf's alignment, a
+//      global three-state (Gotoh) DP in int32, scores in 1/64 row.
+//
+// k_align_profiles: one workgroup per (leaf, 256-column tile), thread = column, the leaf's rows walked in order (a row of
+//   the tile is 256 contiguous bytes: coalesced), the five counts A C G T '-' in registers.  Writes the leaf's profile as
+//   6 x C int32 at profile + poff: rows 0-3 the score of A C G T against the column, row 4 that of R Y K M S W N, row 5 the
+//   cost Dc of a gap in the new sequence there.
+// k_align_pairs: one wavefront per (leaf, new sequence) pair, AL_WAVES pairs per workgroup, no barriers between them.  The
+//   64 lanes own 64 consecutive residues of the sequence (a strip); at step t lane l fills cell (i0 + l, column t - l): the
+//   row above comes from lane l - 1 by a shuffle (lane 0: from the strip above, a row buffer in the workspace that lane 63
+//   of that strip wrote), the profile of the columns in flight from a 128-column LDS ring per wavefront (consecutive lanes
+//   on consecutive columns).  A cell's traceback is 4 bits, a lane packs eight steps per dword, so every store is a 256-byte
+//   row.  Lane 0 then walks the traceback back from (n, C) and writes the ops (reversed) and the score.
+// ---------------------------------------------------------------------------------------------------------------
+#define AL_THREADS 256
+#define AL_WAVES (AL_THREADS / 64)
+#define AL_RING 128
+#define AL_NEG (-2147483647 - 1 + 65536)      // "minus infinity": one penalty below it still fits int32, every real score is above it
+#define AL_OPEN (-704)
+#define AL_INS (-640)
+#define AL_MAX_CELLS_SUM 1000000               // n + C must stay below this: |score| < (n + C) * (640 + 704) < 2^31
+
+KERNEL(k_align_profiles, const uint8_t *cells, const int64_t *leaves, const int32_t *work, int32_t *profile) {
+  const int32_t *wk = work + 2 * (long long)BLOCK_ID;
+  const int64_t *L = leaves + MPRG_AL_LEAF_FIELDS * (long long)wk[0];
+  const long long off = L[0], poff = L[3];
+  const int R = (int)L[1], C = (int)L[2];
+  PAR_FOR(tt, 256) {
+    const int c = wk[1] * 256 + (int)tt;
+    if (c >= C) continue;
+    int cnt[5] = {0, 0, 0, 0, 0};
+    for (int r = 0; r < R; ++r) {
+      const unsigned code = cells[off + (long long)r * C + c];
+#pragma unroll
+      for (int q = 0; q < 5; ++q) cnt[q] += code == (unsigned)q;
+    }
+    const long long acgt = (long long)cnt[0] + cnt[1] + cnt[2] + cnt[3], gap = cnt[4];
+    int32_t *o = profile + poff + c;
+#pragma unroll
+    for (int x = 0; x < 4; ++x) o[(long long)x * C] = (int32_t)(64 * (20 * cnt[x] - 9 * (acgt - cnt[x]) - 10 * gap) / R);
+    o[4LL * C] = (int32_t)(64 * (-10 * gap) / R);
+    o[5LL * C] = (int32_t)(64 * (-10 * ((long long)R - gap)) / R);
+  }
+}
+
+// int32 words of workspace a pair needs: the row buffer (H, I of C + 1 columns, rounded up to 64 words) + the traceback
+// (ceil(n / 64) strips x ceil((C + 63) / 8) dwords x 64 lanes)
+MPRG_DEV long long al_ws_words(long long n, long long C) {
+  return ((2 * (C + 1) + 63) / 64) * 64 + ((n + 63) / 64) * ((C + 63 + 7) / 8) * 64;
+}
+MPRG_DEV int al_hb(long long i) { return i == 0 ? 0 : (int)(AL_OPEN + AL_INS * i); }     // H[i][0]
+
+__global__ void __launch_bounds__(AL_THREADS) k_align_pairs(const int32_t *profile, const int64_t *leaves, int n_leaves,
+                                                            const uint8_t *seqs, const int64_t *pairs, int n_pairs, int32_t *ws,
+                                                            long long ws_words, uint8_t *ops, long long ops_bytes, int32_t *out) {
+  SHARED(int32_t, ring_all, AL_WAVES * 6 * AL_RING);
+  const int lane = wave_lane();
+  const long long p = (long long)BLOCK_ID * AL_WAVES + wave_id();
+  if (p >= n_pairs) return;                                   // (a whole wavefront: nothing below waits for the others)
+  int32_t *ring = ring_all + wave_id() * 6 * AL_RING;
+  const int64_t *PT = pairs + MPRG_AL_PAIR_FIELDS * p;
+  const long long leaf = PT[0], soff = PT[1], n = PT[2], wsoff = PT[3], opoff = PT[4];
+  int32_t *o = out + 3 * p;
+  int status = MPRG_AL_OK;
+  long long C = 0, poff = 0;
+  if (leaf < 0 || leaf >= n_leaves) status = MPRG_AL_BAD_INPUT;
+  else {
+    C = leaves[MPRG_AL_LEAF_FIELDS * leaf + 2];
+    poff = leaves[MPRG_AL_LEAF_FIELDS * leaf + 3];
+    if (C < 1 || n < 0 || leaves[MPRG_AL_LEAF_FIELDS * leaf + 1] < 1) status = MPRG_AL_BAD_INPUT;
+    else if (n + C >= AL_MAX_CELLS_SUM) status = MPRG_AL_TOO_LONG;
+    else if (wsoff < 0 || (wsoff & 63) || wsoff + al_ws_words(n, C) > ws_words || opoff < 0 || opoff + n + C > ops_bytes)
+      status = MPRG_AL_NO_SPACE;
+  }
+  if (status != MPRG_AL_OK) {
+    if (lane == 0) { o[0] = status; o[1] = 0; o[2] = 0; }
+    return;
+  }
+  const int32_t *P = profile + poff;
+  const int Ci = (int)C, ni = (int)n;
+  int32_t *row = ws + wsoff;                                 // row[2J] = H, row[2J + 1] = I of the row above the strip, column J
+  uint32_t *tb = (uint32_t *)(ws + wsoff + ((2 * (C + 1) + 63) / 64) * 64);
+  const long long nst8 = (C + 63 + 7) / 8;
+  // row 0: H[0][J] = D[0][J] = open + the gap costs of columns < J
+  int carry = 0;
+  for (int c0 = 0; c0 < Ci; c0 += 64) {
+    const int c = c0 + lane;
+    const int incl = wave_scan_incl(c < Ci ? P[5LL * C + c] : 0) + carry;
+    if (c < Ci) { row[2 * (c + 1)] = AL_OPEN + incl; row[2 * (c + 1) + 1] = AL_NEG; }
+    carry = __shfl(incl, 63);
+  }
+  if (lane == 0) { row[0] = 0; row[1] = AL_NEG; }
+  WAVE_SYNC_GLOBAL();
+  int score = AL_NEG;
+  const int n_strips = (ni + 63) / 64;
+  for (int s = 0; s < n_strips; ++s) {
+    const int i0 = s * 64, r = i0 + lane, rows = ni - i0 < 64 ? ni - i0 : 64;
+    const bool valid = r < ni;
+    const unsigned code = valid ? seqs[soff + r] : 0u;
+    const int cls = code < 4 ? (int)code : 4;
+    int h_left = al_hb(r + 1), d_left = AL_NEG;            // H, D of this lane's row, the column to the left
+    int h_out = h_left, i_out = AL_NEG;                     // what the lane below reads next step (before the first column: H[i][0])
+    int h_up_prev = al_hb(i0);                               // (lane 0) H of the row above, one column to the left: the diagonal
+    uint32_t acc = 0;
+    const int T = Ci + rows - 1;
+    for (int t = 0; t < T; ++t) {
+      if ((t & 63) == 0) {                                   // the ring takes columns [t, t + 64): the block of columns t - 128 is done with
+        WAVE_SYNC();
+#pragma unroll
+        for (int k = 0; k < 6; ++k) ring[k * AL_RING + ((t + lane) & (AL_RING - 1))] = t + lane < Ci ? P[(long long)k * C + t + lane] : 0;
+        WAVE_SYNC();
+      }
+      int h_up = __shfl_up(h_out, 1), i_up = __shfl_up(i_out, 1);
+      if (lane == 0 && t < Ci) { h_up = row[2 * (t + 1)]; i_up = row[2 * (t + 1) + 1]; }
+      const int h_diag = h_up_prev;
+      h_up_prev = h_up;
+      const int c = t - lane;
+      unsigned cell = 0;
+      if (valid && c >= 0 && c < Ci) {
+        const int slot = c & (AL_RING - 1);
+        const int dc = ring[5 * AL_RING + slot];
+        const int diag = h_diag + ring[cls * AL_RING + slot];
+        const int d_ext = d_left + dc, d_open = h_left + AL_OPEN + dc;
+        const int i_ext = i_up + AL_INS, i_open = h_up + AL_OPEN + AL_INS;
+        const int dd = d_ext >= d_open ? d_ext : d_open, ii = i_ext >= i_open ? i_ext : i_open;
+        int h = diag;
+        unsigned src = 0;
+        if (dd > h) { h = dd; src = 1; }
+        if (ii > h) { h = ii; src = 2; }
+        cell = src | (d_ext >= d_open ? 4u : 0u) | (i_ext >= i_open ? 8u : 0u);
+        h_left = h; d_left = dd; h_out = h; i_out = ii;
+        if (r == ni - 1 && c == Ci - 1) score = h;
+        if (lane == 63 && s + 1 < n_strips) { row[2 * (c + 1)] = h; row[2 * (c + 1) + 1] = ii; }
+      }
+      acc |= cell << (4 * (t & 7));
+      if ((t & 7) == 7 || t == T - 1) { tb[((long long)s * nst8 + (t >> 3)) * 64 + lane] = acc; acc = 0; }
+    }
+    WAVE_SYNC_GLOBAL();                                      // the row buffer and the traceback, written by every lane, read by lane 0
+  }
+  score = ni > 0 ? __shfl(score, (ni - 1) & 63) : row[2 * C];
+  if (lane == 0) {
+    uint8_t *op = ops + opoff;
+    long long k = 0;
+    int i = ni, j = Ci, st = 0;                              // st: 0 H, 1 D, 2 I
+    while (i > 0 && j > 0) {
+      const int rr = i - 1, l = rr & 63, t = j - 1 + l;
+      const unsigned cell = (tb[((long long)(rr >> 6) * nst8 + (t >> 3)) * 64 + l] >> (4 * (t & 7))) & 15u;
+      if (st == 0) {
+        if ((cell & 3u) == 0) { op[k++] = 'M'; --i; --j; }
+        else st = (int)(cell & 3u);
+      } else if (st == 1) { op[k++] = 'D'; --j; st = (cell & 4u) ? 1 : 0; }
+      else { op[k++] = 'I'; --i; st = (cell & 8u) ? 2 : 0; }
+    }
+    for (; j > 0; --j) op[k++] = 'D';                        // row 0: only deletions lead back to (0, 0); column 0: only insertions
+    for (; i > 0; --i) op[k++] = 'I';
+    o[0] = MPRG_AL_OK; o[1] = score; o[2] = (int32_t)k;
+  }
+}

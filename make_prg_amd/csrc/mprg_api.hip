@@ -17,6 +17,7 @@
 #include "k_kloop.inc"
 #include "k_emit.inc"
 #include "k_forest.inc"
+#include "k_align.inc"
 #include "host_encoders.inc"
 #include "host_batch.inc"
 
@@ -536,6 +537,20 @@ int mprg_emit_alleles(const uint8_t *arena, const int64_t *jobs, int64_t n_jobs,
   if (n_jobs <= 0) return 0;
   LAUNCH(k_emit_alleles, (n_jobs + 3) / 4, EMIT_THREADS, stream, arena, jobs, (long long)n_jobs, out);      // a wavefront per job
   return check_launch("k_emit_alleles");
+}
+
+int mprg_align_profiles(const uint8_t *cells, const int64_t *leaves, const int32_t *work, int n_work, int32_t *profile, void *stream) {
+  if (n_work <= 0) return 0;
+  LAUNCH(k_align_profiles, n_work, 256, stream, cells, leaves, work, profile);
+  return check_launch("k_align_profiles");
+}
+
+int mprg_align_pairs(const int32_t *profile, const int64_t *leaves, int n_leaves, const uint8_t *seqs, const int64_t *pairs, int n_pairs,
+                     int32_t *workspace, long long workspace_words, uint8_t *ops, long long ops_bytes, int32_t *out, void *stream) {
+  if (n_pairs <= 0) return 0;
+  LAUNCH(k_align_pairs, (n_pairs + AL_WAVES - 1) / AL_WAVES, AL_THREADS, stream, profile, leaves, n_leaves, seqs, pairs, n_pairs,
+         workspace, workspace_words, ops, ops_bytes, out);      // a wavefront per pair
+  return check_launch("k_align_pairs");
 }
 
 // ---- the recursion forest on the device (k_forest.inc); F: host array of MPRG_F_FIELDS int64 ------------------------------

@@ -2,11 +2,12 @@
 
 Reads the update_DS.zip a previous from_msa / update run of THIS package wrote (pickled PrgBuilders with their recursion
 trees), applies the denovo variants of a denovo_paths.txt to the leaves they fall in, realigns every touched leaf with
-its new sequences (MAFFT --add, or a recorded replay), and rebuilds the sub-tree below each touched leaf.  The reference
-does that leaf by leaf in per-locus worker processes (LeafNode._update_leaf -> NodeFactory.build,
+its new sequences (MAFFT --add, a recorded replay, or the built-in GPU profile aligner), and rebuilds the sub-tree below
+each touched leaf.  The reference does that leaf by leaf in per-locus worker processes (LeafNode._update_leaf -> NodeFactory.build,
 recursion_tree.py:353-388); here the aligner calls run first (in `-t` threads: they are subprocesses) and the re-entries
-of ALL touched leaves of ALL loci go through NodeFactory.build_many as one resident batch on the GPU.  Node ids, the PRG,
-its index and the outputs are what the sequential order gives: leaves of a locus in node-id order, loci independent.
+of ALL touched leaves of ALL loci go through NodeFactory.build_many as one resident batch on the GPU.  With
+`--aligner builtin` the aligner calls are one batch on the GPU as well (BuiltinAligner.get_updated_alignments).  Node ids,
+the PRG, its index and the outputs are what the sequential order gives: leaves of a locus in node-id order, loci independent.
 """
 import logging
 from concurrent.futures import ThreadPoolExecutor
@@ -16,7 +17,7 @@ from typing import Dict, List
 from ..prg_builder import LeafNotFoundException, PrgBuilderZipDatabase
 from ..update.denovo_variants import DenovoVariantsDB
 from ..utils.io_utils import output_files_already_exist
-from ..utils.msa_aligner import MAFFT, ReplayAligner
+from ..utils.msa_aligner import MAFFT, BuiltinAligner, ReplayAligner
 from .from_msa import locus_record, write_final_files
 
 logger = logging.getLogger("make_prg_amd")
@@ -40,9 +41,14 @@ def register_parser(subparsers):
     p.add_argument("-D", "--deletion-threshold", dest="long_deletion_threshold", action="store", type=int, default=10,
                    help="Ignores long deletions of the given size or longer. If long deletions should not be ignored, "
                         "put a large value. Default: %(default)d")
-    p.add_argument("--aligner-replay", dest="aligner_replay", action="store", type=str, default=None,
-                   help="(this implementation) answer the aligner calls from this recorded JSON table instead of running "
-                        "MAFFT (boxes without MAFFT; reproducible runs)")
+    which = p.add_mutually_exclusive_group()
+    which.add_argument("--aligner", dest="aligner", choices=("mafft", "builtin"), default=None,
+                       help="(this implementation) mafft: MAFFT --add, as the reference (default); builtin: the package's own "
+                            "profile aligner on the GPU, nothing external needed — NOT MAFFT, its alignments and so the updated "
+                            "PRGs can differ from the reference's")
+    which.add_argument("--aligner-replay", dest="aligner_replay", action="store", type=str, default=None,
+                       help="(this implementation) answer the aligner calls from this recorded JSON table instead of running "
+                            "MAFFT (boxes without MAFFT; reproducible runs)")
     p.set_defaults(func=run)
     return p
 
@@ -79,8 +85,9 @@ class _LazyAligner:
 
 
 def run(cl_options, aligner=None):
-    """aligner: an object with get_updated_alignment(current_alignment, new_sequences) (tests pass a ReplayAligner);
-    default: --aligner-replay FILE if given, else MAFFT."""
+    """aligner: an object with get_updated_alignment(current_alignment, new_sequences) (tests pass a ReplayAligner), and
+    optionally get_updated_alignments([(alignment, new_sequences), ...]) for all touched leaves at once (BuiltinAligner);
+    default: --aligner-replay FILE if given, else --aligner builtin / mafft (MAFFT when the option is absent)."""
     from ..recursion_tree import NodeFactory
     options = cl_options
     if not options.force and output_files_already_exist(options.output_type, options.output_prefix):
@@ -92,6 +99,8 @@ def run(cl_options, aligner=None):
         replay = getattr(options, "aligner_replay", None)
         if replay:
             aligner = ReplayAligner.from_file(replay)
+        elif getattr(options, "aligner", None) == "builtin":
+            aligner = BuiltinAligner()
         else:
             # made when the first leaf asks for it: an update that touches no leaf needs no MAFFT (this package ships none),
             # and its temp directory goes when the run ends (the reference: a temp root + remove_empty_folders)
@@ -120,13 +129,18 @@ def run(cl_options, aligner=None):
             logger.debug(f"Updated {locus}: {ok} denovo sequences added!")
     finally:
         db.close()
-    # the aligner's part of every touched leaf (external processes: threads are enough), then ONE batched re-entry
+    # the aligner's part of every touched leaf (external processes: threads are enough; a batched aligner: one call), then ONE
+    # batched re-entry
     n_threads = max(1, int(getattr(options, "threads", 1) or 1))
-    logger.info(f"Using {n_threads} threads to realign {len(touched)} leaves...")
-    if n_threads > 1 and len(touched) > 1:
+    if hasattr(aligner, "get_updated_alignments"):
+        logger.info(f"Realigning {len(touched)} leaves in one batch ({aligner.get_aligner_name()})...")
+        updated = aligner.get_updated_alignments([(leaf.alignment, leaf.new_sequences) for leaf in touched]) if touched else []
+    elif n_threads > 1 and len(touched) > 1:
+        logger.info(f"Using {n_threads} threads to realign {len(touched)} leaves...")
         with ThreadPoolExecutor(n_threads) as pool:
             updated = list(pool.map(lambda leaf: leaf.updated_alignment(), touched))
     else:
+        logger.info(f"Using {n_threads} threads to realign {len(touched)} leaves...")
         updated = [leaf.updated_alignment() for leaf in touched]
     subtrees = NodeFactory.build_many([(aln, leaf.prg_builder, leaf.parent) for aln, leaf in zip(updated, touched)])
     for leaf, sub in zip(touched, subtrees):

@@ -1,0 +1,196 @@
+"""Built-in aligner of `update --aligner builtin`: new sequences added to leaf alignments by a batched, integer, deterministic
+profile alignment on the GPU (kernels: csrc/k_align.inc; C ABI: mprg_align_profiles / mprg_align_pairs in include/mprg.h).
+
+It is NOT MAFFT.  Its alignments, and so the PRGs an update builds from them, can differ from what `--aligner mafft` (and the
+reference) gives; byte-identity with the reference holds only for the MAFFT and replay paths.
+
+Spec (the kernels and tests/align_ref.py follow it bit for bit)
+  Inputs.   A leaf alignment A of R rows and C columns (codes ACGT-RYKMSWN, msa.py) and new sequences S_1..S_m, taken in
+            sorted(new_sequences) order (the order the MAFFT wrapper writes them); a '-' in a new sequence is dropped.
+  Pair score sigma.  Identical ACGT +20, different ACGT -9, any pair that involves R Y K M S W N 0, a residue against '-' -10.
+  Profile, in 1/64 row, C's truncating division:
+            residue x against column j:  P[j][x] = (64 * sum_r sigma(x, A[r][j])) / R
+            gap in the new sequence at j: Dc[j] = (64 * -10 * r_j) / R, r_j = the rows of j that are not '-' (all-gap: 0)
+            inserted residue (a new column): -640;  every maximal run of deletions or insertions pays -704 more to open.
+  DP.       Global, three Gotoh states (H, D: column skipped, I: residue inserted), end gaps charged like any other gap,
+            int32 accumulators; a pair with n + C >= 10^6 is refused (the scores could overflow).
+  Ties.     Trace back from (n, C) in state H.  At an H cell take the diagonal if it gives H, else the deletion state if it
+            equals H, else the insertion state.  In a gap state extend if extending gives the state's value, else open from H.
+  Merge.    Every new sequence is aligned on its own against the profile of the original A.  Boundary j (0..C) gets
+            max_k ins_k(j) new columns (ins_k(j): residues sequence k inserts there); each sequence's inserted residues are
+            left-justified in them, every other row has '-' there.
+  Output.   The original rows, then Denovo_path_{i}, with the ids and descriptions that load_alignment_file gives for the
+            MAFFT wrapper's FASTA; letters upper case.
+
+Host side: leaves and sequences packed once, the profiles built for the whole batch in one launch, the pairs sorted by cell
+count (longest first) and launched in chunks that fit a workspace budget (a pair whose traceback alone exceeds the budget is an
+error); the merge is NumPy over the downloaded ops.
+"""
+from typing import Iterable, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from ..msa import MSA, _fasta_title, encode
+
+LEAF_FIELDS, PAIR_FIELDS = 4, 5          # MPRG_AL_LEAF_FIELDS, MPRG_AL_PAIR_FIELDS
+MAX_LEN = 1_000_000                      # MPRG_AL_MAX_LEN
+STATUS = {1: "n + C >= 10^6 (int32 scores could overflow)", 2: "workspace or ops range outside the buffers",
+          3: "bad leaf (index, rows or columns)"}
+DEFAULT_BUDGET_BYTES = 1 << 30           # traceback + row buffers of one launch
+_GAP = ord("-")
+
+
+class ProfileAlignError(ValueError):
+    pass
+
+
+def workspace_words(n: int, C: int) -> int:
+    """int32 words of workspace a pair needs (include/mprg.h, mprg_align_pairs)."""
+    return -(-2 * (C + 1) // 64) * 64 + -(-n // 64) * ((C + 70) // 8) * 64
+
+
+def _codes(seq: str, what: str) -> np.ndarray:
+    raw = np.frombuffer(seq.upper().encode(), np.uint8)
+    raw = raw[raw != _GAP]
+    codes = encode(raw)
+    if (codes == 255).any():
+        raise ProfileAlignError(f"{what}: a character outside ACGT-RYKMSWN")
+    return codes
+
+
+def align_batch(backend, leaves: Sequence[np.ndarray], seqs: Sequence[Sequence[np.ndarray]],
+                budget_bytes: int = DEFAULT_BUDGET_BYTES) -> List[List[Tuple[bytes, int]]]:
+    """leaves: R x C uint8 cell-code matrices; seqs[k]: the gap-free code arrays to align against leaf k.
+    Returns, per leaf, per sequence, (ops as bytes over b"MID" in forward order, score)."""
+    be = backend
+    n_leaves = len(leaves)
+    out: List[List[Optional[Tuple[bytes, int]]]] = [[None] * len(s) for s in seqs]
+    if not n_leaves:
+        return out
+    shapes = np.array([m.shape for m in leaves], np.int64).reshape(-1, 2)
+    if (shapes < 1).any():
+        raise ProfileAlignError("a leaf alignment with no rows or no columns")
+    R, C = shapes[:, 0], shapes[:, 1]
+    cell_off = np.concatenate([[0], np.cumsum(R * C)[:-1]])
+    prof_off = np.concatenate([[0], np.cumsum(6 * C)[:-1]])
+    leaf_tab = np.stack([cell_off, R, C, prof_off], 1).astype(np.int64)
+    tiles = -(-C // 256)
+    work = np.stack([np.repeat(np.arange(n_leaves), tiles),
+                     np.concatenate([np.arange(t) for t in tiles])], 1).astype(np.int32)
+    # pairs: (leaf, index within the leaf, n)
+    pl = np.array([k for k, s in enumerate(seqs) for _ in s], np.int64)
+    pi = np.array([i for s in seqs for i in range(len(s))], np.int64)
+    pn = np.array([len(x) for s in seqs for x in s], np.int64)
+    if not len(pl):
+        return out
+    pc = C[pl]
+    too_long = np.nonzero(pn + pc >= MAX_LEN)[0]
+    if len(too_long):
+        k = too_long[0]
+        raise ProfileAlignError(f"a pair of {pn[k]} residues against {pc[k]} columns: n + C must stay below {MAX_LEN}")
+    seq_all = np.concatenate([x for s in seqs for x in s] + [np.zeros(1, np.uint8)]).astype(np.uint8)
+    seq_off = np.concatenate([[0], np.cumsum(pn)[:-1]])
+    need = np.array([workspace_words(int(n), int(c)) for n, c in zip(pn, pc)], np.int64)
+    budget_words = max(64, int(budget_bytes) // 4)
+    if need.max() > budget_words:
+        k = int(need.argmax())
+        raise ProfileAlignError(f"a pair of {pn[k]} residues against {pc[k]} columns needs {4 * need[k]} bytes of traceback, "
+                                f"more than the workspace budget of {budget_bytes}")
+    order = np.argsort(-((pn + 1) * pc), kind="stable")        # longest first
+    d_cells = be.upload(np.concatenate([m.reshape(-1) for m in leaves]).astype(np.uint8))
+    d_leaves = be.upload(leaf_tab)
+    d_work = be.upload(work)
+    d_prof = be.empty(4 * int((6 * C).sum()))
+    be.call("mprg_align_profiles", be.ptr(d_cells), be.ptr(d_leaves), be.ptr(d_work), len(work), be.ptr(d_prof), be.stream,
+            work=float((R * C).sum()))
+    d_seqs = be.upload(seq_all)
+    pos = 0
+    while pos < len(order):
+        end, used = pos, 0
+        while end < len(order) and used + need[order[end]] <= budget_words:
+            used += int(need[order[end]])
+            end += 1
+        idx = order[pos:end]
+        ws_off = np.concatenate([[0], np.cumsum(need[idx])[:-1]])
+        ops_len = pn[idx] + pc[idx]
+        ops_off = np.concatenate([[0], np.cumsum(ops_len)[:-1]])
+        ptab = np.stack([pl[idx], seq_off[idx], pn[idx], ws_off, ops_off], 1).astype(np.int64)
+        d_pairs = be.upload(ptab)
+        d_ws = be.empty(4 * used)
+        n_ops = int(ops_len.sum())
+        d_ops = be.empty(max(n_ops, 1))
+        d_out = be.empty(12 * len(idx))
+        be.call("mprg_align_pairs", be.ptr(d_prof), be.ptr(d_leaves), n_leaves, be.ptr(d_seqs), be.ptr(d_pairs), len(idx),
+                be.ptr(d_ws), used, be.ptr(d_ops), max(n_ops, 1), be.ptr(d_out), be.stream,
+                work=float(((pn[idx] + 63) // 64 * 64 * pc[idx]).sum()))
+        res = be.download(d_out, np.int32, 3 * len(idx)).reshape(-1, 3)
+        ops = be.download(d_ops, np.uint8, n_ops)
+        bad = np.nonzero(res[:, 0])[0]
+        if len(bad):
+            raise ProfileAlignError(f"mprg_align_pairs: {STATUS.get(int(res[bad[0], 0]), int(res[bad[0], 0]))}")
+        for q, p in enumerate(idx):
+            o = int(ops_off[q])
+            out[pl[p]][pi[p]] = (ops[o:o + int(res[q, 2])][::-1].tobytes(), int(res[q, 1]))
+        pos = end
+    return out
+
+
+def merge(rows: np.ndarray, seqs: Sequence[np.ndarray], ops_list: Sequence[bytes]) -> np.ndarray:
+    """The updated R + m rows (ASCII) of one leaf: rows as R x C ASCII, seqs as gap-free cell codes, their ops."""
+    R, C = rows.shape
+    m = len(seqs)
+    ins = np.zeros((m, C + 1), np.int64)
+    opa = [np.frombuffer(o, np.uint8) for o in ops_list]
+    for k, o in enumerate(opa):
+        is_i = o == ord("I")
+        col = np.cumsum(~is_i) - (~is_i)            # the boundary an op sits at: columns consumed before it
+        np.add.at(ins[k], col[is_i], 1)
+    width = ins.max(0) if m else np.zeros(C + 1, np.int64)
+    start = np.concatenate([[0], np.cumsum(width[:-1] + 1)])          # output column where boundary j's insertions begin
+    W = int(width.sum()) + C
+    out = np.full((R + m, W), _GAP, np.uint8)
+    out[:R, start[:C] + width[:C]] = rows
+    alphabet = np.frombuffer(b"ACGT-RYKMSWN", np.uint8)
+    for k, o in enumerate(opa):
+        is_i = o == ord("I")
+        consumes_col = ~is_i
+        col = np.cumsum(consumes_col) - consumes_col              # boundary / column index of each op
+        is_res = o != ord("D")
+        res = alphabet[seqs[k]]
+        # rank of an inserted residue within its boundary's run
+        run_start = np.zeros(len(o), np.int64)
+        if len(o):
+            new_run = np.concatenate([[True], col[1:] != col[:-1]]) | consumes_col
+            first = np.maximum.accumulate(np.where(new_run, np.arange(len(o)), 0))
+            run_start = np.arange(len(o)) - first
+        dest = np.where(is_i, start[col] + run_start, start[np.minimum(col, C)] + width[np.minimum(col, C)])
+        sel = is_res
+        out[R + k, dest[sel]] = res
+    return out
+
+
+def updated_alignments(backend, items: Iterable[Tuple[MSA, Iterable[str]]],
+                       budget_bytes: int = DEFAULT_BUDGET_BYTES) -> List[MSA]:
+    """[(current alignment, new sequences), ...] -> the alignments with the new sequences added, one batch on the device."""
+    items = list(items)
+    leaves, leaf_rows, seqs = [], [], []
+    for aln, new_sequences in items:
+        data = np.ascontiguousarray(aln.data)
+        lower = (data >= ord("a")) & (data <= ord("z"))
+        upper = np.where(lower, data - 32, data).astype(np.uint8)
+        codes = encode(upper)
+        if (codes == 255).any():
+            raise ProfileAlignError("leaf alignment: a character outside ACGT-RYKMSWN")
+        leaves.append(codes)
+        leaf_rows.append(upper)
+        ordered = sorted(new_sequences)
+        seqs.append([_codes(s, f"new sequence {i}") for i, s in enumerate(ordered)])
+    res = align_batch(backend, leaves, seqs, budget_bytes)
+    out = []
+    for (aln, _), rows, sq, r in zip(items, leaf_rows, seqs, res):
+        data = merge(rows, sq, [ops for ops, _ in r])
+        titles = [_fasta_title(i, d).rstrip() for i, d in zip(aln.ids, aln.descriptions)]
+        titles += [f"Denovo_path_{i}" for i in range(len(sq))]
+        ids = [(t.split(None, 1) or [""])[0] for t in titles]
+        out.append(MSA(_data=data, _ids=ids, _descs=titles))
+    return out

@@ -5,7 +5,8 @@ alignment with those sequences added (MAFFT --add).  The reference bundles a pre
 binaries: `MAFFT` drives an executable named by $MAKE_PRG_MAFFT or found on PATH (`mafft`), with the reference's exact
 arguments.  `ReplayAligner` answers from a recorded table instead (previous alignment + new sequences -> updated
 alignment): the GPU test box has no MAFFT, and a recorded run of the real aligner is what makes `update` reproducible
-there (tests/golden/update.json.gz holds the calls of the reference's own update test cases)."""
+there (tests/golden/update.json.gz holds the calls of the reference's own update test cases).  `BuiltinAligner` needs
+nothing external: a batched profile alignment on the GPU (update/profile_align.py) — not MAFFT, so its alignments can differ."""
 import hashlib
 import json
 import logging
@@ -16,7 +17,7 @@ import tempfile
 import time
 from abc import ABC, abstractmethod
 from pathlib import Path
-from typing import Dict, Iterable, List, Optional, Set
+from typing import Dict, Iterable, List, Optional, Set, Tuple
 
 from ..msa import MSA, Record, load_alignment_file
 
@@ -117,3 +118,31 @@ class ReplayAligner:
                            f"({len(current_alignment)} rows + {sorted(new_sequences)})")
         self.calls += 1
         return MSA([Record(seq, rid, desc) for rid, desc, seq in self._table[key]["updated_rows"]])
+
+
+class BuiltinAligner:
+    """Adds the new sequences with the package's own profile aligner on the device (update/profile_align.py: the spec).  Not
+    MAFFT: the updated alignments, and the PRGs built from them, can differ from the MAFFT path's.  get_updated_alignments
+    takes every touched leaf at once: one profile launch and one launch per workspace-sized chunk of pairs."""
+
+    def __init__(self, backend=None, budget_bytes: Optional[int] = None):
+        self._backend = backend
+        self._budget = budget_bytes
+        self.calls = 0
+
+    @classmethod
+    def get_aligner_name(cls) -> str:
+        return "builtin"
+
+    def get_updated_alignment(self, current_alignment: MSA, new_sequences: Set[str]) -> MSA:
+        return self.get_updated_alignments([(current_alignment, new_sequences)])[0]
+
+    def get_updated_alignments(self, requests: Iterable[Tuple[MSA, Set[str]]]) -> List[MSA]:
+        from .. import device
+        from ..update import profile_align
+        requests = list(requests)
+        be = self._backend or device.get_backend()
+        kw = {} if self._budget is None else {"budget_bytes": self._budget}
+        out = profile_align.updated_alignments(be, requests, **kw)
+        self.calls += len(requests)
+        return out
