@@ -554,6 +554,36 @@ int mprg_align_profiles(const uint8_t *cells, const int64_t *leaves, const int32
 int mprg_align_pairs(const int32_t *profile, const int64_t *leaves, int n_leaves, const uint8_t *seqs, const int64_t *pairs, int n_pairs,
                      int32_t *workspace, long long workspace_words, uint8_t *ops, long long ops_bytes, int32_t *out, void *stream);
 
+/* `from_msa --unaligned`: centre-star MSAs of unaligned loci (the spec: make_prg_amd/from_msa/star_align.py).
+ * Not MAFFT: no reference function is replaced.  The pairs are mprg_align_pairs' (the centre as a 1-row leaf).
+ * codes: the loci's sequences as cell codes (ACGT-RYKMSWN -> 0..11, no gaps), codes_bytes long.  seqs: n_seqs x 2 int64
+ *   {offset in codes, length}.  loci: n_loci x MPRG_ST_LOCUS_FIELDS int64 {first sequence, sequence count, C (the centre's
+ *   length), offset of the locus's C + 1 boundaries in `width` / `start`}.
+ * mprg_star_centres: centre[l] = the smallest index a (within the locus) of a non-empty sequence that maximises
+ *   score(a) = <c_a, T> - <c_a, c_a>, c_a the 4096 counts of a's 6-mers over ACGT (windows with another code skipped),
+ *   T = sum of the c_a; -1 if every sequence is empty; MPRG_ST_CENTRE_BAD if the locus's ranges lie outside the buffers.  One
+ *   workgroup per locus, 32 KB of LDS.  Needs fewer than 2^32 windows per locus.
+ * rows: n_rows x MPRG_ST_ROW_FIELDS int64 {locus, offset of the row's sequence in codes, its length n, offset of its ops in
+ *   `ops` (as mprg_align_pairs wrote them: reversed), op count k (-1: residue i goes to column i, n <= C: the centre row, or an
+ *   empty sequence), offset of the output row in `out` (bytes)}.
+ * mprg_star_merge_columns: width (int32, ZEROED by the caller) receives per boundary j (0..C) the widest insertion of any row
+ *   there, start (int64) the output column where boundary j's insertions begin (sum over j' < j of width + 1), out_width[l] the
+ *   locus's output width W = C + sum of its widths (-1: its width range lies outside n_width).
+ * mprg_star_merge_rows: writes every byte of each row's W bytes at out + out offset: columns, left-justified insertions, '-',
+ *   upper-case letters.  status: n_rows int32 (both calls): MPRG_ST_OK, MPRG_ST_BAD_ROW (fields or ops inconsistent with the
+ *   buffers or with n and C; rows: nothing or part of the row written), MPRG_ST_NO_SPACE (the output row outside out_bytes;
+ *   nothing written).  A row is one wavefront. */
+enum { MPRG_ST_LOCUS_FIELDS = 4, MPRG_ST_ROW_FIELDS = 6, MPRG_ST_CENTRE_BAD = -2,
+       MPRG_ST_OK = 0, MPRG_ST_BAD_ROW = 1, MPRG_ST_NO_SPACE = 2 };
+int mprg_star_centres(const uint8_t *codes, long long codes_bytes, const int64_t *seqs, long long n_seqs, const int64_t *loci,
+                      int n_loci, int32_t *centre, void *stream);
+int mprg_star_merge_columns(const uint8_t *ops, long long ops_bytes, const int64_t *rows, int n_rows, const int64_t *loci, int n_loci,
+                            int32_t *width, int64_t *start, long long n_width, long long codes_bytes, int64_t *out_width,
+                            int32_t *status, void *stream);
+int mprg_star_merge_rows(const uint8_t *codes, long long codes_bytes, const uint8_t *ops, long long ops_bytes, const int64_t *rows,
+                         int n_rows, const int64_t *loci, int n_loci, const int32_t *width, const int64_t *start, long long n_width,
+                         const int64_t *out_width, uint8_t *out, long long out_bytes, int32_t *status, void *stream);
+
 /* (f)-1 output encoders, HOST functions (host pointers), one pass over a PRG string as PrgBuilder emits it.
  * reference make_prg/utils/prg_encoder.py:44-91 and make_prg/utils/gfa.py:16-109.
  * mprg_prg_encode_host: out[n] receives the uint32 stream (A C G T -> 1 2 3 4, markers as integers, the closing

@@ -31,6 +31,8 @@ def main(argv=None):
         par.add_argument("-v", "--verbose", action="count", default=0, help="Increase output verbosity")
         par.add_argument("--log", help="Path to write log to. Default is stderr")
     args = parser.parse_args(argv)
+    if getattr(args, "check", None) is not None:
+        args.check(args, msa_parser)
     if hasattr(args, "func"):
         level = [logging.INFO, logging.DEBUG, logging.DEBUG][min(args.verbose, 2)]
         logging.basicConfig(level=level, **({"filename": args.log} if args.log else {"stream": sys.stderr}))

@@ -18,6 +18,7 @@
 #include "k_emit.inc"
 #include "k_forest.inc"
 #include "k_align.inc"
+#include "k_star.inc"
 #include "host_encoders.inc"
 #include "host_batch.inc"
 
@@ -551,6 +552,36 @@ int mprg_align_pairs(const int32_t *profile, const int64_t *leaves, int n_leaves
   LAUNCH(k_align_pairs, (n_pairs + AL_WAVES - 1) / AL_WAVES, AL_THREADS, stream, profile, leaves, n_leaves, seqs, pairs, n_pairs,
          workspace, workspace_words, ops, ops_bytes, out);      // a wavefront per pair
   return check_launch("k_align_pairs");
+}
+
+int mprg_star_centres(const uint8_t *codes, long long codes_bytes, const int64_t *seqs, long long n_seqs, const int64_t *loci,
+                      int n_loci, int32_t *centre, void *stream) {
+  if (n_loci <= 0) return 0;
+  LAUNCH(k_star_kmer_centre, n_loci, ST_THREADS, stream, codes, codes_bytes, seqs, n_seqs, loci, centre);
+  return check_launch("k_star_kmer_centre");
+}
+
+int mprg_star_merge_columns(const uint8_t *ops, long long ops_bytes, const int64_t *rows, int n_rows, const int64_t *loci, int n_loci,
+                            int32_t *width, int64_t *start, long long n_width, long long codes_bytes, int64_t *out_width,
+                            int32_t *status, void *stream) {
+  if (n_loci <= 0) return 0;
+  if (n_rows > 0) {
+    LAUNCH(k_star_merge_widths, (n_rows + ST_WAVES - 1) / ST_WAVES, ST_THREADS, stream, ops, ops_bytes, rows, n_rows, loci, n_loci,
+           width, n_width, codes_bytes, status);       // a wavefront per row
+    const int rc = check_launch("k_star_merge_widths");
+    if (rc) return rc;
+  }
+  LAUNCH(k_star_merge_columns, (n_loci + ST_WAVES - 1) / ST_WAVES, ST_THREADS, stream, loci, n_loci, width, start, n_width, out_width);
+  return check_launch("k_star_merge_columns");
+}
+
+int mprg_star_merge_rows(const uint8_t *codes, long long codes_bytes, const uint8_t *ops, long long ops_bytes, const int64_t *rows,
+                         int n_rows, const int64_t *loci, int n_loci, const int32_t *width, const int64_t *start, long long n_width,
+                         const int64_t *out_width, uint8_t *out, long long out_bytes, int32_t *status, void *stream) {
+  if (n_rows <= 0) return 0;
+  LAUNCH(k_star_merge_rows, (n_rows + ST_WAVES - 1) / ST_WAVES, ST_THREADS, stream, codes, codes_bytes, ops, ops_bytes, rows, n_rows,
+         loci, n_loci, width, start, n_width, out_width, out, out_bytes, status);
+  return check_launch("k_star_merge_rows");
 }
 
 // ---- the recursion forest on the device (k_forest.inc); F: host array of MPRG_F_FIELDS int64 ------------------------------

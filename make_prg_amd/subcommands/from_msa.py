@@ -11,7 +11,7 @@ import logging
 import os
 import pickle
 from pathlib import Path
-from typing import Dict, List
+from typing import Dict, List, Optional
 
 import numpy as np
 
@@ -47,8 +47,24 @@ def register_parser(subparsers):
                    help="Maximum number of levels to use for nesting. Default: %(default)d")
     p.add_argument("-L", "--min-match-length", dest="min_match_length", action="store", type=int, default=MIN_MATCH_LEN,
                    help="Minimum number of consecutive characters which must be identical for a match. Default: %(default)d")
-    p.set_defaults(func=run)
+    p.add_argument("--unaligned", action="store_true", default=False,
+                   help="(this implementation) the input files are UNALIGNED FASTA(.gz), one locus per file: each locus's MSA is built on "
+                        "the GPU first, a centre-star alignment with the package's own aligner (make_prg_amd/from_msa/star_align.py) — NOT "
+                        "MAFFT, so the PRGs differ from those of a MAFFT alignment — and written as <locus>.fa; the PRGs are then built "
+                        "from those files exactly as from_msa -i on them would.  Only with -f fasta")
+    p.add_argument("--msa-dir", dest="msa_dir", action="store", type=str, default=None,
+                   help="(this implementation) with --unaligned: keep the MSAs in this directory (existing files are not overwritten "
+                        "without -F); default: a private temporary directory beside the output prefix, removed at the end")
+    p.set_defaults(func=run, check=check_options)
     return p
+
+
+def check_options(args, parser):
+    """The combinations argparse cannot refuse by itself (called by the command line right after parsing)."""
+    if args.unaligned and args.alignment_format.lower() != "fasta":
+        parser.error("--unaligned reads FASTA only: it cannot be combined with -f " + args.alignment_format)
+    if args.msa_dir is not None and not args.unaligned:
+        parser.error("--msa-dir needs --unaligned")
 
 
 def get_all_input_files(input_path: str, suffix: str) -> List[Path]:
@@ -480,23 +496,90 @@ def run(cl_options, backend=None):
     if n_workers > 1 and not pipeline:
         import multiprocessing as mp
         pool = mp.get_context("fork").Pool(n_workers)
+    tmp_dir = []
     try:
+        if getattr(options, "unaligned", False):
+            # the MSAs first (this rank's shard, on the GPU), then the unchanged path over the files written
+            files = align_unaligned_inputs(options, backend, tmp_dir)
+            return _run(options, backend, pool, n_workers, msa_files=files)
         return _run(options, backend, pool, n_workers)
     finally:
         if pool is not None:
             pool.close()
             pool.join()
+        if tmp_dir:
+            import shutil
+            shutil.rmtree(tmp_dir[0], ignore_errors=True)
 
 
-def _run(options, backend, pool, n_workers):
-    rank, world, dist = _dist()
+STAR_CHUNK = int(os.environ.get("MPRG_STAR_CHUNK", "2048"))          # loci read, aligned and written per round of --unaligned
+
+
+def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
+    """--unaligned: this rank's shard of the input files (unaligned FASTA), their centre-star MSAs built on the GPU in chunks of
+    loci and written as <locus>.fa into --msa-dir, or into a private temporary directory beside the output prefix (appended to
+    tmp_dir; the caller removes it).  Returns the files written, in the shard's order."""
+    import tempfile
+    import time
+    from ..device import get_backend
+    from ..from_msa import star_align
+    rank, world, _ = _dist()
     input_files = get_all_input_files(options.input, options.suffix)
+    if len(input_files) == 0:
+        raise FileNotFoundError(f"No input files found in {options.input}")
+    seen: Dict[str, Path] = {}
+    for f in input_files:
+        locus = remove_known_input_extensions(f.name)
+        if locus in seen:
+            raise ValueError(f"{seen[locus]} and {f} map to the same locus name {locus}")
+        seen[locus] = f
+    if not options.force and output_files_already_exist(options.output_type, options.output_prefix):
+        raise RuntimeError("One or more output files already exists, aborting run...")
+    mine = shard_files(input_files, rank, world) if world > 1 else input_files
+    loci = [remove_known_input_extensions(f.name) for f in mine]
+    Path(options.output_prefix).parent.mkdir(parents=True, exist_ok=True)
+    if getattr(options, "msa_dir", None) is not None:
+        out_dir = Path(options.msa_dir)
+        out_dir.mkdir(parents=True, exist_ok=True)
+        if not options.force:
+            clash = [l for l in loci if (out_dir / f"{l}.fa").exists()]
+            if clash:
+                raise RuntimeError(f"{out_dir / (clash[0] + '.fa')} already exists (and {len(clash) - 1} more): aborting run (-F overwrites)")
+    else:
+        parent = os.path.dirname(os.path.abspath(options.output_prefix))
+        tmp_dir.append(tempfile.mkdtemp(prefix=f".{os.path.basename(options.output_prefix)}.msa.rank{rank}.", dir=parent))
+        out_dir = Path(tmp_dir[0])
+    be = backend or get_backend("runtime")
+    t_read = t_align = t_write = 0.0
+    written = []
+    for lo in range(0, len(mine), STAR_CHUNK):
+        t0 = time.perf_counter()
+        recs = [star_align.read_unaligned(f) for f in mine[lo:lo + STAR_CHUNK]]
+        t1 = time.perf_counter()
+        msas = star_align.star_msas(be, recs, names=loci[lo:lo + STAR_CHUNK])
+        t2 = time.perf_counter()
+        for locus, m in zip(loci[lo:lo + STAR_CHUNK], msas):
+            path = out_dir / f"{locus}.fa"
+            with open(path, "w") as fh:
+                fh.write(star_align.msa_fasta(m))
+            written.append(path)
+        t_read, t_align, t_write = t_read + t1 - t0, t_align + t2 - t1, t_write + time.perf_counter() - t2
+    logger.info(f"rank {rank}: {len(written)} centre-star MSAs: read {t_read:.2f}s, aligned {t_align:.2f}s, written {t_write:.2f}s "
+                f"into {out_dir}")
+    align_unaligned_inputs.timings = dict(read_s=t_read, align_s=t_align, write_s=t_write)
+    return written
+
+
+def _run(options, backend, pool, n_workers, msa_files: Optional[List[Path]] = None):
+    """msa_files: the inputs are these files, already this rank's shard (--unaligned); else options.input / suffix, sharded."""
+    rank, world, dist = _dist()
+    input_files = get_all_input_files(options.input, options.suffix) if msa_files is None else msa_files
     if len(input_files) == 0:
         raise FileNotFoundError(f"No input files found in {options.input}")
     if not options.force and output_files_already_exist(options.output_type, options.output_prefix):
         raise RuntimeError("One or more output files already exists, aborting run...")
     Path(options.output_prefix).parent.mkdir(parents=True, exist_ok=True)
-    mine = shard_files(input_files, rank, world) if world > 1 else input_files
+    mine = shard_files(input_files, rank, world) if world > 1 and msa_files is None else input_files
     import time
     t0 = time.time()
     if dist is None and len(mine) > 1 and os.environ.get("MPRG_PIPELINE", "1") != "0":

@@ -24,7 +24,8 @@ Spec (the kernels and tests/align_ref.py follow it bit for bit)
 
 Host side: leaves and sequences packed once, the profiles built for the whole batch in one launch, the pairs sorted by cell
 count (longest first) and launched in chunks that fit a workspace budget (a pair whose traceback alone exceeds the budget is an
-error); the merge is NumPy over the downloaded ops.
+error), every pair's ops into one device buffer (pairs_on_device; from_msa --unaligned merges them there, csrc/k_star.inc);
+the merge of `update` is NumPy over the downloaded ops.
 """
 from typing import Iterable, List, Optional, Sequence, Tuple
 
@@ -62,11 +63,34 @@ def align_batch(backend, leaves: Sequence[np.ndarray], seqs: Sequence[Sequence[n
                 budget_bytes: int = DEFAULT_BUDGET_BYTES) -> List[List[Tuple[bytes, int]]]:
     """leaves: R x C uint8 cell-code matrices; seqs[k]: the gap-free code arrays to align against leaf k.
     Returns, per leaf, per sequence, (ops as bytes over b"MID" in forward order, score)."""
+    out: List[List[Optional[Tuple[bytes, int]]]] = [[None] * len(s) for s in seqs]
+    dp = pairs_on_device(backend, leaves, seqs, budget_bytes)
+    if dp is None:
+        return out
+    ops = backend.download(dp.d_ops, np.uint8, dp.ops_bytes)
+    for p in range(len(dp.leaf)):
+        o = int(dp.ops_off[p])
+        out[dp.leaf[p]][dp.index[p]] = (ops[o:o + int(dp.count[p])][::-1].tobytes(), int(dp.score[p]))
+    return out
+
+
+class DevicePairs:
+    """What pairs_on_device leaves: every pair's ops in one device buffer, as mprg_align_pairs wrote them (REVERSED, the last op
+    first) at ops_off[p], count[p] of them; per pair (in leaf order, then sequence order) its leaf, index within the leaf and score."""
+
+    def __init__(self, d_ops, ops_bytes, leaf, index, ops_off, count, score):
+        self.d_ops, self.ops_bytes = d_ops, ops_bytes
+        self.leaf, self.index, self.ops_off, self.count, self.score = leaf, index, ops_off, count, score
+
+
+def pairs_on_device(backend, leaves: Sequence[np.ndarray], seqs: Sequence[Sequence[np.ndarray]],
+                    budget_bytes: int = DEFAULT_BUDGET_BYTES) -> Optional[DevicePairs]:
+    """The pairs of align_batch on the device: the profiles in one launch, the pairs longest first in launches that fit the
+    workspace budget, every pair's ops into one buffer that stays on the device.  None when there is no pair."""
     be = backend
     n_leaves = len(leaves)
-    out: List[List[Optional[Tuple[bytes, int]]]] = [[None] * len(s) for s in seqs]
     if not n_leaves:
-        return out
+        return None
     shapes = np.array([m.shape for m in leaves], np.int64).reshape(-1, 2)
     if (shapes < 1).any():
         raise ProfileAlignError("a leaf alignment with no rows or no columns")
@@ -82,7 +106,7 @@ def align_batch(backend, leaves: Sequence[np.ndarray], seqs: Sequence[Sequence[n
     pi = np.array([i for s in seqs for i in range(len(s))], np.int64)
     pn = np.array([len(x) for s in seqs for x in s], np.int64)
     if not len(pl):
-        return out
+        return None
     pc = C[pl]
     too_long = np.nonzero(pn + pc >= MAX_LEN)[0]
     if len(too_long):
@@ -97,6 +121,11 @@ def align_batch(backend, leaves: Sequence[np.ndarray], seqs: Sequence[Sequence[n
         raise ProfileAlignError(f"a pair of {pn[k]} residues against {pc[k]} columns needs {4 * need[k]} bytes of traceback, "
                                 f"more than the workspace budget of {budget_bytes}")
     order = np.argsort(-((pn + 1) * pc), kind="stable")        # longest first
+    ops_len = pn + pc
+    ops_off = np.concatenate([[0], np.cumsum(ops_len)[:-1]])
+    ops_bytes = max(int(ops_len.sum()), 1)
+    count = np.zeros(len(pl), np.int64)
+    score = np.zeros(len(pl), np.int64)
     d_cells = be.upload(np.concatenate([m.reshape(-1) for m in leaves]).astype(np.uint8))
     d_leaves = be.upload(leaf_tab)
     d_work = be.upload(work)
@@ -104,6 +133,7 @@ def align_batch(backend, leaves: Sequence[np.ndarray], seqs: Sequence[Sequence[n
     be.call("mprg_align_profiles", be.ptr(d_cells), be.ptr(d_leaves), be.ptr(d_work), len(work), be.ptr(d_prof), be.stream,
             work=float((R * C).sum()))
     d_seqs = be.upload(seq_all)
+    d_ops = be.empty(ops_bytes)
     pos = 0
     while pos < len(order):
         end, used = pos, 0
@@ -112,27 +142,21 @@ def align_batch(backend, leaves: Sequence[np.ndarray], seqs: Sequence[Sequence[n
             end += 1
         idx = order[pos:end]
         ws_off = np.concatenate([[0], np.cumsum(need[idx])[:-1]])
-        ops_len = pn[idx] + pc[idx]
-        ops_off = np.concatenate([[0], np.cumsum(ops_len)[:-1]])
-        ptab = np.stack([pl[idx], seq_off[idx], pn[idx], ws_off, ops_off], 1).astype(np.int64)
+        ptab = np.stack([pl[idx], seq_off[idx], pn[idx], ws_off, ops_off[idx]], 1).astype(np.int64)
         d_pairs = be.upload(ptab)
         d_ws = be.empty(4 * used)
-        n_ops = int(ops_len.sum())
-        d_ops = be.empty(max(n_ops, 1))
         d_out = be.empty(12 * len(idx))
         be.call("mprg_align_pairs", be.ptr(d_prof), be.ptr(d_leaves), n_leaves, be.ptr(d_seqs), be.ptr(d_pairs), len(idx),
-                be.ptr(d_ws), used, be.ptr(d_ops), max(n_ops, 1), be.ptr(d_out), be.stream,
+                be.ptr(d_ws), used, be.ptr(d_ops), ops_bytes, be.ptr(d_out), be.stream,
                 work=float(((pn[idx] + 63) // 64 * 64 * pc[idx]).sum()))
         res = be.download(d_out, np.int32, 3 * len(idx)).reshape(-1, 3)
-        ops = be.download(d_ops, np.uint8, n_ops)
         bad = np.nonzero(res[:, 0])[0]
         if len(bad):
             raise ProfileAlignError(f"mprg_align_pairs: {STATUS.get(int(res[bad[0], 0]), int(res[bad[0], 0]))}")
-        for q, p in enumerate(idx):
-            o = int(ops_off[q])
-            out[pl[p]][pi[p]] = (ops[o:o + int(res[q, 2])][::-1].tobytes(), int(res[q, 1]))
+        score[idx] = res[:, 1]
+        count[idx] = res[:, 2]
         pos = end
-    return out
+    return DevicePairs(d_ops, ops_bytes, pl, pi, ops_off, count, score)
 
 
 def merge(rows: np.ndarray, seqs: Sequence[np.ndarray], ops_list: Sequence[bytes]) -> np.ndarray:

@@ -1,0 +1,63 @@
+"""GPU-box helper: `from_msa --unaligned` stage by stage on N config-C-shaped loci (utils/synthetic.py, seeds 0..N-1) with their
+gaps removed, written as unaligned FASTA files into a temporary directory first.  Prints one JSON line: wall seconds of reading
+the files, the centre, pair and merge stages (star_align.star_msas; each ends at a download), writing the MSAs, and the PRG build
+(from_msa's pipeline over the MSAs written), plus the DP cells (sum of n x C over the pairs).  Kernel times: run it under
+`rocprofv3 --kernel-trace --stats -- python tools/star_measure.py N`."""
+import json
+import os
+import shutil
+import sys
+import tempfile
+import time
+from argparse import Namespace
+from pathlib import Path
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from make_prg_amd.device import get_backend  # noqa: E402
+from make_prg_amd.from_msa import star_align as sa  # noqa: E402
+from make_prg_amd.subcommands import from_msa  # noqa: E402
+from make_prg_amd.subcommands.output_type import OutputType  # noqa: E402
+from make_prg_amd.utils.synthetic import config_shape, synth_rows  # noqa: E402
+
+n_loci = int(sys.argv[1]) if len(sys.argv) > 1 else 1000
+work = Path(tempfile.mkdtemp(prefix="star_measure_"))
+try:
+    src, msa_dir = work / "unaligned", work / "msas"
+    src.mkdir()
+    msa_dir.mkdir()
+    t0 = time.perf_counter()
+    for seed in range(n_loci):
+        rows = synth_rows(seed, *config_shape("C", seed))
+        (src / f"gene{seed:05d}.fa").write_text("".join(f">s{i}\n{r.decode().replace('-', '')}\n" for i, r in enumerate(rows)))
+    t_gen = time.perf_counter() - t0
+    files = sorted(src.iterdir())
+    be = get_backend("runtime")
+    sa.star_msas(be, [sa.read_unaligned(f) for f in files[:4]])           # warm-up: first launches
+    t0 = time.perf_counter()
+    recs = [sa.read_unaligned(f) for f in files]
+    t_read = time.perf_counter() - t0
+    timings = {}
+    t0 = time.perf_counter()
+    msas = sa.star_msas(be, recs, timings=timings)
+    t_star = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    written = []
+    for f, m in zip(files, msas):
+        p = msa_dir / f.name
+        p.write_text(sa.msa_fasta(m))
+        written.append(p)
+    t_write = time.perf_counter() - t0
+    codes = [sa.locus_codes(f.name, r) for f, r in zip(files, recs)]
+    cent = sa.centres(be, codes)
+    cells = sum(len(c) * len(cs[int(k)]) for cs, k in zip(codes, cent) for a, c in enumerate(cs) if a != int(k))
+    opts = Namespace(input=str(msa_dir), suffix="", output_prefix=str(work / "out" / "prg"), alignment_format="fasta",
+                     max_nesting=5, min_match_length=7, output_type=OutputType("a"), force=False, threads=16)
+    t0 = time.perf_counter()
+    from_msa._run(opts, None, None, 1, msa_files=written)
+    t_prg = time.perf_counter() - t0
+    print(json.dumps(dict(loci=n_loci, pairs=sum(len(r) - 1 for r in recs), residues=sum(len(s) for r in recs for _, s in r),
+                          generate_s=round(t_gen, 2), read_s=round(t_read, 3), star_s=round(t_star, 3),
+                          **{k: round(v, 3) for k, v in timings.items()}, write_s=round(t_write, 3), prg_build_s=round(t_prg, 3),
+                          dp_cells=cells)))
+finally:
+    shutil.rmtree(work, ignore_errors=True)
