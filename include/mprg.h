@@ -572,11 +572,31 @@ int mprg_align_pairs(const int32_t *profile, const int64_t *leaves, int n_leaves
  * mprg_star_merge_rows: writes every byte of each row's W bytes at out + out offset: columns, left-justified insertions, '-',
  *   upper-case letters.  status: n_rows int32 (both calls): MPRG_ST_OK, MPRG_ST_BAD_ROW (fields or ops inconsistent with the
  *   buffers or with n and C; rows: nothing or part of the row written), MPRG_ST_NO_SPACE (the output row outside out_bytes;
- *   nothing written).  A row is one wavefront. */
+ *   nothing written).  A row is one wavefront.
+ *
+ * `--adjust-direction` (strand detection in front of the calls above; the spec: star_align.py).  rc6(k) of a 6-mer
+ * index k: 4095 - k with its six 2-bit groups in reverse order.
+ * mprg_star_centres_canonical: mprg_star_centres with every window counted in the bin min(k, rc6(k)): the centre it gives does not
+ *   change when any of the locus's sequences are reverse-complemented.  Same arguments, results and LDS.
+ * mprg_star_strand: centre: n_loci int32, each locus's centre index (device memory, as the calls above wrote it).  With h the
+ *   6-mer counts (ACGT windows) of the centre sequence AS STORED, evidence (n_seqs x 3 int64, at 3 * the sequence's index)
+ *   receives for every sequence of the locus, the centre and empty ones included, {fwd = sum of h[k_w], rev = sum of h[rc6(k_w)],
+ *   nw = the number of windows} over its valid windows w.  Against the centre's reverse complement fwd and rev swap (the caller
+ *   does that).  status: n_loci int32: MPRG_ST_OK, or MPRG_ST_CENTRE_BAD (ranges outside the buffers, or a centre index outside
+ *   the locus: none of the locus's triples written).  One workgroup per locus, 16 KB of LDS.
+ * mprg_star_revcomp: jobs: n_jobs x 3 int64 {source offset, n, destination offset}, all in `codes`: codes[destination + i] =
+ *   the complement of codes[source + n - 1 - i] (0<->3, 1<->2, 5<->6, 7<->8, every other code unchanged).  status: n_jobs int32:
+ *   MPRG_ST_OK, or MPRG_ST_BAD_ROW (a range outside codes_bytes, or source and destination overlap: nothing written).  The
+ *   destinations of different jobs must not overlap each other or any job's source.  A job is one wavefront. */
 enum { MPRG_ST_LOCUS_FIELDS = 4, MPRG_ST_ROW_FIELDS = 6, MPRG_ST_CENTRE_BAD = -2,
        MPRG_ST_OK = 0, MPRG_ST_BAD_ROW = 1, MPRG_ST_NO_SPACE = 2 };
 int mprg_star_centres(const uint8_t *codes, long long codes_bytes, const int64_t *seqs, long long n_seqs, const int64_t *loci,
                       int n_loci, int32_t *centre, void *stream);
+int mprg_star_centres_canonical(const uint8_t *codes, long long codes_bytes, const int64_t *seqs, long long n_seqs, const int64_t *loci,
+                                int n_loci, int32_t *centre, void *stream);
+int mprg_star_strand(const uint8_t *codes, long long codes_bytes, const int64_t *seqs, long long n_seqs, const int64_t *loci, int n_loci,
+                     const int32_t *centre, int64_t *evidence, int32_t *status, void *stream);
+int mprg_star_revcomp(uint8_t *codes, long long codes_bytes, const int64_t *jobs, int n_jobs, int32_t *status, void *stream);
 int mprg_star_merge_columns(const uint8_t *ops, long long ops_bytes, const int64_t *rows, int n_rows, const int64_t *loci, int n_loci,
                             int32_t *width, int64_t *start, long long n_width, long long codes_bytes, int64_t *out_width,
                             int32_t *status, void *stream);

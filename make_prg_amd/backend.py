@@ -87,6 +87,10 @@ SIGNATURES = {
     "mprg_align_pairs": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p,
                                  ctypes.c_longlong, c_void_p, c_void_p]),
     "mprg_star_centres": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, c_void_p]),
+    "mprg_star_centres_canonical": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, c_void_p]),
+    "mprg_star_strand": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                 c_void_p]),
+    "mprg_star_revcomp": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, c_void_p]),
     "mprg_star_merge_columns": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, ctypes.c_longlong,
                                         ctypes.c_longlong, c_void_p, c_void_p, c_void_p]),
     "mprg_star_merge_rows": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,

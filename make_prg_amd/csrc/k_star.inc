@@ -6,6 +6,15 @@
 //   window of every sequence; then, sequence by sequence, its own histogram c_a in a second 16 KB of LDS and
 //   score(a) = <c_a, T> - <c_a, c_a> = sum over a's windows w of (T[k_w] - c_a[k_w]) in int64, a block reduction, and the
 //   argmax with the lowest-index tie rule over the non-empty sequences.  Integers only.
+// k_star_kmer_centre_canonical (`--adjust-direction`): the same body with every window counted in the bin min(k, rc6(k)), so the
+//   centre it picks does not change when any subset of the locus's sequences is reverse-complemented.
+// k_star_strand: one workgroup per locus.  The forward 6-mer histogram h of the locus's centre sequence (as stored) is built once
+//   in 16 KB of LDS and then only read: the wavefronts take the locus's sequences round-robin, the lanes stride over a sequence's
+//   windows, a valid window adds h[k] to fwd, h[rc6(k)] to rev and 1 to nw; a wave reduction, lane 0 writes the three int64.
+//   The reference orientation of the spec may be the centre's reverse complement: h_rc(s)[k] = h_s[rc6(k)], so the HOST swaps
+//   fwd and rev for such a locus instead of the kernel reading a reversed centre.
+// k_star_revcomp: one wavefront per job: the reverse complement of a sequence written elsewhere in the same code buffer (the
+//   buffer's tail), consecutive lanes on consecutive bytes of both.
 // k_star_merge_widths: one wavefront per row of a locus that came out of the pair kernel.  The row's ops (stored reversed) are
 //   read forward in 64-op chunks; wave scans give each op its boundary / column (non-I ops before it), its residue index (non-D
 //   ops before it) and, for an I, its rank in the run of I's at that boundary; atomicMax(width[boundary], rank + 1).
@@ -19,6 +28,14 @@
 #define ST_K 6
 #define ST_BINS 4096
 
+// reverse complement of a 6-mer index: complement (4095 - k), then the six 2-bit groups in reverse order
+MPRG_DEV unsigned st_rc6(unsigned k) {
+  k = ~k & (ST_BINS - 1);
+  unsigned r = 0;
+#pragma unroll
+  for (int q = 0; q < ST_K; ++q) r = (r << 2) | ((k >> (2 * q)) & 3u);
+  return r;
+}
 KERNEL(k_star_kmer_centre, const uint8_t *codes, long long codes_bytes, const int64_t *seqs, long long n_seqs, const int64_t *loci,
        int32_t *centre) {
   SHARED(uint32_t, tot, ST_BINS);
@@ -83,6 +100,142 @@ KERNEL(k_star_kmer_centre, const uint8_t *codes, long long codes_bytes, const in
     BARRIER();                                               // (hist and red are rewritten for the next sequence)
   }
   ONE_THREAD centre[BLOCK_ID] = best_a;                     // -1: every sequence is empty
+}
+
+// the strand-blind bin of a window: the smaller of its index and its reverse complement's
+MPRG_DEV unsigned st_canonical(unsigned k) {
+  const unsigned r = st_rc6(k);
+  return r < k ? r : k;
+}
+
+// k_star_kmer_centre with canonical bins.  A kernel of its own, not a shared body: k_star_kmer_centre's code stays what it was
+// (an inlined common body compiles it differently), so a run without --adjust-direction launches the same instructions as before.
+KERNEL(k_star_kmer_centre_canonical, const uint8_t *codes, long long codes_bytes, const int64_t *seqs, long long n_seqs,
+       const int64_t *loci, int32_t *centre) {
+  SHARED(uint32_t, tot, ST_BINS);
+  SHARED(uint32_t, hist, ST_BINS);
+  SHARED(long long, red, ST_WAVES);
+  SHARED(int, bad, 1);
+  const int64_t *L = loci + MPRG_ST_LOCUS_FIELDS * (long long)BLOCK_ID;
+  const long long first = L[0], m = L[1];
+  ONE_THREAD {
+    int b = first < 0 || m < 0 || first + m > n_seqs;
+    for (long long a = 0; !b && a < m; ++a) b = seqs[2 * (first + a)] < 0 || seqs[2 * (first + a) + 1] < 0 ||
+                                               seqs[2 * (first + a)] + seqs[2 * (first + a) + 1] > codes_bytes;
+    bad[0] = b;
+    if (b) centre[BLOCK_ID] = MPRG_ST_CENTRE_BAD;
+  }
+  BARRIER();
+  if (bad[0]) return;                                        // (the whole workgroup)
+  PAR_FOR(b, ST_BINS) tot[b] = 0;
+  BARRIER();
+  for (long long a = 0; a < m; ++a) {
+    const long long off = seqs[2 * (first + a)], n = seqs[2 * (first + a) + 1];
+    PAR_FOR(w, n - (ST_K - 1)) {
+      unsigned k = 0;
+      bool ok = true;
+#pragma unroll
+      for (int q = 0; q < ST_K; ++q) { const unsigned c = codes[off + w + q]; ok = ok && c < 4u; k = (k << 2) | (c & 3u); }
+      if (ok) ATOMIC_ADD(&tot[st_canonical(k)], 1u);
+    }
+  }
+  BARRIER();
+  long long best = 0;
+  int best_a = -1;
+  for (long long a = 0; a < m; ++a) {
+    const long long off = seqs[2 * (first + a)], n = seqs[2 * (first + a) + 1];
+    PAR_FOR(b, ST_BINS) hist[b] = 0;
+    BARRIER();
+    PAR_FOR(w, n - (ST_K - 1)) {
+      unsigned k = 0;
+      bool ok = true;
+#pragma unroll
+      for (int q = 0; q < ST_K; ++q) { const unsigned c = codes[off + w + q]; ok = ok && c < 4u; k = (k << 2) | (c & 3u); }
+      if (ok) ATOMIC_ADD(&hist[st_canonical(k)], 1u);
+    }
+    BARRIER();
+    long long part = 0;
+    PAR_FOR(w, n - (ST_K - 1)) {
+      unsigned k = 0;
+      bool ok = true;
+#pragma unroll
+      for (int q = 0; q < ST_K; ++q) { const unsigned c = codes[off + w + q]; ok = ok && c < 4u; k = (k << 2) | (c & 3u); }
+      if (ok) { k = st_canonical(k); part += (long long)tot[k] - (long long)hist[k]; }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d);
+    if (wave_lane() == 0) red[wave_id()] = part;
+    BARRIER();
+    ONE_THREAD {
+      long long s = 0;
+      for (int w = 0; w < ST_WAVES; ++w) s += red[w];
+      if (n > 0 && (best_a < 0 || s > best)) { best = s; best_a = (int)a; }
+    }
+    BARRIER();                                               // (hist and red are rewritten for the next sequence)
+  }
+  ONE_THREAD centre[BLOCK_ID] = best_a;                     // -1: every sequence is empty
+}
+
+KERNEL(k_star_strand, const uint8_t *codes, long long codes_bytes, const int64_t *seqs, long long n_seqs, const int64_t *loci,
+       const int32_t *centre, int64_t *evidence, int32_t *status) {
+  SHARED(uint32_t, href, ST_BINS);
+  SHARED(int, bad, 1);
+  const int64_t *L = loci + MPRG_ST_LOCUS_FIELDS * (long long)BLOCK_ID;
+  const long long first = L[0], m = L[1], c = centre[BLOCK_ID];
+  ONE_THREAD {
+    int b = first < 0 || m < 0 || first + m > n_seqs || c < 0 || c >= m;
+    for (long long a = 0; !b && a < m; ++a) b = seqs[2 * (first + a)] < 0 || seqs[2 * (first + a) + 1] < 0 ||
+                                               seqs[2 * (first + a)] + seqs[2 * (first + a) + 1] > codes_bytes;
+    bad[0] = b;
+    status[BLOCK_ID] = b ? MPRG_ST_CENTRE_BAD : MPRG_ST_OK;
+  }
+  PAR_FOR(b, ST_BINS) href[b] = 0;
+  BARRIER();
+  if (bad[0]) return;                                        // (the whole workgroup; no triple written)
+  {
+    const long long off = seqs[2 * (first + c)], n = seqs[2 * (first + c) + 1];
+    PAR_FOR(w, n - (ST_K - 1)) {
+      unsigned k = 0;
+      bool ok = true;
+#pragma unroll
+      for (int q = 0; q < ST_K; ++q) { const unsigned x = codes[off + w + q]; ok = ok && x < 4u; k = (k << 2) | (x & 3u); }
+      if (ok) ATOMIC_ADD(&href[k], 1u);
+    }
+  }
+  BARRIER();                                                 // href is read-only from here on: no barrier, no LDS write below
+  for (long long a = wave_id(); a < m; a += ST_WAVES) {
+    const long long off = seqs[2 * (first + a)], n = seqs[2 * (first + a) + 1];
+    long long fwd = 0, rev = 0, nw = 0;
+    for (long long w = wave_lane(); w < n - (ST_K - 1); w += WAVE) {
+      unsigned k = 0;
+      bool ok = true;
+#pragma unroll
+      for (int q = 0; q < ST_K; ++q) { const unsigned x = codes[off + w + q]; ok = ok && x < 4u; k = (k << 2) | (x & 3u); }
+      if (ok) { fwd += href[k]; rev += href[st_rc6(k)]; ++nw; }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { fwd += __shfl_xor(fwd, d); rev += __shfl_xor(rev, d); nw += __shfl_xor(nw, d); }
+    if (wave_lane() == 0) {
+      int64_t *e = evidence + 3 * (first + a);
+      e[0] = fwd; e[1] = rev; e[2] = nw;
+    }
+  }
+}
+
+// a wavefront per job {source offset, n, destination offset}: dst[i] = complement of src[n - 1 - i], both inside `codes`
+__global__ void __launch_bounds__(ST_THREADS) k_star_revcomp(uint8_t *codes, long long codes_bytes, const int64_t *jobs, int n_jobs,
+                                                             int32_t *status) {
+  const long long j = (long long)BLOCK_ID * ST_WAVES + wave_id();
+  if (j >= n_jobs) return;                                   // (a whole wavefront)
+  const long long src = jobs[3 * j], n = jobs[3 * j + 1], dst = jobs[3 * j + 2];
+  const bool ok = src >= 0 && n >= 0 && dst >= 0 && src + n <= codes_bytes && dst + n <= codes_bytes && (dst >= src + n || dst + n <= src);
+  if (wave_lane() == 0) status[j] = ok ? MPRG_ST_OK : MPRG_ST_BAD_ROW;
+  if (!ok) return;
+  // ACGT-RYKMSWN: A<->T, C<->G, R<->Y, K<->M; '-', S, W, N and anything else stay
+  for (long long i = wave_lane(); i < n; i += WAVE) {
+    const unsigned x = codes[src + n - 1 - i];
+    codes[dst + i] = (uint8_t)(x < 4u ? 3u - x : x == 5u || x == 7u ? x + 1u : x == 6u || x == 8u ? x - 1u : x);
+  }
 }
 
 // inclusive max-scan over the lanes of a wave (all 64 lanes call it)

@@ -561,6 +561,26 @@ int mprg_star_centres(const uint8_t *codes, long long codes_bytes, const int64_t
   return check_launch("k_star_kmer_centre");
 }
 
+int mprg_star_centres_canonical(const uint8_t *codes, long long codes_bytes, const int64_t *seqs, long long n_seqs, const int64_t *loci,
+                                int n_loci, int32_t *centre, void *stream) {
+  if (n_loci <= 0) return 0;
+  LAUNCH(k_star_kmer_centre_canonical, n_loci, ST_THREADS, stream, codes, codes_bytes, seqs, n_seqs, loci, centre);
+  return check_launch("k_star_kmer_centre_canonical");
+}
+
+int mprg_star_strand(const uint8_t *codes, long long codes_bytes, const int64_t *seqs, long long n_seqs, const int64_t *loci, int n_loci,
+                     const int32_t *centre, int64_t *evidence, int32_t *status, void *stream) {
+  if (n_loci <= 0) return 0;
+  LAUNCH(k_star_strand, n_loci, ST_THREADS, stream, codes, codes_bytes, seqs, n_seqs, loci, centre, evidence, status);
+  return check_launch("k_star_strand");
+}
+
+int mprg_star_revcomp(uint8_t *codes, long long codes_bytes, const int64_t *jobs, int n_jobs, int32_t *status, void *stream) {
+  if (n_jobs <= 0) return 0;
+  LAUNCH(k_star_revcomp, (n_jobs + ST_WAVES - 1) / ST_WAVES, ST_THREADS, stream, codes, codes_bytes, jobs, n_jobs, status);      // a wavefront per job
+  return check_launch("k_star_revcomp");
+}
+
 int mprg_star_merge_columns(const uint8_t *ops, long long ops_bytes, const int64_t *rows, int n_rows, const int64_t *loci, int n_loci,
                             int32_t *width, int64_t *start, long long n_width, long long codes_bytes, int64_t *out_width,
                             int32_t *status, void *stream) {

@@ -55,6 +55,11 @@ def register_parser(subparsers):
     p.add_argument("--msa-dir", dest="msa_dir", action="store", type=str, default=None,
                    help="(this implementation) with --unaligned: keep the MSAs in this directory (existing files are not overwritten "
                         "without -F); default: a private temporary directory beside the output prefix, removed at the end")
+    p.add_argument("--adjust-direction", dest="adjust_direction", action="store_true", default=False,
+                   help="(this implementation) with --unaligned: records on the opposite strand are detected on the GPU and "
+                        "reverse-complemented before the alignment; the first non-empty record of a locus keeps its orientation, the "
+                        "title of a reversed record gets the prefix _R_ (as MAFFT's --adjustdirection does; the method is the "
+                        "package's own, star_align.py)")
     p.set_defaults(func=run, check=check_options)
     return p
 
@@ -65,6 +70,8 @@ def check_options(args, parser):
         parser.error("--unaligned reads FASTA only: it cannot be combined with -f " + args.alignment_format)
     if args.msa_dir is not None and not args.unaligned:
         parser.error("--msa-dir needs --unaligned")
+    if args.adjust_direction and not args.unaligned:
+        parser.error("--adjust-direction needs --unaligned")
 
 
 def get_all_input_files(input_path: str, suffix: str) -> List[Path]:
@@ -552,11 +559,13 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
     be = backend or get_backend("runtime")
     t_read = t_align = t_write = 0.0
     written = []
+    adjust = bool(getattr(options, "adjust_direction", False))
+    orientation = []
     for lo in range(0, len(mine), STAR_CHUNK):
         t0 = time.perf_counter()
         recs = [star_align.read_unaligned(f) for f in mine[lo:lo + STAR_CHUNK]]
         t1 = time.perf_counter()
-        msas = star_align.star_msas(be, recs, names=loci[lo:lo + STAR_CHUNK])
+        msas = star_align.star_msas(be, recs, names=loci[lo:lo + STAR_CHUNK], adjust_direction=adjust, orientation=orientation)
         t2 = time.perf_counter()
         for locus, m in zip(loci[lo:lo + STAR_CHUNK], msas):
             path = out_dir / f"{locus}.fa"
@@ -566,6 +575,9 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
         t_read, t_align, t_write = t_read + t1 - t0, t_align + t2 - t1, t_write + time.perf_counter() - t2
     logger.info(f"rank {rank}: {len(written)} centre-star MSAs: read {t_read:.2f}s, aligned {t_align:.2f}s, written {t_write:.2f}s "
                 f"into {out_dir}")
+    if adjust:
+        logger.info(f"rank {rank}: --adjust-direction: {sum(sum(rev) for rev, _ in orientation)} records reverse-complemented, "
+                    f"{sum(how.count('d') + how.count('t') for _, how in orientation)} settled by DP")
     align_unaligned_inputs.timings = dict(read_s=t_read, align_s=t_align, write_s=t_write)
     return written
 

@@ -2,9 +2,12 @@
 gaps removed, written as unaligned FASTA files into a temporary directory first.  Prints one JSON line: wall seconds of reading
 the files, the centre, pair and merge stages (star_align.star_msas; each ends at a download), writing the MSAs, and the PRG build
 (from_msa's pipeline over the MSAs written), plus the DP cells (sum of n x C over the pairs).  Kernel times: run it under
-`rocprofv3 --kernel-trace --stats -- python tools/star_measure.py N`."""
+`rocprofv3 --kernel-trace --stats -- python tools/star_measure.py N`.
+`--flip SHARE` (after N): `--adjust-direction` on, with that share of each locus's records but the first reverse-complemented in the
+files (seeded); the line then also gives orient_s, the records reversed, how many of them were flipped, and the number the DP settled."""
 import json
 import os
+import random
 import shutil
 import sys
 import tempfile
@@ -19,26 +22,34 @@ from make_prg_amd.subcommands import from_msa  # noqa: E402
 from make_prg_amd.subcommands.output_type import OutputType  # noqa: E402
 from make_prg_amd.utils.synthetic import config_shape, synth_rows  # noqa: E402
 
-n_loci = int(sys.argv[1]) if len(sys.argv) > 1 else 1000
+n_loci = int(sys.argv[1]) if len(sys.argv) > 1 and not sys.argv[1].startswith("--") else 1000
+COMPLEMENT = str.maketrans("ACGTRYKMSWN", "TGCAYRMKSWN")
+flip = float(sys.argv[sys.argv.index("--flip") + 1]) if "--flip" in sys.argv else None
 work = Path(tempfile.mkdtemp(prefix="star_measure_"))
 try:
     src, msa_dir = work / "unaligned", work / "msas"
     src.mkdir()
     msa_dir.mkdir()
     t0 = time.perf_counter()
+    rng, flipped = random.Random(1), []
     for seed in range(n_loci):
-        rows = synth_rows(seed, *config_shape("C", seed))
-        (src / f"gene{seed:05d}.fa").write_text("".join(f">s{i}\n{r.decode().replace('-', '')}\n" for i, r in enumerate(rows)))
+        seqs = [r.decode().replace("-", "") for r in synth_rows(seed, *config_shape("C", seed))]
+        if flip is not None:
+            flags = [i > 0 and rng.random() < flip for i in range(len(seqs))]
+            seqs = [s.translate(COMPLEMENT)[::-1] if f else s for s, f in zip(seqs, flags)]
+            flipped.append(flags)
+        (src / f"gene{seed:05d}.fa").write_text("".join(f">s{i}\n{s}\n" for i, s in enumerate(seqs)))
     t_gen = time.perf_counter() - t0
     files = sorted(src.iterdir())
     be = get_backend("runtime")
-    sa.star_msas(be, [sa.read_unaligned(f) for f in files[:4]])           # warm-up: first launches
+    sa.star_msas(be, [sa.read_unaligned(f) for f in files[:4]], adjust_direction=flip is not None)           # warm-up: first launches
     t0 = time.perf_counter()
     recs = [sa.read_unaligned(f) for f in files]
     t_read = time.perf_counter() - t0
     timings = {}
     t0 = time.perf_counter()
-    msas = sa.star_msas(be, recs, timings=timings)
+    orientation = []
+    msas = sa.star_msas(be, recs, timings=timings, adjust_direction=flip is not None, orientation=orientation)
     t_star = time.perf_counter() - t0
     t0 = time.perf_counter()
     written = []
@@ -48,6 +59,12 @@ try:
         written.append(p)
     t_write = time.perf_counter() - t0
     codes = [sa.locus_codes(f.name, r) for f, r in zip(files, recs)]
+    extra = {}
+    if flip is not None:
+        codes = [[sa.revcomp(c) if f else c for c, f in zip(cs, rev)] for cs, (rev, _) in zip(codes, orientation)]
+        extra = dict(flip=flip, reversed=sum(sum(rev) for rev, _ in orientation),
+                     reversed_as_flipped=sum(sum(a and b for a, b in zip(rev, fl)) for (rev, _), fl in zip(orientation, flipped)),
+                     flipped=sum(map(sum, flipped)), settled_by_dp=sum(how.count("d") + how.count("t") for _, how in orientation))
     cent = sa.centres(be, codes)
     cells = sum(len(c) * len(cs[int(k)]) for cs, k in zip(codes, cent) for a, c in enumerate(cs) if a != int(k))
     opts = Namespace(input=str(msa_dir), suffix="", output_prefix=str(work / "out" / "prg"), alignment_format="fasta",
@@ -58,6 +75,6 @@ try:
     print(json.dumps(dict(loci=n_loci, pairs=sum(len(r) - 1 for r in recs), residues=sum(len(s) for r in recs for _, s in r),
                           generate_s=round(t_gen, 2), read_s=round(t_read, 3), star_s=round(t_star, 3),
                           **{k: round(v, 3) for k, v in timings.items()}, write_s=round(t_write, 3), prg_build_s=round(t_prg, 3),
-                          dp_cells=cells)))
+                          dp_cells=cells, **extra)))
 finally:
     shutil.rmtree(work, ignore_errors=True)
