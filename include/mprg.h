@@ -554,6 +554,23 @@ int mprg_align_profiles(const uint8_t *cells, const int64_t *leaves, const int32
 int mprg_align_pairs(const int32_t *profile, const int64_t *leaves, int n_leaves, const uint8_t *seqs, const int64_t *pairs, int n_pairs,
                      int32_t *workspace, long long workspace_words, uint8_t *ops, long long ops_bytes, int32_t *out, void *stream);
 
+/* `from_msa --unaligned --band`: mprg_align_pairs over a band of diagonals (the spec, the certificate that makes the result the
+ * full DP's and its proof: make_prg_amd/update/profile_align.py, "Band").
+ * mprg_align_bounds: bounds: n_leaves x 2 int64 {SB = sum_j B_j with B_j = max(max_x P[j][x], Dc[j]), min_j (B_j - Dc[j])} from
+ *   the profiles mprg_align_profiles wrote: what the certificate needs.
+ * mprg_align_pairs_banded: pairs: n_pairs x MPRG_AL_BAND_PAIR_FIELDS int64, mprg_align_pairs' five fields, then dlo and dhi: only
+ *   the cells (i, j) with dlo <= j - i <= dhi are computed, every other cell counts as minus infinity in all three states.  The
+ *   band must hold (0, 0) and (n, C): dlo <= min(0, C - n) and dhi >= max(0, C - n), else MPRG_AL_BAD_INPUT.  With dlo' = max(dlo,
+ *   -n), dhi' = min(dhi, C), W = dhi' - dlo' + 1 a pair needs ceil(2 W / 64) * 64 + ceil(n / 64) * ceil((min(C, W + 63) + 63) / 8)
+ *   * 64 words of `workspace` (a row of the band between two strips and the band's traceback) and n + C bytes of `ops`.  `out`,
+ *   the ops and the other status codes are mprg_align_pairs'.  The score is the best over the paths inside the band: the full
+ *   DP's (and then the ops too) exactly when the certificate holds. */
+enum { MPRG_AL_BAND_PAIR_FIELDS = 7 };
+int mprg_align_bounds(const int32_t *profile, const int64_t *leaves, int n_leaves, int64_t *bounds, void *stream);
+int mprg_align_pairs_banded(const int32_t *profile, const int64_t *leaves, int n_leaves, const uint8_t *seqs, const int64_t *pairs,
+                            int n_pairs, int32_t *workspace, long long workspace_words, uint8_t *ops, long long ops_bytes, int32_t *out,
+                            void *stream);
+
 /* `from_msa --unaligned`: centre-star MSAs of unaligned loci (the spec: make_prg_amd/from_msa/star_align.py).
  * Not MAFFT: no reference function is replaced.  The pairs are mprg_align_pairs' (the centre as a 1-row leaf).
  * codes: the loci's sequences as cell codes (ACGT-RYKMSWN -> 0..11, no gaps), codes_bytes long.  seqs: n_seqs x 2 int64

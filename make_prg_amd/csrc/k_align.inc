@@ -158,3 +158,199 @@ __global__ void __launch_bounds__(AL_THREADS) k_align_pairs(const int32_t *profi
     o[0] = MPRG_AL_OK; o[1] = score; o[2] = (int32_t)k;
   }
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// K-A banded (`from_msa --unaligned --band`; the spec, the certificate and its proof: make_prg_amd/update/profile_align.py,
+// "Band"): the same DP over the cells of the diagonals dlo <= j - i <= dhi only.  Every cell outside the band is AL_NEG in all
+// three states and is never computed; the band holds (0, 0) and (n, C) (dlo <= min(0, C - n), dhi >= max(0, C - n): anything
+// else is MPRG_AL_BAD_INPUT) and is clamped to the matrix ([-n, C]) before anything is sized by it.
+//
+// k_align_bounds: one wavefront per leaf over the profile k_align_profiles wrote: SB = sum_j B_j, B_j = max(max_x P[j][x], Dc[j]),
+//   and min_j (B_j - Dc[j]), both int64: what the host's certificate needs.
+// k_align_pairs_banded: k_align_pairs' wavefront-per-pair, 64-row-strip, anti-diagonal sweep, a kernel of its own (k_align_pairs
+//   stays instruction for instruction what it is).  Strip s (rows i0 + 1 .. i0 + rows) sweeps columns cs + 1 .. min(C, i0 + rows +
+//   dhi), cs = max(0, i0 + dlo): at step t lane l is at 0-based column cs + t - l and computes only where its row's band holds that
+//   column; everywhere else it hands AL_NEG to the lane below (H[i][0] where column 0 is in the row's band), so no lane ever
+//   reads a stale value.  Along a row the first in-band cell starts from (H[i][0], AL_NEG) or (AL_NEG, AL_NEG).  A gap state whose
+//   two predecessors are outside the band is AL_NEG plus one open and one extension at most (>= AL_NEG - 1 344, int32 holds
+//   AL_NEG - 65 536); the H of every in-band cell is a real score (its diagonal predecessor is on the same diagonal), so the next
+//   cell's gap state is real again: no chain of penalties on AL_NEG.
+//   Row buffer: W = dhi - dlo + 1 (H, I) slots; the row above strip s (row i0) keeps column j at slot j - (i0 + dlo).  Lane 0 reads
+//   slot cs + t + 1 - (i0 + dlo) at step t (AL_NEG beyond min(C, i0 + dhi): the columns the strip above did not write), lane 63
+//   writes the next strip's slot 127 below it in the same step: a slot is written only after its last read.
+//   Traceback and ring are indexed by the STEP, not the column: ring slot (t - l) & 127, traceback dword (s * nst8 + t / 8) * 64 + l
+//   with nst8 = ceil((min(C, W + 63) + 63) / 8), so the stores stay 256-byte rows whatever column a strip starts at; lane 0 walks
+//   back through t = j - 1 - cs(strip of i) + l.
+// ---------------------------------------------------------------------------------------------------------------
+// a value every lane of the wavefront holds alike (a field of the pair's table row: the compiler cannot know), moved to scalar
+// registers, so that what is derived from it (loop bounds, bases) stays there too
+#if defined(__HIP_DEVICE_COMPILE__)
+MPRG_DEV long long al_uniform(long long v) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(unsigned long long)v);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)v >> 32));
+  return (long long)(((unsigned long long)hi << 32) | lo);
+}
+#else
+MPRG_DEV long long al_uniform(long long v) { return v; }
+#endif
+// int32 words of workspace a banded pair needs, dlo and dhi already clamped to [-n, C]
+MPRG_DEV long long al_band_ws_words(long long n, long long C, long long dlo, long long dhi) {
+  const long long W = dhi - dlo + 1, nc = W + 63 < C ? W + 63 : C;
+  return ((2 * W + 63) / 64) * 64 + ((n + 63) / 64) * ((nc + 63 + 7) / 8) * 64;
+}
+
+__global__ void __launch_bounds__(AL_THREADS) k_align_bounds(const int32_t *profile, const int64_t *leaves, int n_leaves, int64_t *bounds) {
+  const int lane = wave_lane();
+  const long long leaf = (long long)BLOCK_ID * AL_WAVES + wave_id();
+  if (leaf >= n_leaves) return;
+  const long long C = leaves[MPRG_AL_LEAF_FIELDS * leaf + 2];
+  const int32_t *P = profile + leaves[MPRG_AL_LEAF_FIELDS * leaf + 3];
+  long long sb = 0;
+  int lmin = 2147483647;
+  for (long long c = lane; c < C; c += 64) {
+    const int dc = P[5 * C + c];
+    int b = dc;
+#pragma unroll
+    for (int x = 0; x < 5; ++x) { const int v = P[x * C + c]; b = v > b ? v : b; }
+    sb += b;
+    lmin = b - dc < lmin ? b - dc : lmin;
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    sb += __shfl_xor(sb, d);
+    const int y = __shfl_xor(lmin, d);
+    lmin = y < lmin ? y : lmin;
+  }
+  if (lane == 0) { bounds[2 * leaf] = sb; bounds[2 * leaf + 1] = lmin; }
+}
+
+__global__ void __launch_bounds__(AL_THREADS) k_align_pairs_banded(const int32_t *profile, const int64_t *leaves, int n_leaves,
+                                                                   const uint8_t *seqs, const int64_t *pairs, int n_pairs, int32_t *ws,
+                                                                   long long ws_words, uint8_t *ops, long long ops_bytes, int32_t *out) {
+  SHARED(int32_t, ring_all, AL_WAVES * 6 * AL_RING);
+  const int lane = wave_lane();
+  const long long p = (long long)BLOCK_ID * AL_WAVES + wave_id();
+  if (p >= n_pairs) return;                                   // (a whole wavefront: nothing below waits for the others)
+  int32_t *ring = ring_all + wave_id() * 6 * AL_RING;
+  const int64_t *PT = pairs + MPRG_AL_BAND_PAIR_FIELDS * p;
+  const long long leaf = PT[0], soff = PT[1], n = PT[2], wsoff = PT[3], opoff = PT[4];
+  long long blo = PT[5], bhi = PT[6];
+  int32_t *o = out + 3 * p;
+  int status = MPRG_AL_OK;
+  long long C = 0, poff = 0;
+  if (leaf < 0 || leaf >= n_leaves) status = MPRG_AL_BAD_INPUT;
+  else {
+    C = leaves[MPRG_AL_LEAF_FIELDS * leaf + 2];
+    poff = leaves[MPRG_AL_LEAF_FIELDS * leaf + 3];
+    if (C < 1 || n < 0 || leaves[MPRG_AL_LEAF_FIELDS * leaf + 1] < 1) status = MPRG_AL_BAD_INPUT;
+    else if (n + C >= AL_MAX_CELLS_SUM) status = MPRG_AL_TOO_LONG;
+    else if (blo > 0 || blo > C - n || bhi < 0 || bhi < C - n) status = MPRG_AL_BAD_INPUT;      // the band must hold both corners
+    else {
+      blo = blo < -n ? -n : blo;
+      bhi = bhi > C ? C : bhi;
+      if (wsoff < 0 || (wsoff & 63) || wsoff + al_band_ws_words(n, C, blo, bhi) > ws_words || opoff < 0 || opoff + n + C > ops_bytes)
+        status = MPRG_AL_NO_SPACE;
+    }
+  }
+  if (status != MPRG_AL_OK) {
+    if (lane == 0) { o[0] = status; o[1] = 0; o[2] = 0; }
+    return;
+  }
+  const int32_t *P = profile + al_uniform(poff);
+  const int Ci = (int)al_uniform(C), ni = (int)al_uniform(n), dlo = (int)al_uniform(blo), dhi = (int)al_uniform(bhi);
+  const int W = dhi - dlo + 1;
+  const long long wsoff_u = al_uniform(wsoff), soff_u = al_uniform(soff);
+  int32_t *row = ws + wsoff_u;                               // row[2k] = H, row[2k + 1] = I of the row above the strip (row i0), column i0 + dlo + k
+  uint32_t *tb = (uint32_t *)(ws + wsoff_u + ((2 * (long long)W + 63) / 64) * 64);
+  const long long nst8 = ((W + 63 < Ci ? W + 63 : Ci) + 63 + 7) / 8;
+  // row 0, columns 0 .. dhi: H[0][J] = D[0][J] = open + the gap costs of columns < J
+  int carry = 0;
+  for (int c0 = 0; c0 < dhi; c0 += 64) {
+    const int c = c0 + lane;
+    const int incl = wave_scan_incl(c < dhi ? (P + 5LL * Ci)[(unsigned)c] : 0) + carry;
+    if (c < dhi) { row[2 * (c + 1 - dlo)] = AL_OPEN + incl; row[2 * (c + 1 - dlo) + 1] = AL_NEG; }
+    carry = __shfl(incl, 63);
+  }
+  if (lane == 0) { row[2 * (-dlo)] = 0; row[2 * (-dlo) + 1] = AL_NEG; }
+  WAVE_SYNC_GLOBAL();
+  int score = AL_NEG;
+  const int n_strips = (ni + 63) / 64;
+  for (int s = 0; s < n_strips; ++s) {
+    const int i0 = s * 64, r = i0 + lane, rows = ni - i0 < 64 ? ni - i0 : 64;
+    const bool valid = r < ni;
+    const unsigned code = valid ? (seqs + soff_u)[(unsigned)r] : 0u;
+    const int cls = code < 4 ? (int)code : 4;
+    const int cs = i0 + dlo > 0 ? i0 + dlo : 0;             // the strip's first column, 0-based
+    const int jtop = i0 + dhi < Ci ? i0 + dhi : Ci;         // the last column of row i0 inside the band
+    const int jend = i0 + rows + dhi < Ci ? i0 + rows + dhi : Ci;   // the strip's last column, 1-based
+    const int d0 = cs - r - dlo;                            // 0-based column c = cs + t - lane of this lane's row (r + 1) lies on diagonal c - r:
+                                                            // inside the band where 0 <= d0 + t - lane <= dhi - dlo (and 0 <= c < C)
+    const bool col0 = r + 1 + dlo <= 0;                     // column 0 of this lane's row lies inside the band
+    int h_left = col0 ? al_hb(r + 1) : AL_NEG, d_left = AL_NEG;     // H, D of this lane's row, the column to the left of its first one
+    int h_out = col0 && cs == lane ? al_hb(r + 1) : AL_NEG, i_out = AL_NEG;   // what the lane below reads next step: here of column cs - 1 - lane
+    int h_up_prev = AL_NEG;                                  // H of the row above, one column to the left: the diagonal
+    if (lane == 0) h_up_prev = cs == 0 ? al_hb(i0) : row[0];   // (cs > 0: column cs = i0 + dlo of row i0, its first inside the band)
+    uint32_t acc = 0;
+    uint32_t *tbs = tb + (long long)s * nst8 * 64;           // the strip's traceback: wave-uniform bases, 32-bit lane offsets
+    const int T = jend - cs + rows - 1;
+    for (int t = 0; t < T; ++t) {
+      if ((t & 63) == 0) {                                   // the ring takes columns cs + [t, t + 64): the block 128 before is done with
+        WAVE_SYNC();
+#pragma unroll
+        for (int k = 0; k < 6; ++k)
+          ring[k * AL_RING + ((t + lane) & (AL_RING - 1))] = cs + t + lane < Ci ? (P + (long long)k * Ci)[(unsigned)(cs + t + lane)] : 0;
+        WAVE_SYNC();
+      }
+      int h_up = __shfl_up(h_out, 1), i_up = __shfl_up(i_out, 1);
+      if (lane == 0) {
+        const int j = cs + t + 1, k = j - (i0 + dlo);         // (1 <= k; k <= W - 1 where j <= jtop)
+        h_up = j <= jtop ? row[(unsigned)(2 * k)] : AL_NEG;
+        i_up = j <= jtop ? row[(unsigned)(2 * k + 1)] : AL_NEG;
+      }
+      const int h_diag = h_up_prev;
+      h_up_prev = h_up;
+      const int c = cs + t - lane;
+      unsigned cell = 0;
+      if (valid && (unsigned)c < (unsigned)Ci && (unsigned)(d0 + t - lane) < (unsigned)W) {
+        const int slot = (t - lane) & (AL_RING - 1);
+        const int dc = ring[5 * AL_RING + slot];
+        const int diag = h_diag + ring[cls * AL_RING + slot];
+        const int d_ext = d_left + dc, d_open = h_left + AL_OPEN + dc;
+        const int i_ext = i_up + AL_INS, i_open = h_up + AL_OPEN + AL_INS;
+        const int dd = d_ext >= d_open ? d_ext : d_open, ii = i_ext >= i_open ? i_ext : i_open;
+        int h = diag;
+        unsigned src = 0;
+        if (dd > h) { h = dd; src = 1; }
+        if (ii > h) { h = ii; src = 2; }
+        cell = src | (d_ext >= d_open ? 4u : 0u) | (i_ext >= i_open ? 8u : 0u);
+        h_left = h; d_left = dd; h_out = h; i_out = ii;
+        if (r == ni - 1 && c == Ci - 1) score = h;
+        if (lane == 63 && s + 1 < n_strips) { const int k = c + 1 - (i0 + 64 + dlo); row[(unsigned)(2 * k)] = h; row[(unsigned)(2 * k + 1)] = ii; }
+      } else {
+        h_out = c == -1 && r + 1 + dlo <= 0 ? al_hb(r + 1) : AL_NEG;   // outside the band: minus infinity, never a stale or an accumulated value
+        i_out = AL_NEG;
+      }
+      acc |= cell << (4 * (t & 7));
+      if ((t & 7) == 7 || t == T - 1) { tbs[(unsigned)((t >> 3) * 64 + lane)] = acc; acc = 0; }
+    }
+    WAVE_SYNC_GLOBAL();                                      // the row buffer and the traceback, written by every lane, read by lane 0
+  }
+  score = ni > 0 ? __shfl(score, (ni - 1) & 63) : row[2 * (Ci - dlo)];
+  if (lane == 0) {
+    uint8_t *op = ops + opoff;
+    long long k = 0;
+    int i = ni, j = Ci, st = 0;                              // st: 0 H, 1 D, 2 I
+    while (i > 0 && j > 0) {
+      const int rr = i - 1, l = rr & 63, sc = (rr & ~63) + dlo > 0 ? (rr & ~63) + dlo : 0, t = j - 1 - sc + l;
+      const unsigned cell = (tb[((long long)(rr >> 6) * nst8 + (t >> 3)) * 64 + l] >> (4 * (t & 7))) & 15u;
+      if (st == 0) {
+        if ((cell & 3u) == 0) { op[k++] = 'M'; --i; --j; }
+        else st = (int)(cell & 3u);
+      } else if (st == 1) { op[k++] = 'D'; --j; st = (cell & 4u) ? 1 : 0; }
+      else { op[k++] = 'I'; --i; st = (cell & 8u) ? 2 : 0; }
+    }
+    for (; j > 0; --j) op[k++] = 'D';                        // row 0: only deletions lead back to (0, 0); column 0: only insertions
+    for (; i > 0; --i) op[k++] = 'I';
+    o[0] = MPRG_AL_OK; o[1] = score; o[2] = (int32_t)k;
+  }
+}

@@ -554,6 +554,21 @@ int mprg_align_pairs(const int32_t *profile, const int64_t *leaves, int n_leaves
   return check_launch("k_align_pairs");
 }
 
+int mprg_align_bounds(const int32_t *profile, const int64_t *leaves, int n_leaves, int64_t *bounds, void *stream) {
+  if (n_leaves <= 0) return 0;
+  LAUNCH(k_align_bounds, (n_leaves + AL_WAVES - 1) / AL_WAVES, AL_THREADS, stream, profile, leaves, n_leaves, bounds);      // a wavefront per leaf
+  return check_launch("k_align_bounds");
+}
+
+int mprg_align_pairs_banded(const int32_t *profile, const int64_t *leaves, int n_leaves, const uint8_t *seqs, const int64_t *pairs,
+                            int n_pairs, int32_t *workspace, long long workspace_words, uint8_t *ops, long long ops_bytes, int32_t *out,
+                            void *stream) {
+  if (n_pairs <= 0) return 0;
+  LAUNCH(k_align_pairs_banded, (n_pairs + AL_WAVES - 1) / AL_WAVES, AL_THREADS, stream, profile, leaves, n_leaves, seqs, pairs, n_pairs,
+         workspace, workspace_words, ops, ops_bytes, out);      // a wavefront per pair
+  return check_launch("k_align_pairs_banded");
+}
+
 int mprg_star_centres(const uint8_t *codes, long long codes_bytes, const int64_t *seqs, long long n_seqs, const int64_t *loci,
                       int n_loci, int32_t *centre, void *stream) {
   if (n_loci <= 0) return 0;

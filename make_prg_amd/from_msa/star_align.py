@@ -1,6 +1,9 @@
 """Centre-star MSAs of `from_msa --unaligned`: every locus's unaligned sequences aligned on the GPU against one of them, the
 centre, and the insertions merged (kernels: csrc/k_star.inc for the centre and the merge, csrc/k_align.inc for the pairs; C ABI:
 mprg_star_centres / mprg_star_merge_columns / mprg_star_merge_rows / mprg_align_profiles / mprg_align_pairs in include/mprg.h).
+With `--band` the pairs are computed over a certified band of diagonals in two passes (the spec and the proof that the ops are the
+full DP's: make_prg_amd/update/profile_align.py, "Band"; C ABI: mprg_align_bounds / mprg_align_pairs_banded): the same MSAs, byte
+for byte, from a fraction of the cells and of the traceback memory.
 With `--adjust-direction`, records on the opposite strand are found and reverse-complemented first (Orientation below; kernels in
 csrc/k_star.inc, C ABI: mprg_star_centres_canonical / mprg_star_strand / mprg_star_revcomp).
 
@@ -110,12 +113,15 @@ def _chunks(codes: List[List[np.ndarray]], limit: int):
 
 def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optional[Sequence[str]] = None,
               budget_bytes: int = pa.DEFAULT_BUDGET_BYTES, chunk_bytes: int = CHUNK_BYTES, timings: Optional[dict] = None,
-              adjust_direction: bool = False, orientation: Optional[list] = None) -> List[MSA]:
+              adjust_direction: bool = False, orientation: Optional[list] = None, band=False) -> List[MSA]:
     """loci: per locus its records as (title, sequence).  Returns the loci's centre-star MSAs (ids: the titles' first words,
     descriptions: the titles).  names: the loci's names for error messages (default: their indices).  timings: a dict that
     receives the wall seconds of the stages (orient, centre, pairs, merge: each ends at a download, so includes its kernels).
     adjust_direction: the spec's Orientation step first; the title of a reversed record gets the prefix _R_.  orientation: a list
-    that then receives per locus (reversed: a bool per record, how: a string of one of "-kdt" per record)."""
+    that then receives per locus (reversed: a bool per record, how: a string of one of "-kdt" per record).
+    band: the pairs over a certified band (True: profile_align.BAND_W0, or pass 1's half-width); the same MSAs.  timings then also
+    receives profile_align.pairs_on_device's counters (band_pairs, band_second_passes, band_full_pairs, band_cells, band_full_cells).
+    The score-only DP of adjust_direction keeps the full form."""
     names = [str(i) for i in range(len(loci))] if names is None else list(names)
     for name, recs in zip(names, loci):
         if not len(recs):
@@ -124,7 +130,7 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
     codes = [locus_codes(n, recs) for n, recs in zip(names, loci)]
     out: List[MSA] = []
     for lo, hi in _chunks(codes, chunk_bytes):
-        out.extend(_star_chunk(backend, loci[lo:hi], codes[lo:hi], names[lo:hi], budget_bytes, timings, adjust_direction, orientation))
+        out.extend(_star_chunk(backend, loci[lo:hi], codes[lo:hi], names[lo:hi], budget_bytes, timings, adjust_direction, orientation, band))
     return out
 
 
@@ -289,7 +295,7 @@ def _orient(be, codes, names, host, lens, seq_off, first, counts, budget_bytes):
     return oriented, seq_off, d_codes, codes_bytes, result
 
 
-def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direction=False, orientation=None) -> List[MSA]:
+def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direction=False, orientation=None, band=False) -> List[MSA]:
     import time
     t0 = time.perf_counter()
     host, lens, seq_off, first, counts = _pack(be, codes)
@@ -315,7 +321,8 @@ def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direc
     # the pairs: the centre as a 1-row leaf, every other non-empty sequence against it
     leaves = [codes[l][centre[l]].reshape(1, -1) for l in range(n_loci)]
     others = [[a for a in range(len(cs)) if a != centre[l] and len(cs[a])] for l, cs in enumerate(codes)]
-    dp = pa.pairs_on_device(be, leaves, [[codes[l][a] for a in others[l]] for l in range(n_loci)], budget_bytes)
+    dp = pa.pairs_on_device(be, leaves, [[codes[l][a] for a in others[l]] for l in range(n_loci)], budget_bytes,
+                            None if band is False or band is None else band, timings)
     t2 = time.perf_counter()
     # rows in input order: {locus, sequence offset, n, ops offset, ops count (-1: residue i in column i), output offset}
     rows = np.zeros((int(counts.sum()), ROW_FIELDS), np.int64)

@@ -60,6 +60,11 @@ def register_parser(subparsers):
                         "reverse-complemented before the alignment; the first non-empty record of a locus keeps its orientation, the "
                         "title of a reversed record gets the prefix _R_ (as MAFFT's --adjustdirection does; the method is the "
                         "package's own, star_align.py)")
+    p.add_argument("--band", dest="band", action="store_true", default=False,
+                   help="(this implementation) with --unaligned: the pair alignments are computed over a band of diagonals that a "
+                        "certificate proves wide enough (two passes; make_prg_amd/update/profile_align.py): the same MSAs and PRGs, "
+                        "byte for byte, from a fraction of the DP cells and of the traceback memory, and pairs too long for the "
+                        "full matrix are accepted.  Off by default")
     p.set_defaults(func=run, check=check_options)
     return p
 
@@ -72,6 +77,8 @@ def check_options(args, parser):
         parser.error("--msa-dir needs --unaligned")
     if args.adjust_direction and not args.unaligned:
         parser.error("--adjust-direction needs --unaligned")
+    if getattr(args, "band", False) and not args.unaligned:
+        parser.error("--band needs --unaligned")
 
 
 def get_all_input_files(input_path: str, suffix: str) -> List[Path]:
@@ -561,11 +568,14 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
     written = []
     adjust = bool(getattr(options, "adjust_direction", False))
     orientation = []
+    band = bool(getattr(options, "band", False))
+    counters: Dict[str, float] = {}
     for lo in range(0, len(mine), STAR_CHUNK):
         t0 = time.perf_counter()
         recs = [star_align.read_unaligned(f) for f in mine[lo:lo + STAR_CHUNK]]
         t1 = time.perf_counter()
-        msas = star_align.star_msas(be, recs, names=loci[lo:lo + STAR_CHUNK], adjust_direction=adjust, orientation=orientation)
+        msas = star_align.star_msas(be, recs, names=loci[lo:lo + STAR_CHUNK], adjust_direction=adjust, orientation=orientation,
+                                    **(dict(band=True, timings=counters) if band else {}))
         t2 = time.perf_counter()
         for locus, m in zip(loci[lo:lo + STAR_CHUNK], msas):
             path = out_dir / f"{locus}.fa"
@@ -578,6 +588,10 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
     if adjust:
         logger.info(f"rank {rank}: --adjust-direction: {sum(sum(rev) for rev, _ in orientation)} records reverse-complemented, "
                     f"{sum(how.count('d') + how.count('t') for _, how in orientation)} settled by DP")
+    if band:
+        logger.info(f"rank {rank}: --band: {counters.get('band_pairs', 0)} pairs, {counters.get('band_second_passes', 0)} second passes, "
+                    f"{counters.get('band_full_pairs', 0)} sent to the full DP, {counters.get('band_cells', 0)} of "
+                    f"{counters.get('band_full_cells', 0)} DP cells computed")
     align_unaligned_inputs.timings = dict(read_s=t_read, align_s=t_align, write_s=t_write)
     return written
 

@@ -22,6 +22,43 @@ Spec (the kernels and tests/align_ref.py follow it bit for bit)
   Output.   The original rows, then Denovo_path_{i}, with the ids and descriptions that load_alignment_file gives for the
             MAFFT wrapper's FASTA; letters upper case.
 
+Band (opt-in: pairs_on_device(band=...), `from_msa --unaligned --band`; tests/band_ref.py states it in plain Python;
+kernel: k_align_pairs_banded, C ABI: mprg_align_bounds / mprg_align_pairs_banded).  The same alignments from a fraction of the cells.
+  Band.     The diagonal of cell (i, j) is d = j - i; a path starts on d = 0 and ends on Delta = C - n.  The band [dlo, dhi] keeps
+            the cells with dlo <= d <= dhi in all three states; every cell outside it has the value minus infinity and is never
+            computed.  Half-widths (w-, w+) give dlo = min(0, Delta) - w-, dhi = max(0, Delta) + w+ (clamped to [-n, C], the
+            matrix).  Recurrence, scores, int32 arithmetic and tie order are the DP's above.  A gap state of an in-band cell whose
+            two predecessors lie outside is minus infinity plus one penalty; the H of an in-band cell is always a real score (its
+            diagonal predecessor lies on the same diagonal), so such a gap state is never chosen and nothing accumulates on it.
+  Bounds.   Per leaf: B_j = max(max_x P[j][x], Dc[j]) (the most column j can contribute), SB = sum_j B_j, loss_j = B_j - Dc[j] >= 0
+            (what deleting column j costs against B_j), m = min_j loss_j.  (Computed on the device, mprg_align_bounds: two int64
+            per leaf come back instead of a profile.)
+  Certificate.  An alignment scores  sum_matched P + sum_deleted Dc - 640 #inserted - 704 #gap runs.  A deletion moves a path one
+            diagonal up, an insertion one down.  A path that touches a diagonal d* > max(0, Delta) has at least d* deleted columns
+            (0 -> d*), at least d* - Delta > 0 inserted residues (d* -> Delta) and so at least one run of each; its columns
+            contribute at most SB - sum_deleted loss_j <= SB - m d*.  So its score is at most
+                UB+(d*) = SB - m d* - 640 (d* - Delta) - 1408,
+            and a path that touches d* < min(0, Delta) has at least -d* insertions and Delta - d* > 0 deletions:
+                UB-(d*) = SB - m (Delta - d*) - 640 (-d*) - 1408.
+            (m d* is the issue's weaker form of "the d* smallest loss_j": no sort; for a 1-row ACGT leaf both are 1 920 d*.)
+            Both fall strictly as d* moves away from the corridor.  Let S be the banded DP's score; a side is CLOSED when
+            S > UB+(dhi + 1) (resp. S > UB-(dlo - 1)) or the band reaches the matrix's edge there (dhi = C, dlo = -n).  With both
+            sides closed every optimal path of the full DP lies inside the band: S is the score of a real path, so optimum >= S,
+            and a path that leaves the band touches dhi + 1 or dlo - 1 and scores <= UB < S.  Then every state on an optimal path
+            has its full-DP value in the banded DP (induction along the path: all its predecessors' optimal sub-paths lie inside
+            too), every other candidate has a value no larger than its full-DP value, so every forward tie decision and every
+            traceback step on the path is the full DP's: ops and score are identical.
+  Two passes, never a loop.  Pass 1 runs the pair with w- = w+ = w0 (BAND_W0; a tuning constant, not part of the result) and
+            gives S0 <= optimum.  w*+ = the smallest w >= 0 with UB+(max(0, Delta) + w + 1) < S0, capped where the band reaches
+            the edge: max(0, floor((SB - 1408 + 640 Delta - S0) / (m + 640)) - max(0, Delta)); w*- likewise:
+            max(0, floor((SB - m Delta - 1408 - S0) / (m + 640)) + min(0, Delta)).  If w*- <= w0 and w*+ <= w0 pass 1 is certified.
+            Otherwise the pair runs once more with (w*-, w*+): the pass-1 path scores S0 > UB beyond those widths, so it lies
+            inside the new band, S >= S0, and both sides are closed by construction.  A pair whose band (of pass 1, or of pass 2)
+            needs no less workspace than the full matrix, in total or in the traceback alone (W + 63 >= C with W = dhi - dlo + 1:
+            the strips then sweep every column anyway), goes to the full DP instead (short pairs, unrelated sequences, sparse
+            multi-row profiles whose m is small).  `update --aligner builtin` and the score-only DP of --adjust-direction keep
+            the full form.
+
 Host side: leaves and sequences packed once, the profiles built for the whole batch in one launch, the pairs sorted by cell
 count (longest first) and launched in chunks that fit a workspace budget (a pair whose traceback alone exceeds the budget is an
 error), every pair's ops into one device buffer (pairs_on_device; from_msa --unaligned merges them there, csrc/k_star.inc);
@@ -38,6 +75,8 @@ MAX_LEN = 1_000_000                      # MPRG_AL_MAX_LEN
 STATUS = {1: "n + C >= 10^6 (int32 scores could overflow)", 2: "workspace or ops range outside the buffers",
           3: "bad leaf (index, rows or columns)"}
 DEFAULT_BUDGET_BYTES = 1 << 30           # traceback + row buffers of one launch
+BAND_PAIR_FIELDS = 7                     # MPRG_AL_BAND_PAIR_FIELDS
+BAND_W0 = 64                             # pass 1's half-width (what was tried)
 _GAP = ord("-")
 
 
@@ -50,6 +89,45 @@ def workspace_words(n: int, C: int) -> int:
     return -(-2 * (C + 1) // 64) * 64 + -(-n // 64) * ((C + 70) // 8) * 64
 
 
+def band_limits(n, C, w_minus, w_plus):
+    """(dlo, dhi) of the band of half-widths (w-, w+), clamped to the matrix; scalars or arrays."""
+    delta = C - n
+    return np.maximum(np.minimum(0, delta) - w_minus, -n), np.minimum(np.maximum(0, delta) + w_plus, C)
+
+
+def band_workspace_words(n, C, dlo, dhi):
+    """int32 words of workspace a banded pair needs (include/mprg.h, mprg_align_pairs_banded); dlo, dhi clamped to [-n, C]."""
+    W = dhi - dlo + 1
+    return (2 * W + 63) // 64 * 64 + (n + 63) // 64 * ((np.minimum(C, W + 63) + 70) // 8) * 64
+
+
+def band_helps(n, C, dlo, dhi):
+    """The spec's rule for the full DP, negated: the band needs less workspace than the full matrix, in total and in its traceback."""
+    return (band_workspace_words(n, C, dlo, dhi) < workspace_words_v(n, C)) & (dhi - dlo + 1 + 63 < C)
+
+
+def workspace_words_v(n, C):
+    """workspace_words over arrays."""
+    return (2 * (C + 1) + 63) // 64 * 64 + (n + 63) // 64 * ((C + 70) // 8) * 64
+
+
+def band_cells(n, C, dlo, dhi):
+    """The DP cells (i >= 1, j >= 1) inside the band: n C less the two corner triangles it cuts off; dlo, dhi clamped."""
+    def tri(x):
+        x = np.maximum(x, 0)
+        return x * (x + 1) // 2
+    below, above = n + dlo - 1, C - dhi - 1          # cells with j - i < dlo: sum_j max(0, n + dlo - j); with j - i > dhi likewise
+    return n * C - (tri(below) - tri(below - C)) - (tri(above) - tri(above - n))
+
+
+def certified_widths(n, C, SB, m, S0):
+    """(w*-, w*+) of the spec's two-pass rule from pass 1's score S0: the smallest half-widths whose band is closed on each side."""
+    delta, q = C - n, m + 640
+    w_plus = np.maximum(0, (SB - 1408 + 640 * delta - S0) // q - np.maximum(0, delta))
+    w_minus = np.maximum(0, (SB - m * delta - 1408 - S0) // q + np.minimum(0, delta))
+    return np.minimum(w_minus, n + np.minimum(0, delta)), np.minimum(w_plus, C - np.maximum(0, delta))
+
+
 def _codes(seq: str, what: str) -> np.ndarray:
     raw = np.frombuffer(seq.upper().encode(), np.uint8)
     raw = raw[raw != _GAP]
@@ -60,11 +138,11 @@ def _codes(seq: str, what: str) -> np.ndarray:
 
 
 def align_batch(backend, leaves: Sequence[np.ndarray], seqs: Sequence[Sequence[np.ndarray]],
-                budget_bytes: int = DEFAULT_BUDGET_BYTES) -> List[List[Tuple[bytes, int]]]:
+                budget_bytes: int = DEFAULT_BUDGET_BYTES, band=None, counters: Optional[dict] = None) -> List[List[Tuple[bytes, int]]]:
     """leaves: R x C uint8 cell-code matrices; seqs[k]: the gap-free code arrays to align against leaf k.
-    Returns, per leaf, per sequence, (ops as bytes over b"MID" in forward order, score)."""
+    Returns, per leaf, per sequence, (ops as bytes over b"MID" in forward order, score).  band, counters: as pairs_on_device."""
     out: List[List[Optional[Tuple[bytes, int]]]] = [[None] * len(s) for s in seqs]
-    dp = pairs_on_device(backend, leaves, seqs, budget_bytes)
+    dp = pairs_on_device(backend, leaves, seqs, budget_bytes, band, counters)
     if dp is None:
         return out
     ops = backend.download(dp.d_ops, np.uint8, dp.ops_bytes)
@@ -84,9 +162,13 @@ class DevicePairs:
 
 
 def pairs_on_device(backend, leaves: Sequence[np.ndarray], seqs: Sequence[Sequence[np.ndarray]],
-                    budget_bytes: int = DEFAULT_BUDGET_BYTES) -> Optional[DevicePairs]:
+                    budget_bytes: int = DEFAULT_BUDGET_BYTES, band=None, counters: Optional[dict] = None) -> Optional[DevicePairs]:
     """The pairs of align_batch on the device: the profiles in one launch, the pairs longest first in launches that fit the
-    workspace budget, every pair's ops into one buffer that stays on the device.  None when there is no pair."""
+    workspace budget, every pair's ops into one buffer that stays on the device.  None when there is no pair.
+    band: None: the full DP.  True or a half-width w0: the spec's Band, two passes: the same ops, counts and scores from the
+    cells of a certified band (launches sized by the banded need; a pair the band does not help goes to the full DP).
+    counters: a dict that then receives (added up) band_pairs, band_second_passes, band_full_pairs (pairs sent to the full DP),
+    band_cells (DP cells computed, all passes and the full form) and band_full_cells (n C summed: what the full DP computes)."""
     be = backend
     n_leaves = len(leaves)
     if not n_leaves:
@@ -116,10 +198,14 @@ def pairs_on_device(backend, leaves: Sequence[np.ndarray], seqs: Sequence[Sequen
     seq_off = np.concatenate([[0], np.cumsum(pn)[:-1]])
     need = np.array([workspace_words(int(n), int(c)) for n, c in zip(pn, pc)], np.int64)
     budget_words = max(64, int(budget_bytes) // 4)
-    if need.max() > budget_words:
-        k = int(need.argmax())
-        raise ProfileAlignError(f"a pair of {pn[k]} residues against {pc[k]} columns needs {4 * need[k]} bytes of traceback, "
-                                f"more than the workspace budget of {budget_bytes}")
+
+    def check_budget(sel, words):
+        if len(sel) and words[sel].max() > budget_words:
+            k = sel[int(words[sel].argmax())]
+            raise ProfileAlignError(f"a pair of {pn[k]} residues against {pc[k]} columns needs {4 * words[k]} bytes of traceback, "
+                                    f"more than the workspace budget of {budget_bytes}")
+    if band is None:
+        check_budget(np.arange(len(pl)), need)
     order = np.argsort(-((pn + 1) * pc), kind="stable")        # longest first
     ops_len = pn + pc
     ops_off = np.concatenate([[0], np.cumsum(ops_len)[:-1]])
@@ -134,28 +220,68 @@ def pairs_on_device(backend, leaves: Sequence[np.ndarray], seqs: Sequence[Sequen
             work=float((R * C).sum()))
     d_seqs = be.upload(seq_all)
     d_ops = be.empty(ops_bytes)
-    pos = 0
-    while pos < len(order):
-        end, used = pos, 0
-        while end < len(order) and used + need[order[end]] <= budget_words:
-            used += int(need[order[end]])
-            end += 1
-        idx = order[pos:end]
-        ws_off = np.concatenate([[0], np.cumsum(need[idx])[:-1]])
-        ptab = np.stack([pl[idx], seq_off[idx], pn[idx], ws_off, ops_off[idx]], 1).astype(np.int64)
-        d_pairs = be.upload(ptab)
-        d_ws = be.empty(4 * used)
-        d_out = be.empty(12 * len(idx))
-        be.call("mprg_align_pairs", be.ptr(d_prof), be.ptr(d_leaves), n_leaves, be.ptr(d_seqs), be.ptr(d_pairs), len(idx),
-                be.ptr(d_ws), used, be.ptr(d_ops), ops_bytes, be.ptr(d_out), be.stream,
-                work=float(((pn[idx] + 63) // 64 * 64 * pc[idx]).sum()))
-        res = be.download(d_out, np.int32, 3 * len(idx)).reshape(-1, 3)
-        bad = np.nonzero(res[:, 0])[0]
-        if len(bad):
-            raise ProfileAlignError(f"mprg_align_pairs: {STATUS.get(int(res[bad[0], 0]), int(res[bad[0], 0]))}")
-        score[idx] = res[:, 1]
-        count[idx] = res[:, 2]
-        pos = end
+
+    def launches(call, order, words, dlo=None, dhi=None):
+        """The pairs `order` (longest first) through `call` in launches that fit the workspace budget."""
+        pos = 0
+        while pos < len(order):
+            end, used = pos, 0
+            while end < len(order) and used + words[order[end]] <= budget_words:
+                used += int(words[order[end]])
+                end += 1
+            idx = order[pos:end]
+            ws_off = np.concatenate([[0], np.cumsum(words[idx])[:-1]])
+            cols = [pl[idx], seq_off[idx], pn[idx], ws_off, ops_off[idx]] + ([] if dlo is None else [dlo[idx], dhi[idx]])
+            d_pairs = be.upload(np.stack(cols, 1).astype(np.int64))
+            d_ws = be.empty(4 * used)
+            d_out = be.empty(12 * len(idx))
+            work = (pn[idx] + 63) // 64 * 64 * (pc[idx] if dlo is None else np.minimum(pc[idx], dhi[idx] - dlo[idx] + 64))
+            be.call(call, be.ptr(d_prof), be.ptr(d_leaves), n_leaves, be.ptr(d_seqs), be.ptr(d_pairs), len(idx),
+                    be.ptr(d_ws), used, be.ptr(d_ops), ops_bytes, be.ptr(d_out), be.stream, work=float(work.sum()))
+            res = be.download(d_out, np.int32, 3 * len(idx)).reshape(-1, 3)
+            bad = np.nonzero(res[:, 0])[0]
+            if len(bad):
+                raise ProfileAlignError(f"{call}: {STATUS.get(int(res[bad[0], 0]), int(res[bad[0], 0]))}")
+            score[idx] = res[:, 1]
+            count[idx] = res[:, 2]
+            pos = end
+    if band is None:
+        launches("mprg_align_pairs", order, need)
+        return DevicePairs(d_ops, ops_bytes, pl, pi, ops_off, count, score)
+    # the spec's Band: pass 1 with w0, the certificate over the downloaded scores, pass 2 with the certified widths; the full DP
+    # for the pairs whose band needs no less workspace than the full matrix
+    w0 = BAND_W0 if band is True else int(band)
+    if w0 < 0:
+        raise ProfileAlignError("band: a negative half-width")
+    d_bounds = be.empty(16 * n_leaves)
+    be.call("mprg_align_bounds", be.ptr(d_prof), be.ptr(d_leaves), n_leaves, be.ptr(d_bounds), be.stream, work=float((6 * C).sum()))
+    bounds = be.download(d_bounds, np.int64, 2 * n_leaves).reshape(-1, 2)
+    SB, m = bounds[pl, 0], bounds[pl, 1]
+    dlo, dhi = band_limits(pn, pc, w0, w0)
+    words = band_workspace_words(pn, pc, dlo, dhi)
+    full = ~band_helps(pn, pc, dlo, dhi)
+    first = np.nonzero(~full)[0]
+    check_budget(first, words)
+    cells = band_cells(pn, pc, dlo, dhi)
+    launches("mprg_align_pairs_banded", first[np.argsort(-cells[first], kind="stable")], words, dlo, dhi)
+    w_minus, w_plus = certified_widths(pn, pc, SB, m, score)
+    again = ~full & ((w_minus > w0) | (w_plus > w0))
+    dlo2, dhi2 = band_limits(pn, pc, w_minus, w_plus)
+    dlo, dhi = np.where(again, dlo2, dlo), np.where(again, dhi2, dhi)
+    words = band_workspace_words(pn, pc, dlo, dhi)
+    full |= again & ~band_helps(pn, pc, dlo, dhi)
+    second = np.nonzero(again & ~full)[0]
+    check_budget(second, words)
+    cells2 = band_cells(pn, pc, dlo, dhi)
+    launches("mprg_align_pairs_banded", second[np.argsort(-cells2[second], kind="stable")], words, dlo, dhi)
+    rest = np.nonzero(full)[0]
+    check_budget(rest, need)
+    launches("mprg_align_pairs", rest[np.argsort(-((pn[rest] + 1) * pc[rest]), kind="stable")], need)
+    if counters is not None:
+        for key, v in (("band_pairs", len(pl)), ("band_second_passes", len(second)), ("band_full_pairs", len(rest)),
+                       ("band_cells", cells[first].sum() + cells2[second].sum() + (pn[rest] * pc[rest]).sum()),
+                       ("band_full_cells", (pn * pc).sum())):
+            counters[key] = counters.get(key, 0) + int(v)
     return DevicePairs(d_ops, ops_bytes, pl, pi, ops_off, count, score)
 
 

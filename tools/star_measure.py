@@ -4,7 +4,11 @@ the files, the centre, pair and merge stages (star_align.star_msas; each ends at
 (from_msa's pipeline over the MSAs written), plus the DP cells (sum of n x C over the pairs).  Kernel times: run it under
 `rocprofv3 --kernel-trace --stats -- python tools/star_measure.py N`.
 `--flip SHARE` (after N): `--adjust-direction` on, with that share of each locus's records but the first reverse-complemented in the
-files (seeded); the line then also gives orient_s, the records reversed, how many of them were flipped, and the number the DP settled."""
+files (seeded); the line then also gives orient_s, the records reversed, how many of them were flipped, and the number the DP settled.
+`--band [W0]`: the pairs over a certified band (`from_msa --unaligned --band`; W0: pass 1's half-width, default
+profile_align.BAND_W0); the line then also gives the band's counters (pairs, second passes, pairs sent to the full DP, DP cells
+computed and of the full matrices).  msa_md5: a digest of the MSAs' text, to compare runs."""
+import hashlib
 import json
 import os
 import random
@@ -25,6 +29,10 @@ from make_prg_amd.utils.synthetic import config_shape, synth_rows  # noqa: E402
 n_loci = int(sys.argv[1]) if len(sys.argv) > 1 and not sys.argv[1].startswith("--") else 1000
 COMPLEMENT = str.maketrans("ACGTRYKMSWN", "TGCAYRMKSWN")
 flip = float(sys.argv[sys.argv.index("--flip") + 1]) if "--flip" in sys.argv else None
+band = False
+if "--band" in sys.argv:
+    nxt = sys.argv[sys.argv.index("--band") + 1:][:1]
+    band = int(nxt[0]) if nxt and nxt[0].isdigit() else True
 work = Path(tempfile.mkdtemp(prefix="star_measure_"))
 try:
     src, msa_dir = work / "unaligned", work / "msas"
@@ -42,20 +50,22 @@ try:
     t_gen = time.perf_counter() - t0
     files = sorted(src.iterdir())
     be = get_backend("runtime")
-    sa.star_msas(be, [sa.read_unaligned(f) for f in files[:4]], adjust_direction=flip is not None)           # warm-up: first launches
+    sa.star_msas(be, [sa.read_unaligned(f) for f in files[:4]], adjust_direction=flip is not None, band=band)           # warm-up: first launches
     t0 = time.perf_counter()
     recs = [sa.read_unaligned(f) for f in files]
     t_read = time.perf_counter() - t0
     timings = {}
     t0 = time.perf_counter()
     orientation = []
-    msas = sa.star_msas(be, recs, timings=timings, adjust_direction=flip is not None, orientation=orientation)
+    msas = sa.star_msas(be, recs, timings=timings, adjust_direction=flip is not None, orientation=orientation, band=band)
     t_star = time.perf_counter() - t0
     t0 = time.perf_counter()
-    written = []
+    written, digest = [], hashlib.md5()
     for f, m in zip(files, msas):
         p = msa_dir / f.name
-        p.write_text(sa.msa_fasta(m))
+        text = sa.msa_fasta(m)
+        p.write_text(text)
+        digest.update(text.encode())
         written.append(p)
     t_write = time.perf_counter() - t0
     codes = [sa.locus_codes(f.name, r) for f, r in zip(files, recs)]
@@ -75,6 +85,6 @@ try:
     print(json.dumps(dict(loci=n_loci, pairs=sum(len(r) - 1 for r in recs), residues=sum(len(s) for r in recs for _, s in r),
                           generate_s=round(t_gen, 2), read_s=round(t_read, 3), star_s=round(t_star, 3),
                           **{k: round(v, 3) for k, v in timings.items()}, write_s=round(t_write, 3), prg_build_s=round(t_prg, 3),
-                          dp_cells=cells, **extra)))
+                          dp_cells=cells, msa_md5=digest.hexdigest(), **extra)))
 finally:
     shutil.rmtree(work, ignore_errors=True)
