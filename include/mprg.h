@@ -621,6 +621,38 @@ int mprg_star_merge_rows(const uint8_t *codes, long long codes_bytes, const uint
                          int n_rows, const int64_t *loci, int n_loci, const int32_t *width, const int64_t *start, long long n_width,
                          const int64_t *out_width, uint8_t *out, long long out_bytes, int32_t *status, void *stream);
 
+/* `from_msa --unaligned --refine`: leave-one-out refinement of the star MSAs (the spec: star_align.py, "Refinement").
+ * The realignment is mprg_align_pairs' / mprg_align_pairs_banded's over the profiles written here, the merge
+ * mprg_star_merge_columns' / mprg_star_merge_rows' with C = W.
+ * text: MSAs as mprg_star_merge_rows wrote them (ASCII ACGT-RYKMSWN), text_bytes long.  loci: n_loci x MPRG_RF_LOCUS_FIELDS int64
+ *   {offset of the locus's R x W bytes in text (row-major), R >= 1, W >= 1, offset of its W columns in the column tables (counts,
+ *   keep, dest: n_cols columns)}.  work: n_work x 2 int32 {locus (counts) or row (profiles), 256-column tile}.
+ * mprg_refine_counts: counts (int32, 5 n_cols) receives at 5 * column offset + x * W + c the number of A C G T '-' (x = 0..4) in
+ *   column c, keep (uint8, n_cols) whether the column has a cell that is not '-'.  sums: n_loci x 2 int64, ZEROED by the caller,
+ *   receive {the objective S of the MSA as it stands (every run of '-' of every row counted), its kept columns}, added up over the
+ *   locus's tiles by 64-bit integer atomics: all of a locus's tiles must be in `work`, once.  status: n_work int32.
+ * rows: n_rows x MPRG_RF_ROW_FIELDS int64 {locus, row within the locus, profiles: offset of the row's profile in `profile` (int32
+ *   elements; 6 W per row); compact: offset of the LOCUS's output in `out`}.
+ * mprg_refine_profiles: the profile of the locus WITHOUT that row (R >= 2), exactly what mprg_align_profiles writes for that
+ *   (R - 1) x W matrix: 6 planes of W int32.  A leaf table entry {any, R - 1, W, profile offset} hands it to the pair calls.
+ *   status: n_work int32.
+ * mprg_refine_compact: dest (int32, n_cols) receives per column the kept columns before it, new_width[l] their number W' (-1: the
+ *   locus's ranges lie outside the buffers); row r's kept cells go to out + output offset + r * W' + dest: every byte of the
+ *   locus's R x W' output written once.  text and out must not overlap.  status: n_rows int32.
+ * status: MPRG_RF_OK, MPRG_RF_BAD_LOCUS (a locus index or its ranges outside the buffers), MPRG_RF_BAD_ROW (a row index, a row
+ *   within the locus or a tile out of range; R < 2), MPRG_RF_NO_SPACE (the profile or the output outside its buffer).  With any
+ *   status but MPRG_RF_OK the work item writes nothing else. */
+enum { MPRG_RF_LOCUS_FIELDS = 4, MPRG_RF_ROW_FIELDS = 3,
+       MPRG_RF_OK = 0, MPRG_RF_BAD_LOCUS = 1, MPRG_RF_BAD_ROW = 2, MPRG_RF_NO_SPACE = 3 };
+int mprg_refine_counts(const uint8_t *text, long long text_bytes, const int64_t *loci, int n_loci, const int32_t *work, int n_work,
+                       int32_t *counts, uint8_t *keep, long long n_cols, int64_t *sums, int32_t *status, void *stream);
+int mprg_refine_profiles(const uint8_t *text, long long text_bytes, const int64_t *loci, int n_loci, const int32_t *counts, long long n_cols,
+                         const int64_t *rows, int n_rows, const int32_t *work, int n_work, int32_t *profile, long long profile_words,
+                         int32_t *status, void *stream);
+int mprg_refine_compact(const uint8_t *text, long long text_bytes, const int64_t *loci, int n_loci, const uint8_t *keep, long long n_cols,
+                        int32_t *dest, int64_t *new_width, const int64_t *rows, int n_rows, uint8_t *out, long long out_bytes,
+                        int32_t *status, void *stream);
+
 /* (f)-1 output encoders, HOST functions (host pointers), one pass over a PRG string as PrgBuilder emits it.
  * reference make_prg/utils/prg_encoder.py:44-91 and make_prg/utils/gfa.py:16-109.
  * mprg_prg_encode_host: out[n] receives the uint32 stream (A C G T -> 1 2 3 4, markers as integers, the closing

@@ -98,6 +98,12 @@ SIGNATURES = {
                                         ctypes.c_longlong, c_void_p, c_void_p, c_void_p]),
     "mprg_star_merge_rows": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                      ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
+    "mprg_refine_counts": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, ctypes.c_longlong,
+                                   c_void_p, c_void_p, c_void_p]),
+    "mprg_refine_profiles": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p,
+                                     c_int, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
+    "mprg_refine_compact": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p,
+                                    c_int, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
     "mprg_random_sample_host": (None, [c_uint32, c_int, c_void_p]),
     "mprg_prg_encode_host": (ctypes.c_longlong, [c_void_p, ctypes.c_longlong, c_void_p]),
     "mprg_fasta_scan_host": (ctypes.c_longlong, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),

@@ -19,6 +19,7 @@
 #include "k_forest.inc"
 #include "k_align.inc"
 #include "k_star.inc"
+#include "k_refine.inc"
 #include "host_encoders.inc"
 #include "host_batch.inc"
 
@@ -617,6 +618,34 @@ int mprg_star_merge_rows(const uint8_t *codes, long long codes_bytes, const uint
   LAUNCH(k_star_merge_rows, (n_rows + ST_WAVES - 1) / ST_WAVES, ST_THREADS, stream, codes, codes_bytes, ops, ops_bytes, rows, n_rows,
          loci, n_loci, width, start, n_width, out_width, out, out_bytes, status);
   return check_launch("k_star_merge_rows");
+}
+
+int mprg_refine_counts(const uint8_t *text, long long text_bytes, const int64_t *loci, int n_loci, const int32_t *work, int n_work,
+                       int32_t *counts, uint8_t *keep, long long n_cols, int64_t *sums, int32_t *status, void *stream) {
+  if (n_work <= 0) return 0;
+  LAUNCH(k_refine_counts, n_work, RF_THREADS, stream, text, text_bytes, loci, n_loci, work, counts, keep, n_cols, sums, status);
+  return check_launch("k_refine_counts");
+}
+
+int mprg_refine_profiles(const uint8_t *text, long long text_bytes, const int64_t *loci, int n_loci, const int32_t *counts, long long n_cols,
+                         const int64_t *rows, int n_rows, const int32_t *work, int n_work, int32_t *profile, long long profile_words,
+                         int32_t *status, void *stream) {
+  if (n_work <= 0) return 0;
+  LAUNCH(k_refine_profiles, n_work, RF_THREADS, stream, text, text_bytes, loci, n_loci, counts, n_cols, rows, n_rows, work, profile,
+         profile_words, status);
+  return check_launch("k_refine_profiles");
+}
+
+int mprg_refine_compact(const uint8_t *text, long long text_bytes, const int64_t *loci, int n_loci, const uint8_t *keep, long long n_cols,
+                        int32_t *dest, int64_t *new_width, const int64_t *rows, int n_rows, uint8_t *out, long long out_bytes,
+                        int32_t *status, void *stream) {
+  if (n_loci <= 0) return 0;
+  LAUNCH(k_refine_scan, (n_loci + RF_WAVES - 1) / RF_WAVES, RF_THREADS, stream, loci, n_loci, text_bytes, keep, n_cols, dest, new_width);      // a wavefront per locus
+  const int rc = check_launch("k_refine_scan");
+  if (rc || n_rows <= 0) return rc;
+  LAUNCH(k_refine_compact_rows, (n_rows + RF_WAVES - 1) / RF_WAVES, RF_THREADS, stream, text, text_bytes, loci, n_loci, keep, n_cols, dest,
+         new_width, rows, n_rows, out, out_bytes, status);       // a wavefront per row
+  return check_launch("k_refine_compact_rows");
 }
 
 // ---- the recursion forest on the device (k_forest.inc); F: host array of MPRG_F_FIELDS int64 ------------------------------

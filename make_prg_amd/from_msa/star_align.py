@@ -53,6 +53,33 @@ Orientation (only with adjust_direction; integers only; tests/strand_ref.py foll
   in which nothing is reversed gives the flag-off bytes; reverse-complementing any records but the first non-empty one changes no
   row; every row with its gaps removed is its input sequence or, exactly where the title starts with _R_, its rc.
 
+Refinement (only with refine = N > 0; integers only; tests/refine_ref.py follows it bit for bit; kernels: csrc/k_refine.inc, C ABI:
+mprg_refine_counts / mprg_refine_profiles / mprg_refine_compact).  The star MSA is centre-star, not progressive: a row has only
+ever seen the centre.  Up to N rounds of leave-one-out realignment follow it, each kept only if it raises the objective S.
+  Round.    On a locus's current MSA A (R rows in input order, W columns).  A locus with fewer than 3 non-empty rows is never
+            refined (with two rows the star alignment is already the optimal pair alignment).  s_r: row r with its gaps removed.
+            Every non-empty row r is aligned against the profile of A WITH ROW r DELETED, all non-empty rows at once (every row
+            sees the same A).  That profile is exactly what mprg_align_profiles gives for the (R - 1) x W matrix: the formulas of
+            profile_align.py, its truncating division, by R - 1; the columns that become all-gap without row r are part of it
+            (P = -640, Dc = 0).  DP, scores and tie order: profile_align.py.  An empty row stays all gaps, no launch.  The rows' ops
+            over the W columns are merged by the Merge rule (boundary j gets the widest insertion of any row, inserted residues
+            left-justified); every all-gap column is then removed: A', same row order and titles.
+  Objective.  With c_x the count of x in {A, C, G, T} in a column and g its count of '-':
+                S(A) = 2 sum_columns [20 sum_x c_x (c_x - 1) / 2 - 9 sum_{x<y} c_x c_y - 10 g (R - g)] - 11 (R - 1) runs(A)
+            runs(A): the maximal runs of '-' over all rows, end runs included; int64.  R Y K M S W N score 0 against a residue and
+            -10 against '-', as in sigma.  11 = 704 / 64 is the DP's gap-open cost in row-pair units; 2 SP against (R - 1) 11
+            matches the sum of the rows' DP scores, in which every row pair is seen from both sides.  S is taken on the MSA after
+            its all-gap columns are removed (removing one can join two of a row's runs).
+  Acceptance.  A' replaces A only if S(A') > S(A); otherwise the locus keeps A and takes no further round.  A locus stops after
+            N accepted rounds.  So a locus whose first round is refused is the star MSA byte for byte.
+  Limit.    A round aligns a row of n residues against W columns, not against the centre's C.  A locus whose longest row has
+            n + W >= 10^6 (the DP's int32 limit), or needs more full-DP traceback over n x W than the workspace budget (with or
+            without band: on sparse profiles the band falls back to the full DP), takes no (further) round and keeps the MSA it
+            has; it is reported with the rounds accepted so far.  The run never fails for a locus the star pass aligned.
+  With adjust_direction it runs on the oriented sequences, titles unchanged; with band the realignment goes through the banded
+  two-pass form (the certificate holds for any profile; sparse columns make m small and the bands wide, pairs the band does not
+  help go to the full DP): the same bytes either way.
+
 Host side: loci in chunks (CHUNK_BYTES of estimated ops and output per chunk); per chunk the centres in one launch, the pairs
 through profile_align.pairs_on_device (longest first, workspace-budget launches, ops left on the device), the widths and column
 starts in one call, the output size downloaded (one int64 per locus), the rows in one more launch, the MSAs downloaded.
@@ -61,6 +88,17 @@ launches (the centres stay on the device between them), the decisions in NumPy, 
 sequences in both orientations (none when there are none), one mprg_star_revcomp launch that writes the reversed records into a
 tail of the code buffer, to which the sequence table then points: the centre and merge kernels read oriented sequences from that
 buffer.  The pair stage uploads its sequences from host arrays, so it gets the host-side rc of the reversed records only.
+With refine, per chunk behind the rows launch and on the MSA text it left on the device: one counts launch over the chunk (S of the
+star MSAs, the column counts); then the loci with 3 or more non-empty rows in groups whose leave-one-out profiles (24 W bytes per
+non-empty row, sized from the star widths; a round may widen them a little) fit budget_bytes (a locus that alone exceeds it is a
+group of its own).  What a group holds on the device at once: its profiles (about budget_bytes), the pair stage's workspace
+(budget_bytes more) and ops, its column tables, and one MSA text buffer per round that still has a locus whose last accepted round
+it is (a buffer is dropped as soon as no locus points to it; at most N + 1 texts of the group).  So the refinement's memory is
+bounded by two budgets and the group's texts, not by the chunk.  Per group and round: the profiles in one launch into the buffer the DP kernels read, the pairs through
+profile_align.pairs_on_device(prepared=...) (residues read from the code buffer already on the device, ops left there), the merge
+calls with C = W, one counts launch (S, kept columns), and only where a column emptied the compaction and a second counts launch.
+Per round the host downloads S and the widths per locus and the status words, nothing larger; only the loci whose round was
+accepted go into the next one.  The text of a locus whose MSA changed is downloaded from the buffer of its last accepted round.
 """
 from typing import List, Optional, Sequence, Tuple
 
@@ -75,6 +113,9 @@ CENTRE_BAD = -2                           # MPRG_ST_CENTRE_BAD
 REVERSED_PREFIX = "_R_"                   # of the title of a record that --adjust-direction reverse-complemented
 ROW_STATUS = {1: "row fields or ops inconsistent with the buffers", 2: "output row outside the buffer"}
 CHUNK_BYTES = 1 << 29                     # estimated ops + output bytes of the loci of one chunk
+RF_LOCUS_FIELDS, RF_ROW_FIELDS = 4, 3     # MPRG_RF_LOCUS_FIELDS, MPRG_RF_ROW_FIELDS
+RF_STATUS = {1: "a locus's ranges outside the buffers", 2: "a row or tile out of range", 3: "the profile or the output outside its buffer"}
+REFINE_DEFAULT, REFINE_MAX = 2, 16        # rounds of `--refine` alone, and the most it takes
 _GAP = ord("-")
 _ASCII = np.frombuffer(b"ACGT-RYKMSWN", np.uint8)
 
@@ -113,7 +154,8 @@ def _chunks(codes: List[List[np.ndarray]], limit: int):
 
 def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optional[Sequence[str]] = None,
               budget_bytes: int = pa.DEFAULT_BUDGET_BYTES, chunk_bytes: int = CHUNK_BYTES, timings: Optional[dict] = None,
-              adjust_direction: bool = False, orientation: Optional[list] = None, band=False) -> List[MSA]:
+              adjust_direction: bool = False, orientation: Optional[list] = None, band=False, refine: int = 0,
+              refinement: Optional[list] = None) -> List[MSA]:
     """loci: per locus its records as (title, sequence).  Returns the loci's centre-star MSAs (ids: the titles' first words,
     descriptions: the titles).  names: the loci's names for error messages (default: their indices).  timings: a dict that
     receives the wall seconds of the stages (orient, centre, pairs, merge: each ends at a download, so includes its kernels).
@@ -121,7 +163,12 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
     that then receives per locus (reversed: a bool per record, how: a string of one of "-kdt" per record).
     band: the pairs over a certified band (True: profile_align.BAND_W0, or pass 1's half-width); the same MSAs.  timings then also
     receives profile_align.pairs_on_device's counters (band_pairs, band_second_passes, band_full_pairs, band_cells, band_full_cells).
-    The score-only DP of adjust_direction keeps the full form."""
+    The score-only DP of adjust_direction keeps the full form.
+    refine: N, the spec's Refinement: up to N accepted rounds per locus (0: none, nothing launches differently).  refinement: a list
+    that then receives per locus (rounds accepted, S of the star MSA, S of the result).  timings also receives refine_s; the band
+    counters keep adding up across the rounds."""
+    if not (isinstance(refine, (int, np.integer)) and not isinstance(refine, bool) and 0 <= refine <= REFINE_MAX):
+        raise ValueError(f"refine: a number of rounds from 0 to {REFINE_MAX}, not {refine!r}")
     names = [str(i) for i in range(len(loci))] if names is None else list(names)
     for name, recs in zip(names, loci):
         if not len(recs):
@@ -130,7 +177,8 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
     codes = [locus_codes(n, recs) for n, recs in zip(names, loci)]
     out: List[MSA] = []
     for lo, hi in _chunks(codes, chunk_bytes):
-        out.extend(_star_chunk(backend, loci[lo:hi], codes[lo:hi], names[lo:hi], budget_bytes, timings, adjust_direction, orientation, band))
+        out.extend(_star_chunk(backend, loci[lo:hi], codes[lo:hi], names[lo:hi], budget_bytes, timings, adjust_direction, orientation, band,
+                               int(refine), refinement))
     return out
 
 
@@ -295,7 +343,8 @@ def _orient(be, codes, names, host, lens, seq_off, first, counts, budget_bytes):
     return oriented, seq_off, d_codes, codes_bytes, result
 
 
-def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direction=False, orientation=None, band=False) -> List[MSA]:
+def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direction=False, orientation=None, band=False, refine=0,
+                refinement=None) -> List[MSA]:
     import time
     t0 = time.perf_counter()
     host, lens, seq_off, first, counts = _pack(be, codes)
@@ -354,15 +403,174 @@ def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direc
             n_loci, be.ptr(d_width), be.ptr(d_start), n_width, be.ptr(d_w), be.ptr(d_out), max(out_bytes, 1), be.ptr(d_status),
             be.stream, work=float(out_bytes + ops_bytes))
     _check(be.download(d_status, np.int32, len(rows)), "mprg_star_merge_rows")
+    t3 = time.perf_counter()
+    moved = {}
+    if refine:
+        res = _refine(be, codes, lens, seq_off, first, counts, d_codes, codes_bytes, d_out, max(out_bytes, 1), base, W, refine,
+                      budget_bytes, None if band is False or band is None else band, timings)
+        moved = {l: r[3] for l, r in enumerate(res) if r[3] is not None}
+        if refinement is not None:
+            refinement.extend(r[:3] for r in res)
+        if timings is not None:
+            timings["refine_s"] = timings.get("refine_s", 0.0) + time.perf_counter() - t3
+        t3 = time.perf_counter() - t3
+    else:
+        t3 = 0.0
     text = be.download(d_out, np.uint8, out_bytes)
+    fetched, upto = {}, {}
+    for l, (buf, _, off, w) in moved.items():                   # (a buffer is read up to the last byte a locus needs of it)
+        upto[id(buf)] = max(upto.get(id(buf), 0), off + int(counts[l]) * w)
     msas = []
     for l in range(n_loci):
-        data = text[base[l]:base[l] + counts[l] * W[l]].reshape(int(counts[l]), int(W[l]))
+        if l in moved:                                          # its last accepted round's buffer, downloaded once for all its loci
+            buf, _, off, w = moved[l]
+            if id(buf) not in fetched:
+                fetched[id(buf)] = be.download(buf, np.uint8, upto[id(buf)])
+            data = fetched[id(buf)][off:off + counts[l] * w].reshape(int(counts[l]), int(w))
+        else:
+            data = text[base[l]:base[l] + counts[l] * W[l]].reshape(int(counts[l]), int(W[l]))
         msas.append(MSA(_data=data, _ids=[(t.split(None, 1) or [""])[0] for t in titles[l]], _descs=titles[l]))
     if timings is not None:
-        for k, v in (("centre_s", t1 - t0), ("pairs_s", t2 - t1), ("merge_s", time.perf_counter() - t2)):
+        for k, v in (("centre_s", t1 - t0), ("pairs_s", t2 - t1), ("merge_s", time.perf_counter() - t2 - t3)):
             timings[k] = timings.get(k, 0.0) + v
     return msas
+
+
+def _rf_check(status: np.ndarray, what: str):
+    bad = np.nonzero(status)[0]
+    if len(bad):
+        raise StarAlignError(f"{what}: work item {bad[0]}: {RF_STATUS.get(int(status[bad[0]]), int(status[bad[0]]))}")
+
+
+def _ranges(start: np.ndarray, n: np.ndarray) -> np.ndarray:
+    """start[0], start[0] + 1, ... (n[0] of them), start[1], ...: the concatenated ranges, without a Python loop."""
+    n = np.asarray(n, np.int64)
+    return np.repeat(np.asarray(start, np.int64) - (np.cumsum(n) - n), n) + np.arange(int(n.sum()), dtype=np.int64)
+
+
+def _tile_work(widths: np.ndarray) -> np.ndarray:
+    """{item, 256-column tile} for items of these widths."""
+    tiles = -(-widths // 256)
+    return np.stack([np.repeat(np.arange(len(widths)), tiles), _ranges(np.zeros(len(widths), np.int64), tiles)], 1).astype(np.int32)
+
+
+def refine_counts(be, d_text, text_bytes: int, toff: np.ndarray, R: np.ndarray, W: np.ndarray):
+    """mprg_refine_counts over MSAs on the device (per locus its offset in d_text, rows and columns): (the locus table with
+    the column offsets filled in, the counts buffer, the keep flags, the columns, S per locus, the kept columns per locus)."""
+    n = len(W)
+    coff = np.concatenate([[0], np.cumsum(W)[:-1]]).astype(np.int64)
+    n_cols = int(W.sum())
+    rtab = np.stack([toff, R, W, coff], 1).astype(np.int64)
+    work = _tile_work(W)
+    d_counts, d_keep, d_sums, d_status = be.empty(20 * n_cols), be.empty(n_cols), be.zeros(16 * n), be.empty(4 * len(work))
+    d_rtab, d_work = be.upload(rtab), be.upload(work)
+    be.call("mprg_refine_counts", be.ptr(d_text), text_bytes, be.ptr(d_rtab), n, be.ptr(d_work), len(work),
+            be.ptr(d_counts), be.ptr(d_keep), n_cols, be.ptr(d_sums), be.ptr(d_status), be.stream, work=float((R * W).sum()))
+    _rf_check(be.download(d_status, np.int32, len(work)), "mprg_refine_counts")
+    sums = be.download(d_sums, np.int64, 2 * n).reshape(-1, 2)
+    return rtab, d_counts, d_keep, n_cols, sums[:, 0].copy(), sums[:, 1].copy()
+
+
+def refine_profiles(be, d_text, text_bytes: int, rtab: np.ndarray, d_counts, n_cols: int, row_locus: np.ndarray, row_in_locus: np.ndarray):
+    """mprg_refine_profiles: the leave-one-out profiles of the given rows (locus: an index into rtab) into one buffer:
+    (the buffer, each row's offset in it in int32 elements, its size in int32 elements)."""
+    Wr = rtab[row_locus, 2]
+    poff = np.concatenate([[0], np.cumsum(6 * Wr)[:-1]]).astype(np.int64)
+    words = int((6 * Wr).sum())
+    work = _tile_work(Wr)
+    d_prof, d_status = be.empty(4 * words), be.empty(4 * len(work))
+    rows = np.stack([row_locus, row_in_locus, poff], 1).astype(np.int64)
+    d_rtab, d_rows, d_work = be.upload(rtab), be.upload(rows), be.upload(work)
+    be.call("mprg_refine_profiles", be.ptr(d_text), text_bytes, be.ptr(d_rtab), len(rtab), be.ptr(d_counts), n_cols,
+            be.ptr(d_rows), len(rows), be.ptr(d_work), len(work), be.ptr(d_prof), words, be.ptr(d_status), be.stream,
+            work=float(24 * words))
+    _rf_check(be.download(d_status, np.int32, len(work)), "mprg_refine_profiles")
+    return d_prof, poff, words
+
+
+def refine_compact(be, d_text, text_bytes: int, rtab: np.ndarray, d_keep, n_cols: int, out_off: np.ndarray, out_bytes: int):
+    """mprg_refine_compact: every locus of rtab without its dropped columns, locus k's rows at out_off[k] of a new buffer of
+    out_bytes (row stride: its kept columns).  Returns the buffer."""
+    R = rtab[:, 1]
+    rows = np.stack([np.repeat(np.arange(len(rtab)), R), _ranges(np.zeros(len(R), np.int64), R), np.repeat(out_off, R)], 1).astype(np.int64)
+    d_dest, d_nw, d_out, d_status = be.empty(4 * n_cols), be.empty(8 * len(rtab)), be.empty(out_bytes), be.empty(4 * len(rows))
+    d_rtab, d_rows = be.upload(rtab), be.upload(rows)
+    be.call("mprg_refine_compact", be.ptr(d_text), text_bytes, be.ptr(d_rtab), len(rtab), be.ptr(d_keep), n_cols, be.ptr(d_dest),
+            be.ptr(d_nw), be.ptr(d_rows), len(rows), be.ptr(d_out), out_bytes, be.ptr(d_status), be.stream,
+            work=float(2 * (R * rtab[:, 2]).sum()))
+    _rf_check(be.download(d_status, np.int32, len(rows)), "mprg_refine_compact")
+    return d_out
+
+
+def _refine(be, codes, lens, seq_off, first, counts, d_codes, codes_bytes, d_text, text_bytes, base, W, rounds, budget_bytes, band, counters):
+    """The spec's Refinement over one chunk, on the MSA text mprg_star_merge_rows left on the device.  Per locus: (rounds accepted,
+    S of the star MSA, S of the result, None or where its new text is: (device buffer, its bytes, offset, width))."""
+    n_loci = len(counts)
+    rtab, d_counts, _, n_cols, S0, _ = refine_counts(be, d_text, text_bytes, base, counts, W)
+    out = [[0, int(S0[l]), int(S0[l]), None] for l in range(n_loci)]
+    n_filled = np.add.reduceat((lens > 0).astype(np.int64), first)           # (every locus has a record)
+    longest = np.maximum.reduceat(lens, first)
+    todo = np.nonzero(n_filled >= 3)[0]
+    need = 24 * W[todo] * n_filled[todo]                        # the profiles of a locus's round
+    budget_words = max(64, int(budget_bytes) // 4)
+    pos = 0
+    while pos < len(todo):                                      # groups whose profiles fit the budget
+        end = pos + max(1, int(np.searchsorted(np.cumsum(need[pos:]), budget_bytes, side="right")))
+        act = todo[pos:end]
+        pos = end
+        # the active loci's current MSAs: rows of `tab` {offset in buf, R, W, offset in the column tables of cnt}, S
+        buf, buf_bytes, tab, cnt, cols, S = d_text, text_bytes, rtab[act], d_counts, n_cols, S0[act]
+        for _ in range(rounds):
+            # a locus whose longest row against its W columns the full DP cannot take (the int32 score limit, or more traceback
+            # than the workspace budget: the band falls back to the full DP on sparse profiles) keeps the MSA it has
+            fits = (longest[act] + tab[:, 2] < pa.MAX_LEN) & (pa.workspace_words_v(longest[act], tab[:, 2]) <= budget_words)
+            act, tab, S = act[fits], tab[fits], S[fits]
+            if not len(act):
+                break
+            n_act, R, Wc = len(act), tab[:, 1], tab[:, 2]
+            all_rows = _ranges(first[act], R)                   # the loci's rows in the chunk's sequence table
+            of_locus = np.repeat(np.arange(n_act), R)
+            q = np.nonzero(lens[all_rows] > 0)[0]               # the non-empty ones: a leave-one-out profile and a pair each
+            row_locus, grow = of_locus[q], all_rows[q]
+            row_in = grow - first[act][row_locus]
+            d_prof, poff, _ = refine_profiles(be, buf, buf_bytes, tab, cnt, cols, row_locus, row_in)
+            prepared = pa.PreparedProfiles(d_prof, np.stack([R[row_locus] - 1, Wc[row_locus]], 1), poff, d_codes, seq_off[grow], lens[grow])
+            dp = pa.pairs_on_device(be, None, None, budget_bytes, band, counters, prepared)
+            # the merge over the W columns: every non-empty row has ops, an empty one stays all gaps (count -1, n = 0)
+            lfirst = np.concatenate([[0], np.cumsum(R)[:-1]]).astype(np.int64)
+            rows = np.zeros((int(R.sum()), ROW_FIELDS), np.int64)
+            rows[:, 0] = of_locus
+            rows[:, 1], rows[:, 2], rows[:, 4] = seq_off[all_rows], lens[all_rows], -1
+            rows[q, 3], rows[q, 4] = dp.ops_off, dp.count
+            woff = np.concatenate([[0], np.cumsum(Wc + 1)[:-1]]).astype(np.int64)
+            n_width = int((Wc + 1).sum())
+            d_loci, d_rows = be.upload(np.stack([lfirst, R, Wc, woff], 1).astype(np.int64)), be.upload(rows)
+            d_width, d_start = be.zeros(4 * n_width), be.empty(8 * n_width)
+            d_w, d_status = be.empty(8 * n_act), be.empty(4 * len(rows))
+            be.call("mprg_star_merge_columns", be.ptr(dp.d_ops), dp.ops_bytes, be.ptr(d_rows), len(rows), be.ptr(d_loci), n_act,
+                    be.ptr(d_width), be.ptr(d_start), n_width, codes_bytes, be.ptr(d_w), be.ptr(d_status), be.stream, work=float(dp.ops_bytes))
+            W2 = be.download(d_w, np.int64, n_act)
+            _check(be.download(d_status, np.int32, len(rows)), "mprg_star_merge_columns")
+            if (W2 < Wc).any():
+                raise StarAlignError("mprg_star_merge_columns: a locus's boundaries lie outside the buffers")
+            off2 = np.concatenate([[0], np.cumsum(R * W2)[:-1]]).astype(np.int64)
+            rows[:, 5] = np.repeat(off2, R) + (np.arange(len(rows)) - np.repeat(lfirst, R)) * np.repeat(W2, R)
+            new_bytes = max(int((R * W2).sum()), 1)
+            d_rows, d_new = be.upload(rows), be.empty(new_bytes)
+            be.call("mprg_star_merge_rows", be.ptr(d_codes), codes_bytes, be.ptr(dp.d_ops), dp.ops_bytes, be.ptr(d_rows), len(rows),
+                    be.ptr(d_loci), n_act, be.ptr(d_width), be.ptr(d_start), n_width, be.ptr(d_w), be.ptr(d_new), new_bytes,
+                    be.ptr(d_status), be.stream, work=float(new_bytes + dp.ops_bytes))
+            _check(be.download(d_status, np.int32, len(rows)), "mprg_star_merge_rows")
+            tab2, cnt2, keep2, cols2, S2, kept = refine_counts(be, d_new, new_bytes, off2, R, W2)
+            if (kept < W2).any():                               # a column emptied: drop it, count again (runs may have joined)
+                d_new = refine_compact(be, d_new, new_bytes, tab2, keep2, cols2, off2, new_bytes)
+                tab2, cnt2, keep2, cols2, S2, kept = refine_counts(be, d_new, new_bytes, off2, R, kept)
+            ok = S2 > S
+            for k in np.nonzero(ok)[0]:
+                o = out[act[k]]
+                o[0], o[2], o[3] = o[0] + 1, int(S2[k]), (d_new, new_bytes, int(off2[k]), int(tab2[k, 2]))
+            act, buf, buf_bytes, tab, cnt, cols, S = act[ok], d_new, new_bytes, tab2[ok], cnt2, cols2, S2[ok]
+    return [tuple(o) for o in out]
 
 
 def _check(status: np.ndarray, what: str):

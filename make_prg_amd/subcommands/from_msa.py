@@ -65,6 +65,13 @@ def register_parser(subparsers):
                         "certificate proves wide enough (two passes; make_prg_amd/update/profile_align.py): the same MSAs and PRGs, "
                         "byte for byte, from a fraction of the DP cells and of the traceback memory, and pairs too long for the "
                         "full matrix are accepted.  Off by default")
+    p.add_argument("--refine", dest="refine", action="store", type=int, nargs="?", const=2, default=None, metavar="N",
+                   help="(this implementation) with --unaligned: every locus's centre-star MSA gets up to N rounds (1-16; --refine "
+                        "alone: 2) of leave-one-out refinement on the GPU before it is written: every row is realigned against the "
+                        "profile of all the others, and a round is kept only if it raises the locus's sum-of-pairs objective "
+                        "(star_align.py, Refinement), so a locus the rounds do not improve keeps its star MSA byte for byte; a locus too long for a "
+                        "round's DP over its MSA's columns (star_align.py, Limit) is left as it is.  "
+                        "Off by default")
     p.set_defaults(func=run, check=check_options)
     return p
 
@@ -79,6 +86,11 @@ def check_options(args, parser):
         parser.error("--adjust-direction needs --unaligned")
     if getattr(args, "band", False) and not args.unaligned:
         parser.error("--band needs --unaligned")
+    if getattr(args, "refine", None) is not None:
+        if not args.unaligned:
+            parser.error("--refine needs --unaligned")
+        if not 1 <= args.refine <= 16:
+            parser.error(f"--refine takes 1 to 16 rounds, not {args.refine}")
 
 
 def get_all_input_files(input_path: str, suffix: str) -> List[Path]:
@@ -570,12 +582,15 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
     orientation = []
     band = bool(getattr(options, "band", False))
     counters: Dict[str, float] = {}
+    refine = int(getattr(options, "refine", None) or 0)
+    refinement = []
     for lo in range(0, len(mine), STAR_CHUNK):
         t0 = time.perf_counter()
         recs = [star_align.read_unaligned(f) for f in mine[lo:lo + STAR_CHUNK]]
         t1 = time.perf_counter()
         msas = star_align.star_msas(be, recs, names=loci[lo:lo + STAR_CHUNK], adjust_direction=adjust, orientation=orientation,
-                                    **(dict(band=True, timings=counters) if band else {}))
+                                    **(dict(band=True, timings=counters) if band else {}),
+                                    **(dict(refine=refine, refinement=refinement) if refine else {}))
         t2 = time.perf_counter()
         for locus, m in zip(loci[lo:lo + STAR_CHUNK], msas):
             path = out_dir / f"{locus}.fa"
@@ -592,6 +607,9 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
         logger.info(f"rank {rank}: --band: {counters.get('band_pairs', 0)} pairs, {counters.get('band_second_passes', 0)} second passes, "
                     f"{counters.get('band_full_pairs', 0)} sent to the full DP, {counters.get('band_cells', 0)} of "
                     f"{counters.get('band_full_cells', 0)} DP cells computed")
+    if refine:
+        logger.info(f"rank {rank}: --refine {refine}: {sum(1 for a, _, _ in refinement if a)} loci refined, "
+                    f"{sum(a for a, _, _ in refinement)} rounds accepted, {sum(1 for a, _, _ in refinement if not a)} loci left as the star MSA")
     align_unaligned_inputs.timings = dict(read_s=t_read, align_s=t_align, write_s=t_write)
     return written
 

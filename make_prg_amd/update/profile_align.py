@@ -161,32 +161,49 @@ class DevicePairs:
         self.leaf, self.index, self.ops_off, self.count, self.score = leaf, index, ops_off, count, score
 
 
-def pairs_on_device(backend, leaves: Sequence[np.ndarray], seqs: Sequence[Sequence[np.ndarray]],
-                    budget_bytes: int = DEFAULT_BUDGET_BYTES, band=None, counters: Optional[dict] = None) -> Optional[DevicePairs]:
+class PreparedProfiles:
+    """Profiles the caller wrote on the device itself, for pairs_on_device(prepared=...): d_prof, the profile buffer as
+    mprg_align_profiles lays it out (6 x C int32 per leaf); shapes, an (n_leaves, 2) array of {R, C}; prof_off, each leaf's offset
+    in d_prof (int32 elements).  d_seqs / seq_off / seq_len: optionally the sequences already on the device, ONE per leaf: a buffer
+    of cell codes and per leaf its sequence's offset there and its length (`seqs` is then not read)."""
+
+    def __init__(self, d_prof, shapes, prof_off, d_seqs=None, seq_off=None, seq_len=None):
+        self.d_prof, self.shapes, self.prof_off, self.d_seqs, self.seq_off, self.seq_len = d_prof, shapes, prof_off, d_seqs, seq_off, seq_len
+
+
+def pairs_on_device(backend, leaves: Optional[Sequence[np.ndarray]], seqs: Sequence[Sequence[np.ndarray]],
+                    budget_bytes: int = DEFAULT_BUDGET_BYTES, band=None, counters: Optional[dict] = None,
+                    prepared: Optional[PreparedProfiles] = None) -> Optional[DevicePairs]:
     """The pairs of align_batch on the device: the profiles in one launch, the pairs longest first in launches that fit the
     workspace budget, every pair's ops into one buffer that stays on the device.  None when there is no pair.
     band: None: the full DP.  True or a half-width w0: the spec's Band, two passes: the same ops, counts and scores from the
     cells of a certified band (launches sized by the banded need; a pair the band does not help goes to the full DP).
     counters: a dict that then receives (added up) band_pairs, band_second_passes, band_full_pairs (pairs sent to the full DP),
-    band_cells (DP cells computed, all passes and the full form) and band_full_cells (n C summed: what the full DP computes)."""
+    band_cells (DP cells computed, all passes and the full form) and band_full_cells (n C summed: what the full DP computes).
+    prepared: the leaves' profiles are already on the device (PreparedProfiles; `leaves` is then not read and no profile launch is
+    made): the leave-one-out profiles of from_msa --unaligned --refine."""
     be = backend
-    n_leaves = len(leaves)
+    n_leaves = len(leaves) if prepared is None else len(prepared.shapes)
     if not n_leaves:
         return None
-    shapes = np.array([m.shape for m in leaves], np.int64).reshape(-1, 2)
+    shapes = (np.array([m.shape for m in leaves], np.int64) if prepared is None else np.asarray(prepared.shapes, np.int64)).reshape(-1, 2)
     if (shapes < 1).any():
         raise ProfileAlignError("a leaf alignment with no rows or no columns")
     R, C = shapes[:, 0], shapes[:, 1]
     cell_off = np.concatenate([[0], np.cumsum(R * C)[:-1]])
-    prof_off = np.concatenate([[0], np.cumsum(6 * C)[:-1]])
+    prof_off = np.concatenate([[0], np.cumsum(6 * C)[:-1]]) if prepared is None else np.asarray(prepared.prof_off, np.int64)
     leaf_tab = np.stack([cell_off, R, C, prof_off], 1).astype(np.int64)
     tiles = -(-C // 256)
     work = np.stack([np.repeat(np.arange(n_leaves), tiles),
                      np.concatenate([np.arange(t) for t in tiles])], 1).astype(np.int32)
     # pairs: (leaf, index within the leaf, n)
-    pl = np.array([k for k, s in enumerate(seqs) for _ in s], np.int64)
-    pi = np.array([i for s in seqs for i in range(len(s))], np.int64)
-    pn = np.array([len(x) for s in seqs for x in s], np.int64)
+    on_device = prepared is not None and prepared.d_seqs is not None
+    if on_device:
+        pl, pi, pn = np.arange(n_leaves, dtype=np.int64), np.zeros(n_leaves, np.int64), np.asarray(prepared.seq_len, np.int64)
+    else:
+        pl = np.array([k for k, s in enumerate(seqs) for _ in s], np.int64)
+        pi = np.array([i for s in seqs for i in range(len(s))], np.int64)
+        pn = np.array([len(x) for s in seqs for x in s], np.int64)
     if not len(pl):
         return None
     pc = C[pl]
@@ -194,8 +211,7 @@ def pairs_on_device(backend, leaves: Sequence[np.ndarray], seqs: Sequence[Sequen
     if len(too_long):
         k = too_long[0]
         raise ProfileAlignError(f"a pair of {pn[k]} residues against {pc[k]} columns: n + C must stay below {MAX_LEN}")
-    seq_all = np.concatenate([x for s in seqs for x in s] + [np.zeros(1, np.uint8)]).astype(np.uint8)
-    seq_off = np.concatenate([[0], np.cumsum(pn)[:-1]])
+    seq_off = np.asarray(prepared.seq_off, np.int64) if on_device else np.concatenate([[0], np.cumsum(pn)[:-1]])
     need = np.array([workspace_words(int(n), int(c)) for n, c in zip(pn, pc)], np.int64)
     budget_words = max(64, int(budget_bytes) // 4)
 
@@ -212,13 +228,16 @@ def pairs_on_device(backend, leaves: Sequence[np.ndarray], seqs: Sequence[Sequen
     ops_bytes = max(int(ops_len.sum()), 1)
     count = np.zeros(len(pl), np.int64)
     score = np.zeros(len(pl), np.int64)
-    d_cells = be.upload(np.concatenate([m.reshape(-1) for m in leaves]).astype(np.uint8))
-    d_leaves = be.upload(leaf_tab)
-    d_work = be.upload(work)
-    d_prof = be.empty(4 * int((6 * C).sum()))
-    be.call("mprg_align_profiles", be.ptr(d_cells), be.ptr(d_leaves), be.ptr(d_work), len(work), be.ptr(d_prof), be.stream,
-            work=float((R * C).sum()))
-    d_seqs = be.upload(seq_all)
+    if prepared is None:
+        d_cells = be.upload(np.concatenate([m.reshape(-1) for m in leaves]).astype(np.uint8))
+        d_leaves = be.upload(leaf_tab)
+        d_work = be.upload(work)
+        d_prof = be.empty(4 * int((6 * C).sum()))
+        be.call("mprg_align_profiles", be.ptr(d_cells), be.ptr(d_leaves), be.ptr(d_work), len(work), be.ptr(d_prof), be.stream,
+                work=float((R * C).sum()))
+    else:
+        d_leaves, d_prof = be.upload(leaf_tab), prepared.d_prof
+    d_seqs = prepared.d_seqs if on_device else be.upload(np.concatenate([x for s in seqs for x in s] + [np.zeros(1, np.uint8)]).astype(np.uint8))
     d_ops = be.empty(ops_bytes)
 
     def launches(call, order, words, dlo=None, dhi=None):

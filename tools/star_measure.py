@@ -7,7 +7,12 @@ the files, the centre, pair and merge stages (star_align.star_msas; each ends at
 files (seeded); the line then also gives orient_s, the records reversed, how many of them were flipped, and the number the DP settled.
 `--band [W0]`: the pairs over a certified band (`from_msa --unaligned --band`; W0: pass 1's half-width, default
 profile_align.BAND_W0); the line then also gives the band's counters (pairs, second passes, pairs sent to the full DP, DP cells
-computed and of the full matrices).  msa_md5: a digest of the MSAs' text, to compare runs."""
+computed and of the full matrices).  msa_md5: a digest of the MSAs' text, to compare runs.
+`--refine [N]`: leave-one-out refinement (`from_msa --unaligned --refine`; N rounds, default 2); the line then also gives refine_s,
+the rounds accepted, the loci changed and the total objective S before and after.
+`--diverged R`: instead of the config-C-shaped loci, loci of R sequences mutated from one random root of 800-1200 nt each by the
+model of tests/star_ref.py's mutate(sub=0.06, indel=0.03), restated here (the tool does not import the tests): per root base 1.5 %
+deleted, 6 % substituted, 1.5 % followed by an insertion of 1-4 nt."""
 import hashlib
 import json
 import os
@@ -33,6 +38,30 @@ band = False
 if "--band" in sys.argv:
     nxt = sys.argv[sys.argv.index("--band") + 1:][:1]
     band = int(nxt[0]) if nxt and nxt[0].isdigit() else True
+refine = 0
+if "--refine" in sys.argv:
+    nxt = sys.argv[sys.argv.index("--refine") + 1:][:1]
+    refine = int(nxt[0]) if nxt and nxt[0].isdigit() else sa.REFINE_DEFAULT
+diverged = int(sys.argv[sys.argv.index("--diverged") + 1]) if "--diverged" in sys.argv else 0
+
+
+def diverged_seqs(seed):
+    r = random.Random(seed)
+    root = "".join(r.choice("ACGT") for _ in range(r.randint(800, 1200)))
+    out = []
+    for _ in range(diverged):
+        s = []
+        for ch in root:
+            u = r.random()
+            if u < 0.015:
+                continue
+            s.append(r.choice("ACGT") if u < 0.075 else ch)
+            if u > 0.985:
+                s.append("".join(r.choice("ACGT") for _ in range(r.randint(1, 4))))
+        out.append("".join(s))
+    return out
+
+
 work = Path(tempfile.mkdtemp(prefix="star_measure_"))
 try:
     src, msa_dir = work / "unaligned", work / "msas"
@@ -41,7 +70,7 @@ try:
     t0 = time.perf_counter()
     rng, flipped = random.Random(1), []
     for seed in range(n_loci):
-        seqs = [r.decode().replace("-", "") for r in synth_rows(seed, *config_shape("C", seed))]
+        seqs = diverged_seqs(seed) if diverged else [r.decode().replace("-", "") for r in synth_rows(seed, *config_shape("C", seed))]
         if flip is not None:
             flags = [i > 0 and rng.random() < flip for i in range(len(seqs))]
             seqs = [s.translate(COMPLEMENT)[::-1] if f else s for s, f in zip(seqs, flags)]
@@ -50,14 +79,16 @@ try:
     t_gen = time.perf_counter() - t0
     files = sorted(src.iterdir())
     be = get_backend("runtime")
-    sa.star_msas(be, [sa.read_unaligned(f) for f in files[:4]], adjust_direction=flip is not None, band=band)           # warm-up: first launches
+    sa.star_msas(be, [sa.read_unaligned(f) for f in files[:4]], adjust_direction=flip is not None, band=band, refine=refine)   # warm-up: first launches
     t0 = time.perf_counter()
     recs = [sa.read_unaligned(f) for f in files]
     t_read = time.perf_counter() - t0
     timings = {}
     t0 = time.perf_counter()
     orientation = []
-    msas = sa.star_msas(be, recs, timings=timings, adjust_direction=flip is not None, orientation=orientation, band=band)
+    refinement = []
+    msas = sa.star_msas(be, recs, timings=timings, adjust_direction=flip is not None, orientation=orientation, band=band, refine=refine,
+                        refinement=refinement)
     t_star = time.perf_counter() - t0
     t0 = time.perf_counter()
     written, digest = [], hashlib.md5()
@@ -75,6 +106,9 @@ try:
         extra = dict(flip=flip, reversed=sum(sum(rev) for rev, _ in orientation),
                      reversed_as_flipped=sum(sum(a and b for a, b in zip(rev, fl)) for (rev, _), fl in zip(orientation, flipped)),
                      flipped=sum(map(sum, flipped)), settled_by_dp=sum(how.count("d") + how.count("t") for _, how in orientation))
+    if refine:
+        extra.update(refine=refine, rounds_accepted=sum(a for a, _, _ in refinement), loci_changed=sum(1 for a, _, _ in refinement if a),
+                     s_before=sum(s for _, s, _ in refinement), s_after=sum(s for _, _, s in refinement))
     cent = sa.centres(be, codes)
     cells = sum(len(c) * len(cs[int(k)]) for cs, k in zip(codes, cent) for a, c in enumerate(cs) if a != int(k))
     opts = Namespace(input=str(msa_dir), suffix="", output_prefix=str(work / "out" / "prg"), alignment_format="fasta",
