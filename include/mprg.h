@@ -653,6 +653,49 @@ int mprg_refine_compact(const uint8_t *text, long long text_bytes, const int64_t
                         int32_t *dest, int64_t *new_width, const int64_t *rows, int n_rows, uint8_t *out, long long out_bytes,
                         int32_t *status, void *stream);
 
+/* `from_msa --unaligned --progressive`: guide-tree MSAs (the spec: star_align.py, "Progressive").  The tree is built
+ * on the host from what mprg_prog_distances gives; a tree node's merge is one pair of mprg_align_profile_pairs.
+ * A node's text is its R x W matrix of CELL CODES (0..11, '-' = 4), row-major; a leaf's text is its sequence in `codes`.  bufs:
+ *   n_bufs x 2 int64 {device address, bytes}: the buffers that hold texts; a text names its buffer by index and its range is
+ *   checked against that buffer's bytes.
+ * mprg_prog_distances: codes, seqs as the star calls'; loci: n_loci x MPRG_ST_LOCUS_FIELDS int64 {first sequence, sequence count m,
+ *   unused, offset of the locus's m x m table in `shared` (uint32 elements)}.  work: n_work x 2 int32 {locus, sequence a within
+ *   it}; every (locus, a) once.  shared[offset + a * m + b] receives, for b > a only, s(a, b) = sum_k min(c_a[k], c_b[k]) over the
+ *   4 096 6-mer counts of mprg_star_centres; nw[first + a] (int64, n_seqs) the number of a's valid windows.  status: n_work int32.
+ *   One workgroup per work item, 32 KB of LDS.
+ * mprg_prog_columns: items: n_items x MPRG_PG_ITEM_FIELDS int64 {buffer, offset of the text in it, R >= 1, W >= 1, kind, offset in
+ *   `cols` (int32 elements)}; work: n_work x 2 int32 {item, 256-column tile}.  Kind 0 writes 6 planes of W int32: exactly what
+ *   mprg_align_profiles writes for the R x W matrix.  Kind 1 writes 7 planes: per column the number of A, C, G, T, of
+ *   R Y K M S W N together, of '-', and Ic = (64 * -10 * (R - gaps)) / R (C's truncating division): an X side.  status: n_work int32.
+ * mprg_align_profile_pairs: mprg_align_pairs with a profile on both sides.  profile, leaves, workspace, ops, out, the ops layout
+ *   ('M' X's column with Y's column, 'I' X's column alone, 'D' Y's column alone; REVERSED) and the status codes are
+ *   mprg_align_pairs' (the leaf is Y).  pairs: n_pairs x MPRG_PG_PAIR_FIELDS int64 {leaf, offset of X's 7 planes in `xcols` (int32
+ *   elements, as kind 1 above wrote them), n = X's columns, workspace offset, ops offset, R_X = X's rows}.  Column i against
+ *   column j scores (sum_x count_i[x] P[j][x] + amb_i P[j][amb] + gaps_i Dc[j]) / R_X, truncating; X's column alone costs Ic[i], Y's
+ *   Dc[j]; every maximal run of either pays -704 more.  The workspace need is mprg_align_pairs' with n and C = Y's columns.
+ *   MPRG_AL_BAD_INPUT also for R_X < 1 or R_X > 2^20, MPRG_AL_NO_SPACE also for X's planes outside xcols_words.  With R_X = 1 the
+ *   ops and the score are mprg_align_pairs' for that sequence.  A pair is one wavefront.
+ * mprg_prog_rows: rows: n_rows x MPRG_PG_ROW_FIELDS int64 {buffer, offset of the source row in it, its cells n, offset of the
+ *   merge's ops in `ops`, op count k, side (0: a row of Y: a cell per op that is not 'I'; 1: a row of X: a cell per op that is
+ *   not 'D'; '-' at the other ops), offset of the output row in `out`, its width W (k >= 0: W = k)}.  k < 0: the n cells copied,
+ *   then '-' up to W.  ascii 0: cell codes out (a parent's text); else ASCII ACGT-RYKMSWN (the MSA as mprg_star_merge_rows
+ *   leaves it).  `out` must not overlap a source.  status: n_rows int32.  A row is one wavefront.
+ * status: MPRG_PG_OK, MPRG_PG_BAD_ITEM (an index, a tile or a source range outside its table or buffer: nothing else written),
+ *   MPRG_PG_BAD_OPS (rows: k, W, n and the ops do not fit each other: nothing or part of the row written), MPRG_PG_NO_SPACE (the
+ *   output outside its buffer: nothing else written). */
+enum { MPRG_PG_ITEM_FIELDS = 6, MPRG_PG_PAIR_FIELDS = 6, MPRG_PG_ROW_FIELDS = 8,
+       MPRG_PG_OK = 0, MPRG_PG_BAD_ITEM = 1, MPRG_PG_BAD_OPS = 2, MPRG_PG_NO_SPACE = 3 };
+int mprg_prog_distances(const uint8_t *codes, long long codes_bytes, const int64_t *seqs, long long n_seqs, const int64_t *loci,
+                        int n_loci, const int32_t *work, int n_work, uint32_t *shared, long long shared_words, int64_t *nw,
+                        int32_t *status, void *stream);
+int mprg_prog_columns(const int64_t *bufs, int n_bufs, const int64_t *items, int n_items, const int32_t *work, int n_work,
+                      int32_t *cols, long long cols_words, int32_t *status, void *stream);
+int mprg_align_profile_pairs(const int32_t *profile, const int64_t *leaves, int n_leaves, const int32_t *xcols, long long xcols_words,
+                             const int64_t *pairs, int n_pairs, int32_t *workspace, long long workspace_words, uint8_t *ops,
+                             long long ops_bytes, int32_t *out, void *stream);
+int mprg_prog_rows(const int64_t *bufs, int n_bufs, const uint8_t *ops, long long ops_bytes, const int64_t *rows, int n_rows,
+                   uint8_t *out, long long out_bytes, int ascii, int32_t *status, void *stream);
+
 /* (f)-1 output encoders, HOST functions (host pointers), one pass over a PRG string as PrgBuilder emits it.
  * reference make_prg/utils/prg_encoder.py:44-91 and make_prg/utils/gfa.py:16-109.
  * mprg_prg_encode_host: out[n] receives the uint32 stream (A C G T -> 1 2 3 4, markers as integers, the closing

@@ -104,6 +104,13 @@ SIGNATURES = {
                                      c_int, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
     "mprg_refine_compact": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p,
                                     c_int, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
+    "mprg_prog_distances": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                    ctypes.c_longlong, c_void_p, c_void_p, c_void_p]),
+    "mprg_prog_columns": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
+    "mprg_align_profile_pairs": (c_int, [c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, ctypes.c_longlong,
+                                         c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
+    "mprg_prog_rows": (c_int, [c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_int, c_void_p,
+                               c_void_p]),
     "mprg_random_sample_host": (None, [c_uint32, c_int, c_void_p]),
     "mprg_prg_encode_host": (ctypes.c_longlong, [c_void_p, ctypes.c_longlong, c_void_p]),
     "mprg_fasta_scan_host": (ctypes.c_longlong, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),

@@ -20,6 +20,7 @@
 #include "k_align.inc"
 #include "k_star.inc"
 #include "k_refine.inc"
+#include "k_prog.inc"
 #include "host_encoders.inc"
 #include "host_batch.inc"
 
@@ -646,6 +647,39 @@ int mprg_refine_compact(const uint8_t *text, long long text_bytes, const int64_t
   LAUNCH(k_refine_compact_rows, (n_rows + RF_WAVES - 1) / RF_WAVES, RF_THREADS, stream, text, text_bytes, loci, n_loci, keep, n_cols, dest,
          new_width, rows, n_rows, out, out_bytes, status);       // a wavefront per row
   return check_launch("k_refine_compact_rows");
+}
+
+int mprg_prog_distances(const uint8_t *codes, long long codes_bytes, const int64_t *seqs, long long n_seqs, const int64_t *loci,
+                        int n_loci, const int32_t *work, int n_work, uint32_t *shared, long long shared_words, int64_t *nw,
+                        int32_t *status, void *stream) {
+  if (n_work <= 0) return 0;
+  LAUNCH(k_prog_distances, n_work, PG_THREADS, stream, codes, codes_bytes, seqs, n_seqs, loci, n_loci, work, shared, shared_words, nw,
+         status);
+  return check_launch("k_prog_distances");
+}
+
+int mprg_prog_columns(const int64_t *bufs, int n_bufs, const int64_t *items, int n_items, const int32_t *work, int n_work,
+                      int32_t *cols, long long cols_words, int32_t *status, void *stream) {
+  if (n_work <= 0) return 0;
+  LAUNCH(k_prog_columns, n_work, PG_THREADS, stream, bufs, n_bufs, items, n_items, work, cols, cols_words, status);
+  return check_launch("k_prog_columns");
+}
+
+int mprg_align_profile_pairs(const int32_t *profile, const int64_t *leaves, int n_leaves, const int32_t *xcols, long long xcols_words,
+                             const int64_t *pairs, int n_pairs, int32_t *workspace, long long workspace_words, uint8_t *ops,
+                             long long ops_bytes, int32_t *out, void *stream) {
+  if (n_pairs <= 0) return 0;
+  LAUNCH(k_align_profile_pairs, (n_pairs + AL_WAVES - 1) / AL_WAVES, AL_THREADS, stream, profile, leaves, n_leaves, xcols, xcols_words,
+         pairs, n_pairs, workspace, workspace_words, ops, ops_bytes, out);      // a wavefront per pair
+  return check_launch("k_align_profile_pairs");
+}
+
+int mprg_prog_rows(const int64_t *bufs, int n_bufs, const uint8_t *ops, long long ops_bytes, const int64_t *rows, int n_rows,
+                   uint8_t *out, long long out_bytes, int ascii, int32_t *status, void *stream) {
+  if (n_rows <= 0) return 0;
+  LAUNCH(k_prog_rows, (n_rows + PG_WAVES - 1) / PG_WAVES, PG_THREADS, stream, bufs, n_bufs, ops, ops_bytes, rows, n_rows, out,
+         out_bytes, ascii, status);      // a wavefront per row
+  return check_launch("k_prog_rows");
 }
 
 // ---- the recursion forest on the device (k_forest.inc); F: host array of MPRG_F_FIELDS int64 ------------------------------

@@ -7,6 +7,9 @@ for byte, from a fraction of the cells and of the traceback memory.
 With `--adjust-direction`, records on the opposite strand are found and reverse-complemented first (Orientation below; kernels in
 csrc/k_star.inc, C ABI: mprg_star_centres_canonical / mprg_star_strand / mprg_star_revcomp).
 
+With `--progressive` the MSA is built up a guide tree instead of around a centre (Progressive below; kernels in csrc/k_prog.inc,
+C ABI: mprg_prog_distances / mprg_prog_columns / mprg_align_profile_pairs / mprg_prog_rows).
+
 It is NOT MAFFT.  PRGs built from these alignments differ from PRGs built from a MAFFT alignment of the same sequences.
 
 Spec (the kernels and tests/star_ref.py follow it bit for bit)
@@ -80,6 +83,46 @@ ever seen the centre.  Up to N rounds of leave-one-out realignment follow it, ea
   two-pass form (the certificate holds for any profile; sparse columns make m small and the bands wide, pairs the band does not
   help go to the full DP): the same bytes either way.
 
+Progressive (only with progressive; integers only; tests/prog_ref.py follows it bit for bit; kernels: csrc/k_prog.inc).  The star
+MSA aligns every row against one sequence; a locus with two or three sub-families has no good centre.  Here the rows are merged up
+a guide tree, profile against profile.  It replaces Centre, Pairs and Merge; Input, Orientation and Refinement stay what they are.
+  Input.    As above.  The leaves are the locus's non-empty sequences, by input index.  Empty records become all-gap rows; a locus
+            with one non-empty record is that record; a locus with no record, or only empty ones, fails exactly as above.
+  Distance. c_a: the 4 096 6-mer counts over ACGT of Centre, nw_a their sum.  s(a, b) = sum_k min(c_a[k], c_b[k]), m = min(nw_a,
+            nw_b), D(a, b) = 65 536 - floor(65 536 s / m), and 65 536 when m = 0.  So 0 <= D <= 65 536.
+  Tree.     Average linkage (UPGMA), exact.  A cluster's key is its lowest member index.  dist(U, V) = sum over a in U, b in V of
+            D(a, b) / (|U| |V|), compared by cross-multiplication, never by a rounded quotient.  The pair with the smallest dist is
+            merged; on ties the smallest key(U), then the smallest key(V), with key(U) < key(V).  With at most PROG_MAX_LEAVES =
+            4 096 leaves every cross product stays below 2^60.  A locus with more non-empty records is not built progressively: it
+            gets the star MSA above and is reported; the run never fails on a locus the star pass aligns.
+  Merge of a node's two children.  Y is the child with more rows, on equal rows the one with the lower key; X the other.  Y's
+            profile is what mprg_align_profiles writes for its R_Y x W_Y matrix: P[j][A, C, G, T], P[j][amb], Dc[j].  X's column i
+            has the counts c_i[A, C, G, T], amb_i (R Y K M S W N) and g_i ('-') over its R_X rows.  With C's truncating division:
+                s(i, j) = (sum_x c_i[x] P[j][x] + amb_i P[j][amb] + g_i Dc[j]) / R_X          column i against column j
+                Dc[j]                                                                        Y's column j alone
+                Ic[i] = (64 * -10 * (R_X - g_i)) / R_X                                       X's column i alone
+            and every maximal run of either kind pays -704 more.  The DP is the global three-state DP of profile_align.py: the
+            same int32 arithmetic, the same tie order (diagonal, then Y's column alone, then X's column alone; extend before open),
+            end gaps charged, W_X + W_Y >= 10^6 refused.  The ops give the merged columns one for one (M: both columns, D: Y's
+            column and '-' in X's rows, I: X's column and '-' in Y's rows): the node's width is the op count, nothing is
+            left-justified.  The node's rows are Y's, then X's.  With R_X = 1 this is profile_align's pair DP exactly (same ops,
+            same score).  |sum| <= 1 280 R_X, so the division is a multiplication and a shift on the device (k_prog.inc, pg_div).
+  Output.   The root's rows in input order, the empty records as all-gap rows, titles unchanged.
+  Not promised.  Identical input sequences need not give identical rows (two different sequences can have D = 0 and merge between
+            them).  No sequence weighting.  It is not MAFFT.  The merges use the full DP: a certified band for profile-profile
+            pairs needs a bound for X-side columns with Ic above -640, which is separate work; band together with progressive
+            only affects the realignments of refine.  adjust_direction runs first, on the records; refine runs afterwards, on the
+            progressive MSA's text on the device, unchanged.
+  Invariants (tested): every row with its gaps removed is its input sequence; no column is all gaps.
+
+Progressive, host side: per chunk the distances in launches whose m x m tables fit budget_bytes (loci of three or more leaves), D
+and the tree per locus in NumPy / Python integers (prog_tree: a float64 quotient only shortlists, the choice is exact).  A node's
+round is 1 + the larger of its children's rounds.  All nodes of one round, over all loci of the chunk, go longest first in groups
+whose workspace and column tables fit budget_bytes; per group one mprg_prog_columns launch (Y's profiles, X's column tables), one
+mprg_align_profile_pairs launch, {status, score, op count} per merge downloaded, one mprg_prog_rows launch that writes the
+parents' texts (cell codes) into a buffer of the group's own; a buffer is dropped when its last node has been merged.  One more
+mprg_prog_rows launch puts the roots' rows into input order as ASCII, where the star pass leaves its text.
+
 Host side: loci in chunks (CHUNK_BYTES of estimated ops and output per chunk); per chunk the centres in one launch, the pairs
 through profile_align.pairs_on_device (longest first, workspace-budget launches, ops left on the device), the widths and column
 starts in one call, the output size downloaded (one int64 per locus), the rows in one more launch, the MSAs downloaded.
@@ -116,6 +159,11 @@ CHUNK_BYTES = 1 << 29                     # estimated ops + output bytes of the 
 RF_LOCUS_FIELDS, RF_ROW_FIELDS = 4, 3     # MPRG_RF_LOCUS_FIELDS, MPRG_RF_ROW_FIELDS
 RF_STATUS = {1: "a locus's ranges outside the buffers", 2: "a row or tile out of range", 3: "the profile or the output outside its buffer"}
 REFINE_DEFAULT, REFINE_MAX = 2, 16        # rounds of `--refine` alone, and the most it takes
+PROG_MAX_LEAVES = 4096                    # the spec's leaf limit of a progressive locus
+PROG_SCALE = 1 << 16                      # D = PROG_SCALE - floor(PROG_SCALE s / m)
+PG_ITEM_FIELDS, PG_PAIR_FIELDS, PG_ROW_FIELDS = 6, 6, 8   # MPRG_PG_ITEM_FIELDS, MPRG_PG_PAIR_FIELDS, MPRG_PG_ROW_FIELDS
+PG_STATUS = {1: "an index, a tile or a source range outside its table or buffer", 2: "ops, widths and cells that do not fit each other",
+             3: "the output outside its buffer"}
 _GAP = ord("-")
 _ASCII = np.frombuffer(b"ACGT-RYKMSWN", np.uint8)
 
@@ -155,7 +203,8 @@ def _chunks(codes: List[List[np.ndarray]], limit: int):
 def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optional[Sequence[str]] = None,
               budget_bytes: int = pa.DEFAULT_BUDGET_BYTES, chunk_bytes: int = CHUNK_BYTES, timings: Optional[dict] = None,
               adjust_direction: bool = False, orientation: Optional[list] = None, band=False, refine: int = 0,
-              refinement: Optional[list] = None) -> List[MSA]:
+              refinement: Optional[list] = None, progressive: bool = False, progression: Optional[list] = None,
+              max_leaves: Optional[int] = None) -> List[MSA]:
     """loci: per locus its records as (title, sequence).  Returns the loci's centre-star MSAs (ids: the titles' first words,
     descriptions: the titles).  names: the loci's names for error messages (default: their indices).  timings: a dict that
     receives the wall seconds of the stages (orient, centre, pairs, merge: each ends at a download, so includes its kernels).
@@ -166,7 +215,11 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
     The score-only DP of adjust_direction keeps the full form.
     refine: N, the spec's Refinement: up to N accepted rounds per locus (0: none, nothing launches differently).  refinement: a list
     that then receives per locus (rounds accepted, S of the star MSA, S of the result).  timings also receives refine_s; the band
-    counters keep adding up across the rounds."""
+    counters keep adding up across the rounds.
+    progressive: the spec's Progressive instead of the centre-star pass (orientation first, refinement afterwards, both unchanged;
+    band then only affects the refinement).  progression: a list that then receives per locus (leaves, rounds, fell back to star).
+    max_leaves: PROG_MAX_LEAVES unless given; a locus with more non-empty records gets the star MSA.  timings also receives tree_s
+    (distances and trees) and progressive_s (the merges and the rows)."""
     if not (isinstance(refine, (int, np.integer)) and not isinstance(refine, bool) and 0 <= refine <= REFINE_MAX):
         raise ValueError(f"refine: a number of rounds from 0 to {REFINE_MAX}, not {refine!r}")
     names = [str(i) for i in range(len(loci))] if names is None else list(names)
@@ -176,9 +229,41 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
             raise EmptyMSAError(f"No records found in MSA of locus {name}")
     codes = [locus_codes(n, recs) for n, recs in zip(names, loci)]
     out: List[MSA] = []
+    if progressive:
+        return _progressive_msas(backend, loci, codes, names, budget_bytes, chunk_bytes, timings, adjust_direction, orientation, band,
+                                 int(refine), refinement, progression, PROG_MAX_LEAVES if max_leaves is None else int(max_leaves))
     for lo, hi in _chunks(codes, chunk_bytes):
         out.extend(_star_chunk(backend, loci[lo:hi], codes[lo:hi], names[lo:hi], budget_bytes, timings, adjust_direction, orientation, band,
                                int(refine), refinement))
+    return out
+
+
+def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings, adjust_direction, orientation, band, refine, refinement,
+                      progression, max_leaves) -> List[MSA]:
+    """star_msas with progressive: the loci within the leaf limit through the progressive chunks, the others through the star
+    chunks, the results (and what the caller's lists receive) back in the loci's order."""
+    n_leaves = [sum(1 for c in cs if len(c)) for cs in codes]
+    out = [None] * len(loci)
+    got = {k: [None] * len(loci) for k in ("orientation", "refinement", "progression")}
+    for prog in (True, False):
+        sel = [l for l in range(len(loci)) if (n_leaves[l] <= max_leaves) == prog]
+        sub = [codes[l] for l in sel]
+        ori, ref, pro, msas = [], [], [], []
+        for lo, hi in _chunks(sub, chunk_bytes):
+            idx = sel[lo:hi]
+            msas.extend(_star_chunk(be, [loci[l] for l in idx], sub[lo:hi], [names[l] for l in idx], budget_bytes, timings, adjust_direction,
+                                    ori if orientation is not None else None, band, refine, ref if refinement is not None else None,
+                                    prog, pro))
+        if not prog:
+            pro = [(n_leaves[l], 0, True) for l in sel]
+        for k, l in enumerate(sel):
+            out[l] = msas[k]
+            for key, vals in (("orientation", ori), ("refinement", ref), ("progression", pro)):
+                if vals:
+                    got[key][l] = vals[k]
+    for key, dest in (("orientation", orientation), ("refinement", refinement), ("progression", progression)):
+        if dest is not None:
+            dest.extend(got[key])
     return out
 
 
@@ -344,7 +429,7 @@ def _orient(be, codes, names, host, lens, seq_off, first, counts, budget_bytes):
 
 
 def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direction=False, orientation=None, band=False, refine=0,
-                refinement=None) -> List[MSA]:
+                refinement=None, progressive=False, progression=None) -> List[MSA]:
     import time
     t0 = time.perf_counter()
     host, lens, seq_off, first, counts = _pack(be, codes)
@@ -358,51 +443,59 @@ def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direc
         if timings is not None:
             timings["orient_s"] = timings.get("orient_s", 0.0) + t_or - t0
         t0 = t_or
-        centre = _centre_launch(be, "mprg_star_centres", d_codes, codes_bytes, lens, seq_off, first, counts)[0]
-    else:
+        if not progressive:
+            centre = _centre_launch(be, "mprg_star_centres", d_codes, codes_bytes, lens, seq_off, first, counts)[0]
+    elif not progressive:
         centre, d_codes = _centres(be, host, lens, seq_off, first, counts)
         codes_bytes = len(host)
-    t1 = time.perf_counter()
-    for l in np.nonzero(centre < 0)[0]:
-        raise StarAlignError(f"locus {names[l]}: every sequence is empty")
+    else:
+        _check_sizes(lens, first, counts)
+        d_codes, codes_bytes = be.upload(host), len(host)
     n_loci = len(codes)
-    C = np.array([len(codes[l][centre[l]]) for l in range(n_loci)], np.int64)
-    # the pairs: the centre as a 1-row leaf, every other non-empty sequence against it
-    leaves = [codes[l][centre[l]].reshape(1, -1) for l in range(n_loci)]
-    others = [[a for a in range(len(cs)) if a != centre[l] and len(cs[a])] for l, cs in enumerate(codes)]
-    dp = pa.pairs_on_device(be, leaves, [[codes[l][a] for a in others[l]] for l in range(n_loci)], budget_bytes,
-                            None if band is False or band is None else band, timings)
-    t2 = time.perf_counter()
-    # rows in input order: {locus, sequence offset, n, ops offset, ops count (-1: residue i in column i), output offset}
-    rows = np.zeros((int(counts.sum()), ROW_FIELDS), np.int64)
-    rows[:, 0] = np.repeat(np.arange(n_loci), counts)
-    rows[:, 1], rows[:, 2], rows[:, 4] = seq_off, lens, -1
-    if dp is not None:
-        r = first[dp.leaf] + np.array([others[l][i] for l, i in zip(dp.leaf.tolist(), dp.index.tolist())], np.int64)
-        rows[r, 3], rows[r, 4] = dp.ops_off, dp.count
-    d_ops = dp.d_ops if dp is not None else be.empty(16)
-    ops_bytes = dp.ops_bytes if dp is not None else 0
-    woff = np.concatenate([[0], np.cumsum(C + 1)[:-1]]).astype(np.int64)
-    n_width = int((C + 1).sum())
-    ltab = np.stack([first, counts, C, woff], 1).astype(np.int64)
-    d_loci, d_rows = be.upload(ltab), be.upload(rows)
-    d_width, d_start = be.zeros(4 * n_width), be.empty(8 * n_width)
-    d_w, d_status = be.empty(8 * n_loci), be.empty(4 * len(rows))
-    be.call("mprg_star_merge_columns", be.ptr(d_ops), ops_bytes, be.ptr(d_rows), len(rows), be.ptr(d_loci), n_loci, be.ptr(d_width),
-            be.ptr(d_start), n_width, codes_bytes, be.ptr(d_w), be.ptr(d_status), be.stream, work=float(ops_bytes))
-    W = be.download(d_w, np.int64, n_loci)
-    _check(be.download(d_status, np.int32, len(rows)), "mprg_star_merge_columns")
-    if (W < C).any():
-        raise StarAlignError("mprg_star_merge_columns: a locus's boundaries lie outside the buffers")
-    base = np.concatenate([[0], np.cumsum(counts * W)[:-1]]).astype(np.int64)
-    rank = np.arange(len(rows)) - np.repeat(first, counts)
-    rows[:, 5] = np.repeat(base, counts) + rank * np.repeat(W, counts)
-    out_bytes = int((counts * W).sum())
-    d_rows, d_out = be.upload(rows), be.empty(max(out_bytes, 1))
-    be.call("mprg_star_merge_rows", be.ptr(d_codes), codes_bytes, be.ptr(d_ops), ops_bytes, be.ptr(d_rows), len(rows), be.ptr(d_loci),
-            n_loci, be.ptr(d_width), be.ptr(d_start), n_width, be.ptr(d_w), be.ptr(d_out), max(out_bytes, 1), be.ptr(d_status),
-            be.stream, work=float(out_bytes + ops_bytes))
-    _check(be.download(d_status, np.int32, len(rows)), "mprg_star_merge_rows")
+    if progressive:
+        t1 = t2 = time.perf_counter()
+        d_out, out_bytes, base, W = _progressive(be, names, lens, seq_off, first, counts, d_codes, codes_bytes, budget_bytes, timings, progression)
+    else:
+        t1 = time.perf_counter()
+        for l in np.nonzero(centre < 0)[0]:
+            raise StarAlignError(f"locus {names[l]}: every sequence is empty")
+        C = np.array([len(codes[l][centre[l]]) for l in range(n_loci)], np.int64)
+        # the pairs: the centre as a 1-row leaf, every other non-empty sequence against it
+        leaves = [codes[l][centre[l]].reshape(1, -1) for l in range(n_loci)]
+        others = [[a for a in range(len(cs)) if a != centre[l] and len(cs[a])] for l, cs in enumerate(codes)]
+        dp = pa.pairs_on_device(be, leaves, [[codes[l][a] for a in others[l]] for l in range(n_loci)], budget_bytes,
+                                None if band is False or band is None else band, timings)
+        t2 = time.perf_counter()
+        # rows in input order: {locus, sequence offset, n, ops offset, ops count (-1: residue i in column i), output offset}
+        rows = np.zeros((int(counts.sum()), ROW_FIELDS), np.int64)
+        rows[:, 0] = np.repeat(np.arange(n_loci), counts)
+        rows[:, 1], rows[:, 2], rows[:, 4] = seq_off, lens, -1
+        if dp is not None:
+            r = first[dp.leaf] + np.array([others[l][i] for l, i in zip(dp.leaf.tolist(), dp.index.tolist())], np.int64)
+            rows[r, 3], rows[r, 4] = dp.ops_off, dp.count
+        d_ops = dp.d_ops if dp is not None else be.empty(16)
+        ops_bytes = dp.ops_bytes if dp is not None else 0
+        woff = np.concatenate([[0], np.cumsum(C + 1)[:-1]]).astype(np.int64)
+        n_width = int((C + 1).sum())
+        ltab = np.stack([first, counts, C, woff], 1).astype(np.int64)
+        d_loci, d_rows = be.upload(ltab), be.upload(rows)
+        d_width, d_start = be.zeros(4 * n_width), be.empty(8 * n_width)
+        d_w, d_status = be.empty(8 * n_loci), be.empty(4 * len(rows))
+        be.call("mprg_star_merge_columns", be.ptr(d_ops), ops_bytes, be.ptr(d_rows), len(rows), be.ptr(d_loci), n_loci, be.ptr(d_width),
+                be.ptr(d_start), n_width, codes_bytes, be.ptr(d_w), be.ptr(d_status), be.stream, work=float(ops_bytes))
+        W = be.download(d_w, np.int64, n_loci)
+        _check(be.download(d_status, np.int32, len(rows)), "mprg_star_merge_columns")
+        if (W < C).any():
+            raise StarAlignError("mprg_star_merge_columns: a locus's boundaries lie outside the buffers")
+        base = np.concatenate([[0], np.cumsum(counts * W)[:-1]]).astype(np.int64)
+        rank = np.arange(len(rows)) - np.repeat(first, counts)
+        rows[:, 5] = np.repeat(base, counts) + rank * np.repeat(W, counts)
+        out_bytes = int((counts * W).sum())
+        d_rows, d_out = be.upload(rows), be.empty(max(out_bytes, 1))
+        be.call("mprg_star_merge_rows", be.ptr(d_codes), codes_bytes, be.ptr(d_ops), ops_bytes, be.ptr(d_rows), len(rows), be.ptr(d_loci),
+                n_loci, be.ptr(d_width), be.ptr(d_start), n_width, be.ptr(d_w), be.ptr(d_out), max(out_bytes, 1), be.ptr(d_status),
+                be.stream, work=float(out_bytes + ops_bytes))
+        _check(be.download(d_status, np.int32, len(rows)), "mprg_star_merge_rows")
     t3 = time.perf_counter()
     moved = {}
     if refine:
@@ -431,9 +524,280 @@ def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direc
             data = text[base[l]:base[l] + counts[l] * W[l]].reshape(int(counts[l]), int(W[l]))
         msas.append(MSA(_data=data, _ids=[(t.split(None, 1) or [""])[0] for t in titles[l]], _descs=titles[l]))
     if timings is not None:
-        for k, v in (("centre_s", t1 - t0), ("pairs_s", t2 - t1), ("merge_s", time.perf_counter() - t2 - t3)):
+        for k, v in (() if progressive else (("centre_s", t1 - t0), ("pairs_s", t2 - t1), ("merge_s", time.perf_counter() - t2 - t3))):
             timings[k] = timings.get(k, 0.0) + v
     return msas
+
+
+# ---- progressive
+def _pg_check(status: np.ndarray, what: str):
+    bad = np.nonzero(status)[0]
+    if len(bad):
+        raise StarAlignError(f"{what}: work item {bad[0]}: {PG_STATUS.get(int(status[bad[0]]), int(status[bad[0]]))}")
+
+
+def _prog_shared(be, d_codes, codes_bytes, lens, seq_off, first, counts, sel, budget_bytes):
+    """mprg_prog_distances over the loci `sel` of a chunk, in groups whose m x m tables fit budget_bytes: per locus (s as an
+    (m, m) int64 array of which the part above the diagonal is filled, nw)."""
+    out = {}
+    d_seqs = be.upload(np.stack([seq_off, lens], 1).reshape(-1))
+    need = 4 * counts[sel] ** 2
+    pos = 0
+    while pos < len(sel):
+        end = pos + max(1, int(np.searchsorted(np.cumsum(need[pos:]), budget_bytes, side="right")))
+        grp = sel[pos:end]
+        pos = end
+        m = counts[grp]
+        toff = np.concatenate([[0], np.cumsum(m * m)[:-1]]).astype(np.int64)
+        words = int((m * m).sum())
+        ltab = np.zeros((len(grp), LOCUS_FIELDS), np.int64)
+        ltab[:, 0], ltab[:, 1], ltab[:, 3] = first[grp], m, toff
+        work = np.stack([np.repeat(np.arange(len(grp)), m), _ranges(np.zeros(len(grp), np.int64), m)], 1).astype(np.int32)
+        d_loci, d_work = be.upload(ltab), be.upload(work)
+        d_shared, d_nw, d_status = be.zeros(4 * words), be.zeros(8 * len(lens)), be.empty(4 * len(work))
+        be.call("mprg_prog_distances", be.ptr(d_codes), codes_bytes, be.ptr(d_seqs), len(lens), be.ptr(d_loci), len(grp), be.ptr(d_work),
+                len(work), be.ptr(d_shared), words, be.ptr(d_nw), be.ptr(d_status), be.stream,
+                work=float((m * np.add.reduceat(lens, first)[grp]).sum() + 16384.0 * (m * m).sum()))
+        _pg_check(be.download(d_status, np.int32, len(work)), "mprg_prog_distances")
+        shared = be.download(d_shared, np.uint32, words).astype(np.int64)
+        nw = be.download(d_nw, np.int64, len(lens))
+        for k, l in enumerate(grp.tolist()):
+            out[l] = (shared[toff[k]:toff[k] + m[k] * m[k]].reshape(int(m[k]), int(m[k])), nw[first[l]:first[l] + counts[l]])
+    return out
+
+
+def prog_shared(backend, codes: Sequence[Sequence[np.ndarray]], budget_bytes: int = pa.DEFAULT_BUDGET_BYTES):
+    """mprg_prog_distances over the loci (per locus its gap-free code arrays): per locus (s, nw): s an (m, m) int64 array whose
+    part above the diagonal holds the shared 6-mers of the records a < b, nw the records' valid windows."""
+    host, lens, seq_off, first, counts = _pack(backend, codes)
+    _check_sizes(lens, first, counts)
+    got = _prog_shared(backend, backend.upload(host), len(host), lens, seq_off, first, counts, np.arange(len(counts)), budget_bytes)
+    return [got[l] for l in range(len(counts))]
+
+
+def prog_distance_matrix(shared: np.ndarray, nw: np.ndarray) -> np.ndarray:
+    """The spec's D (symmetric, int64, zero diagonal) from what mprg_prog_distances gave for a locus."""
+    s = np.triu(shared, 1)
+    s = s + s.T
+    m = np.minimum(nw[:, None], nw[None, :])
+    D = np.where(m > 0, PROG_SCALE - (PROG_SCALE * s) // np.maximum(m, 1), PROG_SCALE).astype(np.int64)
+    np.fill_diagonal(D, 0)
+    return D
+
+
+def prog_tree(D: np.ndarray, leaves: Sequence[int]) -> List[Tuple[int, int]]:
+    """The spec's Tree over the leaves (ascending indices into D): the merges in order as (key(U), key(V)), key(U) < key(V); the
+    merged cluster keeps key(U).  Exact: a float64 quotient only shortlists the pairs within 2^-40 of the smallest, the choice
+    among them is made by cross-multiplication in Python integers, ties to the first in (key(U), key(V)) order."""
+    idx = np.asarray(leaves, np.int64)
+    n = len(idx)
+    S = D[np.ix_(idx, idx)].astype(np.int64)                    # sums of D between the clusters, slot = rank of the key
+    size = np.ones(n, np.int64)
+    alive = np.ones(n, bool)
+    Q = np.full((n, n), np.inf)
+    iu = np.triu_indices(n, 1)
+    Q[iu] = S[iu]
+    merges = []
+    for _ in range(n - 1):
+        qmin = Q.min()
+        cu, cv = np.nonzero(Q <= qmin * (1 + 2.0 ** -40))      # row-major: (key(U), key(V)) order
+        u, v = int(cu[0]), int(cv[0])
+        for a, b in zip(cu[1:].tolist(), cv[1:].tolist()):
+            if int(S[a, b]) * int(size[u] * size[v]) < int(S[u, v]) * int(size[a] * size[b]):
+                u, v = a, b
+        merges.append((int(idx[u]), int(idx[v])))
+        S[u, :] += S[v, :]
+        S[:, u] = S[u, :]
+        size[u] += size[v]
+        alive[v] = False
+        Q[v, :] = np.inf
+        Q[:, v] = np.inf
+        r = S[u] / (size[u] * size).astype(np.float64)
+        r[~alive] = np.inf
+        Q[u, u + 1:] = r[u + 1:]
+        Q[:u, u] = r[:u]
+    return merges
+
+
+def _prog_groups(WX, WY, budget_bytes):
+    """The merges (X's and Y's columns) longest first in groups whose workspace and column tables each fit the budget."""
+    need = pa.workspace_words_v(WX, WY)
+    cols = 7 * WX + 6 * WY
+    budget_words = max(64, int(budget_bytes) // 4)
+    if len(need) and need.max() > budget_words:
+        k = int(need.argmax())
+        raise StarAlignError(f"a merge of {WX[k]} columns against {WY[k]} needs {4 * need[k]} bytes of traceback, more than the workspace "
+                             f"budget of {budget_bytes}")
+    order = np.argsort(-((WX + 1) * WY), kind="stable")
+    pos = 0
+    while pos < len(order):
+        end, used, used_cols = pos, 0, 0
+        while end < len(order) and used + need[order[end]] <= budget_words and (end == pos or used_cols + cols[order[end]] <= budget_words):
+            used += int(need[order[end]])
+            used_cols += int(cols[order[end]])
+            end += 1
+        yield order[pos:end]
+        pos = end
+
+
+def _prog_pairs(be, d_bufs, n_bufs, X, Y):
+    """One group of merges on the device: X, Y (n, 4) int64 {buffer, offset, R, W} of the two sides' texts.  mprg_prog_columns (Y's
+    profiles, X's column tables) and mprg_align_profile_pairs in one launch each; {status, score, op count} downloaded.
+    Returns (the ops buffer, its bytes, each merge's ops offset, op count, score)."""
+    n = len(X)
+    WX, WY = X[:, 3], Y[:, 3]
+    k = np.nonzero(WX + WY >= pa.MAX_LEN)[0]
+    if len(k):
+        raise StarAlignError(f"a merge of {WX[k[0]]} columns against {WY[k[0]]}: their sum must stay below {pa.MAX_LEN}")
+    ycol = np.concatenate([[0], np.cumsum(6 * WY + 7 * WX)[:-1]]).astype(np.int64)
+    xcol = ycol + 6 * WY
+    words = int((6 * WY + 7 * WX).sum())
+    items = np.zeros((2 * n, PG_ITEM_FIELDS), np.int64)
+    items[:n, :4], items[:n, 4], items[:n, 5] = Y, 0, ycol
+    items[n:, :4], items[n:, 4], items[n:, 5] = X, 1, xcol
+    work = _tile_work(items[:, 3])
+    d_items, d_work, d_cols, d_status = be.upload(items), be.upload(work), be.empty(4 * words), be.empty(4 * len(work))
+    be.call("mprg_prog_columns", be.ptr(d_bufs), n_bufs, be.ptr(d_items), len(items), be.ptr(d_work), len(work), be.ptr(d_cols), words,
+            be.ptr(d_status), be.stream, work=float((items[:, 2] * items[:, 3]).sum()))
+    need = pa.workspace_words_v(WX, WY)
+    ws_off = np.concatenate([[0], np.cumsum(need)[:-1]]).astype(np.int64)
+    ops_off = np.concatenate([[0], np.cumsum(WX + WY)[:-1]]).astype(np.int64)
+    ops_bytes = int((WX + WY).sum())
+    leaf_tab = np.stack([np.zeros(n, np.int64), Y[:, 2], WY, ycol], 1).astype(np.int64)
+    pairs = np.stack([np.arange(n), xcol, WX, ws_off, ops_off, X[:, 2]], 1).astype(np.int64)
+    d_leaves, d_pairs = be.upload(leaf_tab), be.upload(pairs)
+    d_ws, d_ops, d_out = be.empty(4 * int(need.sum())), be.empty(ops_bytes), be.empty(12 * n)
+    be.call("mprg_align_profile_pairs", be.ptr(d_cols), be.ptr(d_leaves), n, be.ptr(d_cols), words, be.ptr(d_pairs), n, be.ptr(d_ws),
+            int(need.sum()), be.ptr(d_ops), ops_bytes, be.ptr(d_out), be.stream, work=float(((WX + 63) // 64 * 64 * WY).sum()))
+    _pg_check(be.download(d_status, np.int32, len(work)), "mprg_prog_columns")
+    res = be.download(d_out, np.int32, 3 * n).reshape(-1, 3)
+    bad = np.nonzero(res[:, 0])[0]
+    if len(bad):
+        raise StarAlignError(f"mprg_align_profile_pairs: {pa.STATUS.get(int(res[bad[0], 0]), int(res[bad[0], 0]))}")
+    return d_ops, ops_bytes, ops_off, res[:, 2].astype(np.int64), res[:, 1].astype(np.int64)
+
+
+def _bufs_table(be, bufs):
+    """The {address, bytes} table of the text buffers (a dropped one: {0, 0}, no text fits it)."""
+    return be.upload(np.array([[be.ptr(b), n] if b is not None else [0, 0] for b, n in bufs], np.int64))
+
+
+def merge_profiles(backend, pairs: Sequence[Tuple[np.ndarray, np.ndarray]], budget_bytes: int = pa.DEFAULT_BUDGET_BYTES):
+    """mprg_align_profile_pairs on (X, Y) pairs of cell-code matrices (R_X x W_X, R_Y x W_Y), through the launches a round of
+    merges makes: per pair (ops as bytes over b"MID" in forward order, score)."""
+    be = backend
+    mats = [m for xy in pairs for m in xy]
+    off = np.concatenate([[0], np.cumsum([m.size for m in mats])]).astype(np.int64)
+    text = np.concatenate([np.ascontiguousarray(m, np.uint8).reshape(-1) for m in mats])
+    bufs = [(be.upload(text), len(text))]
+    d_bufs = _bufs_table(be, bufs)
+    X = np.array([[0, off[2 * k], *pairs[k][0].shape] for k in range(len(pairs))], np.int64).reshape(-1, 4)
+    Y = np.array([[0, off[2 * k + 1], *pairs[k][1].shape] for k in range(len(pairs))], np.int64).reshape(-1, 4)
+    out = [None] * len(pairs)
+    for grp in _prog_groups(X[:, 3], Y[:, 3], budget_bytes):
+        d_ops, ops_bytes, ops_off, count, score = _prog_pairs(be, d_bufs, 1, X[grp], Y[grp])
+        ops = be.download(d_ops, np.uint8, ops_bytes)
+        for i, k in enumerate(grp.tolist()):
+            out[k] = (ops[ops_off[i]:ops_off[i] + count[i]][::-1].tobytes(), int(score[i]))
+    return out
+
+
+def _progressive(be, names, lens, seq_off, first, counts, d_codes, codes_bytes, budget_bytes, timings, progression):
+    """The spec's Progressive over one chunk, on the (oriented) sequences in d_codes.  Returns what the star pass leaves: the
+    device buffer of the MSAs' ASCII text, its bytes, each locus's offset in it and its width."""
+    import time
+    t0 = time.perf_counter()
+    n_loci = len(counts)
+    leaves = [np.nonzero(lens[first[l]:first[l] + counts[l]] > 0)[0] for l in range(n_loci)]
+    for l in range(n_loci):
+        if not len(leaves[l]):
+            raise StarAlignError(f"locus {names[l]}: every sequence is empty")
+    # the trees: distances on the device for the loci with three or more leaves (two leaves have one tree), UPGMA on the host
+    sel = np.array([l for l in range(n_loci) if len(leaves[l]) >= 3], np.int64)
+    shared = _prog_shared(be, d_codes, codes_bytes, lens, seq_off, first, counts, sel, budget_bytes) if len(sel) else {}
+    # nodes per locus: a leaf's id is its record index, an inner node's counts on from the locus's records.  members: the records
+    # of a node's rows, in row order (Y's rows, then X's)
+    where, members, by_round = {}, {}, {}
+    root = []
+    for l in range(n_loci):
+        lv = leaves[l].tolist()
+        for a in lv:
+            where[l, a] = (0, int(seq_off[first[l] + a]), 1, int(lens[first[l] + a]))
+            members[l, a] = [a]
+        merges = [(lv[0], lv[1])] if len(lv) == 2 else prog_tree(prog_distance_matrix(*shared[l]), lv) if len(lv) > 2 else []
+        node_at, rnd, nxt = {a: a for a in lv}, {a: 0 for a in lv}, int(counts[l])
+        for u, v in merges:
+            a, b = node_at[u], node_at[v]                       # key(a) = u < v = key(b)
+            y, x = (a, b) if len(members[l, a]) >= len(members[l, b]) else (b, a)
+            members[l, nxt] = members[l, y] + members[l, x]
+            rnd[nxt] = 1 + max(rnd[a], rnd[b])
+            by_round.setdefault(rnd[nxt], []).append((l, y, x, nxt))
+            node_at[u] = nxt
+            nxt += 1
+        root.append(node_at[lv[0]])
+        if progression is not None:
+            progression.append((len(lv), rnd[root[-1]], False))
+    t1 = time.perf_counter()
+    # the rounds: every node of a round, over all loci of the chunk, in one set of launches per budget group; a group's parents
+    # go into a text buffer of their own, a buffer is dropped when its last node has been merged into a parent
+    bufs, live = [(d_codes, codes_bytes)], [0]
+    for r in sorted(by_round):
+        todo = by_round[r]
+        Y = np.array([where[l, y] for l, y, _, _ in todo], np.int64)
+        X = np.array([where[l, x] for l, _, x, _ in todo], np.int64)
+        for grp in _prog_groups(X[:, 3], Y[:, 3], budget_bytes):
+            d_bufs = _bufs_table(be, bufs)
+            Xg, Yg = X[grp], Y[grp]
+            d_ops, ops_bytes, ops_off, count, _ = _prog_pairs(be, d_bufs, len(bufs), Xg, Yg)
+            RY, RX = Yg[:, 2], Xg[:, 2]
+            R = RY + RX
+            poff = np.concatenate([[0], np.cumsum(R * count)[:-1]]).astype(np.int64)
+            new_bytes = int((R * count).sum())
+            # the parents' rows: Y's, then X's, each through the merge's ops
+            rows = np.zeros((int(R.sum()), PG_ROW_FIELDS), np.int64)
+            of = np.repeat(np.arange(len(grp)), R)
+            rank = np.arange(len(rows)) - np.repeat(np.concatenate([[0], np.cumsum(R)[:-1]]), R)
+            is_x = rank >= RY[of]
+            src = np.where(is_x[:, None], Xg[of], Yg[of])
+            rows[:, 0] = src[:, 0]
+            rows[:, 1] = src[:, 1] + (rank - np.where(is_x, RY[of], 0)) * src[:, 3]
+            rows[:, 2], rows[:, 3], rows[:, 4], rows[:, 5] = src[:, 3], ops_off[of], count[of], is_x
+            rows[:, 6], rows[:, 7] = poff[of] + rank * count[of], count[of]
+            d_rows, d_new, d_status = be.upload(rows), be.empty(new_bytes), be.empty(4 * len(rows))
+            be.call("mprg_prog_rows", be.ptr(d_bufs), len(bufs), be.ptr(d_ops), ops_bytes, be.ptr(d_rows), len(rows), be.ptr(d_new), new_bytes,
+                    0, be.ptr(d_status), be.stream, work=float(2 * new_bytes))
+            _pg_check(be.download(d_status, np.int32, len(rows)), "mprg_prog_rows")
+            bufs.append((d_new, new_bytes))
+            live.append(len(grp))
+            for i, k in enumerate(grp.tolist()):
+                l, y, x, parent = todo[k]
+                where[l, parent] = (len(bufs) - 1, int(poff[i]), int(R[i]), int(count[i]))
+                for child in (y, x):
+                    b = where.pop((l, child))[0]
+                    live[b] -= 1
+                    if b and not live[b]:
+                        bufs[b] = (None, 0)
+    # the roots' rows into input order, as ASCII; an empty record is a row of '-'
+    W = np.array([where[l, root[l]][3] for l in range(n_loci)], np.int64)
+    base = np.concatenate([[0], np.cumsum(counts * W)[:-1]]).astype(np.int64)
+    out_bytes = int((counts * W).sum())
+    rows = np.zeros((int(counts.sum()), PG_ROW_FIELDS), np.int64)
+    rows[:, 4] = -1
+    rows[:, 6] = np.repeat(base, counts) + (np.arange(len(rows)) - np.repeat(first, counts)) * np.repeat(W, counts)
+    rows[:, 7] = np.repeat(W, counts)
+    for l in range(n_loci):
+        b, off, _, w = where[l, root[l]]
+        rec = first[l] + np.array(members[l, root[l]], np.int64)
+        rows[rec, 0], rows[rec, 1], rows[rec, 2] = b, off + np.arange(len(rec)) * w, w
+    d_bufs = _bufs_table(be, bufs)
+    d_rows, d_out, d_status = be.upload(rows), be.empty(max(out_bytes, 1)), be.empty(4 * len(rows))
+    be.call("mprg_prog_rows", be.ptr(d_bufs), len(bufs), be.ptr(d_out), 0, be.ptr(d_rows), len(rows), be.ptr(d_out), max(out_bytes, 1), 1,
+            be.ptr(d_status), be.stream, work=float(2 * out_bytes))
+    _pg_check(be.download(d_status, np.int32, len(rows)), "mprg_prog_rows")
+    if timings is not None:
+        for k, v in (("tree_s", t1 - t0), ("progressive_s", time.perf_counter() - t1)):
+            timings[k] = timings.get(k, 0.0) + v
+    return d_out, out_bytes, base, W
 
 
 def _rf_check(status: np.ndarray, what: str):

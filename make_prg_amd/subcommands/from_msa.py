@@ -72,6 +72,12 @@ def register_parser(subparsers):
                         "(star_align.py, Refinement), so a locus the rounds do not improve keeps its star MSA byte for byte; a locus too long for a "
                         "round's DP over its MSA's columns (star_align.py, Limit) is left as it is.  "
                         "Off by default")
+    p.add_argument("--progressive", dest="progressive", action="store_true", default=False,
+                   help="(this implementation) with --unaligned: every locus's MSA is built progressively on the GPU instead of "
+                        "centre-star: an exact UPGMA guide tree from 6-mer distances, then profile-profile merges up the tree "
+                        "(star_align.py, Progressive); NOT MAFFT.  --adjust-direction runs first, --refine afterwards, --band then "
+                        "only affects the refinement; a locus of more than 4096 non-empty records gets the centre-star MSA.  "
+                        "Off by default")
     p.set_defaults(func=run, check=check_options)
     return p
 
@@ -86,6 +92,8 @@ def check_options(args, parser):
         parser.error("--adjust-direction needs --unaligned")
     if getattr(args, "band", False) and not args.unaligned:
         parser.error("--band needs --unaligned")
+    if getattr(args, "progressive", False) and not args.unaligned:
+        parser.error("--progressive needs --unaligned")
     if getattr(args, "refine", None) is not None:
         if not args.unaligned:
             parser.error("--refine needs --unaligned")
@@ -584,13 +592,16 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
     counters: Dict[str, float] = {}
     refine = int(getattr(options, "refine", None) or 0)
     refinement = []
+    progressive = bool(getattr(options, "progressive", False))
+    progression = []
     for lo in range(0, len(mine), STAR_CHUNK):
         t0 = time.perf_counter()
         recs = [star_align.read_unaligned(f) for f in mine[lo:lo + STAR_CHUNK]]
         t1 = time.perf_counter()
         msas = star_align.star_msas(be, recs, names=loci[lo:lo + STAR_CHUNK], adjust_direction=adjust, orientation=orientation,
                                     **(dict(band=True, timings=counters) if band else {}),
-                                    **(dict(refine=refine, refinement=refinement) if refine else {}))
+                                    **(dict(refine=refine, refinement=refinement) if refine else {}),
+                                    **(dict(progressive=True, progression=progression) if progressive else {}))
         t2 = time.perf_counter()
         for locus, m in zip(loci[lo:lo + STAR_CHUNK], msas):
             path = out_dir / f"{locus}.fa"
@@ -610,6 +621,10 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
     if refine:
         logger.info(f"rank {rank}: --refine {refine}: {sum(1 for a, _, _ in refinement if a)} loci refined, "
                     f"{sum(a for a, _, _ in refinement)} rounds accepted, {sum(1 for a, _, _ in refinement if not a)} loci left as the star MSA")
+    if progressive:
+        built = [(n, r) for n, r, star in progression if not star]
+        logger.info(f"rank {rank}: --progressive: {len(built)} loci built, {sum(n - 1 for n, _ in built)} merges, "
+                    f"{max((r for _, r in built), default=0)} rounds at most, {len(progression) - len(built)} loci left to the star pass")
     align_unaligned_inputs.timings = dict(read_s=t_read, align_s=t_align, write_s=t_write)
     return written
 

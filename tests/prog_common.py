@@ -1,0 +1,216 @@
+"""What the emulated and the GPU tests of `from_msa --unaligned --progressive` share: the profile pairs of the DP check, the
+loci of the whole-MSA check with their reference (computed once per process), the reference compositions with
+--adjust-direction and --refine, and the status codes of the new C ABI entries for tables that point outside their buffers."""
+import functools
+import random
+
+import numpy as np
+
+from make_prg_amd.from_msa import star_align as sa
+from make_prg_amd.msa import encode
+from tests import prog_ref as pr
+from tests import refine_ref as rr
+from tests import star_ref as sr
+from tests import strand_ref as st
+
+WX = (1, 63, 64, 65, 128, 129, 200)       # around the 64-column strip and the 128-column ring
+WY = (1, 127, 128, 129, 300)
+ROWS = (1, 2, 3, 7)
+
+
+def records(seqs):
+    return [(f"r{i} desc {i}", s) for i, s in enumerate(seqs)]
+
+
+def codes(rows) -> np.ndarray:
+    return encode(np.frombuffer("".join(rows).encode(), np.uint8)).reshape(len(rows), -1)
+
+
+@functools.lru_cache(maxsize=None)
+def dp_cases():
+    """((X, Y) as tuples of row strings, prog_ref's (ops, score)): every W_X x W_Y of the lists above with the row counts taken in
+    turn, dense and mostly-gap columns, ambiguity codes, and two pairs with one side much longer than the other."""
+    rng = random.Random(11)
+    shapes = [(wx, wy) for wx in WX for wy in WY] + [(3, 700), (700, 3), (130, 130)]
+    out = []
+    for k, (wx, wy) in enumerate(shapes):
+        rx, ry = ROWS[k % 4], ROWS[(k // 4 + k) % 4]
+        gx, gy = (0.1, 0.75, 0.3)[k % 3], (0.1, 0.3, 0.75)[(k // 3) % 3]
+        X = tuple(pr.random_profiles(rng, rx, wx, gx, amb=0.1 if k % 2 else 0.0))
+        Y = tuple(pr.random_profiles(rng, ry, wy, gy, amb=0.1 if k % 5 == 0 else 0.02))
+        out.append(((X, Y), pr.align_profiles_np(X, Y)))
+    return out
+
+
+def check_dp(be, **kw):
+    cases = dp_cases()
+    assert {len(x) for (x, _), _ in cases} == set(ROWS) and {len(y) for (_, y), _ in cases} == set(ROWS)
+    got = sa.merge_profiles(be, [(codes(x), codes(y)) for (x, y), _ in cases], **kw)
+    for ((x, y), want), (ops, score) in zip(cases, got):
+        assert (ops.decode(), score) == want, (len(x), len(x[0]), len(y), len(y[0]))
+
+
+def msa_loci():
+    """Edge, special, random and the 18 table loci: balanced trees and caterpillars, one to several rounds."""
+    return sr.edge_loci() + rr.special_loci() + sr.random_loci(3) + sr.random_loci(21, 20) + pr.table_loci()
+
+
+@functools.lru_cache(maxsize=None)
+def msa_spec():
+    return [pr.progressive(l) for l in msa_loci()]
+
+
+def check_msas(be, **kw):
+    loci, info, timings = msa_loci(), [], {}
+    msas = sa.star_msas(be, [records(l) for l in loci], progressive=True, progression=info, timings=timings, **kw)
+    for l, m, got, (rows, want) in zip(loci, msas, info, msa_spec()):
+        assert m.rows_as_strings() == rows, l
+        assert got == want, l
+        assert m.descriptions == [t for t, _ in records(l)]
+    rounds = [r for _, r, _ in info]
+    leaves = [n for n, _, _ in info]
+    assert max(rounds) >= 6 and any(r == n - 1 and n >= 4 for n, r, _ in info) and any(2 <= r < n - 1 for n, r, _ in info)
+    assert min(leaves) == 1 and timings["tree_s"] > 0 and timings["progressive_s"] > 0
+
+
+def check_distances(be, loci):
+    norm = [[sr.normalise(s) for s in l] for l in loci]
+    got = sa.prog_shared(be, [sa.locus_codes(str(k), records(l)) for k, l in enumerate(loci)])
+    for l, (shared, nw) in zip(norm, got):
+        D, S, want_nw = pr.distances(l)
+        assert nw.tolist() == want_nw, l
+        assert np.triu(shared, 1).tolist() == np.triu(np.array(S, np.int64).reshape(len(l), len(l)), 1).tolist(), l
+        assert sa.prog_distance_matrix(shared, nw).tolist() == D, l
+
+
+def flipped_loci():
+    rng = random.Random(4)
+    loci = [pr.clade_locus(s, 8) for s in range(10, 16)] + [rr.diverged_locus(s, 8) for s in range(16, 20)] + sr.random_loci(31, 16)
+    return [[st.rc(s) if i and rng.random() < 0.4 else s for i, s in enumerate(l)] for l in loci]
+
+
+@functools.lru_cache(maxsize=None)
+def flipped_spec():
+    """Per locus (titles, progressive rows, those rows refined by two rounds) of the reference composition: strand_ref's
+    orientation, prog_ref on the oriented sequences, refine_ref on its rows."""
+    out = []
+    for l in flipped_loci():
+        rev, _, ori = st.oriented(l)
+        rows = pr.progressive_rows(ori)
+        out.append((st.titles(records(l), rev), rows, rr.refine_rows(rows, 2)))
+    return out
+
+
+def check_compositions(be):
+    recs = [records(l) for l in flipped_loci()]
+    spec = flipped_spec()
+    msas = sa.star_msas(be, recs, progressive=True, adjust_direction=True)
+    assert [(m.descriptions, m.rows_as_strings()) for m in msas] == [(t, rows) for t, rows, _ in spec]
+    assert sum(t.startswith(sa.REVERSED_PREFIX) for m in msas for t in m.descriptions) >= 20
+    for band in (False, True):
+        info = []
+        msas = sa.star_msas(be, recs, progressive=True, adjust_direction=True, refine=2, refinement=info, band=band)
+        for m, got, (t, _, (rows, acc, trail)) in zip(msas, info, spec):
+            assert m.descriptions == t and m.rows_as_strings() == rows and got == (acc, trail[0], trail[-1])
+        assert any(a for a, _, _ in info) and any(not a for a, _, _ in info)
+
+
+def check_abi_statuses(be):
+    """The new entries, handed tables that point outside a buffer, report their status code and write nothing else."""
+    POISON = 0x5C
+    X, Y = ["AC-T", "A-GT"], ["ACGTA", "AC-TA", "ACGTN"]
+    text = np.concatenate([codes(X).reshape(-1), codes(Y).reshape(-1)])
+    d_text = be.upload(text)
+    d_bufs = be.upload(np.array([[be.ptr(d_text), len(text)]], np.int64))
+
+    def untouched(buf, n):
+        return (be.download(buf, np.uint8, n) == POISON).all()
+
+    def columns(items, work, words=58):
+        d_cols, d_status = be.full(4 * 58, POISON), be.full(4 * len(work), POISON)
+        d_items, d_work = be.upload(np.array(items, np.int64)), be.upload(np.array(work, np.int32))
+        be.call("mprg_prog_columns", be.ptr(d_bufs), 1, be.ptr(d_items), len(items), be.ptr(d_work), len(work), be.ptr(d_cols), words,
+                be.ptr(d_status), be.stream)
+        return be.download(d_status, np.int32, len(work)).tolist(), untouched(d_cols, 4 * 58), d_cols
+    good = [[0, 8, 3, 5, 0, 0], [0, 0, 2, 4, 1, 30]]
+    status, clean, d_cols = columns(good, [[0, 0], [1, 0]])
+    assert status == [0, 0] and not clean
+    cols = be.download(d_cols, np.int32, 58)
+    from tests import align_ref as ar
+    P, Dc = ar.profile(Y)
+    assert cols[:30].reshape(6, 5).tolist() == [[p[x] for p in P] for x in "ACGTN"] + [Dc]
+    assert cols[30:].reshape(7, 4).tolist() == [[2, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, 0], [0, 0, 0, 2], [0, 0, 0, 0], [0, 1, 1, 0],
+                                                [-640, -320, -320, -640]]
+    for items, work, words, code in (([[1, 8, 3, 5, 0, 0]], [[0, 0]], 58, 1),        # no such buffer
+                                     ([[0, 9, 3, 5, 0, 0]], [[0, 0]], 58, 1),        # the text ends one byte outside
+                                     ([[0, -1, 3, 5, 0, 0]], [[0, 0]], 58, 1),
+                                     ([[0, 8, 0, 5, 0, 0]], [[0, 0]], 58, 1),
+                                     ([[0, 8, 3, 5, 2, 0]], [[0, 0]], 58, 1),        # no such kind
+                                     (good, [[2, 0]], 58, 1), (good, [[-1, 0]], 58, 1), (good, [[0, 1]], 58, 1), (good, [[0, -1]], 58, 1),
+                                     (good, [[1, 0]], 57, 3),                        # the planes end one word outside
+                                     ([[0, 8, 3, 5, 0, 29]], [[0, 0]], 58, 3), ([[0, 8, 3, 5, 0, -1]], [[0, 0]], 58, 3)):
+        assert columns(items, work, words)[:2] == ([code], True), (items, work, words)
+
+    def pairs(pair, leaf=(0, 3, 5, 0), xwords=58, ws_words=None, ops_bytes=9):
+        need = sa.pa.workspace_words(4, 5)
+        d_ws, d_ops, d_out = be.empty(4 * need), be.full(9, POISON), be.full(12, POISON)
+        d_leaves, d_pairs = be.upload(np.array([leaf], np.int64)), be.upload(np.array([pair], np.int64))
+        be.call("mprg_align_profile_pairs", be.ptr(d_cols), be.ptr(d_leaves), 1, be.ptr(d_cols), xwords, be.ptr(d_pairs), 1, be.ptr(d_ws),
+                need if ws_words is None else ws_words, be.ptr(d_ops), ops_bytes, be.ptr(d_out), be.stream)
+        out = be.download(d_out, np.int32, 3).tolist()
+        return out, untouched(d_ops, 9), be.download(d_ops, np.uint8, 9)
+    out, clean, ops = pairs([0, 30, 4, 0, 0, 2])
+    want = pr.align_profiles(X, Y)
+    assert out == [0, want[1], len(want[0])] and ops[:out[2]][::-1].tobytes().decode() == want[0]
+    for pair, kw, code in (([1, 30, 4, 0, 0, 2], {}, 3), ([-1, 30, 4, 0, 0, 2], {}, 3), ([0, 30, -1, 0, 0, 2], {}, 3),
+                           ([0, 30, 4, 0, 0, 0], {}, 3), ([0, 30, 4, 0, 0, (1 << 20) + 1], {}, 3),      # R_X out of range
+                           ([0, 30, 4, 0, 0, 2], dict(leaf=(0, 0, 5, 0)), 3),
+                           ([0, 31, 4, 0, 0, 2], {}, 2), ([0, -1, 4, 0, 0, 2], {}, 2), ([0, 30, 4, 0, 0, 2], dict(xwords=57), 2),
+                           ([0, 30, 4, 64, 0, 2], {}, 2), ([0, 30, 4, 1, 0, 2], {}, 2), ([0, 30, 4, 0, 1, 2], {}, 2),
+                           ([0, 30, 4, 0, 0, 2], dict(ops_bytes=8), 2), ([0, 30, 999_996, 0, 0, 2], {}, 1)):
+        assert pairs(pair, **kw)[:2] == ([code, 0, 0], True), (pair, kw)
+
+    d_ops = be.upload(np.frombuffer(want[0][::-1].encode(), np.uint8))
+    k = len(want[0])
+
+    def rows(table, out_bytes=None, ops_bytes=k, ascii=1):
+        n = 5 * k
+        d_out, d_status = be.full(n, POISON), be.full(4 * len(table), POISON)
+        d_rows = be.upload(np.array(table, np.int64))
+        be.call("mprg_prog_rows", be.ptr(d_bufs), 1, be.ptr(d_ops), ops_bytes, be.ptr(d_rows), len(table), be.ptr(d_out),
+                n if out_bytes is None else out_bytes, ascii, be.ptr(d_status), be.stream)
+        return be.download(d_status, np.int32, len(table)).tolist(), be.download(d_out, np.uint8, n).tobytes()
+    table = [[0, 8 + 5 * r, 5, 0, k, 0, r * k, k] for r in range(3)] + [[0, 4 * r, 4, 0, k, 1, (3 + r) * k, k] for r in range(2)]
+    nx, ny = pr.merge_rows(X, Y, want[0])
+    assert rows(table) == ([0] * 5, "".join(ny + nx).encode())
+    assert rows(table, ascii=0) == ([0] * 5, codes(ny + nx).tobytes())
+    assert rows([[0, 8, 5, 0, -1, 0, 0, 7]]) == ([0], b"ACGTA--" + bytes([POISON]) * (5 * k - 7))
+    blank = bytes([POISON]) * (5 * k)
+    for row, kw, code in (([1, 8, 5, 0, k, 0, 0, k], {}, 1), ([0, 19, 5, 0, k, 0, 0, k], {}, 1), ([0, -1, 5, 0, k, 0, 0, k], {}, 1),
+                          ([0, 8, 5, 0, k, 2, 0, k], {}, 1),
+                          ([0, 8, 5, 0, k, 0, 4 * k + 1, k], {}, 3), ([0, 8, 5, 0, k, 0, -1, k], {}, 3), ([0, 8, 5, 0, k, 0, 0, k], dict(out_bytes=k - 1), 3),
+                          ([0, 8, 5, 0, k, 0, 0, k + 1], {}, 2), ([0, 8, 5, 1, k, 0, 0, k], {}, 2), ([0, 8, 5, 0, k, 0, 0, k], dict(ops_bytes=k - 1), 2),
+                          ([0, 8, 5, 0, -1, 0, 0, 4], {}, 2)):
+        assert rows([row], **kw) == ([code], blank), (row, kw)
+    assert rows([[0, 8, 4, 0, k, 0, 0, k]])[0] == [2]          # a row with a cell less than the ops consume
+
+    seqs = ["ACGTACGTAC", "ACGTTCGTAC", ""]
+    packed = np.concatenate([sa.locus_codes("l", records(seqs))[i] for i in range(3)] + [np.zeros(1, np.uint8)])
+    d_codes = be.upload(packed)
+
+    def distances(stab, ltab, work, words=9, codes_bytes=21):
+        d_shared, d_nw, d_status = be.full(4 * 9, POISON), be.full(24, POISON), be.full(4 * len(work), POISON)
+        d_seqs, d_loci, d_work = be.upload(np.array(stab, np.int64)), be.upload(np.array(ltab, np.int64)), be.upload(np.array(work, np.int32))
+        be.call("mprg_prog_distances", be.ptr(d_codes), codes_bytes, be.ptr(d_seqs), 3, be.ptr(d_loci), 1, be.ptr(d_work), len(work),
+                be.ptr(d_shared), words, be.ptr(d_nw), be.ptr(d_status), be.stream)
+        return (be.download(d_status, np.int32, len(work)).tolist(), untouched(d_shared, 36) and untouched(d_nw, 24),
+                be.download(d_shared, np.uint32, 9).tolist(), be.download(d_nw, np.int64, 3).tolist())
+    stab, ltab = [[0, 10], [10, 10], [20, 0]], [[0, 3, 0, 0]]
+    status, clean, shared, nw = distances(stab, ltab, [[0, 0], [0, 1], [0, 2]])
+    _, S, want_nw = pr.distances(seqs)
+    assert status == [0, 0, 0] and nw == want_nw == [5, 5, 0] and [shared[1], shared[2], shared[5]] == [S[0][1], S[0][2], S[1][2]]
+    for s2, l2, work, kw in ((stab, ltab, [[1, 0]], {}), (stab, ltab, [[-1, 0]], {}), (stab, ltab, [[0, 3]], {}), (stab, ltab, [[0, -1]], {}),
+                             (stab, [[1, 3, 0, 0]], [[0, 0]], {}), (stab, [[0, 3, 0, 1]], [[0, 0]], {}), (stab, ltab, [[0, 0]], dict(words=8)),
+                             ([[0, 10], [10, 12], [20, 0]], ltab, [[0, 0]], {}), ([[0, 10], [-1, 10], [20, 0]], ltab, [[0, 0]], {}),
+                             (stab, ltab, [[0, 0]], dict(codes_bytes=19))):
+        assert distances(s2, l2, work, **kw)[:2] == ([1], True), (s2, l2, work, kw)

@@ -12,7 +12,11 @@ computed and of the full matrices).  msa_md5: a digest of the MSAs' text, to com
 the rounds accepted, the loci changed and the total objective S before and after.
 `--diverged R`: instead of the config-C-shaped loci, loci of R sequences mutated from one random root of 800-1200 nt each by the
 model of tests/star_ref.py's mutate(sub=0.06, indel=0.03), restated here (the tool does not import the tests): per root base 1.5 %
-deleted, 6 % substituted, 1.5 % followed by an insertion of 1-4 nt."""
+deleted, 6 % substituted, 1.5 % followed by an insertion of 1-4 nt.
+`--progressive`: guide-tree MSAs (`from_msa --unaligned --progressive`); the line then also gives tree_s and progressive_s, the
+loci built, their merges, the most rounds of a locus and the loci left to the star pass.
+`--objective` (implied by --progressive): the line also gives s_total, the objective S of the MSAs written, summed over the loci
+(mprg_refine_counts over the MSAs, after the timed part): to compare a star run and a progressive run of the same loci."""
 import hashlib
 import json
 import os
@@ -42,6 +46,8 @@ refine = 0
 if "--refine" in sys.argv:
     nxt = sys.argv[sys.argv.index("--refine") + 1:][:1]
     refine = int(nxt[0]) if nxt and nxt[0].isdigit() else sa.REFINE_DEFAULT
+progressive = "--progressive" in sys.argv
+objective = progressive or "--objective" in sys.argv
 diverged = int(sys.argv[sys.argv.index("--diverged") + 1]) if "--diverged" in sys.argv else 0
 
 
@@ -79,7 +85,8 @@ try:
     t_gen = time.perf_counter() - t0
     files = sorted(src.iterdir())
     be = get_backend("runtime")
-    sa.star_msas(be, [sa.read_unaligned(f) for f in files[:4]], adjust_direction=flip is not None, band=band, refine=refine)   # warm-up: first launches
+    sa.star_msas(be, [sa.read_unaligned(f) for f in files[:4]], adjust_direction=flip is not None, band=band, refine=refine,
+                 **(dict(progressive=True) if progressive else {}))   # warm-up: first launches
     t0 = time.perf_counter()
     recs = [sa.read_unaligned(f) for f in files]
     t_read = time.perf_counter() - t0
@@ -87,8 +94,9 @@ try:
     t0 = time.perf_counter()
     orientation = []
     refinement = []
+    progression = []
     msas = sa.star_msas(be, recs, timings=timings, adjust_direction=flip is not None, orientation=orientation, band=band, refine=refine,
-                        refinement=refinement)
+                        refinement=refinement, **(dict(progressive=True, progression=progression) if progressive else {}))
     t_star = time.perf_counter() - t0
     t0 = time.perf_counter()
     written, digest = [], hashlib.md5()
@@ -109,6 +117,20 @@ try:
     if refine:
         extra.update(refine=refine, rounds_accepted=sum(a for a, _, _ in refinement), loci_changed=sum(1 for a, _, _ in refinement if a),
                      s_before=sum(s for _, s, _ in refinement), s_after=sum(s for _, _, s in refinement))
+    if progressive:
+        built = [(n, r) for n, r, star in progression if not star]
+        extra.update(progressive=True, loci_built=len(built), merges=sum(n - 1 for n, _ in built), max_rounds=max((r for _, r in built), default=0),
+                     loci_left_to_star=len(progression) - len(built))
+    if objective:
+        import numpy as np
+        s_total = 0
+        for lo in range(0, len(msas), 64):
+            part = msas[lo:lo + 64]
+            R, W = np.array([m.data.shape[0] for m in part], np.int64), np.array([m.data.shape[1] for m in part], np.int64)
+            toff = np.concatenate([[0], np.cumsum(R * W)[:-1]]).astype(np.int64)
+            text = np.concatenate([np.ascontiguousarray(m.data).reshape(-1) for m in part])
+            s_total += int(sa.refine_counts(be, be.upload(text), len(text), toff, R, W)[4].sum())
+        extra.update(s_total=s_total)
     cent = sa.centres(be, codes)
     cells = sum(len(c) * len(cs[int(k)]) for cs, k in zip(codes, cent) for a, c in enumerate(cs) if a != int(k))
     opts = Namespace(input=str(msa_dir), suffix="", output_prefix=str(work / "out" / "prg"), alignment_format="fasta",
