@@ -111,6 +111,10 @@ int mprg_partition(const uint8_t *arena, const int64_t *views, const int32_t *ro
  * utils/seq_utils.py:58-70 (unique gapped / ungapped counts).  Ungap + hash: one workgroup per (view, row chunk) — work_rows:
  * n x 2 int32 {view, chunk}; a chunk is 256 rows, 8 for a view of more than 4 096 columns —, one wavefront per row; grouping: one
  * workgroup per view, after a scan over the same work items for the views of more than 512 rows.
+ * NARROW views (at most 64 columns and 512 rows) take none of these: one launch over the views of the call does all their stages, a
+ * workgroup per view with a lane per row (k_rows_narrow; k_rows_narrow_s for at most 128 rows), or a wavefront per view of at most 64
+ * rows (k_rows_wave); their work items in work_rows are skipped.  Same outputs, bit for bit.  MPRG_ROW_VIEWS=0 (environment, read
+ * once when the library is loaded) leaves every view to the launches above (and MPRG_WAVE_VIEWS=0 the small ones to a workgroup each).
  * views[AUX0] = byte offset (a multiple of 16) of this view's region in `ucodes`: n_rows * upitch bytes, upitch =
  * round_up(n_cols, 16); ungapped codes are stored ROW-MAJOR: character j of row position i at i*upitch + j.
  * per row (at row_off): ulen, rep_u (smallest row position with identical ungapped content), rep_g (same for gapped

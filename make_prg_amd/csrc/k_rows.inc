@@ -14,6 +14,11 @@
 // SMALLEST row index per key (atomicMin: order independent); a row's nominee is that row.  Every nominated pair is
 // compared 16 bytes per lane; a refuted nominee (a 64-bit collision: practically never) sends the view to the exact
 // all-pairs search.  First-appearance lists come from workgroup prefix sums over "is the first of its group" flags.
+// K3n (k_rows_narrow, k_rows_narrow_s), K3w (k_rows_wave, k_dedupe_wave): NARROW views (at most RV_COLS columns and DD_ROWS rows: the rule
+// below the root) take all of the above in ONE launch — a workgroup per view, or a wavefront for a view of at most 64 rows —, with a
+// LANE per row for the row phase: a lane that walks its row alone keeps the kept-byte count, both hashes and the compaction state in
+// registers (no prefix sum over a group of lanes, no second pass over the compacted rows), and the hashes are in LDS when the dedupe
+// table is built.  Same hashes, lengths, rows and lists as K3a + K3a' + K3b write.  MPRG_ROW_VIEWS=0 leaves every view to those.
 // ---------------------------------------------------------------------------------------------------------------
 MPRG_DEV uint64_t hash_mix(uint64_t x) {          // splitmix64 finaliser
   x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ULL; x ^= x >> 27; x *= 0x94d049bb133111ebULL; x ^= x >> 31;
@@ -51,7 +56,7 @@ MPRG_DEV uint64_t hash_word(uint64_t w, unsigned pos) { return MPRG_HASH_MIX(w ^
 // the kernels that visit the view afterwards (gapped comparison here, cluster_further) then read one contiguous block of a
 // few KB instead of a narrow slice of every arena row (64-byte sectors for 30 useful bytes).
 // small views (the rule below the first levels): all three stages by ONE wavefront, DW_WAVES views per workgroup (k_dedupe_wave
-// below); the workgroup-per-chunk / workgroup-per-view kernels leave them alone when `wave_form` is set
+// below); the workgroup-per-chunk / workgroup-per-view kernels leave them alone when bit 0 of `form` is set
 // (measured on MI355X, 7 500 config-C alignments per pass: the level of ~100-row x ~40-column views 5.1 ms by workgroups, 7.7 ms by
 //  wavefronts — a wavefront alone walks such a view's three stages too long; the level of ~25 x 5 views 2.2 -> 1.6 ms)
 #define DW_WAVES 4
@@ -59,6 +64,21 @@ MPRG_DEV uint64_t hash_word(uint64_t w, unsigned pos) { return MPRG_HASH_MIX(w ^
 #define DW_SLOTS 128
 #define DW_COLS 64
 MPRG_DEV bool dw_is_small(long long S, long long n) { return S >= 1 && S <= DW_ROWS && n >= 1 && n <= DW_COLS; }
+// narrow views (the rule of the first levels below the root: ~100 rows x ~40 columns): all three stages by ONE workgroup, a LANE per
+// row (k_rows_narrow below).  A lane that walks its row alone needs no scan over a group of lanes: the kept-byte count, both hashes and
+// the compaction state stay in its registers, and the hashes are in the workgroup's LDS when the dedupe table is built.
+#define DD_ROWS 512
+#define DD_SLOTS 1024                  // LDS table: twice the rows
+#define RV_COLS 64
+#define RV_ROWS_S 128                  // ... of at most so many rows by k_rows_narrow_s: a quarter of the LDS, four times the workgroups per CU
+#define RV_SLOTS_S 256
+// `form` of the row kernels' launches: bit 0 = the small views are k_dedupe_wave's / k_rows_wave's, bit 1 = the narrow ones
+// k_rows_narrow's / k_rows_narrow_s's (small views stay with the wavefront kernels where both are on)
+#define RF_WAVE 1
+#define RF_ROWS 2
+MPRG_DEV bool rv_is_narrow(long long S, long long n) { return n >= 1 && n <= RV_COLS && S >= 1 && S <= DD_ROWS; }
+MPRG_DEV bool rv_takes(int form, long long S, long long n) { return (form & RF_ROWS) && rv_is_narrow(S, n) && !((form & RF_WAVE) && dw_is_small(S, n)); }
+MPRG_DEV bool rows_elsewhere(int form, long long S, long long n) { return ((form & RF_WAVE) && dw_is_small(S, n)) || rv_takes(form, S, n); }
 // rows [r0, r0 + chunk) of the view, wavefront `wv` of `n_waves`
 MPRG_DEV void ug_hash_rows(const uint8_t *arena, const ViewD &d, const int32_t *rowidx, int r0, int chunk, int wv, int n_waves,
                            uint8_t *ucodes_all, uint64_t *hashes, int32_t *ulen_all, uint8_t *gcodes_all) {
@@ -136,11 +156,11 @@ MPRG_DEV void ug_hash_rows(const uint8_t *arena, const ViewD &d, const int32_t *
   }
 }
 KERNEL(k_ungap_hash, const uint8_t *arena, const int64_t *views, const int32_t *rowidx, const int32_t *work,
-       uint8_t *ucodes_all, uint64_t *hashes, int32_t *ulen_all, uint8_t *gcodes_all, int wave_form, DsCount dc) {
+       uint8_t *ucodes_all, uint64_t *hashes, int32_t *ulen_all, uint8_t *gcodes_all, int form, DsCount dc) {
   DS_GUARD(dc, 1);
   const int32_t *wk = work + 2 * (long long)BLOCK_ID;
   const ViewD d = load_view(views, wk[0]);
-  if (wave_form && dw_is_small(d.n_rows, d.n_cols)) return;
+  if (rows_elsewhere(form, d.n_rows, d.n_cols)) return;
   const int chunk = ug_chunk_rows(d.n_cols);
   ug_hash_rows(arena, d, rowidx, wk[1] * chunk, chunk, wave_id(), N_THREADS / WAVE, ucodes_all, hashes, ulen_all, gcodes_all);
 }
@@ -175,18 +195,16 @@ MPRG_DEV void ug_hash_u_rows(const ViewD &d, int r0, int chunk, int wv, int n_wa
   }
 }
 KERNEL(k_ungap_hash_u, const int64_t *views, const int32_t *work, const uint8_t *ucodes_all, uint64_t *hashes, const int32_t *ulen_all,
-       int wave_form, DsCount dc) {
+       int form, DsCount dc) {
   DS_GUARD(dc, 1);
   const int32_t *wk = work + 2 * (long long)BLOCK_ID;
   const ViewD d = load_view(views, wk[0]);
-  if (wave_form && dw_is_small(d.n_rows, d.n_cols)) return;
+  if (rows_elsewhere(form, d.n_rows, d.n_cols)) return;
   const int chunk = ug_chunk_rows(d.n_cols);
   ug_hash_u_rows(d, wk[1] * chunk, chunk, wave_id(), N_THREADS / WAVE, ucodes_all, hashes, ulen_all);
 }
 
 // K3b  groups of identical rows + first-appearance lists, one view per workgroup
-#define DD_ROWS 512
-#define DD_SLOTS 1024                  // LDS table: twice the rows
 #define DD_EMPTY 0xffffffffffffffffULL
 // 16 ungapped characters of rows i and j differ?  (U is row-major, rows 16-byte aligned)
 MPRG_DEV bool dd_diff_u16(const uint8_t *U, int upitch, int i, int j, int p0, int len) {
@@ -328,7 +346,8 @@ template <bool WV> MPRG_DEV int dd_scan_excl(int v, int *scratch, int *total) {
 }
 // view q of the launch's table (q also places its k-mer occurrence offsets and its summary).  WV: run by ONE wavefront (DW_ROWS rows
 // at most): loops stride the 64 lanes, WAVE_SYNC where the workgroup form has a barrier
-template <bool WV, int ROWS, int SLOTS>
+// LOADED: the caller has put the rows' hashes and lengths into L.s_hu / s_hg / s_len (and passed a barrier)
+template <bool WV, int ROWS, int SLOTS, bool LOADED = false>
 MPRG_DEV void dd_view(const int q, const ViewD &d, const uint8_t *arena, const int32_t *rowidx, int kmer_size,
                       uint8_t *ucodes_all, const uint8_t *gcodes_all, uint64_t *hashes, int32_t *ulen_all, int32_t *rep_u_all, int32_t *rep_g_all,
                       int32_t *d_of_row_all, int32_t *s_of_row_all, int32_t *reps_pos_all, int32_t *reps_len_all,
@@ -353,7 +372,7 @@ MPRG_DEV void dd_view(const int q, const ViewD &d, const uint8_t *arena, const i
   int32_t *RU = in_lds ? s_ru : rep_u, *RG = in_lds ? s_rg : rep_g;
   // (the rows' ungapped hashes come from k_ungap_hash_u)
   if (in_lds) {
-    P_FOR(i, S) { s_hu[i] = hu[i]; s_hg[i] = hg[i]; s_len[i] = ulen[i]; }
+    if (!LOADED) P_FOR(i, S) { s_hu[i] = hu[i]; s_hg[i] = hg[i]; s_len[i] = ulen[i]; }
     P_ONE { refuted[0] = 0; }
     // ---- nominees: smallest row with the same (hash, length), ungapped then gapped content, through the LDS table
     unsigned slots = 64;                  // power of two >= 2 S: a small view does not pay for clearing the whole table
@@ -470,14 +489,110 @@ MPRG_DEV void dd_view(const int q, const ViewD &d, const uint8_t *arena, const i
 KERNEL(k_ungap_dedupe, const uint8_t *arena, const int64_t *views, const int32_t *rowidx, int kmer_size,
        uint8_t *ucodes_all, const uint8_t *gcodes_all, uint64_t *hashes, int32_t *ulen_all, int32_t *rep_u_all, int32_t *rep_g_all,
        int32_t *d_of_row_all, int32_t *s_of_row_all, int32_t *reps_pos_all, int32_t *reps_len_all,
-       int32_t *seqrow_all, int64_t *occ_off_all, int64_t *summary, int wave_form, DsCount dc) {
+       int32_t *seqrow_all, int64_t *occ_off_all, int64_t *summary, int form, DsCount dc) {
   DS_GUARD(dc, 1);
   const ViewD d = load_view(views, BLOCK_ID);
-  if (wave_form && dw_is_small(d.n_rows, d.n_cols)) return;          // k_dedupe_wave's
+  if (rows_elsewhere(form, d.n_rows, d.n_cols)) return;          // k_dedupe_wave's, k_rows_narrow's
   __shared__ DdLds<DD_ROWS, DD_SLOTS> L;
   dd_view<false, DD_ROWS, DD_SLOTS>(BLOCK_ID, d, arena, rowidx, kmer_size, ucodes_all, gcodes_all, hashes, ulen_all, rep_u_all, rep_g_all, d_of_row_all,
                                     s_of_row_all, reps_pos_all, reps_len_all, seqrow_all, occ_off_all, summary, L);
 }
+// K3n  a NARROW selected view (rv_is_narrow) — ungap + dense gapped copy + both hashes + row groups + first-appearance lists — by ONE
+//      workgroup.  Row phase: a LANE per row walks the row's words in column order (word c = columns c .. c + 3 of the view, cells past
+//      n count as gaps: the words k_ungap_hash forms), RV_BATCH words per trip: the gapped hash is the sum of hash_word(w, c); the kept
+//      bytes of a word (all four: the common case; else squeezed together with selects) are appended to a 64-bit accumulator, and
+//      whenever 8 bytes are complete — and once at the end, for the tail, whose upper bytes are zero — they go to the ungapped row as ONE
+//      store and hash_word(8 bytes, their position) is added to the ungapped hash: the sum k_ungap_hash_u forms over the compacted
+//      row (both hashes are commutative sums, so hashes / ulen / the ungapped rows / the gapped copy are what the three launches write).
+//      The row is streamed, not held: nothing here depends on n <= RV_COLS.  Hashes and lengths go straight into the LDS arrays of the
+//      dedupe (and to `hashes` / `ulen`, which the ABI documents); dd_view runs from the nominee table on.
+//      Cells: unaligned 4-byte loads from the row-major copy (a wavefront's load touches 64 rows; the words k_ungap_hash loads).
+//      The views of at most RV_ROWS_S rows go to k_rows_narrow_s, the same body over a quarter of the LDS: these workgroups wait for
+//      memory between their barriers, and the LDS of the 512-row form holds six of them on a CU.
+#define RV_BATCH 8
+template <bool WV>                     // WV: the view is ONE wavefront's (k_dedupe_wave), else the workgroup's
+MPRG_DEV void rv_rows(const uint8_t *arena, const ViewD &d, const int32_t *rowidx, uint8_t *ucodes_all, uint64_t *hashes,
+                      int32_t *ulen_all, uint8_t *gcodes_all, uint64_t *s_hu, uint64_t *s_hg, int32_t *s_len) {
+  const int n = d.n_cols, S = d.n_rows, upitch = u_pitch(n);
+  uint64_t *hu = hashes + 2 * d.row_off, *hg = hu + S;
+  int32_t *ulen = ulen_all + d.row_off;
+  for (long long i = WV ? wave_lane() : MPRG_TID; i < S; i += WV ? WAVE : (int)blockDim.x) {
+    const uint8_t *src = arena + d.rm + (long long)view_row(d, rowidx, i) * d.pitchC + d.col0;
+    uint8_t *dst = ucodes_all + d.aux0 + i * upitch;
+    uint8_t *gdst = gcodes_all ? gcodes_all + d.aux0 + i * upitch : nullptr;
+    uint64_t g = 0, a = 0, acc = 0;      // gapped hash, ungapped hash, kept bytes not yet stored (`fill` of them, the rest zero)
+    int fill = 0, p = 0;                 // p: ungapped bytes stored so far (a multiple of 8)
+    for (int cb = 0; cb < n; cb += 4 * RV_BATCH) {     // (n is the view's: uniform over the workgroup)
+      uint32_t wq[RV_BATCH];
+#pragma unroll
+      for (int q = 0; q < RV_BATCH; ++q) {
+        const int c = cb + 4 * q;
+        wq[q] = 0x04040404u;
+        if (c < n) __builtin_memcpy(&wq[q], src + c, 4);                // the arena is padded: the bytes past n exist
+      }
+#pragma unroll
+      for (int q = 0; q < RV_BATCH; ++q) {
+        const int c = cb + 4 * q;
+        if (c >= n) break;
+        uint32_t w = wq[q];
+        if (c + 4 > n) {                               // the row's last word: cells past n count as gaps
+          const uint32_t keep = 0xffffffffu >> (8 * (c + 4 - n));
+          w = (w & keep) | (0x04040404u & ~keep);
+        }
+        g += hash_word(w, (unsigned)c);
+        if (gdst) __builtin_memcpy(gdst + c, &w, 4);   // (upitch >= n rounded up to 16)
+        const uint32_t v = w ^ 0x04040404u;            // zero bytes = gaps
+        const uint32_t gap = ~(((v & 0x7f7f7f7fu) + 0x7f7f7f7fu) | v) & 0x80808080u;   // 0x80 in every gap byte, exactly
+        uint32_t kw = w;                               // the word's kept bytes, squeezed to its low end; the rest zero
+        int k = 4;
+        if (gap) {
+          kw = 0; k = 0;
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const bool keep = !((gap >> (8 * u + 7)) & 1u);
+            kw |= keep ? ((w >> (8 * u)) & 0xffu) << (8 * k) : 0u;
+            k += keep ? 1 : 0;
+          }
+        }
+        acc |= (uint64_t)kw << (8 * fill);             // (fill <= 7; what does not fit is taken up again below)
+        fill += k;
+        if (fill >= 8) {
+          __builtin_memcpy(dst + p, &acc, 8);
+          a += hash_word(acc, (unsigned)p);
+          p += 8; fill -= 8;
+          acc = (uint64_t)kw >> (8 * (k - fill));      // the last `fill` kept bytes of the word
+        }
+      }
+    }
+    if (fill > 0) {                                    // the tail, upper bytes zero (p + 8 <= upitch: a multiple of 16 >= n)
+      __builtin_memcpy(dst + p, &acc, 8);
+      a += hash_word(acc, (unsigned)p);
+    }
+    const int len = p + fill;
+    hu[i] = a; hg[i] = g; ulen[i] = len;
+    s_hu[i] = a; s_hg[i] = g; s_len[i] = len;
+  }
+}
+#define RV_PARAMS const uint8_t *arena, const int64_t *views, const int32_t *rowidx, int kmer_size,                              \
+       uint8_t *ucodes_all, uint8_t *gcodes_all, uint64_t *hashes, int32_t *ulen_all, int32_t *rep_u_all, int32_t *rep_g_all, \
+       int32_t *d_of_row_all, int32_t *s_of_row_all, int32_t *reps_pos_all, int32_t *reps_len_all,                            \
+       int32_t *seqrow_all, int64_t *occ_off_all, int64_t *summary, int form, DsCount dc
+#define RV_BODY(ROWS_, SLOTS_, mine_) do {                                                                                            \
+    DS_GUARD(dc, 1);                                                                                                                  \
+    const ViewD d = load_view(views, BLOCK_ID);                                                                                       \
+    if (!rv_takes(form, d.n_rows, d.n_cols) || !(mine_)) return;                                                                      \
+    __shared__ DdLds<ROWS_, SLOTS_> L;                                                                                                \
+    rv_rows<false>(arena, d, rowidx, ucodes_all, hashes, ulen_all, gcodes_all, L.s_hu, L.s_hg, L.s_len);                              \
+    __threadfence_block();             /* the rows' stores before the other threads' loads of them (the comparisons of dd_view) */    \
+    BARRIER();                                                                                                                        \
+    dd_view<false, ROWS_, SLOTS_, true>(BLOCK_ID, d, arena, rowidx, kmer_size, ucodes_all, gcodes_all, hashes, ulen_all, rep_u_all,   \
+                                        rep_g_all, d_of_row_all, s_of_row_all, reps_pos_all, reps_len_all, seqrow_all, occ_off_all,   \
+                                        summary, L);                                                                                  \
+  } while (0)
+KERNEL(k_rows_narrow, RV_PARAMS) { RV_BODY(DD_ROWS, DD_SLOTS, d.n_rows > RV_ROWS_S); }
+KERNEL(k_rows_narrow_s, RV_PARAMS) { RV_BODY(RV_ROWS_S, RV_SLOTS_S, d.n_rows <= RV_ROWS_S); }
+#undef RV_BODY
+#undef RV_PARAMS
 // K3w  a SMALL selected view — ungap + hashes + row groups + first-appearance lists — by ONE wavefront, DW_WAVES views per workgroup:
 //      the three stages above in a row (their results pass through global memory as they do between the launches: a
 //      workgroup-scope fence orders a wavefront's stores before its lanes' loads), no workgroup barrier.
@@ -496,5 +611,23 @@ KERNEL(k_dedupe_wave, const uint8_t *arena, const int64_t *views, const int32_t 
   WAVE_SYNC_GLOBAL();
   dd_view<true, DW_ROWS, DW_SLOTS>((int)q, d, arena, rowidx, kmer_size, ucodes_all, gcodes_all, hashes, ulen_all, rep_u_all, rep_g_all, d_of_row_all,
                                    s_of_row_all, reps_pos_all, reps_len_all, seqrow_all, occ_off_all, summary, L_all[wave_id()]);
+}
+// K3w'  k_dedupe_wave with the row phase of k_rows_narrow: a lane per row of the small view (at most DW_ROWS = 64 rows: one pass), hashes
+//       and lengths straight into the wavefront's LDS arrays
+KERNEL(k_rows_wave, const uint8_t *arena, const int64_t *views, const int32_t *rowidx, int n_views, int kmer_size,
+       uint8_t *ucodes_all, uint8_t *gcodes_all, uint64_t *hashes, int32_t *ulen_all, int32_t *rep_u_all, int32_t *rep_g_all,
+       int32_t *d_of_row_all, int32_t *s_of_row_all, int32_t *reps_pos_all, int32_t *reps_len_all,
+       int32_t *seqrow_all, int64_t *occ_off_all, int64_t *summary, DsCount dc) {
+  const long long q = (long long)BLOCK_ID * DW_WAVES + wave_id();
+  if (q >= ds_n(dc, n_views)) return;                 // (per wavefront: nothing below waits for the workgroup)
+  const ViewD d = load_view(views, (int)q);
+  if (!dw_is_small(d.n_rows, d.n_cols)) return;
+  __shared__ DdLds<DW_ROWS, DW_SLOTS> L_all[DW_WAVES];
+  DdLds<DW_ROWS, DW_SLOTS> &L = L_all[wave_id()];
+  rv_rows<true>(arena, d, rowidx, ucodes_all, hashes, ulen_all, gcodes_all, L.s_hu, L.s_hg, L.s_len);
+  WAVE_SYNC_GLOBAL();                  // the rows' stores before the other lanes' loads of them, in global memory and in LDS
+  WAVE_SYNC();
+  dd_view<true, DW_ROWS, DW_SLOTS, true>((int)q, d, arena, rowidx, kmer_size, ucodes_all, gcodes_all, hashes, ulen_all, rep_u_all, rep_g_all, d_of_row_all,
+                                         s_of_row_all, reps_pos_all, reps_len_all, seqrow_all, occ_off_all, summary, L);
 }
 #undef DD_EXACT

@@ -69,6 +69,11 @@ template <class K> static int kml_raise_lds(K kernel, bool *raised, const char *
 // mprg_cluster_further: problems that fit a workgroup's LDS in one workgroup and launch (k_cluster_further_one); MPRG_CF_ONE=0: two launches for all
 static const int g_cf_one = [] { const char *e = getenv("MPRG_CF_ONE"); return (e && atoi(e) == 0) ? 0 : 1; }();
 static const int g_pw_wave = [] { const char *e = getenv("MPRG_WAVE_VIEWS"); return (e && atoi(e) == 0) ? 0 : 1; }();
+// the row groups of narrow views by one workgroup with a lane per row, all stages in one launch (k_rows_narrow, k_rows_narrow_s), and the
+// same row phase for the small views' wavefronts (k_rows_wave); MPRG_ROW_VIEWS=0: the launches of the wider views / k_dedupe_wave for them
+static const int g_row_views = [] { const char *e = getenv("MPRG_ROW_VIEWS"); return (e && atoi(e) == 0) ? 0 : 1; }();
+#define RV_THREADS 128                 // k_rows_narrow: ~100 rows are the rule (256 threads: no faster); k_rows_narrow_s: one wavefront, two rows per lane
+#define RV_THREADS_S 64
 
 extern "C" {
 
@@ -160,7 +165,7 @@ static int d_partition(const uint8_t *arena, const int64_t *views, const int32_t
   }
   if (view_out) {                                  // the packed list of all triples of the call
     if (!iv_packed || !iv_count) return fail("mprg_partition: view_out needs iv_packed and iv_count");
-    LAUNCH(k_pack_scan, 1, 1024, stream, n_views, n_iv, view_out, iv_count, dc_views);
+    LAUNCH(k_pack_scan, (n_views + PK_VIEWS - 1) / PK_VIEWS, PK_SCAN_THREADS, stream, n_views, n_iv, view_out, iv_count, dc_views);
     LAUNCH(k_pack_copy, (n_views + PK_THREADS / WAVE - 1) / (PK_THREADS / WAVE), PK_THREADS, stream, n_views, views, iv, view_out,
            iv_packed, dc_views);
   }
@@ -173,13 +178,25 @@ static int d_ungap_dedupe(const uint8_t *arena, const int64_t *views, const int3
                           int32_t *reps_len, int32_t *seqrow, int64_t *occ_off, int64_t *summary, uint8_t *gcodes, void *stream,
                           DsCount dc_views, DsCount dc_rows, long long max_rows = 0) {
   if (n_views <= 0) return 0;
-  // the SMALL views by a wavefront each, all stages in one launch (k_dedupe_wave); the launches below leave them alone
-  if (g_pw_wave)
+  const int form = (g_pw_wave ? RF_WAVE : 0) | (g_row_views ? RF_ROWS : 0);
+  // the SMALL views by a wavefront each, all stages in one launch (k_rows_wave: a lane per row; k_dedupe_wave: a group of lanes per
+  // row); the launches below leave them alone
+  if (g_pw_wave && g_row_views)
+    LAUNCH(k_rows_wave, (n_views + DW_WAVES - 1) / DW_WAVES, DW_WAVES * WAVE, stream, arena, views, rowidx, n_views, kmer_size, ucodes, gcodes, hashes,
+           ulen, rep_u, rep_g, d_of_row, s_of_row, reps_pos, reps_len, seqrow, occ_off, summary, dc_views);
+  else if (g_pw_wave)
     LAUNCH(k_dedupe_wave, (n_views + DW_WAVES - 1) / DW_WAVES, DW_WAVES * WAVE, stream, arena, views, rowidx, n_views, kmer_size, ucodes, gcodes, hashes,
            ulen, rep_u, rep_g, d_of_row, s_of_row, reps_pos, reps_len, seqrow, occ_off, summary, dc_views);
+  // the NARROW views by a workgroup each with a lane per row, likewise: those of more than RV_ROWS_S rows, then the rest over a quarter of the LDS
+  if (g_row_views) {
+    LAUNCH(k_rows_narrow, n_views, RV_THREADS, stream, arena, views, rowidx, kmer_size, ucodes, gcodes, hashes, ulen, rep_u, rep_g, d_of_row, s_of_row,
+           reps_pos, reps_len, seqrow, occ_off, summary, form, dc_views);
+    LAUNCH(k_rows_narrow_s, n_views, RV_THREADS_S, stream, arena, views, rowidx, kmer_size, ucodes, gcodes, hashes, ulen, rep_u, rep_g, d_of_row, s_of_row,
+           reps_pos, reps_len, seqrow, occ_off, summary, form, dc_views);
+  }
   if (n_work_rows > 0) {
-    LAUNCH(k_ungap_hash, n_work_rows, UG_ROWS, stream, arena, views, rowidx, work_rows, ucodes, hashes, ulen, gcodes, g_pw_wave, dc_rows);
-    LAUNCH(k_ungap_hash_u, n_work_rows, UG_ROWS, stream, views, work_rows, (const uint8_t *)ucodes, hashes, (const int32_t *)ulen, g_pw_wave, dc_rows);
+    LAUNCH(k_ungap_hash, n_work_rows, UG_ROWS, stream, arena, views, rowidx, work_rows, ucodes, hashes, ulen, gcodes, form, dc_rows);
+    LAUNCH(k_ungap_hash_u, n_work_rows, UG_ROWS, stream, views, work_rows, (const uint8_t *)ucodes, hashes, (const int32_t *)ulen, form, dc_rows);
     // views of more rows than k_ungap_dedupe's LDS table holds: their row groups by a scan over (view, 256-row chunk) work items.
     // A list with one chunk per view has no such view; a device-counted list (capacities here) goes by the caller's bound on
     // the rows of a view (max_rows; 0: none known).
@@ -188,7 +205,7 @@ static int d_ungap_dedupe(const uint8_t *arena, const int64_t *views, const int3
              (const int32_t *)ulen, rep_u, rep_g, dc_rows);
   }
   LAUNCH(k_ungap_dedupe, n_views, g_dd_threads, stream, arena, views, rowidx, kmer_size, ucodes, (const uint8_t *)gcodes, hashes, ulen, rep_u, rep_g,
-         d_of_row, s_of_row, reps_pos, reps_len, seqrow, occ_off, summary, g_pw_wave, dc_views);
+         d_of_row, s_of_row, reps_pos, reps_len, seqrow, occ_off, summary, form, dc_views);
   return check_launch("k_ungap_dedupe");
 }
 int mprg_ungap_dedupe(const uint8_t *arena, const int64_t *views, const int32_t *rowidx, int n_views, int kmer_size,
