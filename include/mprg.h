@@ -686,8 +686,22 @@ int mprg_refine_compact(const uint8_t *text, long long text_bytes, const int64_t
  *   leaves it).  `out` must not overlap a source.  status: n_rows int32.  A row is one wavefront.
  * status: MPRG_PG_OK, MPRG_PG_BAD_ITEM (an index, a tile or a source range outside its table or buffer: nothing else written),
  *   MPRG_PG_BAD_OPS (rows: k, W, n and the ops do not fit each other: nothing or part of the row written), MPRG_PG_NO_SPACE (the
- *   output outside its buffer: nothing else written). */
-enum { MPRG_PG_ITEM_FIELDS = 6, MPRG_PG_PAIR_FIELDS = 6, MPRG_PG_ROW_FIELDS = 8,
+ *   output outside its buffer: nothing else written).
+ *
+ * `--progressive --band`: the merges over a certified band of diagonals (the certificate: star_align.py, "Progressive, band").
+ * mprg_align_profile_pairs_banded: mprg_align_profile_pairs over the cells with dlo <= j - i <= dhi (i: X's column, j: Y's); every
+ *   other cell counts as minus infinity in all three states.  The arguments are mprg_align_profile_pairs'; pairs: n_pairs x
+ *   MPRG_PG_BAND_PAIR_FIELDS int64, its six fields, then dlo and dhi.  The band must hold (0, 0) and (n, C), else
+ *   MPRG_AL_BAD_INPUT; workspace need (dlo, dhi clamped to [-n, C]) and the other status codes are mprg_align_pairs_banded's and
+ *   mprg_align_profile_pairs'.  The score is the best over the paths inside the band.
+ * mprg_prog_band_widths: pairs as above (workspace offset, ops offset, dlo and dhi are not read); out: the n_pairs x 3 int32 a
+ *   banded call over the same table wrote.  With B_j = max(P[j][A, C, G, T, amb], Dc[j]), SB = sum_j B_j, LY(k) the sum of the k
+ *   smallest B_j - Dc[j], LX(k) the sum of the k smallest -Ic[i] (k clamped to the number of columns), D = C - n and
+ *   U(w) = SB - LY(max(0, D) + w + 1) - LX(w + 1 - min(0, D)) - 1408, bounds (n_pairs x 2 int64) receives {SB, w* = the smallest w in
+ *   [0, min(n, C)] with U(w) < out's score; min(n, C) if there is none}.  status: n_pairs int32: MPRG_AL_OK, MPRG_AL_BAD_INPUT (the
+ *   leaf, n, R_X out of range, or out's status is not MPRG_AL_OK), MPRG_AL_TOO_LONG, MPRG_AL_NO_SPACE (X's planes outside
+ *   xcols_words); with any other status than MPRG_AL_OK nothing else is written.  One workgroup per merge, 34 KB of LDS. */
+enum { MPRG_PG_ITEM_FIELDS = 6, MPRG_PG_PAIR_FIELDS = 6, MPRG_PG_ROW_FIELDS = 8, MPRG_PG_BAND_PAIR_FIELDS = 8,
        MPRG_PG_OK = 0, MPRG_PG_BAD_ITEM = 1, MPRG_PG_BAD_OPS = 2, MPRG_PG_NO_SPACE = 3 };
 int mprg_prog_distances(const uint8_t *codes, long long codes_bytes, const int64_t *seqs, long long n_seqs, const int64_t *loci,
                         int n_loci, const int32_t *work, int n_work, uint32_t *shared, long long shared_words, int64_t *nw,
@@ -697,6 +711,11 @@ int mprg_prog_columns(const int64_t *bufs, int n_bufs, const int64_t *items, int
 int mprg_align_profile_pairs(const int32_t *profile, const int64_t *leaves, int n_leaves, const int32_t *xcols, long long xcols_words,
                              const int64_t *pairs, int n_pairs, int32_t *workspace, long long workspace_words, uint8_t *ops,
                              long long ops_bytes, int32_t *out, void *stream);
+int mprg_align_profile_pairs_banded(const int32_t *profile, const int64_t *leaves, int n_leaves, const int32_t *xcols,
+                                    long long xcols_words, const int64_t *pairs, int n_pairs, int32_t *workspace,
+                                    long long workspace_words, uint8_t *ops, long long ops_bytes, int32_t *out, void *stream);
+int mprg_prog_band_widths(const int32_t *profile, const int64_t *leaves, int n_leaves, const int32_t *xcols, long long xcols_words,
+                          const int64_t *pairs, int n_pairs, const int32_t *out, int64_t *bounds, int32_t *status, void *stream);
 int mprg_prog_rows(const int64_t *bufs, int n_bufs, const uint8_t *ops, long long ops_bytes, const int64_t *rows, int n_rows,
                    uint8_t *out, long long out_bytes, int ascii, int32_t *status, void *stream);
 

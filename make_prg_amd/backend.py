@@ -109,6 +109,10 @@ SIGNATURES = {
     "mprg_prog_columns": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
     "mprg_align_profile_pairs": (c_int, [c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, ctypes.c_longlong,
                                          c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
+    "mprg_align_profile_pairs_banded": (c_int, [c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p,
+                                                ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
+    "mprg_prog_band_widths": (c_int, [c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_void_p]),
     "mprg_prog_rows": (c_int, [c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_int, c_void_p,
                                c_void_p]),
     "mprg_random_sample_host": (None, [c_uint32, c_int, c_void_p]),

@@ -21,6 +21,7 @@
 #include "k_star.inc"
 #include "k_refine.inc"
 #include "k_prog.inc"
+#include "k_prog_band.inc"
 #include "host_encoders.inc"
 #include "host_batch.inc"
 
@@ -689,6 +690,23 @@ int mprg_align_profile_pairs(const int32_t *profile, const int64_t *leaves, int 
   LAUNCH(k_align_profile_pairs, (n_pairs + AL_WAVES - 1) / AL_WAVES, AL_THREADS, stream, profile, leaves, n_leaves, xcols, xcols_words,
          pairs, n_pairs, workspace, workspace_words, ops, ops_bytes, out);      // a wavefront per pair
   return check_launch("k_align_profile_pairs");
+}
+
+int mprg_align_profile_pairs_banded(const int32_t *profile, const int64_t *leaves, int n_leaves, const int32_t *xcols,
+                                    long long xcols_words, const int64_t *pairs, int n_pairs, int32_t *workspace,
+                                    long long workspace_words, uint8_t *ops, long long ops_bytes, int32_t *out, void *stream) {
+  if (n_pairs <= 0) return 0;
+  LAUNCH(k_align_profile_pairs_banded, (n_pairs + AL_WAVES - 1) / AL_WAVES, AL_THREADS, stream, profile, leaves, n_leaves, xcols,
+         xcols_words, pairs, n_pairs, workspace, workspace_words, ops, ops_bytes, out);      // a wavefront per pair
+  return check_launch("k_align_profile_pairs_banded");
+}
+
+int mprg_prog_band_widths(const int32_t *profile, const int64_t *leaves, int n_leaves, const int32_t *xcols, long long xcols_words,
+                          const int64_t *pairs, int n_pairs, const int32_t *out, int64_t *bounds, int32_t *status, void *stream) {
+  if (n_pairs <= 0) return 0;
+  LAUNCH(k_prog_band_widths, n_pairs, PG_THREADS, stream, profile, leaves, n_leaves, xcols, xcols_words, pairs, n_pairs, out, bounds,
+         status);      // a workgroup per merge
+  return check_launch("k_prog_band_widths");
 }
 
 int mprg_prog_rows(const int64_t *bufs, int n_bufs, const uint8_t *ops, long long ops_bytes, const int64_t *rows, int n_rows,

@@ -8,7 +8,9 @@ With `--adjust-direction`, records on the opposite strand are found and reverse-
 csrc/k_star.inc, C ABI: mprg_star_centres_canonical / mprg_star_strand / mprg_star_revcomp).
 
 With `--progressive` the MSA is built up a guide tree instead of around a centre (Progressive below; kernels in csrc/k_prog.inc,
-C ABI: mprg_prog_distances / mprg_prog_columns / mprg_align_profile_pairs / mprg_prog_rows).
+C ABI: mprg_prog_distances / mprg_prog_columns / mprg_align_profile_pairs / mprg_prog_rows).  With `--band` as well the merges run
+over certified bands of diagonals (Progressive, band below; kernels in csrc/k_prog_band.inc, C ABI: mprg_align_profile_pairs_banded /
+mprg_prog_band_widths): the same MSAs, byte for byte.
 
 It is NOT MAFFT.  PRGs built from these alignments differ from PRGs built from a MAFFT alignment of the same sequences.
 
@@ -109,11 +111,36 @@ a guide tree, profile against profile.  It replaces Centre, Pairs and Merge; Inp
             same score).  |sum| <= 1 280 R_X, so the division is a multiplication and a shift on the device (k_prog.inc, pg_div).
   Output.   The root's rows in input order, the empty records as all-gap rows, titles unchanged.
   Not promised.  Identical input sequences need not give identical rows (two different sequences can have D = 0 and merge between
-            them).  No sequence weighting.  It is not MAFFT.  The merges use the full DP: a certified band for profile-profile
-            pairs needs a bound for X-side columns with Ic above -640, which is separate work; band together with progressive
-            only affects the realignments of refine.  adjust_direction runs first, on the records; refine runs afterwards, on the
-            progressive MSA's text on the device, unchanged.
+            them).  No sequence weighting.  It is not MAFFT.  adjust_direction runs first, on the records; refine runs afterwards,
+            on the progressive MSA's text on the device, unchanged.  With band the merges run over certified bands (below) and
+            the realignments of refine over theirs: the same bytes.
   Invariants (tested): every row with its gaps removed is its input sequence; no column is all gaps.
+
+Progressive, band (only with progressive and band; integers only; tests/progband_ref.py states it in plain Python; kernels:
+csrc/k_prog_band.inc).  The merge's DP over the cells of a band of diagonals, with a certificate that the ops are the full DP's.
+  Notation. X has n = W_X columns and R_X rows, Y has C = W_Y columns; cell (i, j) lies on diagonal d = j - i, Delta = C - n.  'D'
+            (Y's column alone) adds 1 to d, 'I' (X's column alone) subtracts 1.  Band, half-widths, clamping to [-n, C] and the
+            minus infinity outside: profile_align.py, "Band", with the merge's scores in place of the pair's.
+  Bounds.   B_j = max(P[j][A], P[j][C], P[j][G], P[j][T], P[j][amb], Dc[j]), SB = sum_j B_j, loss_j = B_j - Dc[j] >= 0 (at most
+            1 920), ins_i = -Ic[i] >= 0 (at most 640).  LY(k): the sum of the k smallest loss_j, k clamped to C; LX(k): the sum of
+            the k smallest ins_i, k clamped to n.
+  Why B_j bounds a matched column.  s(i, j) is the truncated quotient by R_X of a sum of R_X terms, each one of the six integers
+            above, so the exact quotient is at most B_j; B_j is an integer, so the truncated quotient (a ceiling for negatives) is
+            at most B_j too.  A Y column contributes s(i, j) or Dc[j]; an X column alone contributes Ic[i] <= 0.
+  Upper bound.  A path that touches d* > max(0, Delta) has at least d* D ops, at least d* - Delta I ops and a run of each: it scores
+            at most SB - LY(d*) - LX(d* - Delta) - 1408.  A path that touches d* < min(0, Delta) has at least Delta - d* D ops and
+            -d* I ops: at most SB - LY(Delta - d*) - LX(-d*) - 1408.  (The product form m d* of the pair certificate is useless
+            here: a Y column with one residue among four or more rows has B_j = Dc[j], so the smallest loss is 0 in nearly every
+            merge.)  At half-width w both sides give the same number,
+                U(w) = SB - LY(max(0, Delta) + w + 1) - LX(w + 1 - min(0, Delta)) - 1408,
+            which does not rise with w.  So there is one certified half-width w*: the smallest w >= 0 with U(w) < S0, clamped per
+            side where the band reaches the matrix's edge (w <= n + min(0, Delta) on the minus side, w <= C - max(0, Delta) on the
+            plus side; both are min(n, C), and below it neither k is clamped); a side at the edge is closed.  With R_X = 1 and an
+            ACGT leaf this is the pair certificate in its sorted form.
+  Then      profile_align.py's argument unchanged: with both sides closed the ops and the score are the full DP's; two passes,
+            never a loop: pass 1 with w0 = PROG_BAND_W0 (a tuning constant, not part of the result) gives S0, a merge with w* > w0
+            runs once more with w*; a merge whose band (of pass 1, or of pass 2) does not help, by profile_align.band_helps with
+            n = W_X and C = W_Y, goes to the full DP (mprg_align_profile_pairs).
 
 Progressive, host side: per chunk the distances in launches whose m x m tables fit budget_bytes (loci of three or more leaves), D
 and the tree per locus in NumPy / Python integers (prog_tree: a float64 quotient only shortlists, the choice is exact).  A node's
@@ -122,6 +149,11 @@ whose workspace and column tables fit budget_bytes; per group one mprg_prog_colu
 mprg_align_profile_pairs launch, {status, score, op count} per merge downloaded, one mprg_prog_rows launch that writes the
 parents' texts (cell codes) into a buffer of the group's own; a buffer is dropped when its last node has been merged.  One more
 mprg_prog_rows launch puts the roots' rows into input order as ASCII, where the star pass leaves its text.
+With band the groups are sized by the banded need (pass 1's; the full need for a merge pass 1's band does not help), and per group
+the merges go through: pass 1 (one mprg_align_profile_pairs_banded launch), one mprg_prog_band_widths launch over the same tables
+and pass 1's results, one download of {SB, w*, status} (20 bytes per merge; no histogram or profile leaves the device), pass 2 for
+the merges with w* > w0 and the full DP for the rest, each longest first in launches sized by the budget; a later pass overwrites
+the same ops range.  The {status, score, op count} triples of all launches are downloaded at the end of the group.
 
 Host side: loci in chunks (CHUNK_BYTES of estimated ops and output per chunk); per chunk the centres in one launch, the pairs
 through profile_align.pairs_on_device (longest first, workspace-budget launches, ops left on the device), the widths and column
@@ -162,6 +194,8 @@ REFINE_DEFAULT, REFINE_MAX = 2, 16        # rounds of `--refine` alone, and the 
 PROG_MAX_LEAVES = 4096                    # the spec's leaf limit of a progressive locus
 PROG_SCALE = 1 << 16                      # D = PROG_SCALE - floor(PROG_SCALE s / m)
 PG_ITEM_FIELDS, PG_PAIR_FIELDS, PG_ROW_FIELDS = 6, 6, 8   # MPRG_PG_ITEM_FIELDS, MPRG_PG_PAIR_FIELDS, MPRG_PG_ROW_FIELDS
+PG_BAND_PAIR_FIELDS = 8                   # MPRG_PG_BAND_PAIR_FIELDS
+PROG_BAND_W0 = 64                         # pass 1's half-width of a banded merge (what was tried)
 PG_STATUS = {1: "an index, a tile or a source range outside its table or buffer", 2: "ops, widths and cells that do not fit each other",
              3: "the output outside its buffer"}
 _GAP = ord("-")
@@ -216,8 +250,10 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
     refine: N, the spec's Refinement: up to N accepted rounds per locus (0: none, nothing launches differently).  refinement: a list
     that then receives per locus (rounds accepted, S of the star MSA, S of the result).  timings also receives refine_s; the band
     counters keep adding up across the rounds.
-    progressive: the spec's Progressive instead of the centre-star pass (orientation first, refinement afterwards, both unchanged;
-    band then only affects the refinement).  progression: a list that then receives per locus (leaves, rounds, fell back to star).
+    progressive: the spec's Progressive instead of the centre-star pass (orientation first, refinement afterwards, both unchanged).
+    With band the merges run over certified bands too (True: PROG_BAND_W0, or pass 1's half-width; the same MSAs) and timings
+    also receives prog_band_merges, prog_band_second_passes, prog_band_full_merges (merges sent to the full DP), prog_band_cells
+    (DP cells computed, all passes and the full form) and prog_band_full_cells (W_X W_Y summed).  progression: a list that then receives per locus (leaves, rounds, fell back to star).
     max_leaves: PROG_MAX_LEAVES unless given; a locus with more non-empty records gets the star MSA.  timings also receives tree_s
     (distances and trees) and progressive_s (the merges and the rows)."""
     if not (isinstance(refine, (int, np.integer)) and not isinstance(refine, bool) and 0 <= refine <= REFINE_MAX):
@@ -454,7 +490,8 @@ def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direc
     n_loci = len(codes)
     if progressive:
         t1 = t2 = time.perf_counter()
-        d_out, out_bytes, base, W = _progressive(be, names, lens, seq_off, first, counts, d_codes, codes_bytes, budget_bytes, timings, progression)
+        d_out, out_bytes, base, W = _progressive(be, names, lens, seq_off, first, counts, d_codes, codes_bytes, budget_bytes, timings, progression,
+                                                   None if band is False or band is None else band)
     else:
         t1 = time.perf_counter()
         for l in np.nonzero(centre < 0)[0]:
@@ -619,9 +656,30 @@ def prog_tree(D: np.ndarray, leaves: Sequence[int]) -> List[Tuple[int, int]]:
     return merges
 
 
-def _prog_groups(WX, WY, budget_bytes):
-    """The merges (X's and Y's columns) longest first in groups whose workspace and column tables each fit the budget."""
+def _prog_w0(band):
+    """Pass 1's half-width of the banded merges, or None: the full DP."""
+    if band is None or band is False:
+        return None
+    w0 = PROG_BAND_W0 if band is True else int(band)
+    if w0 < 0:
+        raise StarAlignError("band: a negative half-width")
+    return w0
+
+
+def _prog_need(WX, WY, w0):
+    """What a merge takes of a group's workspace: the full DP's words, or with band pass 1's (the full DP's where its band does
+    not help)."""
     need = pa.workspace_words_v(WX, WY)
+    if w0 is None:
+        return need
+    dlo, dhi = pa.band_limits(WX, WY, w0, w0)
+    return np.where(pa.band_helps(WX, WY, dlo, dhi), pa.band_workspace_words(WX, WY, dlo, dhi), need)
+
+
+def _prog_groups(WX, WY, budget_bytes, band=None):
+    """The merges (X's and Y's columns) longest first in groups whose workspace and column tables each fit the budget; with band
+    the workspace is pass 1's."""
+    need = _prog_need(WX, WY, _prog_w0(band))
     cols = 7 * WX + 6 * WY
     budget_words = max(64, int(budget_bytes) // 4)
     if len(need) and need.max() > budget_words:
@@ -640,9 +698,10 @@ def _prog_groups(WX, WY, budget_bytes):
         pos = end
 
 
-def _prog_pairs(be, d_bufs, n_bufs, X, Y):
+def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUDGET_BYTES, counters=None):
     """One group of merges on the device: X, Y (n, 4) int64 {buffer, offset, R, W} of the two sides' texts.  mprg_prog_columns (Y's
-    profiles, X's column tables) and mprg_align_profile_pairs in one launch each; {status, score, op count} downloaded.
+    profiles, X's column tables) and mprg_align_profile_pairs in one launch each; {status, score, op count} downloaded.  With band
+    the spec's two passes instead (the module docstring, host side), counters receiving the prog_band_* counts.
     Returns (the ops buffer, its bytes, each merge's ops offset, op count, score)."""
     n = len(X)
     WX, WY = X[:, 3], Y[:, 3]
@@ -660,21 +719,95 @@ def _prog_pairs(be, d_bufs, n_bufs, X, Y):
     be.call("mprg_prog_columns", be.ptr(d_bufs), n_bufs, be.ptr(d_items), len(items), be.ptr(d_work), len(work), be.ptr(d_cols), words,
             be.ptr(d_status), be.stream, work=float((items[:, 2] * items[:, 3]).sum()))
     need = pa.workspace_words_v(WX, WY)
-    ws_off = np.concatenate([[0], np.cumsum(need)[:-1]]).astype(np.int64)
     ops_off = np.concatenate([[0], np.cumsum(WX + WY)[:-1]]).astype(np.int64)
     ops_bytes = int((WX + WY).sum())
     leaf_tab = np.stack([np.zeros(n, np.int64), Y[:, 2], WY, ycol], 1).astype(np.int64)
-    pairs = np.stack([np.arange(n), xcol, WX, ws_off, ops_off, X[:, 2]], 1).astype(np.int64)
-    d_leaves, d_pairs = be.upload(leaf_tab), be.upload(pairs)
-    d_ws, d_ops, d_out = be.empty(4 * int(need.sum())), be.empty(ops_bytes), be.empty(12 * n)
-    be.call("mprg_align_profile_pairs", be.ptr(d_cols), be.ptr(d_leaves), n, be.ptr(d_cols), words, be.ptr(d_pairs), n, be.ptr(d_ws),
-            int(need.sum()), be.ptr(d_ops), ops_bytes, be.ptr(d_out), be.stream, work=float(((WX + 63) // 64 * 64 * WY).sum()))
+    d_leaves = be.upload(leaf_tab)
+    d_ops = be.empty(ops_bytes)
+    w0 = _prog_w0(band)
+    if w0 is None:
+        ws_off = np.concatenate([[0], np.cumsum(need)[:-1]]).astype(np.int64)
+        pairs = np.stack([np.arange(n), xcol, WX, ws_off, ops_off, X[:, 2]], 1).astype(np.int64)
+        d_pairs = be.upload(pairs)
+        d_ws, d_out = be.empty(4 * int(need.sum())), be.empty(12 * n)
+        be.call("mprg_align_profile_pairs", be.ptr(d_cols), be.ptr(d_leaves), n, be.ptr(d_cols), words, be.ptr(d_pairs), n, be.ptr(d_ws),
+                int(need.sum()), be.ptr(d_ops), ops_bytes, be.ptr(d_out), be.stream, work=float(((WX + 63) // 64 * 64 * WY).sum()))
+        _pg_check(be.download(d_status, np.int32, len(work)), "mprg_prog_columns")
+        res = be.download(d_out, np.int32, 3 * n).reshape(-1, 3)
+        bad = np.nonzero(res[:, 0])[0]
+        if len(bad):
+            raise StarAlignError(f"mprg_align_profile_pairs: {pa.STATUS.get(int(res[bad[0], 0]), int(res[bad[0], 0]))}")
+        return d_ops, ops_bytes, ops_off, res[:, 2].astype(np.int64), res[:, 1].astype(np.int64)
+    budget_words = max(64, int(budget_bytes) // 4)
+    pending = []                                                # (merges, call, the launch's triples, its table): downloaded at the end
+
+    def launches(call, idx, wordsv, dlo=None, dhi=None):
+        """The merges idx (longest first) through `call` in launches that fit the workspace budget."""
+        if len(idx) and wordsv[idx].max() > budget_words:
+            k = idx[int(wordsv[idx].argmax())]
+            raise StarAlignError(f"a merge of {WX[k]} columns against {WY[k]} needs {4 * wordsv[k]} bytes of traceback, more than the "
+                                 f"workspace budget of {budget_bytes}")
+        pos = 0
+        while pos < len(idx):
+            end, used = pos, 0
+            while end < len(idx) and used + wordsv[idx[end]] <= budget_words:
+                used += int(wordsv[idx[end]])
+                end += 1
+            sel = idx[pos:end]
+            ws_off = np.concatenate([[0], np.cumsum(wordsv[sel])[:-1]])
+            fields = [sel, xcol[sel], WX[sel], ws_off, ops_off[sel], X[sel, 2]] + ([] if dlo is None else [dlo[sel], dhi[sel]])
+            d_pairs = be.upload(np.stack(fields, 1).astype(np.int64))
+            d_ws, d_out = be.empty(4 * used), be.empty(12 * len(sel))
+            cells = (WX[sel] + 63) // 64 * 64 * (WY[sel] if dlo is None else np.minimum(WY[sel], dhi[sel] - dlo[sel] + 64))
+            be.call(call, be.ptr(d_cols), be.ptr(d_leaves), n, be.ptr(d_cols), words, be.ptr(d_pairs), len(sel), be.ptr(d_ws), used,
+                    be.ptr(d_ops), ops_bytes, be.ptr(d_out), be.stream, work=float(cells.sum()))
+            pending.append((sel, call, d_out, d_pairs))
+            pos = end
+    dlo, dhi = pa.band_limits(WX, WY, w0, w0)
+    full = ~pa.band_helps(WX, WY, dlo, dhi)
+    first = np.nonzero(~full)[0]
+    cells = pa.band_cells(WX, WY, dlo, dhi)
+    first = first[np.argsort(-cells[first], kind="stable")]
+    wstar = np.zeros(n, np.int64)
+    if len(first):
+        # pass 1: one launch where the group was sized by its need; the widths over the same table and its triples
+        launches("mprg_align_profile_pairs_banded", first, pa.band_workspace_words(WX, WY, dlo, dhi), dlo, dhi)
+        for sel, _, d_out, d_pairs in list(pending):
+            d_got = be.empty(20 * len(sel))                     # {SB, w*} per merge, then the status words
+            be.call("mprg_prog_band_widths", be.ptr(d_cols), be.ptr(d_leaves), n, be.ptr(d_cols), words, be.ptr(d_pairs), len(sel),
+                    be.ptr(d_out), be.ptr(d_got), be.ptr(d_got) + 16 * len(sel), be.stream, work=float((WX[sel] + WY[sel]).sum()))
+            got = be.download(d_got, np.uint8, 20 * len(sel))
+            status = got[16 * len(sel):].view(np.int32)
+            if status.any():
+                _pg_check(be.download(d_status, np.int32, len(work)), "mprg_prog_columns")
+                res = be.download(d_out, np.int32, 3 * len(sel)).reshape(-1, 3)
+                code = int(res[res[:, 0] != 0][0, 0]) if res[:, 0].any() else int(status[status != 0][0])
+                raise StarAlignError(f"mprg_align_profile_pairs_banded / mprg_prog_band_widths: {pa.STATUS.get(code, code)}")
+            wstar[sel] = got[:16 * len(sel)].view(np.int64).reshape(-1, 2)[:, 1]
+    again = ~full & (wstar > w0)
+    dlo2, dhi2 = pa.band_limits(WX, WY, wstar, wstar)
+    dlo, dhi = np.where(again, dlo2, dlo), np.where(again, dhi2, dhi)
+    full |= again & ~pa.band_helps(WX, WY, dlo, dhi)
+    second = np.nonzero(again & ~full)[0]
+    cells2 = pa.band_cells(WX, WY, dlo, dhi)
+    launches("mprg_align_profile_pairs_banded", second[np.argsort(-cells2[second], kind="stable")],
+             pa.band_workspace_words(WX, WY, dlo, dhi), dlo, dhi)
+    rest = np.nonzero(full)[0]
+    launches("mprg_align_profile_pairs", rest[np.argsort(-((WX[rest] + 1) * WY[rest]), kind="stable")], need)
     _pg_check(be.download(d_status, np.int32, len(work)), "mprg_prog_columns")
-    res = be.download(d_out, np.int32, 3 * n).reshape(-1, 3)
-    bad = np.nonzero(res[:, 0])[0]
-    if len(bad):
-        raise StarAlignError(f"mprg_align_profile_pairs: {pa.STATUS.get(int(res[bad[0], 0]), int(res[bad[0], 0]))}")
-    return d_ops, ops_bytes, ops_off, res[:, 2].astype(np.int64), res[:, 1].astype(np.int64)
+    count, score = np.zeros(n, np.int64), np.zeros(n, np.int64)
+    for sel, call, d_out, _ in pending:                          # in launch order: a later pass's result replaces pass 1's
+        res = be.download(d_out, np.int32, 3 * len(sel)).reshape(-1, 3)
+        bad = np.nonzero(res[:, 0])[0]
+        if len(bad):
+            raise StarAlignError(f"{call}: {pa.STATUS.get(int(res[bad[0], 0]), int(res[bad[0], 0]))}")
+        score[sel], count[sel] = res[:, 1], res[:, 2]
+    if counters is not None:
+        for key, v in (("prog_band_merges", n), ("prog_band_second_passes", len(second)), ("prog_band_full_merges", len(rest)),
+                       ("prog_band_cells", cells[first].sum() + cells2[second].sum() + (WX[rest] * WY[rest]).sum()),
+                       ("prog_band_full_cells", (WX * WY).sum())):
+            counters[key] = counters.get(key, 0) + int(v)
+    return d_ops, ops_bytes, ops_off, count, score
 
 
 def _bufs_table(be, bufs):
@@ -682,9 +815,11 @@ def _bufs_table(be, bufs):
     return be.upload(np.array([[be.ptr(b), n] if b is not None else [0, 0] for b, n in bufs], np.int64))
 
 
-def merge_profiles(backend, pairs: Sequence[Tuple[np.ndarray, np.ndarray]], budget_bytes: int = pa.DEFAULT_BUDGET_BYTES):
+def merge_profiles(backend, pairs: Sequence[Tuple[np.ndarray, np.ndarray]], budget_bytes: int = pa.DEFAULT_BUDGET_BYTES, band=None,
+                   counters: Optional[dict] = None):
     """mprg_align_profile_pairs on (X, Y) pairs of cell-code matrices (R_X x W_X, R_Y x W_Y), through the launches a round of
-    merges makes: per pair (ops as bytes over b"MID" in forward order, score)."""
+    merges makes: per pair (ops as bytes over b"MID" in forward order, score).  band (True: PROG_BAND_W0, or pass 1's half-width):
+    the spec's banded two passes, the same results; counters then receives the prog_band_* counts (added up)."""
     be = backend
     mats = [m for xy in pairs for m in xy]
     off = np.concatenate([[0], np.cumsum([m.size for m in mats])]).astype(np.int64)
@@ -694,15 +829,15 @@ def merge_profiles(backend, pairs: Sequence[Tuple[np.ndarray, np.ndarray]], budg
     X = np.array([[0, off[2 * k], *pairs[k][0].shape] for k in range(len(pairs))], np.int64).reshape(-1, 4)
     Y = np.array([[0, off[2 * k + 1], *pairs[k][1].shape] for k in range(len(pairs))], np.int64).reshape(-1, 4)
     out = [None] * len(pairs)
-    for grp in _prog_groups(X[:, 3], Y[:, 3], budget_bytes):
-        d_ops, ops_bytes, ops_off, count, score = _prog_pairs(be, d_bufs, 1, X[grp], Y[grp])
+    for grp in _prog_groups(X[:, 3], Y[:, 3], budget_bytes, band):
+        d_ops, ops_bytes, ops_off, count, score = _prog_pairs(be, d_bufs, 1, X[grp], Y[grp], band, budget_bytes, counters)
         ops = be.download(d_ops, np.uint8, ops_bytes)
         for i, k in enumerate(grp.tolist()):
             out[k] = (ops[ops_off[i]:ops_off[i] + count[i]][::-1].tobytes(), int(score[i]))
     return out
 
 
-def _progressive(be, names, lens, seq_off, first, counts, d_codes, codes_bytes, budget_bytes, timings, progression):
+def _progressive(be, names, lens, seq_off, first, counts, d_codes, codes_bytes, budget_bytes, timings, progression, band=None):
     """The spec's Progressive over one chunk, on the (oriented) sequences in d_codes.  Returns what the star pass leaves: the
     device buffer of the MSAs' ASCII text, its bytes, each locus's offset in it and its width."""
     import time
@@ -745,10 +880,10 @@ def _progressive(be, names, lens, seq_off, first, counts, d_codes, codes_bytes, 
         todo = by_round[r]
         Y = np.array([where[l, y] for l, y, _, _ in todo], np.int64)
         X = np.array([where[l, x] for l, _, x, _ in todo], np.int64)
-        for grp in _prog_groups(X[:, 3], Y[:, 3], budget_bytes):
+        for grp in _prog_groups(X[:, 3], Y[:, 3], budget_bytes, band):
             d_bufs = _bufs_table(be, bufs)
             Xg, Yg = X[grp], Y[grp]
-            d_ops, ops_bytes, ops_off, count, _ = _prog_pairs(be, d_bufs, len(bufs), Xg, Yg)
+            d_ops, ops_bytes, ops_off, count, _ = _prog_pairs(be, d_bufs, len(bufs), Xg, Yg, band, budget_bytes, timings)
             RY, RX = Yg[:, 2], Xg[:, 2]
             R = RY + RX
             poff = np.concatenate([[0], np.cumsum(R * count)[:-1]]).astype(np.int64)

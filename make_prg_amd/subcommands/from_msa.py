@@ -64,7 +64,8 @@ def register_parser(subparsers):
                    help="(this implementation) with --unaligned: the pair alignments are computed over a band of diagonals that a "
                         "certificate proves wide enough (two passes; make_prg_amd/update/profile_align.py): the same MSAs and PRGs, "
                         "byte for byte, from a fraction of the DP cells and of the traceback memory, and pairs too long for the "
-                        "full matrix are accepted.  Off by default")
+                        "full matrix are accepted; with --progressive the profile-profile merges run over certified bands too "
+                        "(star_align.py, Progressive, band).  Off by default")
     p.add_argument("--refine", dest="refine", action="store", type=int, nargs="?", const=2, default=None, metavar="N",
                    help="(this implementation) with --unaligned: every locus's centre-star MSA gets up to N rounds (1-16; --refine "
                         "alone: 2) of leave-one-out refinement on the GPU before it is written: every row is realigned against the "
@@ -75,8 +76,8 @@ def register_parser(subparsers):
     p.add_argument("--progressive", dest="progressive", action="store_true", default=False,
                    help="(this implementation) with --unaligned: every locus's MSA is built progressively on the GPU instead of "
                         "centre-star: an exact UPGMA guide tree from 6-mer distances, then profile-profile merges up the tree "
-                        "(star_align.py, Progressive); NOT MAFFT.  --adjust-direction runs first, --refine afterwards, --band then "
-                        "only affects the refinement; a locus of more than 4096 non-empty records gets the centre-star MSA.  "
+                        "(star_align.py, Progressive); NOT MAFFT.  --adjust-direction runs first, --refine afterwards, --band computes "
+                        "the merges (and the refinement's realignments) over certified bands, the same bytes; a locus of more than 4096 non-empty records gets the centre-star MSA.  "
                         "Off by default")
     p.set_defaults(func=run, check=check_options)
     return p
@@ -618,6 +619,10 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
         logger.info(f"rank {rank}: --band: {counters.get('band_pairs', 0)} pairs, {counters.get('band_second_passes', 0)} second passes, "
                     f"{counters.get('band_full_pairs', 0)} sent to the full DP, {counters.get('band_cells', 0)} of "
                     f"{counters.get('band_full_cells', 0)} DP cells computed")
+    if band and progressive:
+        logger.info(f"rank {rank}: --progressive --band: {counters.get('prog_band_merges', 0)} merges, "
+                    f"{counters.get('prog_band_second_passes', 0)} second passes, {counters.get('prog_band_full_merges', 0)} sent to the "
+                    f"full DP, {counters.get('prog_band_cells', 0)} of {counters.get('prog_band_full_cells', 0)} DP cells computed")
     if refine:
         logger.info(f"rank {rank}: --refine {refine}: {sum(1 for a, _, _ in refinement if a)} loci refined, "
                     f"{sum(a for a, _, _ in refinement)} rounds accepted, {sum(1 for a, _, _ in refinement if not a)} loci left as the star MSA")

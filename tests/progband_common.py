@@ -1,0 +1,367 @@
+"""What the emulated and the GPU tests of `from_msa --unaligned --progressive --band` share (the spec: star_align.py, "Progressive,
+band"; its plain-Python statement: tests/progband_ref.py): the banded kernel against the reference banded DP on prog_common's
+shapes, the widths kernel against the linear search around every threshold, two-pass merges and whole MSAs against the UNBANDED
+references with the counters of the reference's two-pass rule, the closedness property, and the status codes of the two entries."""
+import functools
+import random
+from collections import Counter
+
+import numpy as np
+
+from make_prg_amd.from_msa import star_align as sa
+from make_prg_amd.update import profile_align as pa
+from tests import band_ref as br
+from tests import prog_common as pc
+from tests import prog_ref as pr
+from tests import progband_ref as pbr
+from tests import refine_ref as rr
+from tests import star_ref as sr
+
+WIDTHS = (1, 2, 63, 64, 65, 127, 128, 129)        # W = dhi - dlo + 1: around the strip, the ring and the row buffer's rounding
+W0 = 6                                            # pass 1's half-width in the two-pass tests: small, so that every kind occurs
+
+
+# ---- the two entries on explicit tables
+class Tables:
+    """mprg_prog_columns over (X, Y) pairs of row-string tuples, as a round of merges lays them out: what both entries read."""
+
+    def __init__(self, be, pairs):
+        self.be, self.n = be, len(pairs)
+        mats = [pc.codes(m) for xy in pairs for m in xy]
+        off = np.concatenate([[0], np.cumsum([m.size for m in mats])]).astype(np.int64)
+        text = np.concatenate([m.reshape(-1) for m in mats])
+        self.d_text = be.upload(text)
+        d_bufs = be.upload(np.array([[be.ptr(self.d_text), len(text)]], np.int64))
+        n = self.n
+        X = np.array([[0, off[2 * k], *mats[2 * k].shape] for k in range(n)], np.int64).reshape(-1, 4)
+        Y = np.array([[0, off[2 * k + 1], *mats[2 * k + 1].shape] for k in range(n)], np.int64).reshape(-1, 4)
+        self.WX, self.WY, self.RX = X[:, 3], Y[:, 3], X[:, 2]
+        self.ycol = np.concatenate([[0], np.cumsum(6 * self.WY + 7 * self.WX)[:-1]]).astype(np.int64)
+        self.xcol = self.ycol + 6 * self.WY
+        self.words = int((6 * self.WY + 7 * self.WX).sum())
+        items = np.zeros((2 * n, sa.PG_ITEM_FIELDS), np.int64)
+        items[:n, :4], items[:n, 4], items[:n, 5] = Y, 0, self.ycol
+        items[n:, :4], items[n:, 4], items[n:, 5] = X, 1, self.xcol
+        work = sa._tile_work(items[:, 3])
+        self.d_cols, d_status = be.empty(4 * self.words), be.empty(4 * len(work))
+        d_items, d_work = be.upload(items), be.upload(work)
+        be.call("mprg_prog_columns", be.ptr(d_bufs), 1, be.ptr(d_items), len(items), be.ptr(d_work), len(work),
+                be.ptr(self.d_cols), self.words, be.ptr(d_status), be.stream)
+        assert not be.download(d_status, np.int32, len(work)).any()
+        self.d_leaves = be.upload(np.stack([np.zeros(n, np.int64), Y[:, 2], self.WY, self.ycol], 1).astype(np.int64))
+        self.ops_off = np.concatenate([[0], np.cumsum(self.WX + self.WY)[:-1]]).astype(np.int64)
+
+    def pair_rows(self, idx, dlo, dhi, ws_off=None):
+        idx = np.asarray(idx, np.int64)
+        z = np.zeros(len(idx), np.int64)
+        return np.stack([idx, self.xcol[idx], self.WX[idx], z if ws_off is None else ws_off, self.ops_off[idx], self.RX[idx],
+                         np.asarray(dlo, np.int64), np.asarray(dhi, np.int64)], 1).astype(np.int64)
+
+    def banded(self, bands):
+        """Every pair over its (dlo, dhi), one launch: [(ops forward, score)]."""
+        be, n = self.be, self.n
+        dlo, dhi = np.array([b[0] for b in bands], np.int64), np.array([b[1] for b in bands], np.int64)
+        need = pa.band_workspace_words(self.WX, self.WY, np.maximum(dlo, -self.WX), np.minimum(dhi, self.WY))
+        ws_off = np.concatenate([[0], np.cumsum(need)[:-1]]).astype(np.int64)
+        ops_bytes = int((self.WX + self.WY).sum())
+        d_ws, d_ops, d_out = be.empty(4 * int(need.sum())), be.empty(ops_bytes), be.empty(12 * n)
+        d_pairs = be.upload(self.pair_rows(np.arange(n), dlo, dhi, ws_off))
+        be.call("mprg_align_profile_pairs_banded", be.ptr(self.d_cols), be.ptr(self.d_leaves), n, be.ptr(self.d_cols), self.words,
+                be.ptr(d_pairs), n, be.ptr(d_ws), int(need.sum()), be.ptr(d_ops), ops_bytes,
+                be.ptr(d_out), be.stream)
+        res = be.download(d_out, np.int32, 3 * n).reshape(-1, 3)
+        assert not res[:, 0].any(), res[:, 0]
+        ops = be.download(d_ops, np.uint8, ops_bytes)
+        return [(ops[o:o + k][::-1].tobytes().decode(), int(s)) for o, k, s in zip(self.ops_off, res[:, 2], res[:, 1])]
+
+    def widths(self, idx, S0):
+        """mprg_prog_band_widths for the pairs idx (repeats allowed) with the pass-1 scores S0: (SB, w*) per entry."""
+        be, m = self.be, len(idx)
+        out = np.zeros((m, 3), np.int32)
+        out[:, 1] = S0
+        d_bounds, d_status = be.empty(16 * m), be.empty(4 * m)
+        z = np.zeros(m, np.int64)
+        d_pairs, d_out = be.upload(self.pair_rows(idx, z, z)), be.upload(out)
+        be.call("mprg_prog_band_widths", be.ptr(self.d_cols), be.ptr(self.d_leaves), self.n, be.ptr(self.d_cols), self.words,
+                be.ptr(d_pairs), m, be.ptr(d_out), be.ptr(d_bounds), be.ptr(d_status), be.stream)
+        assert not be.download(d_status, np.int32, m).any()
+        return be.download(d_bounds, np.int64, 2 * m).reshape(-1, 2)
+
+
+# ---- the banded kernel against the reference banded DP
+def _bands(k, n, C):
+    """A band for case k of the shapes: the half-width pairs in turn (exact corridor, one-sided, narrow, around w0, far beyond the
+    matrix on either or both sides)."""
+    wm, wp = ((0, 0), (1, 0), (0, 1), (5, 9), (40, 23), (64, 64), (10 ** 6, 0), (0, 10 ** 6), (10 ** 6, 10 ** 6), (3, 3))[k % 10]
+    return min(0, C - n) - wm, max(0, C - n) + wp
+
+
+@functools.lru_cache(maxsize=None)
+def kernel_cases():
+    """((X, Y), (dlo, dhi), the reference banded (ops, score), the full DP's score): prog_common's dp_cases (W_X x W_Y of its
+    lists, rows 1, 2, 3, 7, mostly-gap columns, ambiguity codes) each with a band of _bands, then one case per width of WIDTHS."""
+    out = []
+    for k, ((X, Y), full) in enumerate(pc.dp_cases()):
+        band = _bands(k, len(X[0]), len(Y[0]))
+        out.append(((X, Y), band, pbr.align_profiles_banded_np(X, Y, *band), full[1]))
+    rng = random.Random(23)
+    # W = |Delta| + 1 + extra: (W_X, W_Y, extra below the corridor, extra above it)
+    for k, (wx, wy, lo, hi) in enumerate(((128, 128, 0, 0), (129, 128, 0, 0), (128, 129, 0, 0), (65, 127, 0, 0), (127, 65, 0, 0),
+                                          (64, 127, 0, 0), (63, 127, 0, 0), (200, 300, 13, 13), (1, 127, 0, 0), (300, 200, 14, 13),
+                                          (1, 128, 0, 0), (200, 300, 14, 14), (1, 129, 0, 0), (129, 1, 0, 0), (64, 300, 20, 0),
+                                          (130, 130, 32, 31), (130, 130, 64, 63), (130, 130, 0, 1))):
+        X = tuple(pr.random_profiles(rng, pc.ROWS[k % 4], wx, (0.1, 0.6)[k % 2], amb=0.05))
+        Y = tuple(pr.random_profiles(rng, pc.ROWS[(k + 1) % 4], wy, (0.1, 0.3, 0.7)[k % 3], amb=0.05))
+        band = (min(0, wy - wx) - lo, max(0, wy - wx) + hi)
+        out.append(((X, Y), band, pbr.align_profiles_banded_np(X, Y, *band), pr.align_profiles_np(X, Y)[1]))
+    return out
+
+
+def check_kernel(be):
+    cases = kernel_cases()
+    shape = lambda xy: (len(xy[0][0]), len(xy[1][0]))      # noqa: E731
+    clamped = [br.clamp(*shape(xy), *b) for xy, b, _, _ in cases]
+    # what the cases cover, asserted: every width, Delta of both signs and 0, bands clamped at -n and at C and at neither, column 0
+    # of row 1 in and out of the band, and bands too narrow for the optimum
+    assert {hi - lo + 1 for lo, hi in clamped} >= set(WIDTHS)
+    assert {np.sign(shape(xy)[1] - shape(xy)[0]) for xy, _, _, _ in cases} == {-1, 0, 1}
+    assert any(lo == -shape(xy)[0] and b[0] < lo for (xy, b, _, _), (lo, hi) in zip(cases, clamped))
+    assert any(hi == shape(xy)[1] and b[1] > hi for (xy, b, _, _), (lo, hi) in zip(cases, clamped))
+    assert any(lo > -shape(xy)[0] and hi < shape(xy)[1] for (xy, _, _, _), (lo, hi) in zip(cases, clamped))
+    assert any(lo == 0 and shape(xy)[0] > 1 for (xy, _, _, _), (lo, hi) in zip(cases, clamped)) and any(lo <= -2 for lo, _ in clamped)
+    assert sum(want[1] < full for _, _, want, full in cases) >= 10 and any(want[1] == full for _, _, want, full in cases)
+    got = Tables(be, [xy for xy, _, _, _ in cases]).banded([b for _, b, _, _ in cases])
+    for (xy, b, want, _), g in zip(cases, got):
+        assert g == want, (shape(xy), len(xy[0]), len(xy[1]), b)
+
+
+# ---- the widths kernel against the linear search
+@functools.lru_cache(maxsize=None)
+def width_cases():
+    """(X, Y) with Delta > 0, = 0 and < 0; Y's of four and more rows whose columns mostly hold one residue (loss 0); X's of 40 rows
+    with mostly-gap columns (ins_i from 16 up); 1-row sides (every loss 1 920, every ins 640); a 1 x 1 merge."""
+    rng = random.Random(5)
+    shapes = ((1, 90, 1, 90), (1, 90, 1, 70), (1, 70, 1, 90), (3, 150, 7, 100), (2, 100, 7, 150), (40, 120, 4, 120), (40, 60, 40, 200),
+              (7, 200, 5, 60), (1, 1, 1, 1), (2, 1, 3, 40), (3, 40, 2, 1))
+    out = []
+    for k, (rx, wx, ry, wy) in enumerate(shapes):
+        X = tuple(pr.random_profiles(rng, rx, wx, 0.93 if rx == 40 else (0.1, 0.5)[k % 2], amb=0.03))
+        Y = tuple(pr.random_profiles(rng, ry, wy, 0.8 if ry >= 4 else 0.2, amb=0.03))
+        out.append((X, Y))
+    return out
+
+
+def check_widths(be):
+    cases = width_cases()
+    idx, S0, want = [], [], []
+    zero_loss = small_ins = 0
+    for k, (X, Y) in enumerate(cases):
+        n, C = len(X[0]), len(Y[0])
+        SB, loss, ins = pbr.bounds(X, Y)
+        assert SB == br.bounds(Y)[0] and loss == br.bounds(Y)[1]
+        zero_loss += loss.count(0) >= C // 3
+        small_ins += 0 < ins[0] <= 32
+        top = min(n, C)
+        scores = {SB + 5000, -10 ** 8}
+        for w in sorted({0, 1, 2, 3, top // 3, top // 2, top - 2, top - 1, top} & set(range(top + 1))):
+            u = pbr.U(SB, loss, ins, n, C, w)
+            scores |= {u - 1, u, u + 1}                         # at, one below and one above the threshold
+        for s in sorted(scores):
+            idx.append(k)
+            S0.append(s)
+            want.append((SB, pbr.wstar(SB, loss, ins, n, C, s)))
+    assert zero_loss >= 3 and small_ins >= 2
+    deltas = {np.sign(len(Y[0]) - len(X[0])) for X, Y in cases}
+    assert deltas == {-1, 0, 1} and len({w for _, w in want}) >= 30
+    got = Tables(be, cases).widths(idx, S0)
+    for k, s, w, g in zip(idx, S0, want, got.tolist()):
+        assert tuple(g) == w, (k, s)
+
+
+# ---- two passes
+@functools.lru_cache(maxsize=None)
+def related_cases():
+    """(X, Y) that do share an alignment: the two children of the root of progressive MSAs of near-identical, moderately and
+    strongly diverged loci, so that the reference's two-pass rule with W0 certifies some in pass 1, sends some through a second
+    pass and some to the full DP; with the unbanded reference result."""
+    out = []
+    for seed, (sub, indel), L, m in ((1, (0.01, 0.003), 260, 6), (2, (0.01, 0.003), 300, 5), (3, (0.03, 0.02), 260, 6), (4, (0.05, 0.03), 300, 7),
+                                     (5, (0.06, 0.03), 280, 4), (6, (0.02, 0.01), 150, 8), (7, (0.3, 0.1), 200, 4), (8, (0.0, 0.0), 120, 3)):
+        rng = random.Random(seed)
+        root = "".join(rng.choice("ACGT") for _ in range(L))
+        seqs = [sr.mutate(rng, root, sub, indel) for _ in range(m)]
+        X = tuple(pr.progressive_rows(seqs[:m // 3 + 1]))
+        Y = tuple(pr.progressive_rows(seqs[m // 3 + 1:]))
+        if seed == 6:                                           # a long end gap: Delta far from 0
+            X = tuple(r[:70] for r in X)
+            X = tuple(pr.progressive_rows([r.replace("-", "") or "A" for r in X]))
+        out.append(((X, Y), pr.align_profiles_np(X, Y)))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def two_pass_spec():
+    """The reference's (kind, cells) per merge of dp_cases + related_cases with W0, and the merges' (n, C)."""
+    cases = [xy for xy, _ in pc.dp_cases()] + [xy for xy, _ in related_cases()]
+    res = [pbr.two_pass(X, Y, W0) for X, Y in cases]
+    want = [w for _, w in pc.dp_cases()] + [w for _, w in related_cases()]
+    assert [r for r, _, _ in res] == want                       # the reference's own two passes give the unbanded result
+    return [(k, c) for _, k, c in res], [(len(X[0]), len(Y[0])) for X, Y in cases]
+
+
+def check_two_pass_merges(be):
+    cases = pc.dp_cases() + related_cases()
+    log, sizes = two_pass_spec()
+    kinds = Counter(k for k, _ in log)
+    assert kinds["first"] >= 2 and kinds["second"] >= 2 and kinds["full"] >= 2, kinds
+    pairs = [(pc.codes(x), pc.codes(y)) for (x, y), _ in cases]
+    small = 4 * int(max(pa.workspace_words(n, C) for n, C in sizes))         # the largest full DP alone: every pass in several launches
+    for budget in (pa.DEFAULT_BUDGET_BYTES, small):
+        counters = {}
+        got = sa.merge_profiles(be, pairs, budget_bytes=budget, band=W0, counters=counters)
+        for ((x, y), want), (ops, score) in zip(cases, got):
+            assert (ops.decode(), score) == want, (len(x), len(x[0]), len(y), len(y[0]))
+        assert counters == pbr.counters(log, sizes)
+    assert sa.merge_profiles(be, pairs[-3:], band=None) == got[-3:]
+    pc.check_dp(be, band=True)                                  # the default w0
+
+
+def counter_loci():
+    return sr.edge_loci() + [rr.diverged_locus(1, 8), pr.clade_locus(2, 8), pr.clade_locus(3, 9, clades=3)] + near_loci()
+
+
+def near_loci():
+    out = []
+    for seed in (40, 41):
+        rng = random.Random(seed)
+        root = "".join(rng.choice("ACGT") for _ in range(240))
+        out.append([sr.mutate(rng, root, 0.01, 0.003) for _ in range(7)])
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def counter_spec():
+    res = [pbr.progressive(l, W0) for l in counter_loci()]
+    assert [r[0] for r in res] == [pr.progressive_rows(l) for l in counter_loci()]
+    return pbr.counters([kc for r in res for kc in r[2]], [nc for r in res for nc in r[3]]), Counter(k for r in res for k, _ in r[2])
+
+
+def check_msas(be):
+    pc.check_msas(be, band=W0)                                  # msa_loci() against the unbanded reference, rows and rounds
+    pc.check_msas(be, band=W0, budget_bytes=4 * pa.workspace_words(420, 420), chunk_bytes=1 << 14)
+    want, kinds = counter_spec()
+    assert kinds["first"] >= 2 and kinds["second"] >= 2 and kinds["full"] >= 2, kinds
+    loci = counter_loci()
+    for kw in (dict(), dict(budget_bytes=4 * pa.workspace_words(330, 330))):
+        timings = {}
+        msas = sa.star_msas(be, [pc.records(l) for l in loci], progressive=True, band=W0, timings=timings, **kw)
+        assert [m.rows_as_strings() for m in msas] == [pr.progressive_rows(l) for l in loci]
+        assert {k: v for k, v in timings.items() if k.startswith("prog_band_")} == want
+    for kw in (dict(progressive=True), dict(band=W0)):          # one flag alone: no banded merge, no counter
+        timings = {}
+        sa.star_msas(be, [pc.records(l) for l in loci[:4]], timings=timings, **kw)
+        assert not any(k.startswith("prog_band_") for k in timings)
+
+
+def check_compositions(be):
+    """prog_common.check_compositions (whose band=True now bands the merges too) once more with W0, so that merges of every kind
+    occur: --adjust-direction first, two rounds of --refine afterwards, against the unbanded reference composition."""
+    recs = [pc.records(l) for l in pc.flipped_loci()]
+    info, timings = [], {}
+    msas = sa.star_msas(be, recs, progressive=True, adjust_direction=True, refine=2, refinement=info, band=W0, timings=timings)
+    for m, got, (t, _, (rows, acc, trail)) in zip(msas, info, pc.flipped_spec()):
+        assert m.descriptions == t and m.rows_as_strings() == rows and got == (acc, trail[0], trail[-1])
+    assert timings["prog_band_merges"] == sum(sum(1 for s in l if s) - 1 for l in pc.flipped_loci())
+    assert 0 < timings["prog_band_full_merges"] < timings["prog_band_merges"] and timings["band_pairs"] > 0
+
+
+# ---- the property
+def check_property(be):
+    """Random profile pairs, related and not, with random bands: whenever the certificate closes both sides of the band, the banded
+    ops and score are the full DP's."""
+    rng = random.Random(77)
+    cases, bands = [], []
+    for k in range(40):
+        L = rng.randint(20, 140)
+        root = "".join(rng.choice("ACGT") for _ in range(L))
+        sub, indel = rng.choice([(0.0, 0.0), (0.02, 0.01), (0.05, 0.04), (0.2, 0.1)])
+        rows = pr.progressive_rows([sr.mutate(rng, root, sub, indel) or "A" for _ in range(rng.randint(2, 6))])
+        cut = rng.randint(1, len(rows) - 1)
+        X, Y = [tuple(pr.progressive_rows([r.replace("-", "") or "A" for r in part])) for part in (rows[:cut], rows[cut:])]
+        if k % 5 == 0:
+            X = tuple(pr.random_profiles(rng, len(X), len(X[0]), 0.3))
+        n, C = len(X[0]), len(Y[0])
+        cases.append((X, Y))
+        bands.append((min(0, C - n) - rng.choice([0, 1, 3, 8, 20, 200]), max(0, C - n) + rng.choice([0, 1, 3, 8, 20, 200])))
+    got = Tables(be, cases).banded(bands)
+    n_closed = n_open = n_below = 0
+    for (X, Y), b, g in zip(cases, bands, got):
+        n, C = len(X[0]), len(Y[0])
+        full = pr.align_profiles_np(X, Y)
+        assert g[1] <= full[1]
+        if all(pbr.closed(*pbr.bounds(X, Y), n, C, *b, g[1])):
+            n_closed += 1
+            assert g == full, (n, C, b)
+        else:
+            n_open += 1
+            n_below += g[1] < full[1]
+    assert n_closed >= 8 and n_open >= 8 and n_below >= 3, (n_closed, n_open, n_below)
+
+
+# ---- status codes
+def check_abi_statuses(be):
+    """The two entries, handed tables that point outside their buffers or bands that miss a corner, report their status code and
+    write nothing else."""
+    POISON = 0x5C
+    X, Y = ("AC-T", "A-GT"), ("ACGTA", "AC-TA", "ACGTN")
+    t = Tables(be, [(X, Y)])
+    assert (t.words, int(t.xcol[0])) == (58, 30)
+
+    def untouched(buf, n):
+        return (be.download(buf, np.uint8, n) == POISON).all()
+
+    def pairs(pair, leaf=(0, 3, 5, 0), xwords=58, ws_words=None, ops_bytes=9):
+        need = int(pa.band_workspace_words(4, 5, -4, 5))
+        d_ws, d_ops, d_out = be.full(4 * need, POISON), be.full(9, POISON), be.full(12, POISON)
+        d_leaves, d_pairs = be.upload(np.array([leaf], np.int64)), be.upload(np.array([pair], np.int64))
+        be.call("mprg_align_profile_pairs_banded", be.ptr(t.d_cols), be.ptr(d_leaves), 1, be.ptr(t.d_cols), xwords, be.ptr(d_pairs), 1,
+                be.ptr(d_ws), need if ws_words is None else ws_words, be.ptr(d_ops), ops_bytes, be.ptr(d_out), be.stream)
+        return be.download(d_out, np.int32, 3).tolist(), untouched(d_ops, 9) and untouched(d_ws, 4 * need), be.download(d_ops, np.uint8, 9)
+    want = pr.align_profiles(X, Y)
+    for band in ((-4, 5), (-100, 100), (-1, 2)):
+        out, clean, ops = pairs([0, 30, 4, 0, 0, 2, *band])
+        ref = pbr.align_profiles_banded(X, Y, *band)
+        assert out == [0, ref[1], len(ref[0])] and ops[:out[2]][::-1].tobytes().decode() == ref[0] and not clean
+        assert band == (-1, 2) or ref == want
+    narrow = int(pa.band_workspace_words(4, 5, 0, 1))
+    assert pairs([0, 30, 4, 0, 0, 2, 0, 1], ws_words=narrow)[0][0] == 0      # the banded need is enough
+    assert pairs([0, 30, 4, 0, 0, 2, 0, 1], ws_words=narrow - 1)[:2] == ([2, 0, 0], True)
+    for pair, kw, code in (([1, 30, 4, 0, 0, 2, -4, 5], {}, 3), ([-1, 30, 4, 0, 0, 2, -4, 5], {}, 3), ([0, 30, -1, 0, 0, 2, -4, 5], {}, 3),
+                           ([0, 30, 4, 0, 0, 0, -4, 5], {}, 3), ([0, 30, 4, 0, 0, (1 << 20) + 1, -4, 5], {}, 3),
+                           ([0, 30, 4, 0, 0, 2, -4, 5], dict(leaf=(0, 0, 5, 0)), 3),
+                           ([0, 30, 4, 0, 0, 2, 1, 5], {}, 3), ([0, 30, 4, 0, 0, 2, -4, 0], {}, 3),        # (0, 0), (n, C) outside the band
+                           ([0, 30, 4, 0, 0, 2, 0, 0], {}, 3), ([0, 30, 4, 0, 0, 2, 2, 1], {}, 3),
+                           ([0, 31, 4, 0, 0, 2, -4, 5], {}, 2), ([0, -1, 4, 0, 0, 2, -4, 5], {}, 2),
+                           ([0, 30, 4, 0, 0, 2, -4, 5], dict(xwords=57), 2),
+                           ([0, 30, 4, 64, 0, 2, -4, 5], {}, 2), ([0, 30, 4, 1, 0, 2, -4, 5], {}, 2), ([0, 30, 4, 0, 1, 2, -4, 5], {}, 2),
+                           ([0, 30, 4, 0, 0, 2, -4, 5], dict(ops_bytes=8), 2),
+                           ([0, 30, 999_996, 0, 0, 2, -999_996, 5], {}, 1)):
+        assert pairs(pair, **kw)[:2] == ([code, 0, 0], True), (pair, kw)
+
+    def widths(pair, out=(0, 0, 0), leaf=(0, 3, 5, 0), xwords=58):
+        d_bounds, d_status = be.full(16, POISON), be.full(4, POISON)
+        d_leaves, d_pairs = be.upload(np.array([leaf], np.int64)), be.upload(np.array([pair], np.int64))
+        d_out = be.upload(np.array(out, np.int32))
+        be.call("mprg_prog_band_widths", be.ptr(t.d_cols), be.ptr(d_leaves), 1, be.ptr(t.d_cols), xwords, be.ptr(d_pairs), 1,
+                be.ptr(d_out), be.ptr(d_bounds), be.ptr(d_status), be.stream)
+        return be.download(d_status, np.int32, 1).tolist(), untouched(d_bounds, 16), be.download(d_bounds, np.int64, 2).tolist()
+    SB, loss, ins = pbr.bounds(X, Y)
+    for s in (want[1], want[1] - 3000, SB):
+        assert widths([0, 30, 4, 0, 0, 2, 0, 0], (0, s, 0)) == ([0], False, [SB, pbr.wstar(SB, loss, ins, 4, 5, s)])
+    for pair, kw, code in (([1, 30, 4, 0, 0, 2, 0, 0], {}, 3), ([-1, 30, 4, 0, 0, 2, 0, 0], {}, 3), ([0, 30, -1, 0, 0, 2, 0, 0], {}, 3),
+                           ([0, 30, 4, 0, 0, 0, 0, 0], {}, 3), ([0, 30, 4, 0, 0, (1 << 20) + 1, 0, 0], {}, 3),
+                           ([0, 30, 4, 0, 0, 2, 0, 0], dict(leaf=(0, 0, 5, 0)), 3), ([0, 30, 4, 0, 0, 2, 0, 0], dict(leaf=(0, 3, 0, 0)), 3),
+                           ([0, 30, 4, 0, 0, 2, 0, 0], dict(out=(2, 0, 0)), 3),                           # pass 1 refused the merge
+                           ([0, 31, 4, 0, 0, 2, 0, 0], {}, 2), ([0, -1, 4, 0, 0, 2, 0, 0], {}, 2), ([0, 30, 4, 0, 0, 2, 0, 0], dict(xwords=57), 2),
+                           ([0, 30, 999_996, 0, 0, 2, 0, 0], {}, 1)):
+        assert widths(pair, **kw)[:2] == ([code], True), (pair, kw)

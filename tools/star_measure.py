@@ -14,7 +14,9 @@ the rounds accepted, the loci changed and the total objective S before and after
 model of tests/star_ref.py's mutate(sub=0.06, indel=0.03), restated here (the tool does not import the tests): per root base 1.5 %
 deleted, 6 % substituted, 1.5 % followed by an insertion of 1-4 nt.
 `--progressive`: guide-tree MSAs (`from_msa --unaligned --progressive`); the line then also gives tree_s and progressive_s, the
-loci built, their merges, the most rounds of a locus and the loci left to the star pass.
+loci built, their merges, the most rounds of a locus and the loci left to the star pass.  With `--band [W0]` as well the merges run
+over certified bands (W0 then is pass 1's half-width of both stages) and the line also gives prog_band_merges,
+prog_band_second_passes, prog_band_full_merges (sent to the full DP), prog_band_cells and prog_band_full_cells.
 `--objective` (implied by --progressive): the line also gives s_total, the objective S of the MSAs written, summed over the loci
 (mprg_refine_counts over the MSAs, after the timed part): to compare a star run and a progressive run of the same loci."""
 import hashlib
