@@ -13,6 +13,9 @@
 //   of that strip wrote), the profile of the columns in flight from a 128-column LDS ring per wavefront (consecutive lanes
 //   on consecutive columns).  A cell's traceback is 4 bits, a lane packs eight steps per dword, so every store is a 256-byte
 //   row.  Lane 0 then walks the traceback back from (n, C) and writes the ops (reversed) and the score.
+//   The cell's recurrence (al_cell.inc) and the walk back (al_walk.inc) are written once for the four sweep kernels (this one,
+//   k_align_pairs_banded below, k_align_profile_pairs in k_prog.inc, k_align_profile_pairs_banded in k_prog_band.inc) and included
+//   as text: an inlined function body shared between kernels compiles them to other instructions (DESIGN.md §3a).
 // ---------------------------------------------------------------------------------------------------------------
 #define AL_THREADS 256
 #define AL_WAVES (AL_THREADS / 64)
@@ -122,16 +125,8 @@ __global__ void __launch_bounds__(AL_THREADS) k_align_pairs(const int32_t *profi
         const int slot = c & (AL_RING - 1);
         const int dc = ring[5 * AL_RING + slot];
         const int diag = h_diag + ring[cls * AL_RING + slot];
-        const int d_ext = d_left + dc, d_open = h_left + AL_OPEN + dc;
-        const int i_ext = i_up + AL_INS, i_open = h_up + AL_OPEN + AL_INS;
-        const int dd = d_ext >= d_open ? d_ext : d_open, ii = i_ext >= i_open ? i_ext : i_open;
-        int h = diag;
-        unsigned src = 0;
-        if (dd > h) { h = dd; src = 1; }
-        if (ii > h) { h = ii; src = 2; }
-        cell = src | (d_ext >= d_open ? 4u : 0u) | (i_ext >= i_open ? 8u : 0u);
-        h_left = h; d_left = dd; h_out = h; i_out = ii;
-        if (r == ni - 1 && c == Ci - 1) score = h;
+        const int xcost = AL_INS;
+#include "al_cell.inc"
         if (lane == 63 && s + 1 < n_strips) { row[2 * (c + 1)] = h; row[2 * (c + 1) + 1] = ii; }
       }
       acc |= cell << (4 * (t & 7));
@@ -140,23 +135,9 @@ __global__ void __launch_bounds__(AL_THREADS) k_align_pairs(const int32_t *profi
     WAVE_SYNC_GLOBAL();                                      // the row buffer and the traceback, written by every lane, read by lane 0
   }
   score = ni > 0 ? __shfl(score, (ni - 1) & 63) : row[2 * C];
-  if (lane == 0) {
-    uint8_t *op = ops + opoff;
-    long long k = 0;
-    int i = ni, j = Ci, st = 0;                              // st: 0 H, 1 D, 2 I
-    while (i > 0 && j > 0) {
-      const int rr = i - 1, l = rr & 63, t = j - 1 + l;
-      const unsigned cell = (tb[((long long)(rr >> 6) * nst8 + (t >> 3)) * 64 + l] >> (4 * (t & 7))) & 15u;
-      if (st == 0) {
-        if ((cell & 3u) == 0) { op[k++] = 'M'; --i; --j; }
-        else st = (int)(cell & 3u);
-      } else if (st == 1) { op[k++] = 'D'; --j; st = (cell & 4u) ? 1 : 0; }
-      else { op[k++] = 'I'; --i; st = (cell & 8u) ? 2 : 0; }
-    }
-    for (; j > 0; --j) op[k++] = 'D';                        // row 0: only deletions lead back to (0, 0); column 0: only insertions
-    for (; i > 0; --i) op[k++] = 'I';
-    o[0] = MPRG_AL_OK; o[1] = score; o[2] = (int32_t)k;
-  }
+  constexpr bool kBand = false;                              // (the full matrix: every strip starts at column 0)
+  constexpr int dlo = 0;
+#include "al_walk.inc"
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -167,8 +148,8 @@ __global__ void __launch_bounds__(AL_THREADS) k_align_pairs(const int32_t *profi
 //
 // k_align_bounds: one wavefront per leaf over the profile k_align_profiles wrote: SB = sum_j B_j, B_j = max(max_x P[j][x], Dc[j]),
 //   and min_j (B_j - Dc[j]), both int64: what the host's certificate needs.
-// k_align_pairs_banded: k_align_pairs' wavefront-per-pair, 64-row-strip, anti-diagonal sweep, a kernel of its own (k_align_pairs
-//   stays instruction for instruction what it is).  Strip s (rows i0 + 1 .. i0 + rows) sweeps columns cs + 1 .. min(C, i0 + rows +
+// k_align_pairs_banded: k_align_pairs' wavefront-per-pair, 64-row-strip, anti-diagonal sweep, a kernel of its own but for the
+//   cell and the walk back (al_cell.inc, al_walk.inc).  Strip s (rows i0 + 1 .. i0 + rows) sweeps columns cs + 1 .. min(C, i0 + rows +
 //   dhi), cs = max(0, i0 + dlo): at step t lane l is at 0-based column cs + t - l and computes only where its row's band holds that
 //   column; everywhere else it hands AL_NEG to the lane below (H[i][0] where column 0 is in the row's band), so no lane ever
 //   reads a stale value.  Along a row the first in-band cell starts from (H[i][0], AL_NEG) or (AL_NEG, AL_NEG).  A gap state whose
@@ -315,16 +296,8 @@ __global__ void __launch_bounds__(AL_THREADS) k_align_pairs_banded(const int32_t
         const int slot = (t - lane) & (AL_RING - 1);
         const int dc = ring[5 * AL_RING + slot];
         const int diag = h_diag + ring[cls * AL_RING + slot];
-        const int d_ext = d_left + dc, d_open = h_left + AL_OPEN + dc;
-        const int i_ext = i_up + AL_INS, i_open = h_up + AL_OPEN + AL_INS;
-        const int dd = d_ext >= d_open ? d_ext : d_open, ii = i_ext >= i_open ? i_ext : i_open;
-        int h = diag;
-        unsigned src = 0;
-        if (dd > h) { h = dd; src = 1; }
-        if (ii > h) { h = ii; src = 2; }
-        cell = src | (d_ext >= d_open ? 4u : 0u) | (i_ext >= i_open ? 8u : 0u);
-        h_left = h; d_left = dd; h_out = h; i_out = ii;
-        if (r == ni - 1 && c == Ci - 1) score = h;
+        const int xcost = AL_INS;
+#include "al_cell.inc"
         if (lane == 63 && s + 1 < n_strips) { const int k = c + 1 - (i0 + 64 + dlo); row[(unsigned)(2 * k)] = h; row[(unsigned)(2 * k + 1)] = ii; }
       } else {
         h_out = c == -1 && r + 1 + dlo <= 0 ? al_hb(r + 1) : AL_NEG;   // outside the band: minus infinity, never a stale or an accumulated value
@@ -336,21 +309,6 @@ __global__ void __launch_bounds__(AL_THREADS) k_align_pairs_banded(const int32_t
     WAVE_SYNC_GLOBAL();                                      // the row buffer and the traceback, written by every lane, read by lane 0
   }
   score = ni > 0 ? __shfl(score, (ni - 1) & 63) : row[2 * (Ci - dlo)];
-  if (lane == 0) {
-    uint8_t *op = ops + opoff;
-    long long k = 0;
-    int i = ni, j = Ci, st = 0;                              // st: 0 H, 1 D, 2 I
-    while (i > 0 && j > 0) {
-      const int rr = i - 1, l = rr & 63, sc = (rr & ~63) + dlo > 0 ? (rr & ~63) + dlo : 0, t = j - 1 - sc + l;
-      const unsigned cell = (tb[((long long)(rr >> 6) * nst8 + (t >> 3)) * 64 + l] >> (4 * (t & 7))) & 15u;
-      if (st == 0) {
-        if ((cell & 3u) == 0) { op[k++] = 'M'; --i; --j; }
-        else st = (int)(cell & 3u);
-      } else if (st == 1) { op[k++] = 'D'; --j; st = (cell & 4u) ? 1 : 0; }
-      else { op[k++] = 'I'; --i; st = (cell & 8u) ? 2 : 0; }
-    }
-    for (; j > 0; --j) op[k++] = 'D';                        // row 0: only deletions lead back to (0, 0); column 0: only insertions
-    for (; i > 0; --i) op[k++] = 'I';
-    o[0] = MPRG_AL_OK; o[1] = score; o[2] = (int32_t)k;
-  }
+  constexpr bool kBand = true;
+#include "al_walk.inc"
 }

@@ -14,8 +14,8 @@
 // k_prog_columns: one workgroup per (item, 256-column tile), thread = column, the text's rows walked in order (k_align_profiles'
 //   access pattern).  Kind 0 writes exactly k_align_profiles' 6 planes (Y's profile), kind 1 the 7 planes of an X side: the
 //   counts of A C G T, of R Y K M S W N, of '-', and Ic.
-// k_align_profile_pairs: k_align_pairs' structure with a profile on both sides, a kernel of its own (k_align_pairs stays
-//   instruction for instruction what it is): one wavefront per merge, 64-column strips of X on the anti-diagonal, the row above
+// k_align_profile_pairs: k_align_pairs' structure with a profile on both sides, a kernel of its own but for the cell and the
+//   walk back (al_cell.inc, al_walk.inc): one wavefront per merge, 64-column strips of X on the anti-diagonal, the row above
 //   by shuffle, Y's six planes in the 128-column LDS ring, 4-bit traceback, lane 0 walking back.  A lane keeps its X column's six
 //   counts and Ic in registers; a cell's score is six multiply-adds and the truncating division by R_X as a multiplication by a
 //   per-merge constant and a shift (pg_div below).  H[i][0] = open + the Ic before row i: a wave scan per strip.  The row above a
@@ -265,16 +265,8 @@ __global__ void __launch_bounds__(AL_THREADS) k_align_profile_pairs(const int32_
         const int num = x0 * ring[slot] + x1 * ring[AL_RING + slot] + x2 * ring[2 * AL_RING + slot] + x3 * ring[3 * AL_RING + slot] +
                         xa * ring[4 * AL_RING + slot] + xg * dc;
         const int diag = h_diag + pg_div(num, dv);
-        const int d_ext = d_left + dc, d_open = h_left + AL_OPEN + dc;
-        const int i_ext = i_up + ic, i_open = h_up + AL_OPEN + ic;
-        const int dd = d_ext >= d_open ? d_ext : d_open, ii = i_ext >= i_open ? i_ext : i_open;
-        int h = diag;
-        unsigned src = 0;
-        if (dd > h) { h = dd; src = 1; }
-        if (ii > h) { h = ii; src = 2; }
-        cell = src | (d_ext >= d_open ? 4u : 0u) | (i_ext >= i_open ? 8u : 0u);
-        h_left = h; d_left = dd; h_out = h; i_out = ii;
-        if (r == ni - 1 && c == Ci - 1) score = h;
+        const int xcost = ic;
+#include "al_cell.inc"
         if (lane == 63 && s + 1 < n_strips) { row[2 * (c + 1)] = h; row[2 * (c + 1) + 1] = ii; }
       }
       acc |= cell << (4 * (t & 7));
@@ -283,23 +275,9 @@ __global__ void __launch_bounds__(AL_THREADS) k_align_profile_pairs(const int32_
     WAVE_SYNC_GLOBAL();                                      // the row buffer and the traceback, written by every lane, read by lane 0
   }
   score = ni > 0 ? __shfl(score, (ni - 1) & 63) : row[2 * Ci];
-  if (lane == 0) {
-    uint8_t *op = ops + opoff;
-    long long k = 0;
-    int i = ni, j = Ci, st = 0;                              // st: 0 H, 1 D, 2 I
-    while (i > 0 && j > 0) {
-      const int rr = i - 1, l = rr & 63, t = j - 1 + l;
-      const unsigned cell = (tb[((long long)(rr >> 6) * nst8 + (t >> 3)) * 64 + l] >> (4 * (t & 7))) & 15u;
-      if (st == 0) {
-        if ((cell & 3u) == 0) { op[k++] = 'M'; --i; --j; }
-        else st = (int)(cell & 3u);
-      } else if (st == 1) { op[k++] = 'D'; --j; st = (cell & 4u) ? 1 : 0; }
-      else { op[k++] = 'I'; --i; st = (cell & 8u) ? 2 : 0; }
-    }
-    for (; j > 0; --j) op[k++] = 'D';                        // row 0: only Y's columns alone lead back to (0, 0); column 0: only X's
-    for (; i > 0; --i) op[k++] = 'I';
-    o[0] = MPRG_AL_OK; o[1] = score; o[2] = (int32_t)k;
-  }
+  constexpr bool kBand = false;                              // (the full matrix: every strip starts at column 0)
+  constexpr int dlo = 0;
+#include "al_walk.inc"
 }
 
 __global__ void __launch_bounds__(PG_THREADS) k_prog_rows(const int64_t *bufs, int n_bufs, const uint8_t *ops, long long ops_bytes,

@@ -4,7 +4,7 @@
 //      of the diagonals dlo <= j - i <= dhi only, and the certified half-width of every merge of a launch, found on the device.
 //
 // k_align_profile_pairs_banded: k_align_profile_pairs' cell (X's six counts and Ic in registers, six multiply-adds, pg_div) with
-//   k_align_pairs_banded's geometry, a kernel of its own (both stay instruction for instruction what they are).  Strip s (rows
+//   k_align_pairs_banded's geometry, a kernel of its own but for the cell and the walk back (al_cell.inc, al_walk.inc).  Strip s (rows
 //   i0 + 1 .. i0 + rows) sweeps columns cs + 1 .. min(C, i0 + rows + dhi), cs = max(0, i0 + dlo); a lane computes only where its
 //   row's band holds its column and hands AL_NEG to the lane below everywhere else (H[i][0] = open + the Ic of rows 1 .. i where
 //   column 0 is in the row's band).  Row buffer: W = dhi - dlo + 1 (H, I) slots, row i0 keeps column j at slot j - (i0 + dlo).
@@ -127,16 +127,8 @@ __global__ void __launch_bounds__(AL_THREADS) k_align_profile_pairs_banded(const
         const int num = x0 * ring[slot] + x1 * ring[AL_RING + slot] + x2 * ring[2 * AL_RING + slot] + x3 * ring[3 * AL_RING + slot] +
                         xa * ring[4 * AL_RING + slot] + xg * dc;
         const int diag = h_diag + pg_div(num, dv);
-        const int d_ext = d_left + dc, d_open = h_left + AL_OPEN + dc;
-        const int i_ext = i_up + ic, i_open = h_up + AL_OPEN + ic;
-        const int dd = d_ext >= d_open ? d_ext : d_open, ii = i_ext >= i_open ? i_ext : i_open;
-        int h = diag;
-        unsigned src = 0;
-        if (dd > h) { h = dd; src = 1; }
-        if (ii > h) { h = ii; src = 2; }
-        cell = src | (d_ext >= d_open ? 4u : 0u) | (i_ext >= i_open ? 8u : 0u);
-        h_left = h; d_left = dd; h_out = h; i_out = ii;
-        if (r == ni - 1 && c == Ci - 1) score = h;
+        const int xcost = ic;
+#include "al_cell.inc"
         if (lane == 63 && s + 1 < n_strips) { const int k = c + 1 - (i0 + 64 + dlo); row[(unsigned)(2 * k)] = h; row[(unsigned)(2 * k + 1)] = ii; }
       } else {
         h_out = c == -1 && col0 ? hb : AL_NEG;               // outside the band: minus infinity, never a stale or an accumulated value
@@ -148,23 +140,8 @@ __global__ void __launch_bounds__(AL_THREADS) k_align_profile_pairs_banded(const
     WAVE_SYNC_GLOBAL();                                      // the row buffer and the traceback, written by every lane, read by lane 0
   }
   score = ni > 0 ? __shfl(score, (ni - 1) & 63) : row[2 * (Ci - dlo)];
-  if (lane == 0) {
-    uint8_t *op = ops + opoff;
-    long long k = 0;
-    int i = ni, j = Ci, st = 0;                              // st: 0 H, 1 D, 2 I
-    while (i > 0 && j > 0) {
-      const int rr = i - 1, l = rr & 63, sc = (rr & ~63) + dlo > 0 ? (rr & ~63) + dlo : 0, t = j - 1 - sc + l;
-      const unsigned cell = (tb[((long long)(rr >> 6) * nst8 + (t >> 3)) * 64 + l] >> (4 * (t & 7))) & 15u;
-      if (st == 0) {
-        if ((cell & 3u) == 0) { op[k++] = 'M'; --i; --j; }
-        else st = (int)(cell & 3u);
-      } else if (st == 1) { op[k++] = 'D'; --j; st = (cell & 4u) ? 1 : 0; }
-      else { op[k++] = 'I'; --i; st = (cell & 8u) ? 2 : 0; }
-    }
-    for (; j > 0; --j) op[k++] = 'D';                        // row 0: only Y's columns alone lead back to (0, 0); column 0: only X's
-    for (; i > 0; --i) op[k++] = 'I';
-    o[0] = MPRG_AL_OK; o[1] = score; o[2] = (int32_t)k;
-  }
+  constexpr bool kBand = true;
+#include "al_walk.inc"
 }
 
 // cnt[0 .. PER * PG_THREADS) (a histogram over values = bin indices) into cumulative counts, in place, and cumulative sums of

@@ -672,30 +672,17 @@ def _prog_need(WX, WY, w0):
     need = pa.workspace_words_v(WX, WY)
     if w0 is None:
         return need
-    dlo, dhi = pa.band_limits(WX, WY, w0, w0)
-    return np.where(pa.band_helps(WX, WY, dlo, dhi), pa.band_workspace_words(WX, WY, dlo, dhi), need)
+    dlo, dhi, helps = pa.band_first(WX, WY, w0)
+    return np.where(helps, pa.band_workspace_words(WX, WY, dlo, dhi), need)
 
 
 def _prog_groups(WX, WY, budget_bytes, band=None):
     """The merges (X's and Y's columns) longest first in groups whose workspace and column tables each fit the budget; with band
     the workspace is pass 1's."""
-    need = _prog_need(WX, WY, _prog_w0(band))
-    cols = 7 * WX + 6 * WY
-    budget_words = max(64, int(budget_bytes) // 4)
-    if len(need) and need.max() > budget_words:
-        k = int(need.argmax())
-        raise StarAlignError(f"a merge of {WX[k]} columns against {WY[k]} needs {4 * need[k]} bytes of traceback, more than the workspace "
-                             f"budget of {budget_bytes}")
     order = np.argsort(-((WX + 1) * WY), kind="stable")
-    pos = 0
-    while pos < len(order):
-        end, used, used_cols = pos, 0, 0
-        while end < len(order) and used + need[order[end]] <= budget_words and (end == pos or used_cols + cols[order[end]] <= budget_words):
-            used += int(need[order[end]])
-            used_cols += int(cols[order[end]])
-            end += 1
-        yield order[pos:end]
-        pos = end
+    for grp, _, _ in pa.budget_launches(order, _prog_need(WX, WY, _prog_w0(band)), budget_bytes, StarAlignError, "merge", WX, WY,
+                                        also=7 * WX + 6 * WY):
+        yield grp
 
 
 def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUDGET_BYTES, counters=None):
@@ -731,46 +718,28 @@ def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUD
         d_pairs = be.upload(pairs)
         d_ws, d_out = be.empty(4 * int(need.sum())), be.empty(12 * n)
         be.call("mprg_align_profile_pairs", be.ptr(d_cols), be.ptr(d_leaves), n, be.ptr(d_cols), words, be.ptr(d_pairs), n, be.ptr(d_ws),
-                int(need.sum()), be.ptr(d_ops), ops_bytes, be.ptr(d_out), be.stream, work=float(((WX + 63) // 64 * 64 * WY).sum()))
+                int(need.sum()), be.ptr(d_ops), ops_bytes, be.ptr(d_out), be.stream, work=pa.sweep_work(WX, WY))
         _pg_check(be.download(d_status, np.int32, len(work)), "mprg_prog_columns")
         res = be.download(d_out, np.int32, 3 * n).reshape(-1, 3)
         bad = np.nonzero(res[:, 0])[0]
         if len(bad):
             raise StarAlignError(f"mprg_align_profile_pairs: {pa.STATUS.get(int(res[bad[0], 0]), int(res[bad[0], 0]))}")
         return d_ops, ops_bytes, ops_off, res[:, 2].astype(np.int64), res[:, 1].astype(np.int64)
-    budget_words = max(64, int(budget_bytes) // 4)
     pending = []                                                # (merges, call, the launch's triples, its table): downloaded at the end
 
     def launches(call, idx, wordsv, dlo=None, dhi=None):
         """The merges idx (longest first) through `call` in launches that fit the workspace budget."""
-        if len(idx) and wordsv[idx].max() > budget_words:
-            k = idx[int(wordsv[idx].argmax())]
-            raise StarAlignError(f"a merge of {WX[k]} columns against {WY[k]} needs {4 * wordsv[k]} bytes of traceback, more than the "
-                                 f"workspace budget of {budget_bytes}")
-        pos = 0
-        while pos < len(idx):
-            end, used = pos, 0
-            while end < len(idx) and used + wordsv[idx[end]] <= budget_words:
-                used += int(wordsv[idx[end]])
-                end += 1
-            sel = idx[pos:end]
-            ws_off = np.concatenate([[0], np.cumsum(wordsv[sel])[:-1]])
-            fields = [sel, xcol[sel], WX[sel], ws_off, ops_off[sel], X[sel, 2]] + ([] if dlo is None else [dlo[sel], dhi[sel]])
-            d_pairs = be.upload(np.stack(fields, 1).astype(np.int64))
+        for sel, ws_off, used in pa.budget_launches(idx, wordsv, budget_bytes, StarAlignError, "merge", WX, WY):
+            band_cols = () if dlo is None else (dlo[sel], dhi[sel])
+            d_pairs = be.upload(np.stack([sel, xcol[sel], WX[sel], ws_off, ops_off[sel], X[sel, 2], *band_cols], 1).astype(np.int64))
             d_ws, d_out = be.empty(4 * used), be.empty(12 * len(sel))
-            cells = (WX[sel] + 63) // 64 * 64 * (WY[sel] if dlo is None else np.minimum(WY[sel], dhi[sel] - dlo[sel] + 64))
             be.call(call, be.ptr(d_cols), be.ptr(d_leaves), n, be.ptr(d_cols), words, be.ptr(d_pairs), len(sel), be.ptr(d_ws), used,
-                    be.ptr(d_ops), ops_bytes, be.ptr(d_out), be.stream, work=float(cells.sum()))
+                    be.ptr(d_ops), ops_bytes, be.ptr(d_out), be.stream, work=pa.sweep_work(WX[sel], WY[sel], *band_cols))
             pending.append((sel, call, d_out, d_pairs))
-            pos = end
-    dlo, dhi = pa.band_limits(WX, WY, w0, w0)
-    full = ~pa.band_helps(WX, WY, dlo, dhi)
-    first = np.nonzero(~full)[0]
-    cells = pa.band_cells(WX, WY, dlo, dhi)
-    first = first[np.argsort(-cells[first], kind="stable")]
-    wstar = np.zeros(n, np.int64)
-    if len(first):
-        # pass 1: one launch where the group was sized by its need; the widths over the same table and its triples
+
+    def pass1(first, dlo, dhi):
+        # one launch where the group was sized by its need; the widths over the same table and its triples
+        wstar = np.zeros(n, np.int64)
         launches("mprg_align_profile_pairs_banded", first, pa.band_workspace_words(WX, WY, dlo, dhi), dlo, dhi)
         for sel, _, d_out, d_pairs in list(pending):
             d_got = be.empty(20 * len(sel))                     # {SB, w*} per merge, then the status words
@@ -784,16 +753,10 @@ def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUD
                 code = int(res[res[:, 0] != 0][0, 0]) if res[:, 0].any() else int(status[status != 0][0])
                 raise StarAlignError(f"mprg_align_profile_pairs_banded / mprg_prog_band_widths: {pa.STATUS.get(code, code)}")
             wstar[sel] = got[:16 * len(sel)].view(np.int64).reshape(-1, 2)[:, 1]
-    again = ~full & (wstar > w0)
-    dlo2, dhi2 = pa.band_limits(WX, WY, wstar, wstar)
-    dlo, dhi = np.where(again, dlo2, dlo), np.where(again, dhi2, dhi)
-    full |= again & ~pa.band_helps(WX, WY, dlo, dhi)
-    second = np.nonzero(again & ~full)[0]
-    cells2 = pa.band_cells(WX, WY, dlo, dhi)
-    launches("mprg_align_profile_pairs_banded", second[np.argsort(-cells2[second], kind="stable")],
-             pa.band_workspace_words(WX, WY, dlo, dhi), dlo, dhi)
-    rest = np.nonzero(full)[0]
-    launches("mprg_align_profile_pairs", rest[np.argsort(-((WX[rest] + 1) * WY[rest]), kind="stable")], need)
+        return wstar, wstar
+    second, rest, dlo, dhi, counts = pa.band_plan(WX, WY, w0, pass1)
+    launches("mprg_align_profile_pairs_banded", second, pa.band_workspace_words(WX, WY, dlo, dhi), dlo, dhi)
+    launches("mprg_align_profile_pairs", rest, need)
     _pg_check(be.download(d_status, np.int32, len(work)), "mprg_prog_columns")
     count, score = np.zeros(n, np.int64), np.zeros(n, np.int64)
     for sel, call, d_out, _ in pending:                          # in launch order: a later pass's result replaces pass 1's
@@ -803,9 +766,8 @@ def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUD
             raise StarAlignError(f"{call}: {pa.STATUS.get(int(res[bad[0], 0]), int(res[bad[0], 0]))}")
         score[sel], count[sel] = res[:, 1], res[:, 2]
     if counters is not None:
-        for key, v in (("prog_band_merges", n), ("prog_band_second_passes", len(second)), ("prog_band_full_merges", len(rest)),
-                       ("prog_band_cells", cells[first].sum() + cells2[second].sum() + (WX[rest] * WY[rest]).sum()),
-                       ("prog_band_full_cells", (WX * WY).sum())):
+        for key, v in zip(("prog_band_merges", "prog_band_second_passes", "prog_band_full_merges", "prog_band_cells",
+                            "prog_band_full_cells"), counts):
             counters[key] = counters.get(key, 0) + int(v)
     return d_ops, ops_bytes, ops_off, count, score
 

@@ -120,6 +120,72 @@ def band_cells(n, C, dlo, dhi):
     return n * C - (tri(below) - tri(below - C)) - (tri(above) - tri(above - n))
 
 
+def sweep_work(n, C, dlo=None, dhi=None):
+    """The cells the DP kernels sweep for items of n rows against C columns (whole 64-row strips; banded: over the strip's columns),
+    summed: the `work=` of a launch."""
+    return float(((n + 63) // 64 * 64 * (C if dlo is None else np.minimum(C, dhi - dlo + 64))).sum())
+
+
+_ITEM = {"pair": "a pair of {} residues against {} columns", "merge": "a merge of {} columns against {}"}
+
+
+def budget_launches(order, words, budget_bytes, error, noun, n, C, also=None):
+    """The work items `order` (indices; words[k]: the int32 words of workspace item k needs), in that order, in launches whose
+    workspace fits the budget: yields (the launch's items, each one's offset in the launch's workspace, the words used).  An item
+    that alone exceeds the budget is refused before the first launch, as `error`, named as a `noun` ("pair", "merge") of n[k]
+    against C[k].  It only packs: the caller uploads the table, launches and keeps the results per yielded launch.  also: a second need per item (int32 words) that has to fit the budget as well, save for a launch's first item."""
+    budget_words = max(64, int(budget_bytes) // 4)
+    if len(order) and words[order].max() > budget_words:
+        # the item named: the lowest index among the largest, which is what pairs_on_device and _prog_groups named before they shared
+        # this loop (they looked in index order); _prog_pairs looked in launch order, so between two merges of different shape that
+        # tie for the largest need its message can now name the other one
+        k = order[words[order] == words[order].max()].min()
+        raise error(f"{_ITEM[noun].format(n[k], C[k])} needs {4 * words[k]} bytes of traceback, more than the workspace "
+                    f"budget of {budget_bytes}")
+    pos = 0
+    while pos < len(order):
+        end, used, used_also = pos, 0, 0
+        while end < len(order) and used + words[order[end]] <= budget_words and (
+                also is None or end == pos or used_also + also[order[end]] <= budget_words):
+            used += int(words[order[end]])
+            used_also += 0 if also is None else int(also[order[end]])
+            end += 1
+        sel = order[pos:end]
+        yield sel, np.concatenate([[0], np.cumsum(words[sel])[:-1]]), used
+        pos = end
+
+
+def band_first(n, C, w0):
+    """Pass 1's bands (dlo, dhi) of half-width w0 and, per item, whether the band helps (band_helps; no: the full DP)."""
+    dlo, dhi = band_limits(n, C, w0, w0)
+    return dlo, dhi, band_helps(n, C, dlo, dhi)
+
+
+def band_plan(n, C, w0, pass1):
+    """The spec's two passes over items of n rows against C columns (arrays).  pass1(first, dlo, dhi) runs pass 1 over the items
+    `first` with the bands dlo, dhi (arrays over all items) and returns the certified half-widths (w-, w+) per item (read for
+    `first` only); it works by side effect on its caller's state: it makes the pass-1 launches there and leaves their scores where the
+    caller's later launches and downloads find them.  Returns (second, rest, dlo, dhi, counts): the items of pass 2 and of the full DP, each in launch order (most
+    cells first), the final bands, and (items, second passes, items sent to the full DP, DP cells computed, n C summed)."""
+    dlo, dhi, helps = band_first(n, C, w0)
+    full = ~helps
+    cells = band_cells(n, C, dlo, dhi)
+    first = np.nonzero(~full)[0]
+    first = first[np.argsort(-cells[first], kind="stable")]
+    w_minus, w_plus = pass1(first, dlo, dhi)
+    again = ~full & ((w_minus > w0) | (w_plus > w0))
+    dlo2, dhi2 = band_limits(n, C, w_minus, w_plus)
+    dlo, dhi = np.where(again, dlo2, dlo), np.where(again, dhi2, dhi)
+    full |= again & ~band_helps(n, C, dlo, dhi)
+    second = np.nonzero(again & ~full)[0]
+    cells2 = band_cells(n, C, dlo, dhi)
+    second = second[np.argsort(-cells2[second], kind="stable")]
+    rest = np.nonzero(full)[0]
+    rest = rest[np.argsort(-((n[rest] + 1) * C[rest]), kind="stable")]
+    counts = (len(n), len(second), len(rest), cells[first].sum() + cells2[second].sum() + (n[rest] * C[rest]).sum(), (n * C).sum())
+    return second, rest, dlo, dhi, counts
+
+
 def certified_widths(n, C, SB, m, S0):
     """(w*-, w*+) of the spec's two-pass rule from pass 1's score S0: the smallest half-widths whose band is closed on each side."""
     delta, q = C - n, m + 640
@@ -213,16 +279,11 @@ def pairs_on_device(backend, leaves: Optional[Sequence[np.ndarray]], seqs: Seque
         raise ProfileAlignError(f"a pair of {pn[k]} residues against {pc[k]} columns: n + C must stay below {MAX_LEN}")
     seq_off = np.asarray(prepared.seq_off, np.int64) if on_device else np.concatenate([[0], np.cumsum(pn)[:-1]])
     need = np.array([workspace_words(int(n), int(c)) for n, c in zip(pn, pc)], np.int64)
-    budget_words = max(64, int(budget_bytes) // 4)
 
-    def check_budget(sel, words):
-        if len(sel) and words[sel].max() > budget_words:
-            k = sel[int(words[sel].argmax())]
-            raise ProfileAlignError(f"a pair of {pn[k]} residues against {pc[k]} columns needs {4 * words[k]} bytes of traceback, "
-                                    f"more than the workspace budget of {budget_bytes}")
+    def packed(order, words):
+        return budget_launches(order, words, budget_bytes, ProfileAlignError, "pair", pn, pc)
     if band is None:
-        check_budget(np.arange(len(pl)), need)
-    order = np.argsort(-((pn + 1) * pc), kind="stable")        # longest first
+        full_plan = list(packed(np.argsort(-((pn + 1) * pc), kind="stable"), need))       # longest first; refuses before anything is uploaded
     ops_len = pn + pc
     ops_off = np.concatenate([[0], np.cumsum(ops_len)[:-1]])
     ops_bytes = max(int(ops_len.sum()), 1)
@@ -240,32 +301,24 @@ def pairs_on_device(backend, leaves: Optional[Sequence[np.ndarray]], seqs: Seque
     d_seqs = prepared.d_seqs if on_device else be.upload(np.concatenate([x for s in seqs for x in s] + [np.zeros(1, np.uint8)]).astype(np.uint8))
     d_ops = be.empty(ops_bytes)
 
-    def launches(call, order, words, dlo=None, dhi=None):
-        """The pairs `order` (longest first) through `call` in launches that fit the workspace budget."""
-        pos = 0
-        while pos < len(order):
-            end, used = pos, 0
-            while end < len(order) and used + words[order[end]] <= budget_words:
-                used += int(words[order[end]])
-                end += 1
-            idx = order[pos:end]
-            ws_off = np.concatenate([[0], np.cumsum(words[idx])[:-1]])
-            cols = [pl[idx], seq_off[idx], pn[idx], ws_off, ops_off[idx]] + ([] if dlo is None else [dlo[idx], dhi[idx]])
-            d_pairs = be.upload(np.stack(cols, 1).astype(np.int64))
+    def launches(call, plan, dlo=None, dhi=None):
+        """The launches of `plan` (packed) through `call`."""
+        for idx, ws_off, used in plan:
+            band_cols = () if dlo is None else (dlo[idx], dhi[idx])
+            d_pairs = be.upload(np.stack([pl[idx], seq_off[idx], pn[idx], ws_off, ops_off[idx], *band_cols], 1).astype(np.int64))
             d_ws = be.empty(4 * used)
             d_out = be.empty(12 * len(idx))
-            work = (pn[idx] + 63) // 64 * 64 * (pc[idx] if dlo is None else np.minimum(pc[idx], dhi[idx] - dlo[idx] + 64))
             be.call(call, be.ptr(d_prof), be.ptr(d_leaves), n_leaves, be.ptr(d_seqs), be.ptr(d_pairs), len(idx),
-                    be.ptr(d_ws), used, be.ptr(d_ops), ops_bytes, be.ptr(d_out), be.stream, work=float(work.sum()))
+                    be.ptr(d_ws), used, be.ptr(d_ops), ops_bytes, be.ptr(d_out), be.stream,
+                    work=sweep_work(pn[idx], pc[idx], *band_cols))
             res = be.download(d_out, np.int32, 3 * len(idx)).reshape(-1, 3)
             bad = np.nonzero(res[:, 0])[0]
             if len(bad):
                 raise ProfileAlignError(f"{call}: {STATUS.get(int(res[bad[0], 0]), int(res[bad[0], 0]))}")
             score[idx] = res[:, 1]
             count[idx] = res[:, 2]
-            pos = end
     if band is None:
-        launches("mprg_align_pairs", order, need)
+        launches("mprg_align_pairs", full_plan)
         return DevicePairs(d_ops, ops_bytes, pl, pi, ops_off, count, score)
     # the spec's Band: pass 1 with w0, the certificate over the downloaded scores, pass 2 with the certified widths; the full DP
     # for the pairs whose band needs no less workspace than the full matrix
@@ -276,30 +329,15 @@ def pairs_on_device(backend, leaves: Optional[Sequence[np.ndarray]], seqs: Seque
     be.call("mprg_align_bounds", be.ptr(d_prof), be.ptr(d_leaves), n_leaves, be.ptr(d_bounds), be.stream, work=float((6 * C).sum()))
     bounds = be.download(d_bounds, np.int64, 2 * n_leaves).reshape(-1, 2)
     SB, m = bounds[pl, 0], bounds[pl, 1]
-    dlo, dhi = band_limits(pn, pc, w0, w0)
-    words = band_workspace_words(pn, pc, dlo, dhi)
-    full = ~band_helps(pn, pc, dlo, dhi)
-    first = np.nonzero(~full)[0]
-    check_budget(first, words)
-    cells = band_cells(pn, pc, dlo, dhi)
-    launches("mprg_align_pairs_banded", first[np.argsort(-cells[first], kind="stable")], words, dlo, dhi)
-    w_minus, w_plus = certified_widths(pn, pc, SB, m, score)
-    again = ~full & ((w_minus > w0) | (w_plus > w0))
-    dlo2, dhi2 = band_limits(pn, pc, w_minus, w_plus)
-    dlo, dhi = np.where(again, dlo2, dlo), np.where(again, dhi2, dhi)
-    words = band_workspace_words(pn, pc, dlo, dhi)
-    full |= again & ~band_helps(pn, pc, dlo, dhi)
-    second = np.nonzero(again & ~full)[0]
-    check_budget(second, words)
-    cells2 = band_cells(pn, pc, dlo, dhi)
-    launches("mprg_align_pairs_banded", second[np.argsort(-cells2[second], kind="stable")], words, dlo, dhi)
-    rest = np.nonzero(full)[0]
-    check_budget(rest, need)
-    launches("mprg_align_pairs", rest[np.argsort(-((pn[rest] + 1) * pc[rest]), kind="stable")], need)
+
+    def pass1(first, dlo, dhi):
+        launches("mprg_align_pairs_banded", packed(first, band_workspace_words(pn, pc, dlo, dhi)), dlo, dhi)
+        return certified_widths(pn, pc, SB, m, score)
+    second, rest, dlo, dhi, counts = band_plan(pn, pc, w0, pass1)
+    launches("mprg_align_pairs_banded", packed(second, band_workspace_words(pn, pc, dlo, dhi)), dlo, dhi)
+    launches("mprg_align_pairs", packed(rest, need))
     if counters is not None:
-        for key, v in (("band_pairs", len(pl)), ("band_second_passes", len(second)), ("band_full_pairs", len(rest)),
-                       ("band_cells", cells[first].sum() + cells2[second].sum() + (pn[rest] * pc[rest]).sum()),
-                       ("band_full_cells", (pn * pc).sum())):
+        for key, v in zip(("band_pairs", "band_second_passes", "band_full_pairs", "band_cells", "band_full_cells"), counts):
             counters[key] = counters.get(key, 0) + int(v)
     return DevicePairs(d_ops, ops_bytes, pl, pi, ops_off, count, score)
 

@@ -1,7 +1,8 @@
 """What the emulated and the GPU tests of `from_msa --unaligned --progressive --band` share (the spec: star_align.py, "Progressive,
 band"; its plain-Python statement: tests/progband_ref.py): the banded kernel against the reference banded DP on prog_common's
 shapes, the widths kernel against the linear search around every threshold, two-pass merges and whole MSAs against the UNBANDED
-references with the counters of the reference's two-pass rule, the closedness property, and the status codes of the two entries."""
+references with the counters of the reference's two-pass rule, the closedness property, the status codes of the two entries, and
+the four entries of the one DP sweep (sequence or profile as X, full matrix or band) against each other on a one-row X."""
 import functools
 import random
 from collections import Counter
@@ -10,6 +11,7 @@ import numpy as np
 
 from make_prg_amd.from_msa import star_align as sa
 from make_prg_amd.update import profile_align as pa
+from tests import align_ref as ar
 from tests import band_ref as br
 from tests import prog_common as pc
 from tests import prog_ref as pr
@@ -69,6 +71,21 @@ class Tables:
         be.call("mprg_align_profile_pairs_banded", be.ptr(self.d_cols), be.ptr(self.d_leaves), n, be.ptr(self.d_cols), self.words,
                 be.ptr(d_pairs), n, be.ptr(d_ws), int(need.sum()), be.ptr(d_ops), ops_bytes,
                 be.ptr(d_out), be.stream)
+        res = be.download(d_out, np.int32, 3 * n).reshape(-1, 3)
+        assert not res[:, 0].any(), res[:, 0]
+        ops = be.download(d_ops, np.uint8, ops_bytes)
+        return [(ops[o:o + k][::-1].tobytes().decode(), int(s)) for o, k, s in zip(self.ops_off, res[:, 2], res[:, 1])]
+
+    def full(self):
+        """Every pair over the full matrix (mprg_align_profile_pairs), one launch: [(ops forward, score)]."""
+        be, n = self.be, self.n
+        need = pa.workspace_words_v(self.WX, self.WY)
+        ws_off = np.concatenate([[0], np.cumsum(need)[:-1]]).astype(np.int64)
+        ops_bytes = int((self.WX + self.WY).sum())
+        d_ws, d_ops, d_out = be.empty(4 * int(need.sum())), be.empty(ops_bytes), be.empty(12 * n)
+        d_pairs = be.upload(self.pair_rows(np.arange(n), np.zeros(n), np.zeros(n), ws_off)[:, :sa.PG_PAIR_FIELDS])
+        be.call("mprg_align_profile_pairs", be.ptr(self.d_cols), be.ptr(self.d_leaves), n, be.ptr(self.d_cols), self.words,
+                be.ptr(d_pairs), n, be.ptr(d_ws), int(need.sum()), be.ptr(d_ops), ops_bytes, be.ptr(d_out), be.stream)
         res = be.download(d_out, np.int32, 3 * n).reshape(-1, 3)
         assert not res[:, 0].any(), res[:, 0]
         ops = be.download(d_ops, np.uint8, ops_bytes)
@@ -365,3 +382,75 @@ def check_abi_statuses(be):
                            ([0, 31, 4, 0, 0, 2, 0, 0], {}, 2), ([0, -1, 4, 0, 0, 2, 0, 0], {}, 2), ([0, 30, 4, 0, 0, 2, 0, 0], dict(xwords=57), 2),
                            ([0, 30, 999_996, 0, 0, 2, 0, 0], {}, 1)):
         assert widths(pair, **kw)[:2] == ([code], True), (pair, kw)
+
+
+# ---- one sweep, four entries
+FORM_SIZES = (1, 63, 64, 65, 128, 129)            # around the strip, the ring's wrap and the last partial traceback dword
+
+
+@functools.lru_cache(maxsize=None)
+def form_cases():
+    """(X, Y, align_ref's (ops, score)) for every n x C of FORM_SIZES: X a random sequence over the 11 residue codes, Y three rows
+    with gaps and ambiguity codes; then X empty against C of 1, 64, 65."""
+    rng = random.Random(31)
+    out = []
+    for n, C in [(n, C) for n in FORM_SIZES for C in FORM_SIZES] + [(0, 1), (0, 64), (0, 65)]:
+        X = "".join(rng.choice("ACGTRYKMSWN") for _ in range(n))
+        Y = tuple(pr.random_profiles(rng, 3, C, 0.25, amb=0.1))
+        out.append((X, Y, ar.align_pair(Y, X)))
+    return out
+
+
+def _sequence_forms(be, cases):
+    """mprg_align_pairs and mprg_align_pairs_banded (the band open to the whole matrix) over (X, Y) cases, a leaf per case, one
+    launch each: two lists of (status, ops forward, score)."""
+    leaves = [pc.codes(Y) for _, Y in cases]
+    seqs = [pc.codes([X]).reshape(-1) if X else np.zeros(0, np.uint8) for X, _ in cases]
+    n, C, k = np.array([len(x) for x in seqs], np.int64), np.array([m.shape[1] for m in leaves], np.int64), len(cases)
+    leaf_tab = np.stack([np.concatenate([[0], np.cumsum(3 * C)[:-1]]), np.full(k, 3), C, np.concatenate([[0], np.cumsum(6 * C)[:-1]])], 1).astype(np.int64)
+    tiles = -(-C // 256)
+    work = np.stack([np.repeat(np.arange(k), tiles), np.concatenate([np.arange(t) for t in tiles])], 1).astype(np.int32)
+    d_leaves, d_prof = be.upload(leaf_tab), be.empty(4 * int((6 * C).sum()))
+    d_cells, d_work = be.upload(np.concatenate([m.reshape(-1) for m in leaves])), be.upload(work)
+    be.call("mprg_align_profiles", be.ptr(d_cells), be.ptr(d_leaves), be.ptr(d_work), len(work), be.ptr(d_prof), be.stream)
+    d_seqs = be.upload(np.concatenate(seqs + [np.zeros(1, np.uint8)]))
+    seq_off, ops_off = np.concatenate([[0], np.cumsum(n)[:-1]]), np.concatenate([[0], np.cumsum(n + C)[:-1]])
+    ops_bytes = int((n + C).sum())
+    got = []
+    for call, words, band in (("mprg_align_pairs", pa.workspace_words_v(n, C), []),
+                              ("mprg_align_pairs_banded", pa.band_workspace_words(n, C, -n, C), [-n, C])):
+        ws_off = np.concatenate([[0], np.cumsum(words)[:-1]])
+        d_pairs = be.upload(np.stack([np.arange(k), seq_off, n, ws_off, ops_off] + band, 1).astype(np.int64))
+        d_ws, d_ops, d_out = be.empty(4 * int(words.sum())), be.empty(ops_bytes), be.empty(12 * k)
+        be.call(call, be.ptr(d_prof), be.ptr(d_leaves), k, be.ptr(d_seqs), be.ptr(d_pairs), k, be.ptr(d_ws), int(words.sum()),
+                be.ptr(d_ops), ops_bytes, be.ptr(d_out), be.stream)
+        res = be.download(d_out, np.int32, 3 * k).reshape(-1, 3)
+        ops = be.download(d_ops, np.uint8, ops_bytes)
+        got.append([(int(st), ops[o:o + c][::-1].tobytes().decode(), int(sc)) for (st, sc, c), o in zip(res.tolist(), ops_off.tolist())])
+    return got
+
+
+def check_forms_agree(be):
+    """The spec's "a one-row X is profile_align's pair DP exactly (same ops, same score)" on the device: the same problem through
+    mprg_align_pairs, mprg_align_profile_pairs with R_X = 1 and both banded entries with dlo = -n, dhi = C gives four equal
+    {status, score, ops}, align_ref's.  An empty X (C deletions, row 0's score) goes through the two sequence entries only:
+    mprg_prog_columns refuses a text of no columns (MPRG_PG_BAD_ITEM), so there is no X table to hand to the profile entries."""
+    cases = form_cases()
+    some = [(X, Y) for X, Y, _ in cases if X]
+    t = Tables(be, [((X,), Y) for X, Y in some])
+    assert t.RX.tolist() == [1] * len(some)
+    prof_full, prof_band = t.full(), t.banded([(-len(X), len(Y[0])) for X, Y in some])
+    seq_full, seq_band = _sequence_forms(be, [(X, Y) for X, Y, _ in cases])
+    for k, (X, Y, want) in enumerate(cases):
+        assert seq_full[k] == seq_band[k] == (0, *want), (len(X), len(Y[0]))
+        if not X:
+            assert want == ("D" * len(Y[0]), -704 + sum(ar.profile(Y)[1]))
+    for k, (X, Y) in enumerate(some):
+        assert prof_full[k] == prof_band[k] == seq_full[k][1:], (len(X), len(Y[0]))
+    # an X of no columns has no column table
+    d_text = be.upload(np.zeros(16, np.uint8))
+    d_bufs, d_items = be.upload(np.array([[be.ptr(d_text), 16]], np.int64)), be.upload(np.array([[0, 0, 1, 0, 1, 0]], np.int64))
+    d_cols, d_status = be.empty(64), be.empty(4)
+    be.call("mprg_prog_columns", be.ptr(d_bufs), 1, be.ptr(d_items), 1, be.ptr(be.upload(np.zeros(2, np.int32))), 1, be.ptr(d_cols), 16,
+            be.ptr(d_status), be.stream)
+    assert be.download(d_status, np.int32, 1).tolist() == [1]

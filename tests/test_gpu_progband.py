@@ -40,3 +40,7 @@ def test_certified_bands_give_the_full_dp(be):
 
 def test_abi_statuses(be):
     pbc.check_abi_statuses(be)
+
+
+def test_the_four_entries_of_the_sweep_agree_on_a_one_row_x(be):
+    pbc.check_forms_agree(be)

@@ -92,6 +92,10 @@ def test_abi_statuses(emu):
     pbc.check_abi_statuses(emu)
 
 
+def test_the_four_entries_of_the_sweep_agree_on_a_one_row_x(emu):
+    pbc.check_forms_agree(emu)
+
+
 def test_constants_and_a_negative_half_width():
     assert sa.PROG_BAND_W0 == pbr.W0 == 64 and sa.PG_BAND_PAIR_FIELDS == 8
     with pytest.raises(sa.StarAlignError, match="negative half-width"):
