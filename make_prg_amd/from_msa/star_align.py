@@ -175,12 +175,14 @@ calls with C = W, one counts launch (S, kept columns), and only where a column e
 Per round the host downloads S and the widths per locus and the status words, nothing larger; only the loci whose round was
 accepted go into the next one.  The text of a locus whose MSA changed is downloaded from the buffer of its last accepted round.
 """
-from typing import List, Optional, Sequence, Tuple
+import time
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
 from ..msa import MSA, encode
 from ..update import profile_align as pa
+from ..update.profile_align import _ranges, _tile_work, add_to, exclusive_sum   # (tests reach _tile_work through this module too)
 
 K = 6
 LOCUS_FIELDS, ROW_FIELDS = 4, 6           # MPRG_ST_LOCUS_FIELDS, MPRG_ST_ROW_FIELDS
@@ -204,6 +206,45 @@ _ASCII = np.frombuffer(b"ACGT-RYKMSWN", np.uint8)
 
 class StarAlignError(ValueError):
     pass
+
+
+def _check(status: np.ndarray, what: str, table: dict, noun: str = "work item"):
+    """The first non-zero status word of a launch as an error: `what` (the entry point), the `noun` it counts, its text in `table`."""
+    bad = np.nonzero(status)[0]
+    if len(bad):
+        raise StarAlignError(f"{what}: {noun} {bad[0]}: {table.get(int(status[bad[0]]), int(status[bad[0]]))}")
+
+
+class Chunk(NamedTuple):
+    """The loci of one chunk: per locus its name, its records' titles and gap-free code arrays; lens, seq_off: each record's
+    length and offset in the code buffer (all loci's records in one table); first, counts: each locus's records in that table;
+    d_codes, codes_bytes: the code buffer on the device."""
+    names: list
+    titles: list
+    codes: list
+    lens: np.ndarray
+    seq_off: np.ndarray
+    first: np.ndarray
+    counts: np.ndarray
+    d_codes: object
+    codes_bytes: int
+
+    @property
+    def n_loci(self) -> int:
+        return len(self.counts)
+
+
+class _Laps:
+    """The wall seconds of a chunk's stages: lap(key) adds what passed since the last lap to timings[key] (no key: to nothing)."""
+
+    def __init__(self, timings: Optional[dict]):
+        self.timings, self.t = timings, time.perf_counter()
+
+    def lap(self, key: Optional[str] = None):
+        now = time.perf_counter()
+        if key:
+            add_to(self.timings, key, now - self.t)
+        self.t = now
 
 
 def locus_codes(name: str, records: Sequence[Tuple[str, str]]) -> List[np.ndarray]:
@@ -258,20 +299,19 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
     (distances and trees) and progressive_s (the merges and the rows)."""
     if not (isinstance(refine, (int, np.integer)) and not isinstance(refine, bool) and 0 <= refine <= REFINE_MAX):
         raise ValueError(f"refine: a number of rounds from 0 to {REFINE_MAX}, not {refine!r}")
+    band = None if band is False or band is None else band      # from here on: None, True or pass 1's half-width
     names = [str(i) for i in range(len(loci))] if names is None else list(names)
     for name, recs in zip(names, loci):
         if not len(recs):
             from ..subcommands.from_msa import EmptyMSAError
             raise EmptyMSAError(f"No records found in MSA of locus {name}")
     codes = [locus_codes(n, recs) for n, recs in zip(names, loci)]
-    out: List[MSA] = []
     if progressive:
         return _progressive_msas(backend, loci, codes, names, budget_bytes, chunk_bytes, timings, adjust_direction, orientation, band,
                                  int(refine), refinement, progression, PROG_MAX_LEAVES if max_leaves is None else int(max_leaves))
-    for lo, hi in _chunks(codes, chunk_bytes):
-        out.extend(_star_chunk(backend, loci[lo:hi], codes[lo:hi], names[lo:hi], budget_bytes, timings, adjust_direction, orientation, band,
-                               int(refine), refinement))
-    return out
+    return [m for lo, hi in _chunks(codes, chunk_bytes)
+            for m in _star_chunk(backend, loci[lo:hi], codes[lo:hi], names[lo:hi], budget_bytes, timings, adjust_direction, orientation, band,
+                                 int(refine), refinement)]
 
 
 def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings, adjust_direction, orientation, band, refine, refinement,
@@ -303,49 +343,144 @@ def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings
     return out
 
 
-def centres(backend, codes: Sequence[Sequence[np.ndarray]]) -> np.ndarray:
-    """mprg_star_centres over the loci (per locus its gap-free code arrays): the centre index per locus, -1 if all are empty."""
-    return _centres(backend, *_pack(backend, codes))[0]
+def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direction=False, orientation=None, band=None, refine=0,
+                refinement=None, progressive=False, progression=None) -> List[MSA]:
+    """One chunk: pack, optionally orient, the star pass or the progressive one, optionally refine, collect."""
+    laps = _Laps(timings)
+    chunk = _pack(be, codes, names, [[t for t, _ in recs] for recs in loci])
+    if adjust_direction:
+        chunk, result = _orient(be, chunk, budget_bytes)
+        if orientation is not None:
+            orientation.extend(result)
+        laps.lap("orient_s")
+    text = _progressive(be, chunk, budget_bytes, band, laps, progression) if progressive else _star_pass(be, chunk, budget_bytes, band, laps)
+    moved = {}
+    if refine:
+        res = _refine(be, chunk, text, refine, budget_bytes, band, timings)
+        moved = {l: r[3] for l, r in enumerate(res) if r[3] is not None}
+        if refinement is not None:
+            refinement.extend(r[:3] for r in res)
+        laps.lap("refine_s")
+    msas = _collect(be, chunk, text, moved)
+    laps.lap(None if progressive else "merge_s")                # (merge_s ends at the star MSAs' download)
+    return msas
 
 
-def _pack(be, codes):
+def _pack(be, codes, names=None, titles=None) -> Chunk:
+    """The chunk of these loci (per locus its gap-free code arrays), its residues uploaded."""
     flat = [c for cs in codes for c in cs]
     lens = np.array([len(c) for c in flat], np.int64)
-    seq_off = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
     counts = np.array([len(cs) for cs in codes], np.int64)
-    first = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
+    first = exclusive_sum(counts)
+    if (np.add.reduceat(lens, first) >= 1 << 32).any():         # (every locus has a record)
+        raise StarAlignError("a locus of 2^32 residues or more")
     host = np.concatenate(flat + [np.zeros(1, np.uint8)]).astype(np.uint8)
-    return host, lens, seq_off, first, counts
+    return Chunk([str(l) for l in range(len(codes))] if names is None else names, [[""] * len(cs) for cs in codes] if titles is None else titles,
+                 codes, lens, exclusive_sum(lens), first, counts, be.upload(host), len(host))
 
 
-def _centres(be, host, lens, seq_off, first, counts):
-    _check_sizes(lens, first, counts)
-    d_codes = be.upload(host)
-    return _centre_launch(be, "mprg_star_centres", d_codes, len(host), lens, seq_off, first, counts)[0], d_codes
+def _collect(be, chunk: Chunk, text, moved) -> List[MSA]:
+    """The chunk's MSAs from the device: `text` as the star or progressive pass left it; moved: per refined locus where its text
+    is instead, (device buffer, its bytes, offset, width)."""
+    d_out, out_bytes, base, W = text
+    counts, titles = chunk.counts, chunk.titles
+    data = be.download(d_out, np.uint8, out_bytes)
+    fetched, upto = {}, {}
+    for l, (buf, _, off, w) in moved.items():                   # (a buffer is read up to the last byte a locus needs of it)
+        upto[id(buf)] = max(upto.get(id(buf), 0), off + int(counts[l]) * w)
+    msas = []
+    for l in range(chunk.n_loci):
+        src, off, w = data, base[l], W[l]
+        if l in moved:                                          # its last accepted round's buffer, downloaded once for all its loci
+            buf, _, off, w = moved[l]
+            if id(buf) not in fetched:
+                fetched[id(buf)] = be.download(buf, np.uint8, upto[id(buf)])
+            src = fetched[id(buf)]
+        rows = src[off:off + counts[l] * w].reshape(int(counts[l]), int(w))
+        msas.append(MSA(_data=rows, _ids=[(t.split(None, 1) or [""])[0] for t in titles[l]], _descs=titles[l]))
+    return msas
 
 
-def _check_sizes(lens, first, counts):
-    for l in range(len(counts)):
-        if int(lens[first[l]:first[l] + counts[l]].sum()) >= 1 << 32:
-            raise StarAlignError("a locus of 2^32 residues or more")
+# ---- the star pass
+def centres(backend, codes: Sequence[Sequence[np.ndarray]]) -> np.ndarray:
+    """mprg_star_centres over the loci (per locus its gap-free code arrays): the centre index per locus, -1 if all are empty."""
+    return _centre_launch(backend, "mprg_star_centres", _pack(backend, codes))[0]
 
 
-def _centre_launch(be, call, d_codes, codes_bytes, lens, seq_off, first, counts):
+def _seq_tables(be, chunk: Chunk):
+    """The chunk's sequence table {offset, n} and locus table {first sequence, sequences, 0, 0}, uploaded."""
+    ltab = np.zeros((chunk.n_loci, LOCUS_FIELDS), np.int64)
+    ltab[:, 0], ltab[:, 1] = chunk.first, chunk.counts
+    return be.upload(np.stack([chunk.seq_off, chunk.lens], 1).reshape(-1)), be.upload(ltab)
+
+
+def _centre_launch(be, call, chunk: Chunk):
     """mprg_star_centres or mprg_star_centres_canonical over sequence and locus tables uploaded here: (the centres, the device
     buffers of the sequence table, the locus table and the centres)."""
-    d_seqs = be.upload(np.stack([seq_off, lens], 1).reshape(-1))
-    ltab = np.zeros((len(counts), LOCUS_FIELDS), np.int64)
-    ltab[:, 0], ltab[:, 1] = first, counts
-    d_loci = be.upload(ltab)
-    d_centre = be.empty(4 * len(counts))
-    be.call(call, be.ptr(d_codes), codes_bytes, be.ptr(d_seqs), len(lens), be.ptr(d_loci), len(counts),
-            be.ptr(d_centre), be.stream, work=float(3 * lens.sum()))
-    centre = be.download(d_centre, np.int32, len(counts)).astype(np.int64)
+    d_seqs, d_loci = _seq_tables(be, chunk)
+    d_centre = be.empty(4 * chunk.n_loci)
+    be.call(call, be.ptr(chunk.d_codes), chunk.codes_bytes, be.ptr(d_seqs), len(chunk.lens), be.ptr(d_loci), chunk.n_loci,
+            be.ptr(d_centre), be.stream, work=float(3 * chunk.lens.sum()))
+    centre = be.download(d_centre, np.int32, chunk.n_loci).astype(np.int64)
     if (centre == CENTRE_BAD).any():
         raise StarAlignError(f"{call}: a locus's sequences lie outside the buffers")
     return centre, (d_seqs, d_loci, d_centre)
 
 
+def _star_pass(be, chunk: Chunk, budget_bytes, band, laps: _Laps):
+    """The spec's Centre, Pairs and Merge over one chunk, on the (oriented) sequences in chunk.d_codes.  Returns the MSAs' ASCII
+    text on the device: (the buffer, its bytes, each locus's offset in it, its width)."""
+    codes, first, counts, n_loci = chunk.codes, chunk.first, chunk.counts, chunk.n_loci
+    centre = _centre_launch(be, "mprg_star_centres", chunk)[0]
+    laps.lap("centre_s")
+    for l in np.nonzero(centre < 0)[0]:
+        raise StarAlignError(f"locus {chunk.names[l]}: every sequence is empty")
+    C = np.array([len(codes[l][centre[l]]) for l in range(n_loci)], np.int64)
+    # the pairs: the centre as a 1-row leaf, every other non-empty sequence against it
+    leaves = [codes[l][centre[l]].reshape(1, -1) for l in range(n_loci)]
+    others = [[a for a in range(len(cs)) if a != centre[l] and len(cs[a])] for l, cs in enumerate(codes)]
+    dp = pa.pairs_on_device(be, leaves, [[codes[l][a] for a in others[l]] for l in range(n_loci)], budget_bytes, band, laps.timings)
+    laps.lap("pairs_s")
+    # rows in input order: {locus, sequence offset, n, ops offset, ops count (-1: residue i in column i), output offset}
+    rows = np.zeros((len(chunk.lens), ROW_FIELDS), np.int64)
+    rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 4] = np.repeat(np.arange(n_loci), counts), chunk.seq_off, chunk.lens, -1
+    d_ops, ops_bytes = be.empty(16), 0
+    if dp is not None:
+        r = first[dp.leaf] + np.array([others[l][i] for l, i in zip(dp.leaf.tolist(), dp.index.tolist())], np.int64)
+        rows[r, 3], rows[r, 4] = dp.ops_off, dp.count
+        d_ops, ops_bytes = dp.d_ops, dp.ops_bytes
+    text = _star_merge(be, chunk, d_ops, ops_bytes, rows, first, counts, C)
+    laps.lap("merge_s")
+    return text
+
+
+def _star_merge(be, chunk: Chunk, d_ops, ops_bytes, rows, lfirst, R, C):
+    """The spec's Merge on the device: `rows` (the row table without output offsets) of loci that have rows lfirst .. lfirst + R of
+    it and C columns before the merge; residues from the chunk's code buffer, ops from d_ops.  mprg_star_merge_columns, the
+    widths downloaded, mprg_star_merge_rows into a new buffer: (the buffer, its bytes, each locus's offset in it, its width)."""
+    n_loci = len(R)
+    n_width = int((C + 1).sum())
+    d_loci, d_rows = be.upload(np.stack([lfirst, R, C, exclusive_sum(C + 1)], 1).astype(np.int64)), be.upload(rows)
+    d_width, d_start = be.zeros(4 * n_width), be.empty(8 * n_width)
+    d_w, d_status = be.empty(8 * n_loci), be.empty(4 * len(rows))
+    be.call("mprg_star_merge_columns", be.ptr(d_ops), ops_bytes, be.ptr(d_rows), len(rows), be.ptr(d_loci), n_loci, be.ptr(d_width),
+            be.ptr(d_start), n_width, chunk.codes_bytes, be.ptr(d_w), be.ptr(d_status), be.stream, work=float(ops_bytes))
+    W = be.download(d_w, np.int64, n_loci)
+    _check(be.download(d_status, np.int32, len(rows)), "mprg_star_merge_columns", ROW_STATUS, "row")
+    if (W < C).any():
+        raise StarAlignError("mprg_star_merge_columns: a locus's boundaries lie outside the buffers")
+    base = exclusive_sum(R * W)
+    rows[:, 5] = np.repeat(base, R) + (np.arange(len(rows)) - np.repeat(lfirst, R)) * np.repeat(W, R)
+    out_bytes = int((R * W).sum())
+    d_rows, d_out = be.upload(rows), be.empty(max(out_bytes, 1))
+    be.call("mprg_star_merge_rows", be.ptr(chunk.d_codes), chunk.codes_bytes, be.ptr(d_ops), ops_bytes, be.ptr(d_rows), len(rows),
+            be.ptr(d_loci), n_loci, be.ptr(d_width), be.ptr(d_start), n_width, be.ptr(d_w), be.ptr(d_out), max(out_bytes, 1),
+            be.ptr(d_status), be.stream, work=float(out_bytes + ops_bytes))
+    _check(be.download(d_status, np.int32, len(rows)), "mprg_star_merge_rows", ROW_STATUS, "row")
+    return d_out, out_bytes, base, W
+
+
+# ---- orientation
 _COMP = np.array([3, 2, 1, 0, 4, 6, 5, 8, 7, 9, 10, 11], np.uint8)
 
 
@@ -362,26 +497,22 @@ def _lex_less(x: np.ndarray, y: np.ndarray) -> bool:
 
 def canonical_centres(backend, codes: Sequence[Sequence[np.ndarray]]) -> np.ndarray:
     """mprg_star_centres_canonical over the loci: the orientation centre per locus, -1 if all its sequences are empty."""
-    host, lens, seq_off, first, counts = _pack(backend, codes)
-    _check_sizes(lens, first, counts)
-    return _centre_launch(backend, "mprg_star_centres_canonical", backend.upload(host), len(host), lens, seq_off, first, counts)[0]
+    return _centre_launch(backend, "mprg_star_centres_canonical", _pack(backend, codes))[0]
 
 
 def strand_evidence(backend, codes: Sequence[Sequence[np.ndarray]], centre: Sequence[int]) -> np.ndarray:
     """mprg_star_strand over the loci against the given centre per locus, AS STORED (no swap): {fwd, rev, nw} per sequence, all
     loci's sequences in one (n, 3) int64 array."""
-    host, lens, seq_off, first, counts = _pack(backend, codes)
-    ltab = np.zeros((len(counts), LOCUS_FIELDS), np.int64)
-    ltab[:, 0], ltab[:, 1] = first, counts
-    d = (backend.upload(np.stack([seq_off, lens], 1).reshape(-1)), backend.upload(ltab), backend.upload(np.asarray(centre, np.int32)))
-    return _evidence(backend, backend.upload(host), len(host), len(lens), len(counts), d)
+    chunk = _pack(backend, codes)
+    return _evidence(backend, chunk, (*_seq_tables(backend, chunk), backend.upload(np.asarray(centre, np.int32))))
 
 
-def _evidence(be, d_codes, codes_bytes, n_seqs, n_loci, tables):
+def _evidence(be, chunk: Chunk, tables):
     d_seqs, d_loci, d_centre = tables
+    n_seqs, n_loci = len(chunk.lens), chunk.n_loci
     d_ev, d_status = be.empty(24 * n_seqs), be.empty(4 * n_loci)
-    be.call("mprg_star_strand", be.ptr(d_codes), codes_bytes, be.ptr(d_seqs), n_seqs, be.ptr(d_loci), n_loci, be.ptr(d_centre),
-            be.ptr(d_ev), be.ptr(d_status), be.stream, work=float(codes_bytes))
+    be.call("mprg_star_strand", be.ptr(chunk.d_codes), chunk.codes_bytes, be.ptr(d_seqs), n_seqs, be.ptr(d_loci), n_loci, be.ptr(d_centre),
+            be.ptr(d_ev), be.ptr(d_status), be.stream, work=float(chunk.codes_bytes))
     if be.download(d_status, np.int32, n_loci).any():
         raise StarAlignError("mprg_star_strand: a locus's sequences or its centre lie outside the buffers")
     return be.download(d_ev, np.int64, 3 * n_seqs).reshape(-1, 3)
@@ -399,23 +530,21 @@ def revcomp_on_device(be, d_codes, codes_bytes: int, jobs: np.ndarray):
 def orientations(backend, codes: Sequence[Sequence[np.ndarray]], names: Optional[Sequence[str]] = None,
                  budget_bytes: int = pa.DEFAULT_BUDGET_BYTES) -> List[Tuple[List[bool], str]]:
     """The spec's Orientation step alone over the loci (per locus its gap-free code arrays): per locus (reversed, how)."""
-    names = [str(i) for i in range(len(codes))] if names is None else names
-    return _orient(backend, codes, names, *_pack(backend, codes), budget_bytes)[4]
+    return _orient(backend, _pack(backend, codes, names), budget_bytes)[1]
 
 
-def _orient(be, codes, names, host, lens, seq_off, first, counts, budget_bytes):
-    """The spec's Orientation step for one chunk.  The residues are uploaded once; the reverse complements of the records it
-    reverses are written by the device into a tail of that buffer, and the sequence table points there.  Returns the oriented
-    code arrays per locus (host side: what the pair stage uploads), the sequence offsets, the device buffer and its size, and per
+def _orient(be, chunk: Chunk, budget_bytes):
+    """The spec's Orientation step for one chunk.  The reverse complements of the records it reverses are written by the device
+    into a tail of the code buffer, and the sequence table points there.  Returns the oriented chunk (its code arrays: what the
+    pair stage uploads; the sequence offsets, the device buffer and its size; the reversed records' titles prefixed) and per
     locus (reversed flags, how codes)."""
-    _check_sizes(lens, first, counts)
-    n_loci, n_seqs = len(counts), len(lens)
-    d_codes = be.upload(host)
-    centre, tables = _centre_launch(be, "mprg_star_centres_canonical", d_codes, len(host), lens, seq_off, first, counts)
+    lens, seq_off, first, counts, n_loci = chunk.lens, chunk.seq_off, chunk.first, chunk.counts, chunk.n_loci
+    n_seqs = len(lens)
+    centre, tables = _centre_launch(be, "mprg_star_centres_canonical", chunk)
     for l in np.nonzero(centre < 0)[0]:
-        raise StarAlignError(f"locus {names[l]}: every sequence is empty")
-    ev = _evidence(be, d_codes, len(host), n_seqs, n_loci, tables)
-    flat = [c for cs in codes for c in cs]
+        raise StarAlignError(f"locus {chunk.names[l]}: every sequence is empty")
+    ev = _evidence(be, chunk, tables)
+    flat = [c for cs in chunk.codes for c in cs]
     locus_of = np.repeat(np.arange(n_loci), counts)
     cidx = first + centre
     # the reference orientation: the smaller of the centre and its reverse complement; against the latter fwd and rev swap
@@ -448,154 +577,43 @@ def _orient(be, codes, names, host, lens, seq_off, first, counts, budget_bytes):
     anchor = np.minimum.reduceat(np.where(nonempty, np.arange(n_seqs), n_seqs), first)
     rev_flag = nonempty & (opp != opp[anchor[locus_of]])
     rv = np.nonzero(rev_flag)[0]
-    codes_bytes = len(host)
+    d_codes, codes_bytes = chunk.d_codes, chunk.codes_bytes
     if len(rv):
-        dst = len(host) + np.concatenate([[0], np.cumsum(lens[rv])[:-1]]).astype(np.int64)
-        codes_bytes = len(host) + int(lens[rv].sum())
-        d_codes = be.grown(d_codes, len(host), codes_bytes)
+        dst = chunk.codes_bytes + exclusive_sum(lens[rv])
+        codes_bytes = chunk.codes_bytes + int(lens[rv].sum())
+        d_codes = be.grown(d_codes, chunk.codes_bytes, codes_bytes)
         revcomp_on_device(be, d_codes, codes_bytes, np.stack([seq_off[rv], lens[rv], dst], 1))
         seq_off = seq_off.copy()
         seq_off[rv] = dst
-        flat = list(flat)
         for u in rv:
             flat[u] = revcomp(flat[u])
-    oriented = [flat[first[l]:first[l] + counts[l]] for l in range(n_loci)]
-    result = [(rev_flag[first[l]:first[l] + counts[l]].tolist(), how[first[l]:first[l] + counts[l]].tobytes().decode()) for l in range(n_loci)]
-    return oriented, seq_off, d_codes, codes_bytes, result
-
-
-def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direction=False, orientation=None, band=False, refine=0,
-                refinement=None, progressive=False, progression=None) -> List[MSA]:
-    import time
-    t0 = time.perf_counter()
-    host, lens, seq_off, first, counts = _pack(be, codes)
-    titles = [[t for t, _ in recs] for recs in loci]
-    if adjust_direction:
-        codes, seq_off, d_codes, codes_bytes, result = _orient(be, codes, names, host, lens, seq_off, first, counts, budget_bytes)
-        titles = [[REVERSED_PREFIX + t if r else t for t, r in zip(ts, rev)] for ts, (rev, _) in zip(titles, result)]
-        if orientation is not None:
-            orientation.extend(result)
-        t_or = time.perf_counter()
-        if timings is not None:
-            timings["orient_s"] = timings.get("orient_s", 0.0) + t_or - t0
-        t0 = t_or
-        if not progressive:
-            centre = _centre_launch(be, "mprg_star_centres", d_codes, codes_bytes, lens, seq_off, first, counts)[0]
-    elif not progressive:
-        centre, d_codes = _centres(be, host, lens, seq_off, first, counts)
-        codes_bytes = len(host)
-    else:
-        _check_sizes(lens, first, counts)
-        d_codes, codes_bytes = be.upload(host), len(host)
-    n_loci = len(codes)
-    if progressive:
-        t1 = t2 = time.perf_counter()
-        d_out, out_bytes, base, W = _progressive(be, names, lens, seq_off, first, counts, d_codes, codes_bytes, budget_bytes, timings, progression,
-                                                   None if band is False or band is None else band)
-    else:
-        t1 = time.perf_counter()
-        for l in np.nonzero(centre < 0)[0]:
-            raise StarAlignError(f"locus {names[l]}: every sequence is empty")
-        C = np.array([len(codes[l][centre[l]]) for l in range(n_loci)], np.int64)
-        # the pairs: the centre as a 1-row leaf, every other non-empty sequence against it
-        leaves = [codes[l][centre[l]].reshape(1, -1) for l in range(n_loci)]
-        others = [[a for a in range(len(cs)) if a != centre[l] and len(cs[a])] for l, cs in enumerate(codes)]
-        dp = pa.pairs_on_device(be, leaves, [[codes[l][a] for a in others[l]] for l in range(n_loci)], budget_bytes,
-                                None if band is False or band is None else band, timings)
-        t2 = time.perf_counter()
-        # rows in input order: {locus, sequence offset, n, ops offset, ops count (-1: residue i in column i), output offset}
-        rows = np.zeros((int(counts.sum()), ROW_FIELDS), np.int64)
-        rows[:, 0] = np.repeat(np.arange(n_loci), counts)
-        rows[:, 1], rows[:, 2], rows[:, 4] = seq_off, lens, -1
-        if dp is not None:
-            r = first[dp.leaf] + np.array([others[l][i] for l, i in zip(dp.leaf.tolist(), dp.index.tolist())], np.int64)
-            rows[r, 3], rows[r, 4] = dp.ops_off, dp.count
-        d_ops = dp.d_ops if dp is not None else be.empty(16)
-        ops_bytes = dp.ops_bytes if dp is not None else 0
-        woff = np.concatenate([[0], np.cumsum(C + 1)[:-1]]).astype(np.int64)
-        n_width = int((C + 1).sum())
-        ltab = np.stack([first, counts, C, woff], 1).astype(np.int64)
-        d_loci, d_rows = be.upload(ltab), be.upload(rows)
-        d_width, d_start = be.zeros(4 * n_width), be.empty(8 * n_width)
-        d_w, d_status = be.empty(8 * n_loci), be.empty(4 * len(rows))
-        be.call("mprg_star_merge_columns", be.ptr(d_ops), ops_bytes, be.ptr(d_rows), len(rows), be.ptr(d_loci), n_loci, be.ptr(d_width),
-                be.ptr(d_start), n_width, codes_bytes, be.ptr(d_w), be.ptr(d_status), be.stream, work=float(ops_bytes))
-        W = be.download(d_w, np.int64, n_loci)
-        _check(be.download(d_status, np.int32, len(rows)), "mprg_star_merge_columns")
-        if (W < C).any():
-            raise StarAlignError("mprg_star_merge_columns: a locus's boundaries lie outside the buffers")
-        base = np.concatenate([[0], np.cumsum(counts * W)[:-1]]).astype(np.int64)
-        rank = np.arange(len(rows)) - np.repeat(first, counts)
-        rows[:, 5] = np.repeat(base, counts) + rank * np.repeat(W, counts)
-        out_bytes = int((counts * W).sum())
-        d_rows, d_out = be.upload(rows), be.empty(max(out_bytes, 1))
-        be.call("mprg_star_merge_rows", be.ptr(d_codes), codes_bytes, be.ptr(d_ops), ops_bytes, be.ptr(d_rows), len(rows), be.ptr(d_loci),
-                n_loci, be.ptr(d_width), be.ptr(d_start), n_width, be.ptr(d_w), be.ptr(d_out), max(out_bytes, 1), be.ptr(d_status),
-                be.stream, work=float(out_bytes + ops_bytes))
-        _check(be.download(d_status, np.int32, len(rows)), "mprg_star_merge_rows")
-    t3 = time.perf_counter()
-    moved = {}
-    if refine:
-        res = _refine(be, codes, lens, seq_off, first, counts, d_codes, codes_bytes, d_out, max(out_bytes, 1), base, W, refine,
-                      budget_bytes, None if band is False or band is None else band, timings)
-        moved = {l: r[3] for l, r in enumerate(res) if r[3] is not None}
-        if refinement is not None:
-            refinement.extend(r[:3] for r in res)
-        if timings is not None:
-            timings["refine_s"] = timings.get("refine_s", 0.0) + time.perf_counter() - t3
-        t3 = time.perf_counter() - t3
-    else:
-        t3 = 0.0
-    text = be.download(d_out, np.uint8, out_bytes)
-    fetched, upto = {}, {}
-    for l, (buf, _, off, w) in moved.items():                   # (a buffer is read up to the last byte a locus needs of it)
-        upto[id(buf)] = max(upto.get(id(buf), 0), off + int(counts[l]) * w)
-    msas = []
-    for l in range(n_loci):
-        if l in moved:                                          # its last accepted round's buffer, downloaded once for all its loci
-            buf, _, off, w = moved[l]
-            if id(buf) not in fetched:
-                fetched[id(buf)] = be.download(buf, np.uint8, upto[id(buf)])
-            data = fetched[id(buf)][off:off + counts[l] * w].reshape(int(counts[l]), int(w))
-        else:
-            data = text[base[l]:base[l] + counts[l] * W[l]].reshape(int(counts[l]), int(W[l]))
-        msas.append(MSA(_data=data, _ids=[(t.split(None, 1) or [""])[0] for t in titles[l]], _descs=titles[l]))
-    if timings is not None:
-        for k, v in (() if progressive else (("centre_s", t1 - t0), ("pairs_s", t2 - t1), ("merge_s", time.perf_counter() - t2 - t3))):
-            timings[k] = timings.get(k, 0.0) + v
-    return msas
+    per_locus = [slice(first[l], first[l] + counts[l]) for l in range(n_loci)]
+    result = [(rev_flag[s].tolist(), how[s].tobytes().decode()) for s in per_locus]
+    titles = [[REVERSED_PREFIX + t if r else t for t, r in zip(ts, rev)] for ts, (rev, _) in zip(chunk.titles, result)]
+    return chunk._replace(titles=titles, codes=[flat[s] for s in per_locus], seq_off=seq_off, d_codes=d_codes, codes_bytes=codes_bytes), result
 
 
 # ---- progressive
-def _pg_check(status: np.ndarray, what: str):
-    bad = np.nonzero(status)[0]
-    if len(bad):
-        raise StarAlignError(f"{what}: work item {bad[0]}: {PG_STATUS.get(int(status[bad[0]]), int(status[bad[0]]))}")
-
-
-def _prog_shared(be, d_codes, codes_bytes, lens, seq_off, first, counts, sel, budget_bytes):
+def _prog_shared(be, chunk: Chunk, sel, budget_bytes):
     """mprg_prog_distances over the loci `sel` of a chunk, in groups whose m x m tables fit budget_bytes: per locus (s as an
     (m, m) int64 array of which the part above the diagonal is filled, nw)."""
+    lens, first, counts = chunk.lens, chunk.first, chunk.counts
     out = {}
-    d_seqs = be.upload(np.stack([seq_off, lens], 1).reshape(-1))
-    need = 4 * counts[sel] ** 2
-    pos = 0
-    while pos < len(sel):
-        end = pos + max(1, int(np.searchsorted(np.cumsum(need[pos:]), budget_bytes, side="right")))
-        grp = sel[pos:end]
-        pos = end
+    d_seqs = be.upload(np.stack([chunk.seq_off, lens], 1).reshape(-1))
+    for lo, hi in pa.budget_groups(4 * counts[sel] ** 2, budget_bytes):
+        grp = sel[lo:hi]
         m = counts[grp]
-        toff = np.concatenate([[0], np.cumsum(m * m)[:-1]]).astype(np.int64)
+        toff = exclusive_sum(m * m)
         words = int((m * m).sum())
         ltab = np.zeros((len(grp), LOCUS_FIELDS), np.int64)
         ltab[:, 0], ltab[:, 1], ltab[:, 3] = first[grp], m, toff
         work = np.stack([np.repeat(np.arange(len(grp)), m), _ranges(np.zeros(len(grp), np.int64), m)], 1).astype(np.int32)
         d_loci, d_work = be.upload(ltab), be.upload(work)
         d_shared, d_nw, d_status = be.zeros(4 * words), be.zeros(8 * len(lens)), be.empty(4 * len(work))
-        be.call("mprg_prog_distances", be.ptr(d_codes), codes_bytes, be.ptr(d_seqs), len(lens), be.ptr(d_loci), len(grp), be.ptr(d_work),
-                len(work), be.ptr(d_shared), words, be.ptr(d_nw), be.ptr(d_status), be.stream,
+        be.call("mprg_prog_distances", be.ptr(chunk.d_codes), chunk.codes_bytes, be.ptr(d_seqs), len(lens), be.ptr(d_loci), len(grp),
+                be.ptr(d_work), len(work), be.ptr(d_shared), words, be.ptr(d_nw), be.ptr(d_status), be.stream,
                 work=float((m * np.add.reduceat(lens, first)[grp]).sum() + 16384.0 * (m * m).sum()))
-        _pg_check(be.download(d_status, np.int32, len(work)), "mprg_prog_distances")
+        _check(be.download(d_status, np.int32, len(work)), "mprg_prog_distances", PG_STATUS)
         shared = be.download(d_shared, np.uint32, words).astype(np.int64)
         nw = be.download(d_nw, np.int64, len(lens))
         for k, l in enumerate(grp.tolist()):
@@ -606,10 +624,8 @@ def _prog_shared(be, d_codes, codes_bytes, lens, seq_off, first, counts, sel, bu
 def prog_shared(backend, codes: Sequence[Sequence[np.ndarray]], budget_bytes: int = pa.DEFAULT_BUDGET_BYTES):
     """mprg_prog_distances over the loci (per locus its gap-free code arrays): per locus (s, nw): s an (m, m) int64 array whose
     part above the diagonal holds the shared 6-mers of the records a < b, nw the records' valid windows."""
-    host, lens, seq_off, first, counts = _pack(backend, codes)
-    _check_sizes(lens, first, counts)
-    got = _prog_shared(backend, backend.upload(host), len(host), lens, seq_off, first, counts, np.arange(len(counts)), budget_bytes)
-    return [got[l] for l in range(len(counts))]
+    got = _prog_shared(backend, _pack(backend, codes), np.arange(len(codes)), budget_bytes)
+    return [got[l] for l in range(len(codes))]
 
 
 def prog_distance_matrix(shared: np.ndarray, nw: np.ndarray) -> np.ndarray:
@@ -656,6 +672,33 @@ def prog_tree(D: np.ndarray, leaves: Sequence[int]) -> List[Tuple[int, int]]:
     return merges
 
 
+def _prog_plan(lens, first, counts, shared):
+    """What the spec's Tree decides for a chunk, from its tables and _prog_shared's of the loci of three or more leaves (two leaves
+    have one tree); no device, no clock.  A leaf's node id is its record index, an inner node's counts on from the locus's records.
+    Returns (per locus its leaves: the non-empty records; per round its merges (locus, y, x, parent), Y the child with more rows;
+    per locus its root node; per locus the records of the root's rows in row order: Y's rows, then X's, at every node; per locus
+    the progression tuple (leaves, rounds, False))."""
+    leaves, by_round, roots, root_members, progression = [], {}, [], [], []
+    for l in range(len(counts)):
+        lv = np.nonzero(lens[first[l]:first[l] + counts[l]] > 0)[0].tolist()
+        merges = [(lv[0], lv[1])] if len(lv) == 2 else prog_tree(prog_distance_matrix(*shared[l]), lv) if len(lv) > 2 else []
+        members = {a: [a] for a in lv}
+        node_at, rnd, nxt = {a: a for a in lv}, {a: 0 for a in lv}, int(counts[l])
+        for u, v in merges:
+            a, b = node_at[u], node_at[v]                       # key(a) = u < v = key(b)
+            y, x = (a, b) if len(members[a]) >= len(members[b]) else (b, a)
+            members[nxt] = members.pop(y) + members.pop(x)
+            rnd[nxt] = 1 + max(rnd[a], rnd[b])
+            by_round.setdefault(rnd[nxt], []).append((l, y, x, nxt))
+            node_at[u] = nxt
+            nxt += 1
+        leaves.append(lv)
+        roots.append(node_at[lv[0]])
+        root_members.append(members[roots[-1]])
+        progression.append((len(lv), rnd[roots[-1]], False))
+    return leaves, by_round, roots, root_members, progression
+
+
 def _prog_w0(band):
     """Pass 1's half-width of the banded merges, or None: the full DP."""
     if band is None or band is False:
@@ -666,22 +709,15 @@ def _prog_w0(band):
     return w0
 
 
-def _prog_need(WX, WY, w0):
-    """What a merge takes of a group's workspace: the full DP's words, or with band pass 1's (the full DP's where its band does
-    not help)."""
-    need = pa.workspace_words_v(WX, WY)
-    if w0 is None:
-        return need
-    dlo, dhi, helps = pa.band_first(WX, WY, w0)
-    return np.where(helps, pa.band_workspace_words(WX, WY, dlo, dhi), need)
-
-
 def _prog_groups(WX, WY, budget_bytes, band=None):
     """The merges (X's and Y's columns) longest first in groups whose workspace and column tables each fit the budget; with band
-    the workspace is pass 1's."""
+    the workspace is pass 1's (the full DP's for a merge its band does not help)."""
     order = np.argsort(-((WX + 1) * WY), kind="stable")
-    for grp, _, _ in pa.budget_launches(order, _prog_need(WX, WY, _prog_w0(band)), budget_bytes, StarAlignError, "merge", WX, WY,
-                                        also=7 * WX + 6 * WY):
+    need, w0 = pa.workspace_words_v(WX, WY), _prog_w0(band)
+    if w0 is not None:
+        dlo, dhi, helps = pa.band_first(WX, WY, w0)
+        need = np.where(helps, pa.band_workspace_words(WX, WY, dlo, dhi), need)
+    for grp, _, _ in pa.budget_launches(order, need, budget_bytes, StarAlignError, "merge", WX, WY, also=7 * WX + 6 * WY):
         yield grp
 
 
@@ -695,7 +731,7 @@ def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUD
     k = np.nonzero(WX + WY >= pa.MAX_LEN)[0]
     if len(k):
         raise StarAlignError(f"a merge of {WX[k[0]]} columns against {WY[k[0]]}: their sum must stay below {pa.MAX_LEN}")
-    ycol = np.concatenate([[0], np.cumsum(6 * WY + 7 * WX)[:-1]]).astype(np.int64)
+    ycol = exclusive_sum(6 * WY + 7 * WX)
     xcol = ycol + 6 * WY
     words = int((6 * WY + 7 * WX).sum())
     items = np.zeros((2 * n, PG_ITEM_FIELDS), np.int64)
@@ -706,25 +742,12 @@ def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUD
     be.call("mprg_prog_columns", be.ptr(d_bufs), n_bufs, be.ptr(d_items), len(items), be.ptr(d_work), len(work), be.ptr(d_cols), words,
             be.ptr(d_status), be.stream, work=float((items[:, 2] * items[:, 3]).sum()))
     need = pa.workspace_words_v(WX, WY)
-    ops_off = np.concatenate([[0], np.cumsum(WX + WY)[:-1]]).astype(np.int64)
+    ops_off = exclusive_sum(WX + WY)
     ops_bytes = int((WX + WY).sum())
     leaf_tab = np.stack([np.zeros(n, np.int64), Y[:, 2], WY, ycol], 1).astype(np.int64)
     d_leaves = be.upload(leaf_tab)
     d_ops = be.empty(ops_bytes)
     w0 = _prog_w0(band)
-    if w0 is None:
-        ws_off = np.concatenate([[0], np.cumsum(need)[:-1]]).astype(np.int64)
-        pairs = np.stack([np.arange(n), xcol, WX, ws_off, ops_off, X[:, 2]], 1).astype(np.int64)
-        d_pairs = be.upload(pairs)
-        d_ws, d_out = be.empty(4 * int(need.sum())), be.empty(12 * n)
-        be.call("mprg_align_profile_pairs", be.ptr(d_cols), be.ptr(d_leaves), n, be.ptr(d_cols), words, be.ptr(d_pairs), n, be.ptr(d_ws),
-                int(need.sum()), be.ptr(d_ops), ops_bytes, be.ptr(d_out), be.stream, work=pa.sweep_work(WX, WY))
-        _pg_check(be.download(d_status, np.int32, len(work)), "mprg_prog_columns")
-        res = be.download(d_out, np.int32, 3 * n).reshape(-1, 3)
-        bad = np.nonzero(res[:, 0])[0]
-        if len(bad):
-            raise StarAlignError(f"mprg_align_profile_pairs: {pa.STATUS.get(int(res[bad[0], 0]), int(res[bad[0], 0]))}")
-        return d_ops, ops_bytes, ops_off, res[:, 2].astype(np.int64), res[:, 1].astype(np.int64)
     pending = []                                                # (merges, call, the launch's triples, its table): downloaded at the end
 
     def launches(call, idx, wordsv, dlo=None, dhi=None):
@@ -748,16 +771,19 @@ def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUD
             got = be.download(d_got, np.uint8, 20 * len(sel))
             status = got[16 * len(sel):].view(np.int32)
             if status.any():
-                _pg_check(be.download(d_status, np.int32, len(work)), "mprg_prog_columns")
+                _check(be.download(d_status, np.int32, len(work)), "mprg_prog_columns", PG_STATUS)
                 res = be.download(d_out, np.int32, 3 * len(sel)).reshape(-1, 3)
                 code = int(res[res[:, 0] != 0][0, 0]) if res[:, 0].any() else int(status[status != 0][0])
                 raise StarAlignError(f"mprg_align_profile_pairs_banded / mprg_prog_band_widths: {pa.STATUS.get(code, code)}")
             wstar[sel] = got[:16 * len(sel)].view(np.int64).reshape(-1, 2)[:, 1]
         return wstar, wstar
-    second, rest, dlo, dhi, counts = pa.band_plan(WX, WY, w0, pass1)
-    launches("mprg_align_profile_pairs_banded", second, pa.band_workspace_words(WX, WY, dlo, dhi), dlo, dhi)
-    launches("mprg_align_profile_pairs", rest, need)
-    _pg_check(be.download(d_status, np.int32, len(work)), "mprg_prog_columns")
+    if w0 is None:                                              # (one launch: _prog_groups sized the group by this need)
+        launches("mprg_align_profile_pairs", np.arange(n), need)
+    else:
+        second, rest, dlo, dhi, counts = pa.band_plan(WX, WY, w0, pass1)
+        launches("mprg_align_profile_pairs_banded", second, pa.band_workspace_words(WX, WY, dlo, dhi), dlo, dhi)
+        launches("mprg_align_profile_pairs", rest, need)
+    _check(be.download(d_status, np.int32, len(work)), "mprg_prog_columns", PG_STATUS)
     count, score = np.zeros(n, np.int64), np.zeros(n, np.int64)
     for sel, call, d_out, _ in pending:                          # in launch order: a later pass's result replaces pass 1's
         res = be.download(d_out, np.int32, 3 * len(sel)).reshape(-1, 3)
@@ -765,10 +791,9 @@ def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUD
         if len(bad):
             raise StarAlignError(f"{call}: {pa.STATUS.get(int(res[bad[0], 0]), int(res[bad[0], 0]))}")
         score[sel], count[sel] = res[:, 1], res[:, 2]
-    if counters is not None:
-        for key, v in zip(("prog_band_merges", "prog_band_second_passes", "prog_band_full_merges", "prog_band_cells",
-                            "prog_band_full_cells"), counts):
-            counters[key] = counters.get(key, 0) + int(v)
+    for key, v in zip(("prog_band_merges", "prog_band_second_passes", "prog_band_full_merges", "prog_band_cells", "prog_band_full_cells"),
+                      () if w0 is None else counts):
+        add_to(counters, key, int(v))
     return d_ops, ops_bytes, ops_off, count, score
 
 
@@ -799,61 +824,58 @@ def merge_profiles(backend, pairs: Sequence[Tuple[np.ndarray, np.ndarray]], budg
     return out
 
 
-def _progressive(be, names, lens, seq_off, first, counts, d_codes, codes_bytes, budget_bytes, timings, progression, band=None):
-    """The spec's Progressive over one chunk, on the (oriented) sequences in d_codes.  Returns what the star pass leaves: the
+def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression):
+    """The spec's Progressive over one chunk, on the (oriented) sequences in chunk.d_codes.  Returns what the star pass leaves: the
     device buffer of the MSAs' ASCII text, its bytes, each locus's offset in it and its width."""
-    import time
-    t0 = time.perf_counter()
-    n_loci = len(counts)
-    leaves = [np.nonzero(lens[first[l]:first[l] + counts[l]] > 0)[0] for l in range(n_loci)]
-    for l in range(n_loci):
-        if not len(leaves[l]):
-            raise StarAlignError(f"locus {names[l]}: every sequence is empty")
+    laps.lap()
+    lens, first, counts = chunk.lens, chunk.first, chunk.counts
+    n_leaves = np.add.reduceat((lens > 0).astype(np.int64), first)          # (every locus has a record)
+    for l in np.nonzero(n_leaves == 0)[0]:
+        raise StarAlignError(f"locus {chunk.names[l]}: every sequence is empty")
     # the trees: distances on the device for the loci with three or more leaves (two leaves have one tree), UPGMA on the host
-    sel = np.array([l for l in range(n_loci) if len(leaves[l]) >= 3], np.int64)
-    shared = _prog_shared(be, d_codes, codes_bytes, lens, seq_off, first, counts, sel, budget_bytes) if len(sel) else {}
-    # nodes per locus: a leaf's id is its record index, an inner node's counts on from the locus's records.  members: the records
-    # of a node's rows, in row order (Y's rows, then X's)
-    where, members, by_round = {}, {}, {}
-    root = []
-    for l in range(n_loci):
-        lv = leaves[l].tolist()
-        for a in lv:
-            where[l, a] = (0, int(seq_off[first[l] + a]), 1, int(lens[first[l] + a]))
-            members[l, a] = [a]
-        merges = [(lv[0], lv[1])] if len(lv) == 2 else prog_tree(prog_distance_matrix(*shared[l]), lv) if len(lv) > 2 else []
-        node_at, rnd, nxt = {a: a for a in lv}, {a: 0 for a in lv}, int(counts[l])
-        for u, v in merges:
-            a, b = node_at[u], node_at[v]                       # key(a) = u < v = key(b)
-            y, x = (a, b) if len(members[l, a]) >= len(members[l, b]) else (b, a)
-            members[l, nxt] = members[l, y] + members[l, x]
-            rnd[nxt] = 1 + max(rnd[a], rnd[b])
-            by_round.setdefault(rnd[nxt], []).append((l, y, x, nxt))
-            node_at[u] = nxt
-            nxt += 1
-        root.append(node_at[lv[0]])
-        if progression is not None:
-            progression.append((len(lv), rnd[root[-1]], False))
-    t1 = time.perf_counter()
-    # the rounds: every node of a round, over all loci of the chunk, in one set of launches per budget group; a group's parents
-    # go into a text buffer of their own, a buffer is dropped when its last node has been merged into a parent
-    bufs, live = [(d_codes, codes_bytes)], [0]
-    for r in sorted(by_round):
-        todo = by_round[r]
+    sel = np.nonzero(n_leaves >= 3)[0]
+    plan = _prog_plan(lens, first, counts, _prog_shared(be, chunk, sel, budget_bytes) if len(sel) else {})
+    if progression is not None:
+        progression.extend(plan[-1])
+    laps.lap("tree_s")
+    text = _prog_rounds(be, chunk, plan, budget_bytes, band, laps.timings)
+    laps.lap("progressive_s")
+    return text
+
+
+def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters):
+    """_progressive's device part: the plan's rounds (every node of a round, over all loci of the chunk, in one set of launches
+    per budget group), then the roots' rows in input order.
+    The texts' lifetime: bufs[b] is (buffer, bytes) of text buffer b, 0 the chunk's code buffer (the leaves); where[locus, node]
+    is (b, offset, rows, width) of a node not yet merged; live[b] counts the nodes of where in b.  A group's parents go into a
+    buffer of their own; a buffer (but 0) is dropped when its last node has been merged into a parent."""
+    lens, seq_off, first, counts, n_loci = chunk.lens, chunk.seq_off, chunk.first, chunk.counts, chunk.n_loci
+    leaves, by_round, root, root_members, _ = plan
+    bufs, live = [(chunk.d_codes, chunk.codes_bytes)], [0]
+    where = {(l, a): (0, int(seq_off[first[l] + a]), 1, int(lens[first[l] + a])) for l in range(n_loci) for a in leaves[l]}
+
+    def merged(l, node):
+        """The node has gone into its parent: its buffer goes with its last node."""
+        b = where.pop((l, node))[0]
+        live[b] -= 1
+        if b and not live[b]:
+            bufs[b] = (None, 0)
+
+    for _, todo in sorted(by_round.items()):
         Y = np.array([where[l, y] for l, y, _, _ in todo], np.int64)
         X = np.array([where[l, x] for l, _, x, _ in todo], np.int64)
         for grp in _prog_groups(X[:, 3], Y[:, 3], budget_bytes, band):
             d_bufs = _bufs_table(be, bufs)
             Xg, Yg = X[grp], Y[grp]
-            d_ops, ops_bytes, ops_off, count, _ = _prog_pairs(be, d_bufs, len(bufs), Xg, Yg, band, budget_bytes, timings)
+            d_ops, ops_bytes, ops_off, count, _ = _prog_pairs(be, d_bufs, len(bufs), Xg, Yg, band, budget_bytes, counters)
             RY, RX = Yg[:, 2], Xg[:, 2]
             R = RY + RX
-            poff = np.concatenate([[0], np.cumsum(R * count)[:-1]]).astype(np.int64)
+            poff = exclusive_sum(R * count)
             new_bytes = int((R * count).sum())
             # the parents' rows: Y's, then X's, each through the merge's ops
             rows = np.zeros((int(R.sum()), PG_ROW_FIELDS), np.int64)
             of = np.repeat(np.arange(len(grp)), R)
-            rank = np.arange(len(rows)) - np.repeat(np.concatenate([[0], np.cumsum(R)[:-1]]), R)
+            rank = np.arange(len(rows)) - np.repeat(exclusive_sum(R), R)
             is_x = rank >= RY[of]
             src = np.where(is_x[:, None], Xg[of], Yg[of])
             rows[:, 0] = src[:, 0]
@@ -863,20 +885,17 @@ def _progressive(be, names, lens, seq_off, first, counts, d_codes, codes_bytes, 
             d_rows, d_new, d_status = be.upload(rows), be.empty(new_bytes), be.empty(4 * len(rows))
             be.call("mprg_prog_rows", be.ptr(d_bufs), len(bufs), be.ptr(d_ops), ops_bytes, be.ptr(d_rows), len(rows), be.ptr(d_new), new_bytes,
                     0, be.ptr(d_status), be.stream, work=float(2 * new_bytes))
-            _pg_check(be.download(d_status, np.int32, len(rows)), "mprg_prog_rows")
+            _check(be.download(d_status, np.int32, len(rows)), "mprg_prog_rows", PG_STATUS)
             bufs.append((d_new, new_bytes))
             live.append(len(grp))
             for i, k in enumerate(grp.tolist()):
                 l, y, x, parent = todo[k]
                 where[l, parent] = (len(bufs) - 1, int(poff[i]), int(R[i]), int(count[i]))
-                for child in (y, x):
-                    b = where.pop((l, child))[0]
-                    live[b] -= 1
-                    if b and not live[b]:
-                        bufs[b] = (None, 0)
+                merged(l, y)
+                merged(l, x)
     # the roots' rows into input order, as ASCII; an empty record is a row of '-'
     W = np.array([where[l, root[l]][3] for l in range(n_loci)], np.int64)
-    base = np.concatenate([[0], np.cumsum(counts * W)[:-1]]).astype(np.int64)
+    base = exclusive_sum(counts * W)
     out_bytes = int((counts * W).sum())
     rows = np.zeros((int(counts.sum()), PG_ROW_FIELDS), np.int64)
     rows[:, 4] = -1
@@ -884,50 +903,29 @@ def _progressive(be, names, lens, seq_off, first, counts, d_codes, codes_bytes, 
     rows[:, 7] = np.repeat(W, counts)
     for l in range(n_loci):
         b, off, _, w = where[l, root[l]]
-        rec = first[l] + np.array(members[l, root[l]], np.int64)
+        rec = first[l] + np.array(root_members[l], np.int64)
         rows[rec, 0], rows[rec, 1], rows[rec, 2] = b, off + np.arange(len(rec)) * w, w
     d_bufs = _bufs_table(be, bufs)
     d_rows, d_out, d_status = be.upload(rows), be.empty(max(out_bytes, 1)), be.empty(4 * len(rows))
     be.call("mprg_prog_rows", be.ptr(d_bufs), len(bufs), be.ptr(d_out), 0, be.ptr(d_rows), len(rows), be.ptr(d_out), max(out_bytes, 1), 1,
             be.ptr(d_status), be.stream, work=float(2 * out_bytes))
-    _pg_check(be.download(d_status, np.int32, len(rows)), "mprg_prog_rows")
-    if timings is not None:
-        for k, v in (("tree_s", t1 - t0), ("progressive_s", time.perf_counter() - t1)):
-            timings[k] = timings.get(k, 0.0) + v
+    _check(be.download(d_status, np.int32, len(rows)), "mprg_prog_rows", PG_STATUS)
     return d_out, out_bytes, base, W
 
 
-def _rf_check(status: np.ndarray, what: str):
-    bad = np.nonzero(status)[0]
-    if len(bad):
-        raise StarAlignError(f"{what}: work item {bad[0]}: {RF_STATUS.get(int(status[bad[0]]), int(status[bad[0]]))}")
-
-
-def _ranges(start: np.ndarray, n: np.ndarray) -> np.ndarray:
-    """start[0], start[0] + 1, ... (n[0] of them), start[1], ...: the concatenated ranges, without a Python loop."""
-    n = np.asarray(n, np.int64)
-    return np.repeat(np.asarray(start, np.int64) - (np.cumsum(n) - n), n) + np.arange(int(n.sum()), dtype=np.int64)
-
-
-def _tile_work(widths: np.ndarray) -> np.ndarray:
-    """{item, 256-column tile} for items of these widths."""
-    tiles = -(-widths // 256)
-    return np.stack([np.repeat(np.arange(len(widths)), tiles), _ranges(np.zeros(len(widths), np.int64), tiles)], 1).astype(np.int32)
-
-
+# ---- refinement
 def refine_counts(be, d_text, text_bytes: int, toff: np.ndarray, R: np.ndarray, W: np.ndarray):
     """mprg_refine_counts over MSAs on the device (per locus its offset in d_text, rows and columns): (the locus table with
     the column offsets filled in, the counts buffer, the keep flags, the columns, S per locus, the kept columns per locus)."""
     n = len(W)
-    coff = np.concatenate([[0], np.cumsum(W)[:-1]]).astype(np.int64)
     n_cols = int(W.sum())
-    rtab = np.stack([toff, R, W, coff], 1).astype(np.int64)
+    rtab = np.stack([toff, R, W, exclusive_sum(W)], 1).astype(np.int64)
     work = _tile_work(W)
     d_counts, d_keep, d_sums, d_status = be.empty(20 * n_cols), be.empty(n_cols), be.zeros(16 * n), be.empty(4 * len(work))
     d_rtab, d_work = be.upload(rtab), be.upload(work)
     be.call("mprg_refine_counts", be.ptr(d_text), text_bytes, be.ptr(d_rtab), n, be.ptr(d_work), len(work),
             be.ptr(d_counts), be.ptr(d_keep), n_cols, be.ptr(d_sums), be.ptr(d_status), be.stream, work=float((R * W).sum()))
-    _rf_check(be.download(d_status, np.int32, len(work)), "mprg_refine_counts")
+    _check(be.download(d_status, np.int32, len(work)), "mprg_refine_counts", RF_STATUS)
     sums = be.download(d_sums, np.int64, 2 * n).reshape(-1, 2)
     return rtab, d_counts, d_keep, n_cols, sums[:, 0].copy(), sums[:, 1].copy()
 
@@ -936,7 +934,7 @@ def refine_profiles(be, d_text, text_bytes: int, rtab: np.ndarray, d_counts, n_c
     """mprg_refine_profiles: the leave-one-out profiles of the given rows (locus: an index into rtab) into one buffer:
     (the buffer, each row's offset in it in int32 elements, its size in int32 elements)."""
     Wr = rtab[row_locus, 2]
-    poff = np.concatenate([[0], np.cumsum(6 * Wr)[:-1]]).astype(np.int64)
+    poff = exclusive_sum(6 * Wr)
     words = int((6 * Wr).sum())
     work = _tile_work(Wr)
     d_prof, d_status = be.empty(4 * words), be.empty(4 * len(work))
@@ -945,7 +943,7 @@ def refine_profiles(be, d_text, text_bytes: int, rtab: np.ndarray, d_counts, n_c
     be.call("mprg_refine_profiles", be.ptr(d_text), text_bytes, be.ptr(d_rtab), len(rtab), be.ptr(d_counts), n_cols,
             be.ptr(d_rows), len(rows), be.ptr(d_work), len(work), be.ptr(d_prof), words, be.ptr(d_status), be.stream,
             work=float(24 * words))
-    _rf_check(be.download(d_status, np.int32, len(work)), "mprg_refine_profiles")
+    _check(be.download(d_status, np.int32, len(work)), "mprg_refine_profiles", RF_STATUS)
     return d_prof, poff, words
 
 
@@ -959,26 +957,26 @@ def refine_compact(be, d_text, text_bytes: int, rtab: np.ndarray, d_keep, n_cols
     be.call("mprg_refine_compact", be.ptr(d_text), text_bytes, be.ptr(d_rtab), len(rtab), be.ptr(d_keep), n_cols, be.ptr(d_dest),
             be.ptr(d_nw), be.ptr(d_rows), len(rows), be.ptr(d_out), out_bytes, be.ptr(d_status), be.stream,
             work=float(2 * (R * rtab[:, 2]).sum()))
-    _rf_check(be.download(d_status, np.int32, len(rows)), "mprg_refine_compact")
+    _check(be.download(d_status, np.int32, len(rows)), "mprg_refine_compact", RF_STATUS)
     return d_out
 
 
-def _refine(be, codes, lens, seq_off, first, counts, d_codes, codes_bytes, d_text, text_bytes, base, W, rounds, budget_bytes, band, counters):
-    """The spec's Refinement over one chunk, on the MSA text mprg_star_merge_rows left on the device.  Per locus: (rounds accepted,
-    S of the star MSA, S of the result, None or where its new text is: (device buffer, its bytes, offset, width))."""
-    n_loci = len(counts)
-    rtab, d_counts, _, n_cols, S0, _ = refine_counts(be, d_text, text_bytes, base, counts, W)
-    out = [[0, int(S0[l]), int(S0[l]), None] for l in range(n_loci)]
+def _refine(be, chunk: Chunk, text, rounds, budget_bytes, band, counters):
+    """The spec's Refinement over one chunk, on the MSA text the star or progressive pass left on the device (text: what they
+    return).  Per locus: (rounds accepted, S of the star MSA, S of the result, None or where its new text is: (device buffer, its
+    bytes, offset, width))."""
+    lens, seq_off, first = chunk.lens, chunk.seq_off, chunk.first
+    d_text, text_bytes, base, W = text
+    text_bytes = max(text_bytes, 1)
+    rtab, d_counts, _, n_cols, S0, _ = refine_counts(be, d_text, text_bytes, base, chunk.counts, W)
+    out = [[0, int(S0[l]), int(S0[l]), None] for l in range(chunk.n_loci)]
     n_filled = np.add.reduceat((lens > 0).astype(np.int64), first)           # (every locus has a record)
     longest = np.maximum.reduceat(lens, first)
     todo = np.nonzero(n_filled >= 3)[0]
-    need = 24 * W[todo] * n_filled[todo]                        # the profiles of a locus's round
     budget_words = max(64, int(budget_bytes) // 4)
-    pos = 0
-    while pos < len(todo):                                      # groups whose profiles fit the budget
-        end = pos + max(1, int(np.searchsorted(np.cumsum(need[pos:]), budget_bytes, side="right")))
-        act = todo[pos:end]
-        pos = end
+    # groups whose profiles of a round (24 W bytes per non-empty row) fit the budget
+    for lo, hi in pa.budget_groups(24 * W[todo] * n_filled[todo], budget_bytes):
+        act = todo[lo:hi]
         # the active loci's current MSAs: rows of `tab` {offset in buf, R, W, offset in the column tables of cnt}, S
         buf, buf_bytes, tab, cnt, cols, S = d_text, text_bytes, rtab[act], d_counts, n_cols, S0[act]
         for _ in range(rounds):
@@ -988,40 +986,19 @@ def _refine(be, codes, lens, seq_off, first, counts, d_codes, codes_bytes, d_tex
             act, tab, S = act[fits], tab[fits], S[fits]
             if not len(act):
                 break
-            n_act, R, Wc = len(act), tab[:, 1], tab[:, 2]
-            all_rows = _ranges(first[act], R)                   # the loci's rows in the chunk's sequence table
-            of_locus = np.repeat(np.arange(n_act), R)
+            R, Wc = tab[:, 1], tab[:, 2]
+            all_rows = _ranges(first[act], R)                # the loci's rows in the chunk's sequence table
+            of_locus = np.repeat(np.arange(len(act)), R)
             q = np.nonzero(lens[all_rows] > 0)[0]               # the non-empty ones: a leave-one-out profile and a pair each
             row_locus, grow = of_locus[q], all_rows[q]
-            row_in = grow - first[act][row_locus]
-            d_prof, poff, _ = refine_profiles(be, buf, buf_bytes, tab, cnt, cols, row_locus, row_in)
-            prepared = pa.PreparedProfiles(d_prof, np.stack([R[row_locus] - 1, Wc[row_locus]], 1), poff, d_codes, seq_off[grow], lens[grow])
+            d_prof, poff, _ = refine_profiles(be, buf, buf_bytes, tab, cnt, cols, row_locus, grow - first[act][row_locus])
+            prepared = pa.PreparedProfiles(d_prof, np.stack([R[row_locus] - 1, Wc[row_locus]], 1), poff, chunk.d_codes, seq_off[grow], lens[grow])
             dp = pa.pairs_on_device(be, None, None, budget_bytes, band, counters, prepared)
             # the merge over the W columns: every non-empty row has ops, an empty one stays all gaps (count -1, n = 0)
-            lfirst = np.concatenate([[0], np.cumsum(R)[:-1]]).astype(np.int64)
-            rows = np.zeros((int(R.sum()), ROW_FIELDS), np.int64)
-            rows[:, 0] = of_locus
-            rows[:, 1], rows[:, 2], rows[:, 4] = seq_off[all_rows], lens[all_rows], -1
+            rows = np.zeros((len(all_rows), ROW_FIELDS), np.int64)
+            rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 4] = of_locus, seq_off[all_rows], lens[all_rows], -1
             rows[q, 3], rows[q, 4] = dp.ops_off, dp.count
-            woff = np.concatenate([[0], np.cumsum(Wc + 1)[:-1]]).astype(np.int64)
-            n_width = int((Wc + 1).sum())
-            d_loci, d_rows = be.upload(np.stack([lfirst, R, Wc, woff], 1).astype(np.int64)), be.upload(rows)
-            d_width, d_start = be.zeros(4 * n_width), be.empty(8 * n_width)
-            d_w, d_status = be.empty(8 * n_act), be.empty(4 * len(rows))
-            be.call("mprg_star_merge_columns", be.ptr(dp.d_ops), dp.ops_bytes, be.ptr(d_rows), len(rows), be.ptr(d_loci), n_act,
-                    be.ptr(d_width), be.ptr(d_start), n_width, codes_bytes, be.ptr(d_w), be.ptr(d_status), be.stream, work=float(dp.ops_bytes))
-            W2 = be.download(d_w, np.int64, n_act)
-            _check(be.download(d_status, np.int32, len(rows)), "mprg_star_merge_columns")
-            if (W2 < Wc).any():
-                raise StarAlignError("mprg_star_merge_columns: a locus's boundaries lie outside the buffers")
-            off2 = np.concatenate([[0], np.cumsum(R * W2)[:-1]]).astype(np.int64)
-            rows[:, 5] = np.repeat(off2, R) + (np.arange(len(rows)) - np.repeat(lfirst, R)) * np.repeat(W2, R)
-            new_bytes = max(int((R * W2).sum()), 1)
-            d_rows, d_new = be.upload(rows), be.empty(new_bytes)
-            be.call("mprg_star_merge_rows", be.ptr(d_codes), codes_bytes, be.ptr(dp.d_ops), dp.ops_bytes, be.ptr(d_rows), len(rows),
-                    be.ptr(d_loci), n_act, be.ptr(d_width), be.ptr(d_start), n_width, be.ptr(d_w), be.ptr(d_new), new_bytes,
-                    be.ptr(d_status), be.stream, work=float(new_bytes + dp.ops_bytes))
-            _check(be.download(d_status, np.int32, len(rows)), "mprg_star_merge_rows")
+            d_new, new_bytes, off2, W2 = _star_merge(be, chunk, dp.d_ops, dp.ops_bytes, rows, exclusive_sum(R), R, Wc)
             tab2, cnt2, keep2, cols2, S2, kept = refine_counts(be, d_new, new_bytes, off2, R, W2)
             if (kept < W2).any():                               # a column emptied: drop it, count again (runs may have joined)
                 d_new = refine_compact(be, d_new, new_bytes, tab2, keep2, cols2, off2, new_bytes)
@@ -1032,12 +1009,6 @@ def _refine(be, codes, lens, seq_off, first, counts, d_codes, codes_bytes, d_tex
                 o[0], o[2], o[3] = o[0] + 1, int(S2[k]), (d_new, new_bytes, int(off2[k]), int(tab2[k, 2]))
             act, buf, buf_bytes, tab, cnt, cols, S = act[ok], d_new, new_bytes, tab2[ok], cnt2, cols2, S2[ok]
     return [tuple(o) for o in out]
-
-
-def _check(status: np.ndarray, what: str):
-    bad = np.nonzero(status)[0]
-    if len(bad):
-        raise StarAlignError(f"{what}: row {bad[0]}: {ROW_STATUS.get(int(status[bad[0]]), int(status[bad[0]]))}")
 
 
 # ---- files

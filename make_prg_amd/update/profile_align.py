@@ -84,9 +84,36 @@ class ProfileAlignError(ValueError):
     pass
 
 
-def workspace_words(n: int, C: int) -> int:
-    """int32 words of workspace a pair needs (include/mprg.h, mprg_align_pairs)."""
-    return -(-2 * (C + 1) // 64) * 64 + -(-n // 64) * ((C + 70) // 8) * 64
+def exclusive_sum(x) -> np.ndarray:
+    """0, x[0], x[0] + x[1], ...: where each of consecutive items of these sizes begins (int64, as long as x)."""
+    x = np.asarray(x, np.int64)
+    return np.cumsum(x) - x
+
+
+def add_to(totals: Optional[dict], key: str, value):
+    """totals[key] += value, from 0; nothing without a dict (the timings and counters a caller may ask for)."""
+    if totals is not None:
+        totals[key] = totals.get(key, 0) + value
+
+
+def _ranges(start: np.ndarray, n: np.ndarray) -> np.ndarray:
+    """start[0], start[0] + 1, ... (n[0] of them), start[1], ...: the concatenated ranges, without a Python loop."""
+    n = np.asarray(n, np.int64)
+    return np.repeat(np.asarray(start, np.int64) - (np.cumsum(n) - n), n) + np.arange(int(n.sum()), dtype=np.int64)
+
+
+def _tile_work(widths: np.ndarray) -> np.ndarray:
+    """{item, 256-column tile} for items of these widths."""
+    tiles = -(-widths // 256)
+    return np.stack([np.repeat(np.arange(len(widths)), tiles), _ranges(np.zeros(len(widths), np.int64), tiles)], 1).astype(np.int32)
+
+
+def workspace_words(n, C):
+    """int32 words of workspace a pair needs (include/mprg.h, mprg_align_pairs); plain integers or arrays."""
+    return (2 * (C + 1) + 63) // 64 * 64 + (n + 63) // 64 * ((C + 70) // 8) * 64
+
+
+workspace_words_v = workspace_words
 
 
 def band_limits(n, C, w_minus, w_plus):
@@ -104,11 +131,6 @@ def band_workspace_words(n, C, dlo, dhi):
 def band_helps(n, C, dlo, dhi):
     """The spec's rule for the full DP, negated: the band needs less workspace than the full matrix, in total and in its traceback."""
     return (band_workspace_words(n, C, dlo, dhi) < workspace_words_v(n, C)) & (dhi - dlo + 1 + 63 < C)
-
-
-def workspace_words_v(n, C):
-    """workspace_words over arrays."""
-    return (2 * (C + 1) + 63) // 64 * 64 + (n + 63) // 64 * ((C + 70) // 8) * 64
 
 
 def band_cells(n, C, dlo, dhi):
@@ -151,7 +173,17 @@ def budget_launches(order, words, budget_bytes, error, noun, n, C, also=None):
             used_also += 0 if also is None else int(also[order[end]])
             end += 1
         sel = order[pos:end]
-        yield sel, np.concatenate([[0], np.cumsum(words[sel])[:-1]]), used
+        yield sel, exclusive_sum(words[sel]), used
+        pos = end
+
+
+def budget_groups(need_bytes, budget_bytes):
+    """(lo, hi) of consecutive groups of the items, in the order given, whose bytes fit the budget.  Not budget_launches: it never
+    refuses (an item that alone exceeds the budget is a group of its own) and has no second need."""
+    pos = 0
+    while pos < len(need_bytes):
+        end = pos + max(1, int(np.searchsorted(np.cumsum(need_bytes[pos:]), budget_bytes, side="right")))
+        yield pos, end
         pos = end
 
 
@@ -256,12 +288,9 @@ def pairs_on_device(backend, leaves: Optional[Sequence[np.ndarray]], seqs: Seque
     if (shapes < 1).any():
         raise ProfileAlignError("a leaf alignment with no rows or no columns")
     R, C = shapes[:, 0], shapes[:, 1]
-    cell_off = np.concatenate([[0], np.cumsum(R * C)[:-1]])
-    prof_off = np.concatenate([[0], np.cumsum(6 * C)[:-1]]) if prepared is None else np.asarray(prepared.prof_off, np.int64)
-    leaf_tab = np.stack([cell_off, R, C, prof_off], 1).astype(np.int64)
-    tiles = -(-C // 256)
-    work = np.stack([np.repeat(np.arange(n_leaves), tiles),
-                     np.concatenate([np.arange(t) for t in tiles])], 1).astype(np.int32)
+    prof_off = exclusive_sum(6 * C) if prepared is None else np.asarray(prepared.prof_off, np.int64)
+    leaf_tab = np.stack([exclusive_sum(R * C), R, C, prof_off], 1).astype(np.int64)
+    work = _tile_work(C)
     # pairs: (leaf, index within the leaf, n)
     on_device = prepared is not None and prepared.d_seqs is not None
     if on_device:
@@ -277,15 +306,15 @@ def pairs_on_device(backend, leaves: Optional[Sequence[np.ndarray]], seqs: Seque
     if len(too_long):
         k = too_long[0]
         raise ProfileAlignError(f"a pair of {pn[k]} residues against {pc[k]} columns: n + C must stay below {MAX_LEN}")
-    seq_off = np.asarray(prepared.seq_off, np.int64) if on_device else np.concatenate([[0], np.cumsum(pn)[:-1]])
-    need = np.array([workspace_words(int(n), int(c)) for n, c in zip(pn, pc)], np.int64)
+    seq_off = np.asarray(prepared.seq_off, np.int64) if on_device else exclusive_sum(pn)
+    need = workspace_words_v(pn, pc)
 
     def packed(order, words):
         return budget_launches(order, words, budget_bytes, ProfileAlignError, "pair", pn, pc)
     if band is None:
         full_plan = list(packed(np.argsort(-((pn + 1) * pc), kind="stable"), need))       # longest first; refuses before anything is uploaded
     ops_len = pn + pc
-    ops_off = np.concatenate([[0], np.cumsum(ops_len)[:-1]])
+    ops_off = exclusive_sum(ops_len)
     ops_bytes = max(int(ops_len.sum()), 1)
     count = np.zeros(len(pl), np.int64)
     score = np.zeros(len(pl), np.int64)
@@ -336,9 +365,8 @@ def pairs_on_device(backend, leaves: Optional[Sequence[np.ndarray]], seqs: Seque
     second, rest, dlo, dhi, counts = band_plan(pn, pc, w0, pass1)
     launches("mprg_align_pairs_banded", packed(second, band_workspace_words(pn, pc, dlo, dhi)), dlo, dhi)
     launches("mprg_align_pairs", packed(rest, need))
-    if counters is not None:
-        for key, v in zip(("band_pairs", "band_second_passes", "band_full_pairs", "band_cells", "band_full_cells"), counts):
-            counters[key] = counters.get(key, 0) + int(v)
+    for key, v in zip(("band_pairs", "band_second_passes", "band_full_pairs", "band_cells", "band_full_cells"), counts):
+        add_to(counters, key, int(v))
     return DevicePairs(d_ops, ops_bytes, pl, pi, ops_off, count, score)
 
 
@@ -353,7 +381,7 @@ def merge(rows: np.ndarray, seqs: Sequence[np.ndarray], ops_list: Sequence[bytes
         col = np.cumsum(~is_i) - (~is_i)            # the boundary an op sits at: columns consumed before it
         np.add.at(ins[k], col[is_i], 1)
     width = ins.max(0) if m else np.zeros(C + 1, np.int64)
-    start = np.concatenate([[0], np.cumsum(width[:-1] + 1)])          # output column where boundary j's insertions begin
+    start = exclusive_sum(width + 1)          # output column where boundary j's insertions begin
     W = int(width.sum()) + C
     out = np.full((R + m, W), _GAP, np.uint8)
     out[:R, start[:C] + width[:C]] = rows
