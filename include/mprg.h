@@ -93,7 +93,9 @@ int mprg_compact_columns(const uint8_t *arena, const int64_t *views, const int32
  *      status int32[n_views].
  * optional (all three NULL or all three set): view_out int32[8*n_views] = {n_iv, status, type of the first interval,
  *      flags (1: some column is not one plain base, i.e. the consensus has a '*' or a gap; 2: N or ambiguity codes
- *      occur), first triple of this view in iv_packed, 0, 0, 0}; iv_packed int32[3*total_cols] = the triples of all
+ *      occur; 4: N occurs — a column of one base and N still has that base as its consensus, so a view of one match
+ *      interval is one allele only with bits 1 and 4 both clear: with either set its alleles are its distinct rows, those
+ *      with N left out), first triple of this view in iv_packed, 0, 0, 0}; iv_packed int32[3*total_cols] = the triples of all
  *      views back to back (a view's triples are contiguous; views in index order: their places are the exclusive prefix
  *      sum of n_iv, laid out by two small launches after the partition kernels); iv_count int32[1] = triples in the list.
  * fused_list / other_list (both NULL, or int32 device lists that together hold 0..n_views-1): the views of fused_list

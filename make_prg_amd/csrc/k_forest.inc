@@ -300,7 +300,9 @@ KERNEL(k_lv_classify, int64_t *nodes, long long f0, long long n, int lvl, const 
   const long long vi = nd[MPRG_N_AUX];
   if (vi >= 0) {
     const int32_t *o = view_out + 8 * vi;
-    n_iv = o[0]; first_type = o[2]; has_star = o[3] & 1; special = (o[3] & 2) != 0;
+    // a leaf's rows are its alleles unless every column is one plain base in ALL of them: a column of one base and N is a match
+    // column (N never counts towards the consensus), yet the rows with N are left out (or no row is left: the host's expansion raises)
+    n_iv = o[0]; first_type = o[2]; has_star = (o[3] & 5) != 0; special = (o[3] & 2) != 0;
   }
   const bool alive = !failed[nd[MPRG_N_MSA]];
   const bool is_leaf = alive && n_iv == 1 && first_type == 0;

@@ -344,7 +344,7 @@ MPRG_DEV void pt_outputs(int v, int *sh, bool fast, const uint8_t *nmz_s, int32_
     if (view_out) {
       int32_t *o = view_out + 8 * (long long)v;
       o[0] = cnt; o[1] = status; o[2] = sh[7];
-      o[3] = (sh[0] ? 1 : 0) | ((sh[4] || sh[5]) ? 2 : 0);
+      o[3] = (sh[0] ? 1 : 0) | ((sh[4] || sh[5]) ? 2 : 0) | (sh[4] ? 4 : 0);       // (N is no part of a column's consensus: its own bit)
       o[4] = 0; o[5] = 0; o[6] = 0; o[7] = 0;       // o[4]: first packed triple (k_pack_scan)
     }
   }

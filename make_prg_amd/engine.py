@@ -351,6 +351,7 @@ class BatchEngine:
         cons = np.full(total_cols, 255, np.uint8)
         cons[single] = np.log2(m[single]).astype(np.uint8)
         allgap = mask == BIT_GAP
+        has_n = (mask & np.uint32(BIT_N)) != 0          # N is no part of the consensus, yet a row that holds one is no allele
 
         next_frontier: List[int] = []
         cluster_cands: List[int] = []      # positions j in frontier
@@ -372,7 +373,7 @@ class BatchEngine:
             ivs = iv[co:co + k]
             if k == 1 and ivs[0, 2] == 0:
                 nd.kind = "leaf"
-                if (nd.consensus == 255).any():
+                if (nd.consensus == 255).any() or has_n[co:co + nd.ncols].any():
                     dedupe_leaves.append(j)
                 else:
                     nd.leaf_rows = None       # single sequence == the consensus string

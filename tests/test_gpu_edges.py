@@ -9,6 +9,7 @@ import pytest
 
 from tests import parity_common as pc
 from tests import view_edges as ve
+from tests.view_edges import RANDOM_WITH_N
 
 pytestmark = pytest.mark.gpu
 
@@ -107,6 +108,107 @@ def test_big_problem_through_the_byte_matrix(rt, monkeypatch, no_tables_from):
     monkeypatch.setattr(pc, "ENGINE", "forest")
     eng = pc.check_vs_oracle(rt, *ve.byte_matrix_problem())
     assert eng._big_seen and eng.counters["max_problem_bytes"] > 156 * 1024
+
+
+# ---------------------------------------------------------------- the same paths over ambiguity codes (tests/view_edges.sprinkle)
+@pytest.mark.parametrize("N,L,S,C,p", ve.WIDE_VIEWS)
+def test_wide_views_with_ambiguity_codes(rt, N, L, S, C, p, monkeypatch):
+    monkeypatch.setattr(pc, "ENGINE", "forest")
+    eng = pc.check_vs_oracle(rt, *ve.sprinkled(ve.wide_view(N, L, S, C, p), ve.SEED_AMB_WIDE, ve.P_AMB_WIDE))
+    assert eng.tab["special"].any()
+
+
+def test_gap_runs_across_column_segments_with_ambiguity_codes(rt, monkeypatch):
+    monkeypatch.setattr(pc, "ENGINE", "forest")
+    for N, L in ve.GAP_RUN_NL:
+        eng = pc.check_vs_oracle(rt, *ve.sprinkled(ve.gap_runs_across_segments(N, L), ve.SEED_AMB, ve.P_AMB))
+        assert eng.tab["special"].any()
+
+
+def test_leaf_of_many_alleles_with_ambiguity_codes(rt, monkeypatch):
+    monkeypatch.setattr(pc, "ENGINE", "forest")
+    eng = pc.check_vs_oracle(rt, *ve.sprinkled(ve.leaf_of_many_alleles(), ve.SEED_AMB, ve.P_AMB))
+    assert eng.tab["special"].any()
+    assert int(eng.tab["nseq"][ve.special_leaves(eng)].max()) > 128
+
+
+def test_tall_view_with_ambiguity_codes(rt, monkeypatch):
+    monkeypatch.setattr(pc, "ENGINE", "forest")
+    eng = pc.check_vs_oracle(rt, *ve.sprinkled(ve.tall_view(), ve.SEED_AMB, ve.P_AMB))
+    assert eng.tab["special"].any()
+
+
+def test_more_clusters_than_the_lds_offsets_with_ambiguity_codes(rt, monkeypatch):
+    """The codes only in the columns between the two match intervals (ve.SHORT_CLUSTER_COLS): the node of more than 1 024 clusters
+    stays, and some of its one-sequence clusters are leaves that the host expands."""
+    monkeypatch.setattr(pc, "ENGINE", "forest")
+    eng = pc.check_vs_oracle(rt, *ve.sprinkled(ve.many_short_clusters(), ve.SEED_AMB, ve.P_AMB, cols=ve.SHORT_CLUSTER_COLS))
+    assert eng.tab["special"].any()
+    assert np.bincount(eng.tab["parent"][eng.tab["parent"] >= 0]).max() > 1024
+
+
+def test_wide_and_tall_view_with_ambiguity_codes_against_the_oracles_record(rt):
+    """k_dedupe_scan_big / k_ungap_hash over 530 x 4 200 cells with codes 5..10 in the rows.  The oracle needs 15 s for this one: its
+    answer is tests/golden/rare_paths_codes.json (oracle/tools/gen_rare_paths_golden.py; tests/test_oracle_golden.py holds the record
+    against the oracle)."""
+    import json
+    import os
+    from make_prg_amd.utils.gfa import GFA_Output
+    name = "wide_and_tall_view"
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "rare_paths_codes.json")) as fh:
+        g = json.load(fh)[name]
+    texts, N, L = ve.sprinkled(getattr(ve, name)(), g["seed"], g["p"])
+    assert pc.sha(texts[0]) == g["fasta_sha256"] and (N, L) == (g["N"], g["L"]), "the builder changed under the record"
+    got, eng = pc.run_batch(rt, texts, N, L, "forest")
+    got, e = got[0], g["expect"]
+    assert "error" not in got, got
+    assert (len(got["prg"]), pc.sha(got["prg"])) == (e["prg_len"], e["prg_sha256"])
+    assert pc.sha(pc.product_bin_bytes(got["prg"])) == e["bin_sha256"]
+    assert pc.sha(GFA_Output.gfa_text(got["prg"])) == e["gfa_sha256"]
+    assert pc.sha(got["tree"]) == e["tree_sha256"], "recursion tree differs from the oracle's"
+    assert pc.sha(got["prg_index"]) == e["prg_index_sha256"]
+    assert (got["next_node_id"], got["site_num"]) == (e["next_node_id"], e["site_num"])
+    assert eng.tab["special"].any()
+
+
+@pytest.mark.parametrize("N,L,S,C,p", ve.WIDE_VIEWS)
+def test_wide_views_with_n_through_the_loader(rt, N, L, S, C, p, monkeypatch):
+    monkeypatch.setattr(pc, "ENGINE", "forest")
+    pc.check_vs_oracle(rt, *ve.sprinkled(ve.wide_view(N, L, S, C, p), ve.SEED_AMB_WIDE, ve.P_AMB_WIDE, "N"))
+
+
+def test_more_special_leaves_than_the_first_capacity(rt, monkeypatch):
+    monkeypatch.setattr(pc, "ENGINE", "forest")
+    eng = pc.check_vs_oracle(rt, *ve.many_special_leaves())
+    assert int(ve.special_leaves(eng).sum()) > 1024
+
+
+# ---------------------------------------------------------------- alignments that still hold N, through the object path
+@pytest.mark.parametrize("host", ["forest", "nodes"])
+@pytest.mark.parametrize("N,L,seed,want", RANDOM_WITH_N)
+def test_random_alignments_that_hold_n(rt, N, L, seed, want, host):
+    from tests.random_msas import random_cases
+    c, _ = pc.check_objects_vs_oracle(rt, random_cases(seed, 150), N, L, host)
+    assert (c["matched"], c["errors"], c["matched_with_n"]) == want
+
+
+@pytest.mark.parametrize("host", ["forest", "nodes"])
+def test_views_on_the_rare_paths_that_hold_n(rt, host):
+    got = []
+    for w in ve.WIDE_VIEWS:
+        got.append(pc.check_objects_vs_oracle(rt, *ve.sprinkled(ve.wide_view(*w), ve.SEED_AMB_WIDE, ve.P_N_WIDE, "N"), host)[0])
+    got.append(pc.check_objects_vs_oracle(rt, *ve.sprinkled(ve.tall_view(), ve.SEED_AMB, ve.P_N_TALL, "N"), host)[0])
+    got.append(pc.check_objects_vs_oracle(rt, *ve.sprinkled(ve.leaf_of_many_alleles(), ve.SEED_AMB, ve.P_N_LEAF, "N"), host)[0])
+    assert [(c["matched_with_n"], c["errors"]) for c in got] == ve.N_VIEWS_ORACLE
+
+
+@pytest.mark.parametrize("host", ["forest", "nodes"])
+def test_n_by_hand(rt, host):
+    names = sorted(ve.N_BY_HAND)
+    got, _ = pc.run_msas(rt, [pc.msa_as_it_is(ve.N_BY_HAND[n][0]) for n in names], 5, 7, host)
+    assert [g.get("error", g.get("prg")) for g in got] == [ve.N_BY_HAND[n][1] for n in names]
+    c, _ = pc.check_objects_vs_oracle(rt, [ve.N_BY_HAND[n][0] for n in names], 5, 7, host)
+    assert (c["matched"], c["errors"]) == (2, 2)
 
 
 # ---------------------------------------------------------------- KMeans fits across the LDS form's range (tests/test_kmeans_edges.py)

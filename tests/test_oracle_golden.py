@@ -110,3 +110,23 @@ def test_load_time_consensus_array_form_equals_the_column_by_column_form():
         m = alpha[rng.choice(len(alpha), size=(S, C), p=p / p.sum())].astype(np.uint8)
         upto = None if trial % 3 else int(rng.integers(0, C + 1))
         assert (msa._majority_consensus(m, upto) == msa._majority_consensus_by_column(m, upto)).all()
+
+
+@pytest.mark.parametrize("name", ["wide_and_tall_view"])
+def test_rare_path_records_are_the_oracles_answers(name):
+    """tests/golden/rare_paths_codes.json (oracle/tools/gen_rare_paths_golden.py): what the GPU test of the wide and tall view with
+    ambiguity codes compares with, so that it need not wait 15 s for the oracle — it must be what the oracle answers now."""
+    import os
+    from tests import view_edges as ve
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "rare_paths_codes.json")) as fh:
+        g = json.load(fh)[name]
+    assert g["reference"]["prg_identical"] and g["reference"]["next_node_id_identical"]          # (the record's own run of the real reference)
+    texts, N, L = ve.sprinkled(getattr(ve, name)(), g["seed"], g["p"])
+    assert sha(texts[0]) == g["fasta_sha256"] and (N, L) == (g["N"], g["L"])
+    prg, b, root = orc.build_locus_from_text(texts[0], N, L)
+    e = g["expect"]
+    assert (len(prg), sha(prg)) == (e["prg_len"], e["prg_sha256"])
+    assert sha(orc.encode_prg_bytes(prg)) == e["bin_sha256"] and sha(orc.gfa_text(prg)) == e["gfa_sha256"]
+    assert sha(orc.tree_dump(root)) == e["tree_sha256"]
+    assert sha(sorted([s, e_, n] for (s, e_), n in b.prg_index.items())) == e["prg_index_sha256"]
+    assert (b.next_node_id, b.site_num) == (e["next_node_id"], e["site_num"])

@@ -6,6 +6,7 @@ from tests import parity_common as pc
 from tests import view_edges as ve
 from tests.emu.backend import EmuBackend
 from tests.random_msas import random_cases
+from tests.view_edges import RANDOM_WITH_N
 
 
 @pytest.fixture(scope="module")
@@ -213,3 +214,84 @@ def test_sample_tables_by_tiles_equal_the_chains_by_threads(emu):
     from tests.kmeans_tables import check_lds_tables, check_tiled_tables
     assert check_tiled_tables(emu) == []
     assert check_lds_tables(emu) == []          # K6's LDS form: a thread per pair over the matrix in LDS
+
+
+# ---------------------------------------------------------------- ambiguity codes on the rare paths (tests/view_edges.sprinkle)
+@pytest.mark.parametrize("N,L,S,C,p", ve.WIDE_VIEWS)
+def test_wide_views_with_ambiguity_codes(emu, N, L, S, C, p, monkeypatch):
+    """Phase 3 of pt_phases<false, ..> with scan_amb (global stacks, the flag word polled in global memory, masks read directly) and
+    the walk by runs over ambiguity columns: the codes make leaves that the host expands."""
+    monkeypatch.setattr(pc, "ENGINE", "forest")
+    eng = pc.check_vs_oracle(emu, *ve.sprinkled(ve.wide_view(N, L, S, C, p), ve.SEED_AMB_WIDE, ve.P_AMB_WIDE))
+    assert eng.tab["special"].any()
+
+
+def test_gap_runs_across_column_segments_with_ambiguity_codes(emu, monkeypatch):
+    monkeypatch.setattr(pc, "ENGINE", "forest")
+    for N, L in ve.GAP_RUN_NL:
+        eng = pc.check_vs_oracle(emu, *ve.sprinkled(ve.gap_runs_across_segments(N, L), ve.SEED_AMB, ve.P_AMB))
+        assert eng.tab["special"].any()
+
+
+def test_leaf_of_many_alleles_with_ambiguity_codes(emu, monkeypatch):
+    """k_as_leaf_jobs for a leaf of more than 128 distinct rows whose alleles the host's expansion counted (k_as_patch)."""
+    monkeypatch.setattr(pc, "ENGINE", "forest")
+    eng = pc.check_vs_oracle(emu, *ve.sprinkled(ve.leaf_of_many_alleles(), ve.SEED_AMB, ve.P_AMB))
+    assert eng.tab["special"].any()
+    assert int(eng.tab["nseq"][ve.special_leaves(eng)].max()) > 128
+
+
+def test_tall_view_with_ambiguity_codes(emu, monkeypatch):
+    """k_cluster_majority_big (and the row grouping of 1 100 rows) over rows with codes 5..10."""
+    monkeypatch.setattr(pc, "ENGINE", "forest")
+    eng = pc.check_vs_oracle(emu, *ve.sprinkled(ve.tall_view(), ve.SEED_AMB, ve.P_AMB))
+    assert eng.tab["special"].any()
+
+
+@pytest.mark.parametrize("N,L,S,C,p", ve.WIDE_VIEWS)
+def test_wide_views_with_n_through_the_loader(emu, N, L, S, C, p, monkeypatch):
+    """N at the same rate: load_alignment_text overwrites them from the device's column counts (defer_n)."""
+    monkeypatch.setattr(pc, "ENGINE", "forest")
+    pc.check_vs_oracle(emu, *ve.sprinkled(ve.wide_view(N, L, S, C, p), ve.SEED_AMB_WIDE, ve.P_AMB_WIDE, "N"))
+
+
+def test_more_special_leaves_than_the_first_capacity(emu, monkeypatch):
+    """assemble_prgs lists the leaves for the host's expansion in a buffer of 1 024 entries and, told of more, lists them again in
+    one that holds them all: 1 300 alignments with one such leaf each."""
+    monkeypatch.setattr(pc, "ENGINE", "forest")
+    eng = pc.check_vs_oracle(emu, *ve.many_special_leaves())
+    assert int(ve.special_leaves(eng).sum()) > 1024
+
+
+# ---------------------------------------------------------------- alignments that still hold N, through the object path
+@pytest.mark.parametrize("host", ["forest", "nodes"])
+@pytest.mark.parametrize("N,L,seed,want", RANDOM_WITH_N)
+def test_random_alignments_that_hold_n(emu, N, L, seed, want, host):
+    """Pass A of phase 3, the first N-free row as the reference row, NTYPE 3 and leaves whose only irregularity is N: rows with N are
+    left out of a leaf's alleles, a slice without an N-free row drops the locus."""
+    c, _ = pc.check_objects_vs_oracle(emu, random_cases(seed, 150), N, L, host)
+    assert (c["matched"], c["errors"], c["matched_with_n"]) == want
+
+
+@pytest.mark.parametrize("host", ["forest", "nodes"])
+def test_views_on_the_rare_paths_that_hold_n(emu, host):
+    """The same on the global stacks / directly read masks (one match interval of the 13 000-column view has N in every row: the
+    locus is dropped), the wide majority workgroups and a leaf of many alleles."""
+    got = []
+    for w in ve.WIDE_VIEWS:
+        got.append(pc.check_objects_vs_oracle(emu, *ve.sprinkled(ve.wide_view(*w), ve.SEED_AMB_WIDE, ve.P_N_WIDE, "N"), host)[0])
+    got.append(pc.check_objects_vs_oracle(emu, *ve.sprinkled(ve.tall_view(), ve.SEED_AMB, ve.P_N_TALL, "N"), host)[0])
+    got.append(pc.check_objects_vs_oracle(emu, *ve.sprinkled(ve.leaf_of_many_alleles(), ve.SEED_AMB, ve.P_N_LEAF, "N"), host)[0])
+    assert [(c["matched_with_n"], c["errors"]) for c in got] == ve.N_VIEWS_ORACLE
+
+
+@pytest.mark.parametrize("host", ["forest", "nodes"])
+@pytest.mark.parametrize("name", sorted(ve.N_BY_HAND))
+def test_n_by_hand(emu, name, host):
+    text, want = ve.N_BY_HAND[name]
+    got, eng = pc.run_msas(emu, [pc.msa_as_it_is(text)], 5, 7, host)
+    assert got[0].get("error", got[0].get("prg")) == want
+    if host == "forest" and want == "SequenceCurationError":          # who refused: the partition (status 2, its own words) or a leaf's expansion
+        assert ("\nSequences:" not in str(eng.errors[0])) == name.startswith("nonmatch")
+    c, _ = pc.check_objects_vs_oracle(emu, [text], 5, 7, host)
+    assert c["matched"] + c["errors"] == 1

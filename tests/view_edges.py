@@ -22,6 +22,37 @@ def wide_fasta(seed, S, C, p_mut, gaps=True):
     return "".join(out)
 
 
+def sprinkle(text, seed, p, alphabet="RYKMSW", cols=None):
+    """The FASTA text with every non-gap cell of its sequence lines replaced, with probability p, by a uniform draw from `alphabet`
+    (ambiguity codes by default; "N" for cells that no base was called for).  cols = (first, end): only cells of these columns."""
+    rng = np.random.default_rng(seed)
+    letters = np.frombuffer(alphabet.encode(), np.uint8)
+    out = []
+    for line in text.splitlines():
+        if not line.startswith(">"):
+            cells = np.frombuffer(line.encode(), np.uint8).copy()
+            hit = (rng.random(len(cells)) < p) & (cells != ord("-"))
+            if cols is not None:
+                hit[:cols[0]] = hit[cols[1]:] = False
+            cells[hit] = letters[rng.integers(0, len(letters), int(hit.sum()))]
+            line = cells.tobytes().decode()
+        out.append(line + "\n")
+    return "".join(out)
+
+
+def sprinkled(built, seed, p, alphabet="RYKMSW", cols=None):
+    """A builder's (texts, N, L) with sprinkle() over every text."""
+    texts, N, L = built
+    return [sprinkle(t, seed, p, alphabet, cols) for t in texts], N, L
+
+
+P_AMB_WIDE, SEED_AMB_WIDE = 0.002, 7          # ambiguity codes in the three WIDE_VIEWS
+P_AMB, SEED_AMB = 0.0008, 8                   # ... and in the other builders: few enough that the expansion of a leaf stays small
+# many_short_clusters: only the columns between its two match intervals.  A code in one of those makes the whole alignment one
+# interval of sequences longer than the k-mer size, which ten clusters hold: no node with more than SC_RANKS children is left
+SHORT_CLUSTER_COLS = (10, 22)
+P_N_WIDE, P_N_TALL, P_N_LEAF = 0.003, 0.001, 0.002          # N left in place (object path): WIDE_VIEWS, tall_view, leaf_of_many_alleles
+
 WIDE_VIEWS = [(2, 1, 5, 900, 0.02),       # n/(L-1) exceeds the LDS interval stacks: global stacks
               (2, 2, 4, 1400, 0.05),
               (1, 7, 3, 13000, 0.002)]    # wider than the LDS column bytes (PT_COLS): masks read directly
@@ -151,3 +182,45 @@ def byte_matrix_problem():
         rows.append("ACGTACGT" + np.frombuffer(b"ACGT", np.uint8)[y].tobytes().decode() + "TTGACCAT")
     text = "".join(f">q{i}\n{r}\n" for i, r in enumerate(rows))
     return [text], 2, 4
+
+
+def many_special_leaves(n=1300):
+    """n three-row alignments whose one non-match column holds R, A, C between two match intervals: a leaf with an ambiguity code in
+    every alignment, more of them in one batch than the first capacity (1 024) of assemble_prgs' list of such leaves."""
+    texts = []
+    for i in range(n):
+        b = "ACGT"[i % 4]
+        texts.append(f">a\nACGTACG{b}R{b}CGTACGT\n>b\nACGTACG{b}A{b}CGTACGT\n>c\nACGTACG{b}C{b}CGTACGT\n")
+    return texts, 5, 7
+
+
+def special_leaves(eng):
+    """The leaves that assemble_prgs hands to the host's expansion: distinct rows listed, ambiguity codes or N in the view."""
+    t = eng.tab
+    return (t["kind"] == 0) & (t["reps_off"] >= 0) & t["special"]
+
+
+# Alignments that still hold N (object path: nothing overwrites them), a few rows each; N = 5, L = 7.
+N_BY_HAND = {
+    # a match interval (columns 0-8) whose first row holds N: its one allele is the N-free row's
+    "match_interval_one_row_with_n": (">a\nACNTACGTTTTACGTGCA\n>b\nACGTACGTTATACGTGCA\n>c\nACGTACGTTTTACGTGCA\n",
+                                      "ACGTACGTT 5 T 6 A 5 TACGTGCA"),
+    # a match interval in which every row holds N, each in another column: no sequence is left
+    "match_interval_every_row_with_n": (">a\nNCGTACGTT\n>b\nANGTACGTT\n>c\nACNTACGTT\n", "SequenceCurationError"),
+    # a non-match interval (columns 8-10) in which every row holds N: partition status 2
+    "nonmatch_interval_every_row_with_n": (">a\nACGTACGTNACTTGCATGC\n>b\nACGTACGTCNGTTGCATGC\n>c\nACGTACGTGTNTTGCATGC\n",
+                                           "SequenceCurationError"),
+    # a non-match interval (columns 8-10) whose N-free rows are one sequence: retyped to a match interval, three leaves in a row
+    "nonmatch_interval_one_sequence_left": (">a\nACGTACGTCNCTTGCATGC\n>b\nACGTACGTATATTGCATGC\n>c\nACGTACGTATATTGCATGC\n",
+                                            "ACGTACGTATATTGCATGC"),
+}
+
+# (products of alignments that hold N, errors) that the ORACLE ALONE gives for the three WIDE_VIEWS, tall_view and leaf_of_many_alleles
+# with N sprinkled at P_N_WIDE, P_N_TALL, P_N_LEAF: in the wider views and among the 1 100 rows some slice has N in every row
+N_VIEWS_ORACLE = [(1, 0), (0, 1), (0, 1), (0, 1), (3, 0)]
+
+# tests/random_msas.random_cases(seed, 150) with their N left in place, as (N, L, seed, counts): what the ORACLE ALONE makes of each batch —
+# (cases with a product, cases it refuses, products of alignments that hold N).  The checks must find exactly these, so none passes by
+# comparing errors only or by leaving the N cases out.  (A row with N is often a cluster of its own, whose only sequence then holds N:
+# about half of the alignments with N are refused, as are those with a disallowed base.)
+RANDOM_WITH_N = [(5, 7, 11, (116, 34, 31)), (2, 1, 13, (121, 29, 27)), (5, 2, 15, (111, 39, 25))]
