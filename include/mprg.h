@@ -593,9 +593,12 @@ int mprg_align_pairs_banded(const int32_t *profile, const int64_t *leaves, int n
  *   there, start (int64) the output column where boundary j's insertions begin (sum over j' < j of width + 1), out_width[l] the
  *   locus's output width W = C + sum of its widths (-1: its width range lies outside n_width).
  * mprg_star_merge_rows: writes every byte of each row's W bytes at out + out offset: columns, left-justified insertions, '-',
- *   upper-case letters.  status: n_rows int32 (both calls): MPRG_ST_OK, MPRG_ST_BAD_ROW (fields or ops inconsistent with the
- *   buffers or with n and C; rows: nothing or part of the row written), MPRG_ST_NO_SPACE (the output row outside out_bytes;
- *   nothing written).  A row is one wavefront.
+ *   upper-case letters; a byte of `codes` that is no cell code comes out as '-'.  status: n_rows int32 (both calls): MPRG_ST_OK,
+ *   MPRG_ST_BAD_ROW (the row's fields inconsistent with the buffers, with n and C or with its locus's fields: no width raised,
+ *   nothing written; or its ops inconsistent with n and C: a byte that is none of M, I, D, more or fewer than C column ops, more
+ *   or fewer than n residues: both calls report it, widths of its locus may have been raised, nothing or part of the row's W bytes
+ *   written and nothing beside them), MPRG_ST_NO_SPACE (rows only: the output row outside out_bytes, or out_width below C: nothing
+ *   written).  A row is one wavefront.
  *
  * `--adjust-direction` (strand detection in front of the calls above; the spec: star_align.py).  rc6(k) of a 6-mer
  * index k: 4095 - k with its six 2-bit groups in reverse order.

@@ -368,7 +368,7 @@ __global__ void __launch_bounds__(ST_THREADS) k_star_merge_rows(const uint8_t *c
     for (long long q0 = 0; q0 < k; q0 += WAVE) {
       const StOp p = st_op_step(ops, ops_off, k, q0, c_col, c_res, c_last);
       if (q0 + wave_lane() >= k) continue;
-      if (p.col > C || (p.op != 'D' && p.res >= n)) { bad = true; continue; }
+      if ((p.op != 'M' && p.op != 'I' && p.op != 'D') || p.col > C || (p.op != 'D' && p.res >= n)) { bad = true; continue; }
       const uint8_t ch = p.op == 'D' ? (uint8_t)'-' : (uint8_t)abc[codes[soff + p.res] < 12 ? codes[soff + p.res] : 4];
       if (p.op == 'I') {
         if (p.rank >= wd[p.col]) bad = true;
@@ -376,6 +376,7 @@ __global__ void __launch_bounds__(ST_THREADS) k_star_merge_rows(const uint8_t *c
       } else if (p.col >= C) bad = true;
       else { pad(p.col, p.rank); o[st[p.col] + wd[p.col]] = ch; }
     }
+    if (c_col != C || c_res != n) bad = true;                // (as k_star_merge_widths: a column or a residue too few)
     if (wave_lane() == 0 && !bad) pad(C, k - 1 - c_last);    // the I's after the last column op
   }
   bad = __ballot(bad) != 0ull;

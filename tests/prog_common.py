@@ -1,4 +1,5 @@
-"""What the emulated and the GPU tests of `from_msa --unaligned --progressive` share: the profile pairs of the DP check, the
+"""What the emulated and the GPU tests of `from_msa --unaligned --progressive` share: the profile pairs of the DP check, the tall
+pairs (8 to 2^20 rows a side, and 1 x 1 merges whose numerators sit on and beside multiples of R_X) and tall column texts, the
 loci of the whole-MSA check with their reference (computed once per process), the reference compositions with
 --adjust-direction and --refine, and the status codes of the new C ABI entries for tables that point outside their buffers."""
 import functools
@@ -8,6 +9,7 @@ import numpy as np
 
 from make_prg_amd.from_msa import star_align as sa
 from make_prg_amd.msa import encode
+from tests import align_ref as ar
 from tests import prog_ref as pr
 from tests import refine_ref as rr
 from tests import star_ref as sr
@@ -48,6 +50,130 @@ def check_dp(be, **kw):
     got = sa.merge_profiles(be, [(codes(x), codes(y)) for (x, y), _ in cases], **kw)
     for ((x, y), want), (ops, score) in zip(cases, got):
         assert (ops.decode(), score) == want, (len(x), len(x[0]), len(y), len(y[0]))
+
+
+TALL = (8, 9, 31, 33, 64, 255, 256, 257, 1000, 4095, 4096, 65537)        # rows per side: around the powers of two pg_div's shift turns on
+TALL_MAX = 1 << 20                                                       # PG_MAX_ROWS
+TALL_WX, TALL_WY = (63, 65, 130), (66, 129)                              # around the strip and the ring
+DIVISORS = (255, 256, 257, 65535, 65536, 65537, TALL_MAX - 1, TALL_MAX)  # R_X just below, at and just above a power of two
+Y_POOL = ("AAAAAAAAA", "CCCCCCCCC", "---------", "AAAAACC-N", "AAAAAAAC-", "AACCGGTT-", "A--------", "AAAANNN--", "AAAAAAAAC")
+
+
+def related_codes(rng, L, anc, R, W, spare=()):
+    """An R x W matrix of cell codes whose columns are W of the ancestor's L (in order): its base, 6 % another base, 3 % an
+    ambiguity code, '-' at a rate of the column's own (2 %, 10 % or 60 %); no all-gap column."""
+    cols = np.sort(rng.choice(L, W, replace=False))
+    base = anc[cols].astype(np.uint8)
+    u = rng.random((R, W), dtype=np.float32)
+    m = np.repeat(base[None], R, 0)
+    sub = u < 0.06
+    m[sub] = rng.integers(0, 4, int(sub.sum()), dtype=np.uint8)
+    amb = (u >= 0.06) & (u < 0.09)
+    m[amb] = rng.integers(5, 12, int(amb.sum()), dtype=np.uint8)
+    m[u > 1 - rng.choice([0.02, 0.1, 0.6], W, p=[0.6, 0.3, 0.1]).astype(np.float32)[None]] = 4
+    empty = (m == 4).all(0)
+    m[0, empty] = base[empty]
+    return m
+
+
+def engineered_columns(R):
+    """1 x 1 merges whose score is one quotient num / R_X exactly (the column pair always beats the two gaps): per class of
+    numerator (X's column, Y's column, num).  X's column: a A's, m N's, the rest '-'; Y's: a column of Y_POOL (9 rows).  The
+    classes: an exact multiple q R of R_X, one above and one below it, for q > 0 and q < 0; the largest numerator there is,
+    1 280 R_X (all A against all A); -576 R_X (all A against all C); the smallest, -640 R_X, both ways (all A against all '-',
+    all '-' against all A).  (-1 280 R_X does not exist: no term of a numerator is below -640 per row.)"""
+    pool = codes(Y_POOL).T.copy()                                        # 9 rows x the pool's columns
+    P, Pamb, Dc, _, _, _, _ = pr._column_tables(pool, pool)
+
+    def column(a, m):
+        return np.concatenate([np.zeros(a, np.uint8), np.full(m, 11, np.uint8), np.full(R - a - m, 4, np.uint8)]).reshape(R, 1)
+    out = {}
+    a = np.arange(R + 1, dtype=np.int64)
+    for sign in (1, -1):
+        for name, rem in (("multiple", 0), ("above", 1), ("below", R - 1)):
+            found = None
+            for j in range(1, pool.shape[1]):
+                for m in range(4):
+                    num = a[:R + 1 - m] * int(P["A"][j]) + m * int(Pamb[j]) + (R - m - a[:R + 1 - m]) * int(Dc[j])
+                    hit = np.nonzero((num % R == rem) & (num * sign >= R))[0]
+                    if len(hit) and found is None:
+                        found = (column(int(hit[len(hit) // 2]), m), pool[:, j:j + 1], int(num[hit[len(hit) // 2]]))
+            assert found is not None, (R, sign, name)
+            out[name, sign] = found
+    out["largest", 1] = (column(R, 0), pool[:, 0:1], 1280 * R)
+    out["mismatch", -1] = (column(R, 0), pool[:, 1:2], -576 * R)
+    out["smallest, Y's gaps", -1] = (column(R, 0), pool[:, 2:3], -640 * R)
+    out["smallest, X's gaps", -1] = (column(0, 0), pool[:, 0:1], -640 * R)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def tall_dp_cases():
+    """((X, Y) as matrices of cell codes, prog_ref's (ops, score)): related sides (columns of one ancestor) with every row count
+    of TALL on either side and 2^20 rows once on each, then engineered_columns of every R_X of DIVISORS."""
+    rng = np.random.default_rng(17)
+    shapes = [(rx, TALL_WX[k % 3], TALL[(5 * k + 3) % len(TALL)], TALL_WY[k % 2]) for k, rx in enumerate(TALL)]
+    shapes += [(TALL_MAX, 8, 31, 12), (255, 10, TALL_MAX, 8)]            # (a 2^20-row side stays narrow: k_prog_columns walks a column's rows one by one)
+    out = []
+    for rx, wx, ry, wy in shapes:
+        L = max(wx, wy) + 8
+        anc = rng.integers(0, 4, L)
+        X, Y = related_codes(rng, L, anc, rx, wx), related_codes(rng, L, anc, ry, wy)
+        out.append(((X, Y), pr.align_profiles_np(X, Y)))
+    for R in DIVISORS:
+        for (name, sign), (X, Y, num) in engineered_columns(R).items():
+            # through the reference: the numerator is what the class says, and the merge's score is its quotient
+            assert int(pr.numerators(X, Y)[0, 0]) == num and num * sign >= R and len(X) == R, (R, name)
+            assert {"multiple": num % R == 0, "above": num % R == 1, "below": num % R == R - 1}.get(name, abs(num) in (1280 * R, 576 * R, 640 * R))
+            want = pr.align_profiles_np(X, Y)
+            assert want == ("M", ar.tdiv(num, R)), (R, name)
+            out.append(((X, Y), want))
+    return out
+
+
+def check_tall_dp(be, **kw):
+    """merge_profiles (band=True: the banded two passes) on tall_dp_cases: ops and score, exactly."""
+    cases = tall_dp_cases()
+    assert {len(x) for (x, _), _ in cases} >= set(TALL + DIVISORS) and {len(y) for (_, y), _ in cases} >= set(TALL + (TALL_MAX,))
+    related = cases[:len(TALL) + 2]
+    assert set("".join(ops for _, (ops, _) in related)) == set("MID") and sum(score > 0 for _, (_, score) in related) >= 3
+    got = sa.merge_profiles(be, [xy for xy, _ in cases], **kw)
+    for ((x, y), want), (ops, score) in zip(cases, got):
+        assert (ops.decode(), score) == want, (x.shape, y.shape)
+
+
+def check_tall_columns(be):
+    """mprg_prog_columns called directly, kind 0 and kind 1, on texts of 255 to 2^20 rows (one of them across a 256-column tile):
+    every plane equals the NumPy statement with C's truncating division."""
+    rng = np.random.default_rng(8)
+    texts = []
+    for R, W in ((255, 300), (256, 64), (257, 257), (65537, 40), (TALL_MAX, 8)):
+        t = related_codes(rng, W, rng.integers(0, 4, W), R, W)
+        t[:, 0], t[:, 1], t[:, 2], t[:, 3] = 0, 4, 11, 4                 # all A, all '-', all N, one C among '-'
+        t[R // 2, 3] = 1
+        texts.append(t)
+    off = sa.exclusive_sum([t.size for t in texts])
+    text = np.concatenate([t.reshape(-1) for t in texts])
+    d_text = be.upload(text)
+    d_bufs = be.upload(np.array([[be.ptr(d_text), len(text)]], np.int64))
+    items, work, words = [], [], 0
+    for kind in (0, 1):
+        for t, o in zip(texts, off.tolist()):
+            work += [[len(items), tile] for tile in range(-(-t.shape[1] // 256))]
+            items.append([0, o, *t.shape, kind, words])
+            words += (6 + kind) * t.shape[1]
+    d_cols, d_status = be.full(4 * words + 64, 0x5C), be.full(4 * len(work), 0x5C)
+    d_items, d_work = be.upload(np.array(items, np.int64)), be.upload(np.array(work, np.int32))
+    be.call("mprg_prog_columns", be.ptr(d_bufs), 1, be.ptr(d_items), len(items), be.ptr(d_work), len(work), be.ptr(d_cols), words,
+            be.ptr(d_status), be.stream)
+    assert not be.download(d_status, np.int32, len(work)).any()
+    assert (be.download(d_cols, np.uint8, 4 * words + 64)[4 * words:] == 0x5C).all()
+    cols = be.download(d_cols, np.int32, words)
+    for (_, _, R, W, kind, o), t in zip(items, texts + texts):
+        P, Pamb, Dc, cx, ambx, _, Ic = pr._column_tables(t, t)
+        want = [P[x] for x in "ACGT"] + [Pamb, Dc] if kind == 0 else [cx[x] for x in "ACGT"] + [ambx, cx["-"], Ic]
+        assert (cols[o:o + (6 + kind) * W].reshape(6 + kind, W) == np.stack(want)).all(), (R, W, kind)
+        assert min(int(v.min()) for v in want) < 0 < max(int(v.max()) for v in want)
 
 
 def msa_loci():
@@ -136,7 +262,6 @@ def check_abi_statuses(be):
     status, clean, d_cols = columns(good, [[0, 0], [1, 0]])
     assert status == [0, 0] and not clean
     cols = be.download(d_cols, np.int32, 58)
-    from tests import align_ref as ar
     P, Dc = ar.profile(Y)
     assert cols[:30].reshape(6, 5).tolist() == [[p[x] for p in P] for x in "ACGTN"] + [Dc]
     assert cols[30:].reshape(7, 4).tolist() == [[2, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, 0], [0, 0, 0, 2], [0, 0, 0, 0], [0, 1, 1, 0],

@@ -1,7 +1,8 @@
 """Test-side statement of the Progressive spec of `from_msa --unaligned --progressive` (make_prg_amd/from_msa/star_align.py, DESIGN.md
 §3b) in plain Python on top of tests/align_ref.py, tests/star_ref.py and tests/refine_ref.py: the 6-mer distances, the exact UPGMA
 tree with its tie rule, the profile-profile DP cell by cell (`align_profiles`) and by rows in NumPy (`align_profiles_np`, exact
-integers; the emulated tests pin it to the cell form), the merge of a node's two children and the rows in input order."""
+integers, over row strings or matrices of cell codes; the emulated tests pin it to the cell form), the merge of a node's two
+children and the rows in input order."""
 import random
 from typing import List, Sequence, Tuple
 
@@ -111,8 +112,13 @@ def align_profiles(X: Sequence[str], Y: Sequence[str]) -> Tuple[str, int]:
 
 
 def _counts(rows):
-    A = np.frombuffer("".join(rows).encode(), np.uint8).reshape(len(rows), -1)
-    c = {x: (A == ord(x)).sum(0).astype(np.int64) for x in "ACGT-"}
+    """Per column the counts of A C G T '-', of the ambiguity codes together, and R: of row strings, or of an R x W matrix of cell
+    codes (uint8; tall profiles, whose rows nobody wants as Python strings)."""
+    if isinstance(rows, np.ndarray):
+        c = {x: (rows == q).sum(0).astype(np.int64) for q, x in enumerate("ACGT-")}
+    else:
+        A = np.frombuffer("".join(rows).encode(), np.uint8).reshape(len(rows), -1)
+        c = {x: (A == ord(x)).sum(0).astype(np.int64) for x in "ACGT-"}
     return c, len(rows) - sum(c.values()), len(rows)
 
 
@@ -120,16 +126,28 @@ def _tdv(a, R):
     return np.sign(a) * (np.abs(a) // R)
 
 
-def align_profiles_np(X: Sequence[str], Y: Sequence[str]) -> Tuple[str, int]:
-    """align_profiles by rows: D of a row as a running maximum over the row's other values (as align_ref.align_pair_np)."""
+def _column_tables(X, Y):
+    """(P per base, Pamb, Dc of Y; the counts per base, of the ambiguity codes, R_X and Ic of X), all per column."""
     cy, _, RY = _counts(Y)
     acgt = sum(cy[x] for x in "ACGT")
     P = {x: _tdv(64 * (20 * cy[x] - 9 * (acgt - cy[x]) - 10 * cy["-"]), RY) for x in "ACGT"}
     Pamb = _tdv(64 * -10 * cy["-"], RY)
     Dc = _tdv(64 * -10 * (RY - cy["-"]), RY)
     cx, ambx, RX = _counts(X)
+    return P, Pamb, Dc, cx, ambx, RX, _tdv(64 * -10 * (RX - cx["-"]), RX)
+
+
+def numerators(X, Y) -> np.ndarray:
+    """The W_X x W_Y numerators of the column scores, before the truncating division by R_X (int64)."""
+    P, Pamb, Dc, cx, ambx, _, _ = _column_tables(X, Y)
+    return sum(cx[x][:, None] * P[x][None] for x in "ACGT") + ambx[:, None] * Pamb[None] + cx["-"][:, None] * Dc[None]
+
+
+def align_profiles_np(X: Sequence[str], Y: Sequence[str]) -> Tuple[str, int]:
+    """align_profiles by rows: D of a row as a running maximum over the row's other values (as align_ref.align_pair_np).  X and Y:
+    row strings, or R x W matrices of cell codes."""
+    P, Pamb, Dc, cx, ambx, RX, Ic = _column_tables(X, Y)
     n, C = len(X[0]), len(Y[0])
-    Ic = _tdv(64 * -10 * (RX - cx["-"]), RX)
 
     def srow(i):
         return _tdv(sum(int(cx[x][i]) * P[x] for x in "ACGT") + int(ambx[i]) * Pamb + int(cx["-"][i]) * Dc, RX)

@@ -41,6 +41,14 @@ def test_profile_pairs_in_split_launches(backend):
     pc.check_dp(backend, budget_bytes=4 * pa.workspace_words(200, 300))
 
 
+def test_tall_profiles_equal_the_spec(backend):
+    pc.check_tall_dp(backend)
+
+
+def test_columns_of_tall_texts(backend):
+    pc.check_tall_columns(backend)
+
+
 def test_msas_equal_the_spec(backend):
     pc.check_msas(backend)
 

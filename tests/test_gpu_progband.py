@@ -2,6 +2,7 @@
 tests/progband_common.py's checks against the plain-Python references (tests/progband_ref.py, tests/prog_ref.py)."""
 import pytest
 
+from tests import prog_common as pc
 from tests import progband_common as pbc
 
 pytestmark = pytest.mark.gpu
@@ -24,6 +25,10 @@ def test_widths_kernel_equals_the_linear_search(be):
 
 def test_two_pass_merges_equal_the_unbanded_results(be):
     pbc.check_two_pass_merges(be)
+
+
+def test_tall_profiles_equal_the_unbanded_results(be):
+    pc.check_tall_dp(be, band=True)
 
 
 def test_msas_and_counters_equal_the_references(be):

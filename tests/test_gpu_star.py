@@ -1,6 +1,6 @@
 """Centre-star MSAs of `from_msa --unaligned` on the MI355X, through both backends: centres and MSAs byte-equal to the spec's
 statement (tests/star_ref.py) on random, edge and golden loci and on config-C-shaped synthetic loci (several pair launches and
-locus chunks), and the command line: the MSAs it writes, the PRG outputs identical to from_msa on those MSAs, and `update
+locus chunks), the merge and centre entries called directly on hand-built tables (tests/star_common.py), and the command line: the MSAs it writes, the PRG outputs identical to from_msa on those MSAs, and `update
 --aligner builtin` on its update_DS.zip."""
 import gzip
 import json
@@ -14,6 +14,7 @@ import pytest
 from make_prg_amd.from_msa import star_align as sa
 from make_prg_amd.update import profile_align as pa
 from tests import align_ref as ar
+from tests import star_common as sc
 from tests import star_ref as sr
 
 pytestmark = pytest.mark.gpu
@@ -80,6 +81,18 @@ def test_config_c_shaped_loci(backend):
                 assert (res[k][q][0].decode(), res[k][q][1]) == ar.align_pair_np([l[c]], l[others[k][q]])
                 checked += 1
     assert checked == 12
+
+
+def test_merge_entries_on_hand_built_ops(backend):
+    sc.check_merge(backend)
+
+
+def test_merge_entries_refuse_bad_rows_and_loci(backend):
+    sc.check_merge_statuses(backend)
+
+
+def test_centre_entries_directly(backend):
+    sc.check_centres(backend)
 
 
 def run_cli(args):

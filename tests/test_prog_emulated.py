@@ -37,6 +37,9 @@ def test_row_form_equals_cell_form():
         X = pr.random_profiles(rng, rng.choice(pc.ROWS), rng.randint(1, 30), rng.choice([0.1, 0.7]), rng.choice([0.0, 0.2]))
         Y = pr.random_profiles(rng, rng.choice(pc.ROWS), rng.randint(1, 30), rng.choice([0.1, 0.7]), rng.choice([0.0, 0.2]))
         assert pr.align_profiles(X, Y) == pr.align_profiles_np(X, Y)
+    for rx, ry, w in ((1, 10, 17), (10, 9, 30), (8, 3, 5), (7, 10, 64)):      # ... and over matrices of cell codes, as the tall cases hand them in
+        X, Y = pr.random_profiles(rng, rx, w + rx, 0.3, 0.2), pr.random_profiles(rng, ry, w, 0.2, 0.1)
+        assert pr.align_profiles_np(pc.codes(X), pc.codes(Y)) == pr.align_profiles_np(pc.codes(X), Y) == pr.align_profiles(X, Y)
 
 
 def test_one_row_x_is_the_pair_dp(emu):
@@ -105,6 +108,14 @@ def test_progressive_scores_above_star_on_the_table_loci():
 def test_dp_equals_the_spec(emu):
     pc.check_dp(emu)
     pc.check_dp(emu, budget_bytes=4 * pa.workspace_words(200, 300))          # one merge per launch at the top, several below
+
+
+def test_tall_profiles_equal_the_spec(emu):
+    pc.check_tall_dp(emu)
+
+
+def test_columns_of_tall_texts(emu):
+    pc.check_tall_columns(emu)
 
 
 def test_distances_equal_the_spec(emu):

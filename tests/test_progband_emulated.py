@@ -76,6 +76,10 @@ def test_two_pass_merges_equal_the_unbanded_results(emu):
     pbc.check_two_pass_merges(emu)
 
 
+def test_tall_profiles_equal_the_unbanded_results(emu):
+    pc.check_tall_dp(emu, band=True)
+
+
 def test_msas_and_counters_equal_the_references(emu):
     pbc.check_msas(emu)
 

@@ -1,6 +1,7 @@
 """Centre-star MSAs of `from_msa --unaligned` (make_prg_amd/from_msa/star_align.py, csrc/k_star.inc) on the CPU emulation build:
 centres and MSAs byte-equal to the spec's plain-Python statement (tests/star_ref.py), the spec's invariants, its quality on
-synthetic loci of known alignment, and the command line's refusals."""
+synthetic loci of known alignment, the merge and centre entries called directly on hand-built tables (tests/star_common.py), and the
+command line's refusals."""
 import random
 
 import numpy as np
@@ -8,6 +9,7 @@ import pytest
 
 from make_prg_amd.from_msa import star_align as sa
 from tests import align_ref as ar
+from tests import star_common as sc
 from tests import star_ref as sr
 from tests.emu.backend import EmuBackend
 
@@ -31,6 +33,18 @@ def test_centres_and_msas_equal_the_spec(emu):
         assert c == want_c, l
         assert m.rows_as_strings() == want_rows, l
         assert m.descriptions == [t for t, _ in records(l)] and m.ids == [f"r{i}" for i in range(len(l))]
+
+
+def test_merge_entries_on_hand_built_ops(emu):
+    sc.check_merge(emu)
+
+
+def test_merge_entries_refuse_bad_rows_and_loci(emu):
+    sc.check_merge_statuses(emu)
+
+
+def test_centre_entries_directly(emu):
+    sc.check_centres(emu)
 
 
 def test_small_chunks_and_budget_give_the_same_msas(emu):
