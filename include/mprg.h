@@ -724,6 +724,27 @@ int mprg_prog_band_widths(const int32_t *profile, const int64_t *leaves, int n_l
 int mprg_prog_rows(const int64_t *bufs, int n_bufs, const uint8_t *ops, long long ops_bytes, const int64_t *rows, int n_rows,
                    uint8_t *out, long long out_bytes, int ascii, int32_t *status, void *stream);
 
+/* `from_msa --unaligned --collapse-identical`: every distinct sequence of a locus aligned once (the spec: star_align.py, "Collapse";
+ * DESIGN.md §3b).  The pair, merge and row calls above are used unchanged, on tables that name a class's representative.
+ * mprg_star_identical: codes, seqs, loci as the star calls' (only {first sequence, sequence count} of a locus are read).
+ *   rep[first + a] (int32, n_seqs) receives the index WITHIN THE LOCUS of the smallest b <= a whose sequence equals a's (the same
+ *   length and the same bytes); an empty sequence gets itself.  status: n_loci int32: MPRG_ST_OK, or MPRG_ST_CENTRE_BAD (ranges
+ *   outside the buffers: none of the locus's rep written).  A 64-bit hash of every sequence filters the comparisons and never
+ *   decides: filter_bits (0 .. 64, else the call fails) of it are compared, with 0 every earlier sequence of equal length is
+ *   compared byte by byte; the result does not depend on it.  One workgroup per locus, a wavefront per sequence, 8 KB of LDS, any
+ *   number of sequences per locus.
+ * mprg_prog_columns_weighted: mprg_prog_columns on a text whose row r counts weights[offset + r] times.  items: n_items x
+ *   MPRG_PG_WITEM_FIELDS int64, mprg_prog_columns' six fields, then {offset of the item's R weights in `weights` (int32 elements,
+ *   weights_words long), S = their sum}.  The planes of kind 0 and kind 1 are exactly what mprg_prog_columns writes for the S x W
+ *   text with row r written weights[r] times.  MPRG_PG_BAD_ITEM also for weights outside weights_words, a weight below 1, an S
+ *   that is not the sum, or S > 2^20. */
+enum { MPRG_PG_WITEM_FIELDS = 8 };
+int mprg_star_identical(const uint8_t *codes, long long codes_bytes, const int64_t *seqs, long long n_seqs, const int64_t *loci,
+                        int n_loci, int filter_bits, int32_t *rep, int32_t *status, void *stream);
+int mprg_prog_columns_weighted(const int64_t *bufs, int n_bufs, const int64_t *items, int n_items, const int32_t *work, int n_work,
+                               const int32_t *weights, long long weights_words, int32_t *cols, long long cols_words, int32_t *status,
+                               void *stream);
+
 /* (f)-1 output encoders, HOST functions (host pointers), one pass over a PRG string as PrgBuilder emits it.
  * reference make_prg/utils/prg_encoder.py:44-91 and make_prg/utils/gfa.py:16-109.
  * mprg_prg_encode_host: out[n] receives the uint32 stream (A C G T -> 1 2 3 4, markers as integers, the closing

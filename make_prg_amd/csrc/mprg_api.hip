@@ -22,6 +22,7 @@
 #include "k_refine.inc"
 #include "k_prog.inc"
 #include "k_prog_band.inc"
+#include "k_collapse.inc"
 #include "host_encoders.inc"
 #include "host_batch.inc"
 
@@ -715,6 +716,23 @@ int mprg_prog_rows(const int64_t *bufs, int n_bufs, const uint8_t *ops, long lon
   LAUNCH(k_prog_rows, (n_rows + PG_WAVES - 1) / PG_WAVES, PG_THREADS, stream, bufs, n_bufs, ops, ops_bytes, rows, n_rows, out,
          out_bytes, ascii, status);      // a wavefront per row
   return check_launch("k_prog_rows");
+}
+
+int mprg_star_identical(const uint8_t *codes, long long codes_bytes, const int64_t *seqs, long long n_seqs, const int64_t *loci,
+                        int n_loci, int filter_bits, int32_t *rep, int32_t *status, void *stream) {
+  if (filter_bits < 0 || filter_bits > 64) return fail("mprg_star_identical: filter_bits outside 0 .. 64");
+  if (n_loci <= 0) return 0;
+  LAUNCH(k_star_identical, n_loci, ID_THREADS, stream, codes, codes_bytes, seqs, n_seqs, loci, filter_bits, rep, status);      // a workgroup per locus
+  return check_launch("k_star_identical");
+}
+
+int mprg_prog_columns_weighted(const int64_t *bufs, int n_bufs, const int64_t *items, int n_items, const int32_t *work, int n_work,
+                               const int32_t *weights, long long weights_words, int32_t *cols, long long cols_words, int32_t *status,
+                               void *stream) {
+  if (n_work <= 0) return 0;
+  LAUNCH(k_prog_columns_weighted, n_work, PG_THREADS, stream, bufs, n_bufs, items, n_items, work, weights, weights_words, cols,
+         cols_words, status);
+  return check_launch("k_prog_columns_weighted");
 }
 
 // ---- the recursion forest on the device (k_forest.inc); F: host array of MPRG_F_FIELDS int64 ------------------------------

@@ -12,6 +12,10 @@ C ABI: mprg_prog_distances / mprg_prog_columns / mprg_align_profile_pairs / mprg
 over certified bands of diagonals (Progressive, band below; kernels in csrc/k_prog_band.inc, C ABI: mprg_align_profile_pairs_banded /
 mprg_prog_band_widths): the same MSAs, byte for byte.
 
+With `--collapse-identical` the records of a locus whose (oriented) sequences are identical are found on the device and aligned
+once, with the class size as an integer weight; every member gets its representative's row (Collapse below; kernels in
+csrc/k_collapse.inc, C ABI: mprg_star_identical / mprg_prog_columns_weighted).
+
 It is NOT MAFFT.  PRGs built from these alignments differ from PRGs built from a MAFFT alignment of the same sequences.
 
 Spec (the kernels and tests/star_ref.py follow it bit for bit)
@@ -142,6 +146,36 @@ csrc/k_prog_band.inc).  The merge's DP over the cells of a band of diagonals, wi
             runs once more with w*; a merge whose band (of pass 1, or of pass 2) does not help, by profile_align.band_helps with
             n = W_X and C = W_Y, goes to the full DP (mprg_align_profile_pairs).
 
+Collapse (only with collapse; integers only; tests/collapse_ref.py states it in plain Python; kernels: csrc/k_collapse.inc).  It takes
+effect after Input and, with adjust_direction, after Orientation: it works on the oriented sequences, so a record and a
+reverse-complemented copy of it fall into one class.
+  Classes.  Records a and b of a locus are identical when their sequences have the same length and the same cell codes.  rep(a) is
+            the smallest index of a's class, w(a) the size of a's class, for a = rep(a).  Empty records stay what they are:
+            all-gap rows with no launch (each is its own representative).
+  Star.     The centre is computed as above, over ALL records, so T still counts every copy; it is then a representative by the
+            lowest-index rule (equal sequences score equally).  Pairs run only for representatives other than the centre.  Members of
+            the centre's class get the centre row's k = -1 form: a sequence against itself has the gap-free alignment as its unique
+            optimum, so this is what the DP would have written.  mprg_star_merge_columns sees the representatives' rows only (a
+            member's insertions are its representative's, so no width changes); mprg_star_merge_rows sees every row, a member's ops
+            offset and op count being its representative's.  The MSA is the flag-off MSA, byte for byte; with refine after it (on
+            the MSA's text, unchanged) this holds as well.
+  Progressive.  The leaves are the representatives of the non-empty classes, each with weight w.  Distances are taken between
+            representatives only.  The tree is exact UPGMA, as above, with |U| = sum of w over U's leaves and dist(U, V) = sum over a
+            in U, b in V of w_a w_b D(a, b) / (|U| |V|), compared by cross-multiplication; keys and the tie rule are unchanged.  A
+            locus with more than PROG_MAX_LEAVES non-empty RECORDS (not classes) still gets the star MSA and is reported: the 2^60
+            bound stays where it is.  The merge of a node's two children takes Y as the child with the larger weight sum, on equal
+            sums the one with the lower key.  Every count, P, Dc, Ic and R_X are those Progressive gives for the node's matrix with
+            row r written w_r times; R is the weight sum (mprg_prog_columns_weighted; the DP kernels, the band certificate and
+            pg_div work on such profiles as they are: a weighted sum is a sum of R_X terms).  A node's text holds one row per
+            class.  Output: the root's rows in input order, every record its representative's row.
+  Promised (tested): identical input sequences give identical rows, also after refine (identical rows see identical
+            leave-one-out profiles); a locus without duplicates gives the plain progressive bytes; band gives the same bytes as
+            no band.
+  Host side: a _collapse stage after _orient: one mprg_star_identical launch over the chunk, one download of rep and the status
+            words; the star pass and the progressive one take the class tables.  The progressive pass runs on the chunk's tables
+            with the representatives only (the distance tables cover them alone), with the weights beside them; the last
+            mprg_prog_rows launch names the representative's root row as the source of every member's output row.
+
 Progressive, host side: per chunk the distances in launches whose m x m tables fit budget_bytes (loci of three or more leaves), D
 and the tree per locus in NumPy / Python integers (prog_tree: a float64 quotient only shortlists, the choice is exact).  A node's
 round is 1 + the larger of its children's rounds.  All nodes of one round, over all loci of the chunk, go longest first in groups
@@ -197,6 +231,7 @@ PROG_MAX_LEAVES = 4096                    # the spec's leaf limit of a progressi
 PROG_SCALE = 1 << 16                      # D = PROG_SCALE - floor(PROG_SCALE s / m)
 PG_ITEM_FIELDS, PG_PAIR_FIELDS, PG_ROW_FIELDS = 6, 6, 8   # MPRG_PG_ITEM_FIELDS, MPRG_PG_PAIR_FIELDS, MPRG_PG_ROW_FIELDS
 PG_BAND_PAIR_FIELDS = 8                   # MPRG_PG_BAND_PAIR_FIELDS
+PG_WITEM_FIELDS = 8                       # MPRG_PG_WITEM_FIELDS
 PROG_BAND_W0 = 64                         # pass 1's half-width of a banded merge (what was tried)
 PG_STATUS = {1: "an index, a tile or a source range outside its table or buffer", 2: "ops, widths and cells that do not fit each other",
              3: "the output outside its buffer"}
@@ -279,7 +314,7 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
               budget_bytes: int = pa.DEFAULT_BUDGET_BYTES, chunk_bytes: int = CHUNK_BYTES, timings: Optional[dict] = None,
               adjust_direction: bool = False, orientation: Optional[list] = None, band=False, refine: int = 0,
               refinement: Optional[list] = None, progressive: bool = False, progression: Optional[list] = None,
-              max_leaves: Optional[int] = None) -> List[MSA]:
+              max_leaves: Optional[int] = None, collapse: bool = False) -> List[MSA]:
     """loci: per locus its records as (title, sequence).  Returns the loci's centre-star MSAs (ids: the titles' first words,
     descriptions: the titles).  names: the loci's names for error messages (default: their indices).  timings: a dict that
     receives the wall seconds of the stages (orient, centre, pairs, merge: each ends at a download, so includes its kernels).
@@ -296,7 +331,11 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
     also receives prog_band_merges, prog_band_second_passes, prog_band_full_merges (merges sent to the full DP), prog_band_cells
     (DP cells computed, all passes and the full form) and prog_band_full_cells (W_X W_Y summed).  progression: a list that then receives per locus (leaves, rounds, fell back to star).
     max_leaves: PROG_MAX_LEAVES unless given; a locus with more non-empty records gets the star MSA.  timings also receives tree_s
-    (distances and trees) and progressive_s (the merges and the rows)."""
+    (distances and trees) and progressive_s (the merges and the rows).
+    collapse: the spec's Collapse: every class of identical (oriented) sequences is aligned once and its row written for every
+    member; the star MSAs are the same bytes, the progressive ones get equal rows for equal sequences.  timings also receives
+    collapse_s, collapse_records, collapse_classes (the representatives, empty records included) and collapse_pairs (star) or
+    collapse_merges (progressive): the pair alignments and merges made.  False: nothing launches differently."""
     if not (isinstance(refine, (int, np.integer)) and not isinstance(refine, bool) and 0 <= refine <= REFINE_MAX):
         raise ValueError(f"refine: a number of rounds from 0 to {REFINE_MAX}, not {refine!r}")
     band = None if band is False or band is None else band      # from here on: None, True or pass 1's half-width
@@ -308,14 +347,14 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
     codes = [locus_codes(n, recs) for n, recs in zip(names, loci)]
     if progressive:
         return _progressive_msas(backend, loci, codes, names, budget_bytes, chunk_bytes, timings, adjust_direction, orientation, band,
-                                 int(refine), refinement, progression, PROG_MAX_LEAVES if max_leaves is None else int(max_leaves))
+                                 int(refine), refinement, progression, PROG_MAX_LEAVES if max_leaves is None else int(max_leaves), bool(collapse))
     return [m for lo, hi in _chunks(codes, chunk_bytes)
             for m in _star_chunk(backend, loci[lo:hi], codes[lo:hi], names[lo:hi], budget_bytes, timings, adjust_direction, orientation, band,
-                                 int(refine), refinement)]
+                                 int(refine), refinement, collapse=bool(collapse))]
 
 
 def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings, adjust_direction, orientation, band, refine, refinement,
-                      progression, max_leaves) -> List[MSA]:
+                      progression, max_leaves, collapse=False) -> List[MSA]:
     """star_msas with progressive: the loci within the leaf limit through the progressive chunks, the others through the star
     chunks, the results (and what the caller's lists receive) back in the loci's order."""
     n_leaves = [sum(1 for c in cs if len(c)) for cs in codes]
@@ -329,7 +368,7 @@ def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings
             idx = sel[lo:hi]
             msas.extend(_star_chunk(be, [loci[l] for l in idx], sub[lo:hi], [names[l] for l in idx], budget_bytes, timings, adjust_direction,
                                     ori if orientation is not None else None, band, refine, ref if refinement is not None else None,
-                                    prog, pro))
+                                    prog, pro, collapse))
         if not prog:
             pro = [(n_leaves[l], 0, True) for l in sel]
         for k, l in enumerate(sel):
@@ -344,8 +383,8 @@ def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings
 
 
 def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direction=False, orientation=None, band=None, refine=0,
-                refinement=None, progressive=False, progression=None) -> List[MSA]:
-    """One chunk: pack, optionally orient, the star pass or the progressive one, optionally refine, collect."""
+                refinement=None, progressive=False, progression=None, collapse=False) -> List[MSA]:
+    """One chunk: pack, optionally orient, optionally collapse, the star pass or the progressive one, optionally refine, collect."""
     laps = _Laps(timings)
     chunk = _pack(be, codes, names, [[t for t, _ in recs] for recs in loci])
     if adjust_direction:
@@ -353,7 +392,9 @@ def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direc
         if orientation is not None:
             orientation.extend(result)
         laps.lap("orient_s")
-    text = _progressive(be, chunk, budget_bytes, band, laps, progression) if progressive else _star_pass(be, chunk, budget_bytes, band, laps)
+    classes = _collapse(be, chunk, laps) if collapse else None
+    text = (_progressive(be, chunk, budget_bytes, band, laps, progression, classes) if progressive else
+            _star_pass(be, chunk, budget_bytes, band, laps, classes))
     moved = {}
     if refine:
         res = _refine(be, chunk, text, refine, budget_bytes, band, timings)
@@ -401,6 +442,48 @@ def _collect(be, chunk: Chunk, text, moved) -> List[MSA]:
     return msas
 
 
+# ---- collapse
+class Classes(NamedTuple):
+    """The spec's Classes over a chunk's sequence table: rep: per record the index IN THAT TABLE of its representative; weight: the
+    size of the class at a representative, 0 at every other record."""
+    rep: np.ndarray
+    weight: np.ndarray
+
+
+def _identical(be, chunk: Chunk, filter_bits: int = 64) -> np.ndarray:
+    """mprg_star_identical over a chunk: rep per record, as an index within its locus; one launch, one download."""
+    d_seqs, d_loci = _seq_tables(be, chunk)
+    n_seqs, n_loci = len(chunk.lens), chunk.n_loci
+    d_got = be.empty(4 * (n_seqs + n_loci))                     # rep, then the status words
+    be.call("mprg_star_identical", be.ptr(chunk.d_codes), chunk.codes_bytes, be.ptr(d_seqs), n_seqs, be.ptr(d_loci), n_loci, int(filter_bits),
+            be.ptr(d_got), be.ptr(d_got) + 4 * n_seqs, be.stream, work=float(2 * chunk.lens.sum()))
+    got = be.download(d_got, np.int32, n_seqs + n_loci)
+    if got[n_seqs:].any():
+        raise StarAlignError("mprg_star_identical: a locus's sequences lie outside the buffers")
+    return got[:n_seqs].astype(np.int64)
+
+
+def identical(backend, codes: Sequence[Sequence[np.ndarray]], filter_bits: int = 64) -> List[np.ndarray]:
+    """mprg_star_identical over the loci (per locus its gap-free code arrays): per locus rep, the smallest index of an equal
+    sequence per record.  filter_bits: how many bits of the hash filter the comparisons (the result does not depend on it)."""
+    chunk = _pack(backend, codes)
+    got = _identical(backend, chunk, filter_bits)
+    return [got[f:f + c] for f, c in zip(chunk.first.tolist(), chunk.counts.tolist())]
+
+
+def _collapse(be, chunk: Chunk, laps: _Laps) -> Classes:
+    """The spec's Classes for one chunk, on the (oriented) sequences in chunk.d_codes."""
+    t0 = time.perf_counter()
+    rep = np.repeat(chunk.first, chunk.counts) + _identical(be, chunk)
+    weight = np.bincount(rep, minlength=len(rep)).astype(np.int64)
+    spent = time.perf_counter() - t0
+    add_to(laps.timings, "collapse_s", spent)
+    laps.t += spent                                             # (the stage before and the stage behind keep what is theirs)
+    add_to(laps.timings, "collapse_records", len(rep))
+    add_to(laps.timings, "collapse_classes", int((weight > 0).sum()))
+    return Classes(rep, weight)
+
+
 # ---- the star pass
 def centres(backend, codes: Sequence[Sequence[np.ndarray]]) -> np.ndarray:
     """mprg_star_centres over the loci (per locus its gap-free code arrays): the centre index per locus, -1 if all are empty."""
@@ -427,9 +510,10 @@ def _centre_launch(be, call, chunk: Chunk):
     return centre, (d_seqs, d_loci, d_centre)
 
 
-def _star_pass(be, chunk: Chunk, budget_bytes, band, laps: _Laps):
+def _star_pass(be, chunk: Chunk, budget_bytes, band, laps: _Laps, classes: Optional[Classes] = None):
     """The spec's Centre, Pairs and Merge over one chunk, on the (oriented) sequences in chunk.d_codes.  Returns the MSAs' ASCII
-    text on the device: (the buffer, its bytes, each locus's offset in it, its width)."""
+    text on the device: (the buffer, its bytes, each locus's offset in it, its width).  classes: the spec's Collapse: pairs for
+    the representatives only, the columns from their rows, every member's row through its representative's ops."""
     codes, first, counts, n_loci = chunk.codes, chunk.first, chunk.counts, chunk.n_loci
     centre = _centre_launch(be, "mprg_star_centres", chunk)[0]
     laps.lap("centre_s")
@@ -439,6 +523,10 @@ def _star_pass(be, chunk: Chunk, budget_bytes, band, laps: _Laps):
     # the pairs: the centre as a 1-row leaf, every other non-empty sequence against it
     leaves = [codes[l][centre[l]].reshape(1, -1) for l in range(n_loci)]
     others = [[a for a in range(len(cs)) if a != centre[l] and len(cs[a])] for l, cs in enumerate(codes)]
+    if classes is not None:                                     # (the centre is the lowest index of its class: equal sequences score equally)
+        is_rep = classes.weight > 0
+        others = [[a for a in oth if is_rep[first[l] + a]] for l, oth in enumerate(others)]
+        add_to(laps.timings, "collapse_pairs", sum(map(len, others)))
     dp = pa.pairs_on_device(be, leaves, [[codes[l][a] for a in others[l]] for l in range(n_loci)], budget_bytes, band, laps.timings)
     laps.lap("pairs_s")
     # rows in input order: {locus, sequence offset, n, ops offset, ops count (-1: residue i in column i), output offset}
@@ -449,24 +537,30 @@ def _star_pass(be, chunk: Chunk, budget_bytes, band, laps: _Laps):
         r = first[dp.leaf] + np.array([others[l][i] for l, i in zip(dp.leaf.tolist(), dp.index.tolist())], np.int64)
         rows[r, 3], rows[r, 4] = dp.ops_off, dp.count
         d_ops, ops_bytes = dp.d_ops, dp.ops_bytes
-    text = _star_merge(be, chunk, d_ops, ops_bytes, rows, first, counts, C)
+    col_rows = None
+    if classes is not None:                                     # a member's ops are its representative's; the centre's class keeps k = -1
+        rows[:, 3:5] = rows[classes.rep, 3:5]
+        col_rows = np.nonzero(is_rep)[0]
+    text = _star_merge(be, chunk, d_ops, ops_bytes, rows, first, counts, C, col_rows)
     laps.lap("merge_s")
     return text
 
 
-def _star_merge(be, chunk: Chunk, d_ops, ops_bytes, rows, lfirst, R, C):
+def _star_merge(be, chunk: Chunk, d_ops, ops_bytes, rows, lfirst, R, C, col_rows=None):
     """The spec's Merge on the device: `rows` (the row table without output offsets) of loci that have rows lfirst .. lfirst + R of
     it and C columns before the merge; residues from the chunk's code buffer, ops from d_ops.  mprg_star_merge_columns, the
-    widths downloaded, mprg_star_merge_rows into a new buffer: (the buffer, its bytes, each locus's offset in it, its width)."""
+    widths downloaded, mprg_star_merge_rows into a new buffer: (the buffer, its bytes, each locus's offset in it, its width).
+    col_rows: the rows mprg_star_merge_columns sees (default: all)."""
     n_loci = len(R)
+    cols = rows if col_rows is None else rows[col_rows]
     n_width = int((C + 1).sum())
-    d_loci, d_rows = be.upload(np.stack([lfirst, R, C, exclusive_sum(C + 1)], 1).astype(np.int64)), be.upload(rows)
+    d_loci, d_rows = be.upload(np.stack([lfirst, R, C, exclusive_sum(C + 1)], 1).astype(np.int64)), be.upload(cols)
     d_width, d_start = be.zeros(4 * n_width), be.empty(8 * n_width)
     d_w, d_status = be.empty(8 * n_loci), be.empty(4 * len(rows))
-    be.call("mprg_star_merge_columns", be.ptr(d_ops), ops_bytes, be.ptr(d_rows), len(rows), be.ptr(d_loci), n_loci, be.ptr(d_width),
+    be.call("mprg_star_merge_columns", be.ptr(d_ops), ops_bytes, be.ptr(d_rows), len(cols), be.ptr(d_loci), n_loci, be.ptr(d_width),
             be.ptr(d_start), n_width, chunk.codes_bytes, be.ptr(d_w), be.ptr(d_status), be.stream, work=float(ops_bytes))
     W = be.download(d_w, np.int64, n_loci)
-    _check(be.download(d_status, np.int32, len(rows)), "mprg_star_merge_columns", ROW_STATUS, "row")
+    _check(be.download(d_status, np.int32, len(cols)), "mprg_star_merge_columns", ROW_STATUS, "row")
     if (W < C).any():
         raise StarAlignError("mprg_star_merge_columns: a locus's boundaries lie outside the buffers")
     base = exclusive_sum(R * W)
@@ -638,10 +732,11 @@ def prog_distance_matrix(shared: np.ndarray, nw: np.ndarray) -> np.ndarray:
     return D
 
 
-def prog_tree(D: np.ndarray, leaves: Sequence[int]) -> List[Tuple[int, int]]:
+def prog_tree(D: np.ndarray, leaves: Sequence[int], weights=None) -> List[Tuple[int, int]]:
     """The spec's Tree over the leaves (ascending indices into D): the merges in order as (key(U), key(V)), key(U) < key(V); the
     merged cluster keeps key(U).  Exact: a float64 quotient only shortlists the pairs within 2^-40 of the smallest, the choice
-    among them is made by cross-multiplication in Python integers, ties to the first in (key(U), key(V)) order."""
+    among them is made by cross-multiplication in Python integers, ties to the first in (key(U), key(V)) order.
+    weights: per leaf how many times it counts (the spec's Collapse): the tree of the leaves written that often, one leaf each."""
     idx = np.asarray(leaves, np.int64)
     n = len(idx)
     S = D[np.ix_(idx, idx)].astype(np.int64)                    # sums of D between the clusters, slot = rank of the key
@@ -650,6 +745,9 @@ def prog_tree(D: np.ndarray, leaves: Sequence[int]) -> List[Tuple[int, int]]:
     Q = np.full((n, n), np.inf)
     iu = np.triu_indices(n, 1)
     Q[iu] = S[iu]
+    if weights is not None:                                     # S: sums of w_a w_b D(a, b); a cluster's size: its weight sum
+        size = np.asarray(weights, np.int64).copy()            # (Q stays D: the quotient of w_a w_b D(a, b) by w_a w_b)
+        S = S * np.outer(size, size)
     merges = []
     for _ in range(n - 1):
         qmin = Q.min()
@@ -672,22 +770,27 @@ def prog_tree(D: np.ndarray, leaves: Sequence[int]) -> List[Tuple[int, int]]:
     return merges
 
 
-def _prog_plan(lens, first, counts, shared):
+def _prog_plan(lens, first, counts, shared, weights=None):
     """What the spec's Tree decides for a chunk, from its tables and _prog_shared's of the loci of three or more leaves (two leaves
     have one tree); no device, no clock.  A leaf's node id is its record index, an inner node's counts on from the locus's records.
     Returns (per locus its leaves: the non-empty records; per round its merges (locus, y, x, parent), Y the child with more rows;
     per locus its root node; per locus the records of the root's rows in row order: Y's rows, then X's, at every node; per locus
-    the progression tuple (leaves, rounds, False))."""
+    the progression tuple (leaves, rounds, False)).  weights: per record of the tables how many rows it stands for (the spec's
+    Collapse): the tree is the weighted one and Y the child with the larger weight sum."""
     leaves, by_round, roots, root_members, progression = [], {}, [], [], []
     for l in range(len(counts)):
         lv = np.nonzero(lens[first[l]:first[l] + counts[l]] > 0)[0].tolist()
-        merges = [(lv[0], lv[1])] if len(lv) == 2 else prog_tree(prog_distance_matrix(*shared[l]), lv) if len(lv) > 2 else []
+        wl = None if weights is None else weights[first[l]:first[l] + counts[l]]
+        merges = ([(lv[0], lv[1])] if len(lv) == 2 else
+                  prog_tree(prog_distance_matrix(*shared[l]), lv, None if wl is None else wl[lv]) if len(lv) > 2 else [])
         members = {a: [a] for a in lv}
+        size = {a: 1 if wl is None else int(wl[a]) for a in lv}
         node_at, rnd, nxt = {a: a for a in lv}, {a: 0 for a in lv}, int(counts[l])
         for u, v in merges:
             a, b = node_at[u], node_at[v]                       # key(a) = u < v = key(b)
-            y, x = (a, b) if len(members[a]) >= len(members[b]) else (b, a)
+            y, x = (a, b) if size[a] >= size[b] else (b, a)
             members[nxt] = members.pop(y) + members.pop(x)
+            size[nxt] = size.pop(y) + size.pop(x)
             rnd[nxt] = 1 + max(rnd[a], rnd[b])
             by_round.setdefault(rnd[nxt], []).append((l, y, x, nxt))
             node_at[u] = nxt
@@ -721,10 +824,12 @@ def _prog_groups(WX, WY, budget_bytes, band=None):
         yield grp
 
 
-def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUDGET_BYTES, counters=None):
+def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUDGET_BYTES, counters=None, weights=None):
     """One group of merges on the device: X, Y (n, 4) int64 {buffer, offset, R, W} of the two sides' texts.  mprg_prog_columns (Y's
     profiles, X's column tables) and mprg_align_profile_pairs in one launch each; {status, score, op count} downloaded.  With band
     the spec's two passes instead (the module docstring, host side), counters receiving the prog_band_* counts.
+    weights: (per merge the weights of X's rows, of Y's rows), the spec's Collapse: the column tables through
+    mprg_prog_columns_weighted and R_X the weight sum; everything else is the same.
     Returns (the ops buffer, its bytes, each merge's ops offset, op count, score)."""
     n = len(X)
     WX, WY = X[:, 3], Y[:, 3]
@@ -734,13 +839,24 @@ def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUD
     ycol = exclusive_sum(6 * WY + 7 * WX)
     xcol = ycol + 6 * WY
     words = int((6 * WY + 7 * WX).sum())
-    items = np.zeros((2 * n, PG_ITEM_FIELDS), np.int64)
+    items = np.zeros((2 * n, PG_ITEM_FIELDS if weights is None else PG_WITEM_FIELDS), np.int64)
     items[:n, :4], items[:n, 4], items[:n, 5] = Y, 0, ycol
     items[n:, :4], items[n:, 4], items[n:, 5] = X, 1, xcol
     work = _tile_work(items[:, 3])
+    RX, columns = X[:, 2], "mprg_prog_columns"
+    if weights is not None:
+        per_item = list(weights[1]) + list(weights[0])          # Y's items, then X's
+        flat = np.concatenate(per_item).astype(np.int32)
+        items[:, 6], items[:, 7] = exclusive_sum(items[:, 2]), [int(w.sum()) for w in per_item]
+        RX, columns = items[n:, 7], "mprg_prog_columns_weighted"
     d_items, d_work, d_cols, d_status = be.upload(items), be.upload(work), be.empty(4 * words), be.empty(4 * len(work))
-    be.call("mprg_prog_columns", be.ptr(d_bufs), n_bufs, be.ptr(d_items), len(items), be.ptr(d_work), len(work), be.ptr(d_cols), words,
-            be.ptr(d_status), be.stream, work=float((items[:, 2] * items[:, 3]).sum()))
+    if weights is None:
+        be.call("mprg_prog_columns", be.ptr(d_bufs), n_bufs, be.ptr(d_items), len(items), be.ptr(d_work), len(work), be.ptr(d_cols), words,
+                be.ptr(d_status), be.stream, work=float((items[:, 2] * items[:, 3]).sum()))
+    else:
+        d_weights = be.upload(flat)
+        be.call("mprg_prog_columns_weighted", be.ptr(d_bufs), n_bufs, be.ptr(d_items), len(items), be.ptr(d_work), len(work), be.ptr(d_weights),
+                len(flat), be.ptr(d_cols), words, be.ptr(d_status), be.stream, work=float((items[:, 2] * items[:, 3]).sum()))
     need = pa.workspace_words_v(WX, WY)
     ops_off = exclusive_sum(WX + WY)
     ops_bytes = int((WX + WY).sum())
@@ -754,7 +870,7 @@ def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUD
         """The merges idx (longest first) through `call` in launches that fit the workspace budget."""
         for sel, ws_off, used in pa.budget_launches(idx, wordsv, budget_bytes, StarAlignError, "merge", WX, WY):
             band_cols = () if dlo is None else (dlo[sel], dhi[sel])
-            d_pairs = be.upload(np.stack([sel, xcol[sel], WX[sel], ws_off, ops_off[sel], X[sel, 2], *band_cols], 1).astype(np.int64))
+            d_pairs = be.upload(np.stack([sel, xcol[sel], WX[sel], ws_off, ops_off[sel], RX[sel], *band_cols], 1).astype(np.int64))
             d_ws, d_out = be.empty(4 * used), be.empty(12 * len(sel))
             be.call(call, be.ptr(d_cols), be.ptr(d_leaves), n, be.ptr(d_cols), words, be.ptr(d_pairs), len(sel), be.ptr(d_ws), used,
                     be.ptr(d_ops), ops_bytes, be.ptr(d_out), be.stream, work=pa.sweep_work(WX[sel], WY[sel], *band_cols))
@@ -771,7 +887,7 @@ def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUD
             got = be.download(d_got, np.uint8, 20 * len(sel))
             status = got[16 * len(sel):].view(np.int32)
             if status.any():
-                _check(be.download(d_status, np.int32, len(work)), "mprg_prog_columns", PG_STATUS)
+                _check(be.download(d_status, np.int32, len(work)), columns, PG_STATUS)
                 res = be.download(d_out, np.int32, 3 * len(sel)).reshape(-1, 3)
                 code = int(res[res[:, 0] != 0][0, 0]) if res[:, 0].any() else int(status[status != 0][0])
                 raise StarAlignError(f"mprg_align_profile_pairs_banded / mprg_prog_band_widths: {pa.STATUS.get(code, code)}")
@@ -783,7 +899,7 @@ def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUD
         second, rest, dlo, dhi, counts = pa.band_plan(WX, WY, w0, pass1)
         launches("mprg_align_profile_pairs_banded", second, pa.band_workspace_words(WX, WY, dlo, dhi), dlo, dhi)
         launches("mprg_align_profile_pairs", rest, need)
-    _check(be.download(d_status, np.int32, len(work)), "mprg_prog_columns", PG_STATUS)
+    _check(be.download(d_status, np.int32, len(work)), columns, PG_STATUS)
     count, score = np.zeros(n, np.int64), np.zeros(n, np.int64)
     for sel, call, d_out, _ in pending:                          # in launch order: a later pass's result replaces pass 1's
         res = be.download(d_out, np.int32, 3 * len(sel)).reshape(-1, 3)
@@ -824,35 +940,50 @@ def merge_profiles(backend, pairs: Sequence[Tuple[np.ndarray, np.ndarray]], budg
     return out
 
 
-def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression):
+def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression, classes: Optional[Classes] = None):
     """The spec's Progressive over one chunk, on the (oriented) sequences in chunk.d_codes.  Returns what the star pass leaves: the
-    device buffer of the MSAs' ASCII text, its bytes, each locus's offset in it and its width."""
+    device buffer of the MSAs' ASCII text, its bytes, each locus's offset in it and its width.  classes: the spec's Collapse: the
+    tree and the merges over the representatives with their weights, the root's rows written for every member."""
     laps.lap()
     lens, first, counts = chunk.lens, chunk.first, chunk.counts
     n_leaves = np.add.reduceat((lens > 0).astype(np.int64), first)          # (every locus has a record)
     for l in np.nonzero(n_leaves == 0)[0]:
         raise StarAlignError(f"locus {chunk.names[l]}: every sequence is empty")
+    weights = expand = None
+    if classes is not None:
+        # the chunk's tables with the representatives only (an empty record is one): what the distances, the tree and the rounds see
+        keep = np.nonzero(classes.weight > 0)[0]
+        kept = np.add.reduceat((classes.weight > 0).astype(np.int64), first)
+        slot = np.cumsum(classes.weight > 0) - 1                # a representative's index in those tables
+        expand = (counts, first, slot[classes.rep])
+        chunk = chunk._replace(lens=lens[keep], seq_off=chunk.seq_off[keep], first=exclusive_sum(kept), counts=kept)
+        lens, first, counts, weights = chunk.lens, chunk.first, chunk.counts, classes.weight[keep]
+        n_leaves = np.add.reduceat((lens > 0).astype(np.int64), first)
     # the trees: distances on the device for the loci with three or more leaves (two leaves have one tree), UPGMA on the host
     sel = np.nonzero(n_leaves >= 3)[0]
-    plan = _prog_plan(lens, first, counts, _prog_shared(be, chunk, sel, budget_bytes) if len(sel) else {})
+    plan = _prog_plan(lens, first, counts, _prog_shared(be, chunk, sel, budget_bytes) if len(sel) else {}, weights)
     if progression is not None:
         progression.extend(plan[-1])
     laps.lap("tree_s")
-    text = _prog_rounds(be, chunk, plan, budget_bytes, band, laps.timings)
+    text = _prog_rounds(be, chunk, plan, budget_bytes, band, laps.timings, weights, expand)
     laps.lap("progressive_s")
     return text
 
 
-def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters):
+def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters, weights=None, expand=None):
     """_progressive's device part: the plan's rounds (every node of a round, over all loci of the chunk, in one set of launches
     per budget group), then the roots' rows in input order.
     The texts' lifetime: bufs[b] is (buffer, bytes) of text buffer b, 0 the chunk's code buffer (the leaves); where[locus, node]
     is (b, offset, rows, width) of a node not yet merged; live[b] counts the nodes of where in b.  A group's parents go into a
-    buffer of their own; a buffer (but 0) is dropped when its last node has been merged into a parent."""
+    buffer of their own; a buffer (but 0) is dropped when its last node has been merged into a parent.
+    weights, expand (the spec's Collapse): the chunk's tables hold the representatives only, weights per record of them; rw[locus,
+    node] then is the weights of the node's rows.  expand: (records per locus, each locus's first record, per record its
+    representative's index in the chunk's tables) of the output: every record gets its representative's row."""
     lens, seq_off, first, counts, n_loci = chunk.lens, chunk.seq_off, chunk.first, chunk.counts, chunk.n_loci
     leaves, by_round, root, root_members, _ = plan
     bufs, live = [(chunk.d_codes, chunk.codes_bytes)], [0]
     where = {(l, a): (0, int(seq_off[first[l] + a]), 1, int(lens[first[l] + a])) for l in range(n_loci) for a in leaves[l]}
+    rw = {} if weights is None else {(l, a): weights[first[l] + a:first[l] + a + 1] for l in range(n_loci) for a in leaves[l]}
 
     def merged(l, node):
         """The node has gone into its parent: its buffer goes with its last node."""
@@ -867,7 +998,11 @@ def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters):
         for grp in _prog_groups(X[:, 3], Y[:, 3], budget_bytes, band):
             d_bufs = _bufs_table(be, bufs)
             Xg, Yg = X[grp], Y[grp]
-            d_ops, ops_bytes, ops_off, count, _ = _prog_pairs(be, d_bufs, len(bufs), Xg, Yg, band, budget_bytes, counters)
+            wg = None
+            if weights is not None:
+                wg = ([rw[todo[k][0], todo[k][2]] for k in grp.tolist()], [rw[todo[k][0], todo[k][1]] for k in grp.tolist()])
+                add_to(counters, "collapse_merges", len(grp))
+            d_ops, ops_bytes, ops_off, count, _ = _prog_pairs(be, d_bufs, len(bufs), Xg, Yg, band, budget_bytes, counters, wg)
             RY, RX = Yg[:, 2], Xg[:, 2]
             R = RY + RX
             poff = exclusive_sum(R * count)
@@ -891,20 +1026,30 @@ def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters):
             for i, k in enumerate(grp.tolist()):
                 l, y, x, parent = todo[k]
                 where[l, parent] = (len(bufs) - 1, int(poff[i]), int(R[i]), int(count[i]))
+                if weights is not None:
+                    rw[l, parent] = np.concatenate([rw.pop((l, y)), rw.pop((l, x))])
                 merged(l, y)
                 merged(l, x)
     # the roots' rows into input order, as ASCII; an empty record is a row of '-'
     W = np.array([where[l, root[l]][3] for l in range(n_loci)], np.int64)
-    base = exclusive_sum(counts * W)
-    out_bytes = int((counts * W).sum())
-    rows = np.zeros((int(counts.sum()), PG_ROW_FIELDS), np.int64)
+    o_counts, o_first, slot = (counts, first, None) if expand is None else expand
+    base = exclusive_sum(o_counts * W)
+    out_bytes = int((o_counts * W).sum())
+    rows = np.zeros((int(o_counts.sum()), PG_ROW_FIELDS), np.int64)
     rows[:, 4] = -1
-    rows[:, 6] = np.repeat(base, counts) + (np.arange(len(rows)) - np.repeat(first, counts)) * np.repeat(W, counts)
-    rows[:, 7] = np.repeat(W, counts)
+    rows[:, 6] = np.repeat(base, o_counts) + (np.arange(len(rows)) - np.repeat(o_first, o_counts)) * np.repeat(W, o_counts)
+    rows[:, 7] = np.repeat(W, o_counts)
     for l in range(n_loci):
         b, off, _, w = where[l, root[l]]
         rec = first[l] + np.array(root_members[l], np.int64)
-        rows[rec, 0], rows[rec, 1], rows[rec, 2] = b, off + np.arange(len(rec)) * w, w
+        at = np.arange(len(rec))
+        if slot is not None:                                    # every record whose representative has a row of the root: that row
+            at_of = np.full(int(counts[l]), -1, np.int64)
+            at_of[root_members[l]] = at
+            rec = np.arange(o_first[l], o_first[l] + o_counts[l])
+            at = at_of[slot[rec] - first[l]]
+            rec, at = rec[at >= 0], at[at >= 0]
+        rows[rec, 0], rows[rec, 1], rows[rec, 2] = b, off + at * w, w
     d_bufs = _bufs_table(be, bufs)
     d_rows, d_out, d_status = be.upload(rows), be.empty(max(out_bytes, 1)), be.empty(4 * len(rows))
     be.call("mprg_prog_rows", be.ptr(d_bufs), len(bufs), be.ptr(d_out), 0, be.ptr(d_rows), len(rows), be.ptr(d_out), max(out_bytes, 1), 1,

@@ -79,6 +79,13 @@ def register_parser(subparsers):
                         "(star_align.py, Progressive); NOT MAFFT.  --adjust-direction runs first, --refine afterwards, --band computes "
                         "the merges (and the refinement's realignments) over certified bands, the same bytes; a locus of more than 4096 non-empty records gets the centre-star MSA.  "
                         "Off by default")
+    p.add_argument("--collapse-identical", dest="collapse_identical", action="store_true", default=False,
+                   help="(this implementation) with --unaligned: the records of a locus whose sequences are identical (after "
+                        "--adjust-direction: a record and a reverse-complemented copy of it are) are found on the GPU and aligned "
+                        "once; every copy gets its representative's row (star_align.py, Collapse).  The centre-star MSAs are the "
+                        "same bytes from fewer pair alignments; with --progressive the tree has one weighted leaf per distinct "
+                        "sequence, so equal sequences get equal rows (also after --refine), and a locus without duplicates keeps "
+                        "its --progressive bytes.  Combines with --adjust-direction, --band, --refine and --progressive.  Off by default")
     p.set_defaults(func=run, check=check_options)
     return p
 
@@ -95,6 +102,8 @@ def check_options(args, parser):
         parser.error("--band needs --unaligned")
     if getattr(args, "progressive", False) and not args.unaligned:
         parser.error("--progressive needs --unaligned")
+    if getattr(args, "collapse_identical", False) and not args.unaligned:
+        parser.error("--collapse-identical needs --unaligned")
     if getattr(args, "refine", None) is not None:
         if not args.unaligned:
             parser.error("--refine needs --unaligned")
@@ -595,12 +604,14 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
     refinement = []
     progressive = bool(getattr(options, "progressive", False))
     progression = []
+    collapse = bool(getattr(options, "collapse_identical", False))
     for lo in range(0, len(mine), STAR_CHUNK):
         t0 = time.perf_counter()
         recs = [star_align.read_unaligned(f) for f in mine[lo:lo + STAR_CHUNK]]
         t1 = time.perf_counter()
         msas = star_align.star_msas(be, recs, names=loci[lo:lo + STAR_CHUNK], adjust_direction=adjust, orientation=orientation,
-                                    **(dict(band=True, timings=counters) if band else {}),
+                                    **(dict(band=True) if band else {}), **(dict(timings=counters) if band or collapse else {}),
+                                    **(dict(collapse=True) if collapse else {}),
                                     **(dict(refine=refine, refinement=refinement) if refine else {}),
                                     **(dict(progressive=True, progression=progression) if progressive else {}))
         t2 = time.perf_counter()
@@ -626,6 +637,9 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
     if refine:
         logger.info(f"rank {rank}: --refine {refine}: {sum(1 for a, _, _ in refinement if a)} loci refined, "
                     f"{sum(a for a, _, _ in refinement)} rounds accepted, {sum(1 for a, _, _ in refinement if not a)} loci left as the star MSA")
+    if collapse:
+        logger.info(f"rank {rank}: --collapse-identical: {counters.get('collapse_records', 0)} records, "
+                    f"{counters.get('collapse_classes', 0)} classes")
     if progressive:
         built = [(n, r) for n, r, star in progression if not star]
         logger.info(f"rank {rank}: --progressive: {len(built)} loci built, {sum(n - 1 for n, _ in built)} merges, "

@@ -14,11 +14,16 @@ the rounds accepted, the loci changed and the total objective S before and after
 model of tests/star_ref.py's mutate(sub=0.06, indel=0.03), restated here (the tool does not import the tests): per root base 1.5 %
 deleted, 6 % substituted, 1.5 % followed by an insertion of 1-4 nt.
 `--progressive`: guide-tree MSAs (`from_msa --unaligned --progressive`); the line then also gives tree_s and progressive_s, the
-loci built, their merges, the most rounds of a locus and the loci left to the star pass.  With `--band [W0]` as well the merges run
+loci built, their merges, the most and the mean rounds of a locus and the loci left to the star pass.  With `--band [W0]` as well the merges run
 over certified bands (W0 then is pass 1's half-width of both stages) and the line also gives prog_band_merges,
 prog_band_second_passes, prog_band_full_merges (sent to the full DP), prog_band_cells and prog_band_full_cells.
 `--objective` (implied by --progressive): the line also gives s_total, the objective S of the MSAs written, summed over the loci
-(mprg_refine_counts over the MSAs, after the timed part): to compare a star run and a progressive run of the same loci."""
+(mprg_refine_counts over the MSAs, after the timed part): to compare a star run and a progressive run of the same loci.
+`--collapse-identical`: every distinct sequence of a locus aligned once (`from_msa --unaligned --collapse-identical`); the line then
+also gives collapse_s, collapse_records, collapse_classes and collapse_pairs or collapse_merges (the alignments made).  Every line
+gives dup_share: the share of the records whose sequence an earlier record of their locus has.
+`--dup FRACTION`: after a locus's sequences are made, each record but the first is replaced, with that probability, by a copy of
+an earlier record of the locus picked at random (seeded): loci with a known share of exact copies."""
 import hashlib
 import json
 import os
@@ -51,6 +56,8 @@ if "--refine" in sys.argv:
 progressive = "--progressive" in sys.argv
 objective = progressive or "--objective" in sys.argv
 diverged = int(sys.argv[sys.argv.index("--diverged") + 1]) if "--diverged" in sys.argv else 0
+collapse = "--collapse-identical" in sys.argv
+dup = float(sys.argv[sys.argv.index("--dup") + 1]) if "--dup" in sys.argv else 0.0
 
 
 def diverged_seqs(seed):
@@ -79,6 +86,11 @@ try:
     rng, flipped = random.Random(1), []
     for seed in range(n_loci):
         seqs = diverged_seqs(seed) if diverged else [r.decode().replace("-", "") for r in synth_rows(seed, *config_shape("C", seed))]
+        if dup:
+            drng = random.Random(1000003 + seed)
+            for i in range(1, len(seqs)):
+                if drng.random() < dup:
+                    seqs[i] = seqs[drng.randrange(i)]
         if flip is not None:
             flags = [i > 0 and rng.random() < flip for i in range(len(seqs))]
             seqs = [s.translate(COMPLEMENT)[::-1] if f else s for s, f in zip(seqs, flags)]
@@ -88,7 +100,7 @@ try:
     files = sorted(src.iterdir())
     be = get_backend("runtime")
     sa.star_msas(be, [sa.read_unaligned(f) for f in files[:4]], adjust_direction=flip is not None, band=band, refine=refine,
-                 **(dict(progressive=True) if progressive else {}))   # warm-up: first launches
+                 **(dict(progressive=True) if progressive else {}), **(dict(collapse=True) if collapse else {}))   # warm-up: first launches
     t0 = time.perf_counter()
     recs = [sa.read_unaligned(f) for f in files]
     t_read = time.perf_counter() - t0
@@ -98,7 +110,8 @@ try:
     refinement = []
     progression = []
     msas = sa.star_msas(be, recs, timings=timings, adjust_direction=flip is not None, orientation=orientation, band=band, refine=refine,
-                        refinement=refinement, **(dict(progressive=True, progression=progression) if progressive else {}))
+                        refinement=refinement, **(dict(progressive=True, progression=progression) if progressive else {}),
+                        **(dict(collapse=True) if collapse else {}))
     t_star = time.perf_counter() - t0
     t0 = time.perf_counter()
     written, digest = [], hashlib.md5()
@@ -110,10 +123,14 @@ try:
         written.append(p)
     t_write = time.perf_counter() - t0
     codes = [sa.locus_codes(f.name, r) for f, r in zip(files, recs)]
-    extra = {}
+    extra = dict(dup_share=round(sum(len(r) - len({s for _, s in r}) for r in recs) / max(1, sum(len(r) for r in recs)), 4))
+    if collapse:
+        extra.update(collapse=True)
+    if dup:
+        extra.update(dup=dup)
     if flip is not None:
         codes = [[sa.revcomp(c) if f else c for c, f in zip(cs, rev)] for cs, (rev, _) in zip(codes, orientation)]
-        extra = dict(flip=flip, reversed=sum(sum(rev) for rev, _ in orientation),
+        extra.update(flip=flip, reversed=sum(sum(rev) for rev, _ in orientation),
                      reversed_as_flipped=sum(sum(a and b for a, b in zip(rev, fl)) for (rev, _), fl in zip(orientation, flipped)),
                      flipped=sum(map(sum, flipped)), settled_by_dp=sum(how.count("d") + how.count("t") for _, how in orientation))
     if refine:
@@ -121,7 +138,7 @@ try:
                      s_before=sum(s for _, s, _ in refinement), s_after=sum(s for _, _, s in refinement))
     if progressive:
         built = [(n, r) for n, r, star in progression if not star]
-        extra.update(progressive=True, loci_built=len(built), merges=sum(n - 1 for n, _ in built), max_rounds=max((r for _, r in built), default=0),
+        extra.update(progressive=True, loci_built=len(built), merges=sum(n - 1 for n, _ in built), max_rounds=max((r for _, r in built), default=0), mean_rounds=round(sum(r for _, r in built) / max(1, len(built)), 2),
                      loci_left_to_star=len(progression) - len(built))
     if objective:
         import numpy as np
