@@ -663,7 +663,8 @@ int mprg_refine_compact(const uint8_t *text, long long text_bytes, const int64_t
                         int32_t *status, void *stream);
 
 /* `from_msa --unaligned --progressive`: guide-tree MSAs (the spec: star_align.py, "Progressive").  The tree is built
- * on the host from what mprg_prog_distances gives; a tree node's merge is one pair of mprg_align_profile_pairs.
+ * from what mprg_prog_distances gives, by mprg_prog_tree on the device (below) or by the caller (star_align.prog_tree is the host's
+ * form: the same merges); a tree node's merge is one pair of mprg_align_profile_pairs.
  * A node's text is its R x W matrix of CELL CODES (0..11, '-' = 4), row-major; a leaf's text is its sequence in `codes`.  bufs:
  *   n_bufs x 2 int64 {device address, bytes}: the buffers that hold texts; a text names its buffer by index and its range is
  *   checked against that buffer's bytes.
@@ -744,6 +745,30 @@ int mprg_star_identical(const uint8_t *codes, long long codes_bytes, const int64
 int mprg_prog_columns_weighted(const int64_t *bufs, int n_bufs, const int64_t *items, int n_items, const int32_t *work, int n_work,
                                const int32_t *weights, long long weights_words, int32_t *cols, long long cols_words, int32_t *status,
                                void *stream);
+
+/* `--progressive --device-tree`: the spec's Tree on the device (star_align.py, "Progressive": Tree, and "Collapse").
+ * mprg_prog_tree: shared, shared_words, nw, seqs, n_seqs: what mprg_prog_distances read and wrote (only b > a of a table is read).
+ *   loci: n_loci x MPRG_PG_TREE_FIELDS int64 {first sequence, sequence count m, offset of the locus's m x m table in `shared`
+ *   (uint32 elements), offset of the locus's workspace in `workspace` (int64 elements, workspace_words long), offset of the locus's
+ *   merges in `merges` (int32 elements, merges_words long)}.  The leaves of a locus are its sequences of length > 0, named by their
+ *   index within the locus; L is their number.  weights: null (every leaf counts once), or n_seqs int32: weights[first + a] is how
+ *   many times leaf a counts (the class size of Collapse); only the leaves' are read.
+ *   D(a, b) = 65 536 - floor(65 536 s(a, b) / min(nw_a, nw_b)), 65 536 when the minimum is 0.  The tree is average linkage with |U|
+ *   the weight sum of U's leaves and dist(U, V) = sum of w_a w_b D(a, b) over a in U, b in V, divided by |U| |V|, compared by
+ *   cross-multiplication in int64; the smallest dist is merged, equal ones go to the smallest key(U), then the smallest key(V), key
+ *   the lowest member and key(U) < key(V); the merged cluster keeps key(U).  merges[offset + 2 k], merges[offset + 2 k + 1] receive
+ *   key(U), key(V) of merge k = 0 .. L - 2: exactly star_align.prog_tree's list.  L < 2 writes nothing (MPRG_PG_OK).
+ *   The workspace need of a locus is m (m + 2) int64 words, whatever L is.
+ *   status: n_loci int32: MPRG_PG_OK; MPRG_PG_BAD_ITEM (the sequences outside n_seqs, m < 1, the table outside shared_words, the
+ *   2 (L - 1) merges outside merges_words, a leaf's weight below 1, a weight sum above 4 096: the 2^60 bound of the cross products
+ *   rests on it; nothing else written.  Also for a leaf's nw below 0 or an s(a, b) between leaves above min(nw_a, nw_b) > 0: the
+ *   locus's workspace may have been written, its merges are not); MPRG_PG_NO_SPACE (the workspace need outside workspace_words:
+ *   nothing else written).  One workgroup per locus, 8.1 KB of LDS; the per-sequence state of a locus of more than 512 sequences
+ *   lives in its workspace. */
+enum { MPRG_PG_TREE_FIELDS = 5 };
+int mprg_prog_tree(const uint32_t *shared, long long shared_words, const int64_t *nw, const int64_t *seqs, long long n_seqs,
+                   const int64_t *loci, int n_loci, const int32_t *weights, int64_t *workspace, long long workspace_words,
+                   int32_t *merges, long long merges_words, int32_t *status, void *stream);
 
 /* (f)-1 output encoders, HOST functions (host pointers), one pass over a PRG string as PrgBuilder emits it.
  * reference make_prg/utils/prg_encoder.py:44-91 and make_prg/utils/gfa.py:16-109.

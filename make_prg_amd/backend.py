@@ -119,6 +119,8 @@ SIGNATURES = {
                                     c_void_p]),
     "mprg_prog_columns_weighted": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p,
                                            ctypes.c_longlong, c_void_p, c_void_p]),
+    "mprg_prog_tree": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, c_void_p,
+                               ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
     "mprg_random_sample_host": (None, [c_uint32, c_int, c_void_p]),
     "mprg_prg_encode_host": (ctypes.c_longlong, [c_void_p, ctypes.c_longlong, c_void_p]),
     "mprg_fasta_scan_host": (ctypes.c_longlong, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),

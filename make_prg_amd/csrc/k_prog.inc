@@ -1,7 +1,7 @@
 // ---------------------------------------------------------------------------------------------------------------
 // K-P  progressive MSAs of `from_msa --unaligned --progressive` (make_prg_amd/from_msa/star_align.py holds the spec,
 //      "Progressive"; DESIGN.md §3b): the guide tree's distances, the profile-profile DP of a merge, the children's rows written
-//      through a merge's ops.  Integers only.  The tree itself is built on the host.
+//      through a merge's ops.  Integers only.  The tree itself is built on the host, or by k_prog_tree.inc.
 //
 // A node's text is its R x W matrix of CELL CODES (0..11, '-' = 4), row-major; a leaf's text is its sequence in the code buffer.
 // Texts of different rounds live in different device buffers: the kernels that read texts take a table `bufs` of

@@ -23,6 +23,7 @@
 #include "k_prog.inc"
 #include "k_prog_band.inc"
 #include "k_collapse.inc"
+#include "k_prog_tree.inc"
 #include "host_encoders.inc"
 #include "host_batch.inc"
 
@@ -733,6 +734,15 @@ int mprg_prog_columns_weighted(const int64_t *bufs, int n_bufs, const int64_t *i
   LAUNCH(k_prog_columns_weighted, n_work, PG_THREADS, stream, bufs, n_bufs, items, n_items, work, weights, weights_words, cols,
          cols_words, status);
   return check_launch("k_prog_columns_weighted");
+}
+
+int mprg_prog_tree(const uint32_t *shared, long long shared_words, const int64_t *nw, const int64_t *seqs, long long n_seqs,
+                   const int64_t *loci, int n_loci, const int32_t *weights, int64_t *workspace, long long workspace_words,
+                   int32_t *merges, long long merges_words, int32_t *status, void *stream) {
+  if (n_loci <= 0) return 0;
+  LAUNCH(k_prog_tree, n_loci, PG_THREADS, stream, shared, shared_words, nw, seqs, n_seqs, loci, weights, workspace, workspace_words,
+         merges, merges_words, status);      // a workgroup per locus
+  return check_launch("k_prog_tree");
 }
 
 // ---- the recursion forest on the device (k_forest.inc); F: host array of MPRG_F_FIELDS int64 ------------------------------

@@ -178,7 +178,11 @@ reverse-complemented copy of it fall into one class.
 
 Progressive, host side: per chunk the distances in launches whose m x m tables fit budget_bytes (loci of three or more leaves), D
 and the tree per locus in NumPy / Python integers (prog_tree: a float64 quotient only shortlists, the choice is exact).  A node's
-round is 1 + the larger of its children's rounds.  All nodes of one round, over all loci of the chunk, go longest first in groups
+round is 1 + the larger of its children's rounds.  With device_tree the tree is built on the device instead (csrc/k_prog_tree.inc):
+per group, sized by the tables plus the tree workspaces (8 m (m + 2) bytes a locus), the distances launch and one mprg_prog_tree
+launch over the tables it left there; the merges (8 bytes each) and the status words are downloaded, the shared tables and nw are
+not; the plan (_prog_plan: rounds, Y and X, node ids, row order) is made on the host from either source's merges.
+All nodes of one round, over all loci of the chunk, go longest first in groups
 whose workspace and column tables fit budget_bytes; per group one mprg_prog_columns launch (Y's profiles, X's column tables), one
 mprg_align_profile_pairs launch, {status, score, op count} per merge downloaded, one mprg_prog_rows launch that writes the
 parents' texts (cell codes) into a buffer of the group's own; a buffer is dropped when its last node has been merged.  One more
@@ -232,9 +236,11 @@ PROG_SCALE = 1 << 16                      # D = PROG_SCALE - floor(PROG_SCALE s 
 PG_ITEM_FIELDS, PG_PAIR_FIELDS, PG_ROW_FIELDS = 6, 6, 8   # MPRG_PG_ITEM_FIELDS, MPRG_PG_PAIR_FIELDS, MPRG_PG_ROW_FIELDS
 PG_BAND_PAIR_FIELDS = 8                   # MPRG_PG_BAND_PAIR_FIELDS
 PG_WITEM_FIELDS = 8                       # MPRG_PG_WITEM_FIELDS
+PG_TREE_FIELDS = 5                        # MPRG_PG_TREE_FIELDS
 PROG_BAND_W0 = 64                         # pass 1's half-width of a banded merge (what was tried)
 PG_STATUS = {1: "an index, a tile or a source range outside its table or buffer", 2: "ops, widths and cells that do not fit each other",
              3: "the output outside its buffer"}
+TREE_STATUS = {1: "a range outside its buffer, a leaf's weight below 1 or a weight sum above 4 096", 3: "the workspace outside its buffer"}
 _GAP = ord("-")
 _ASCII = np.frombuffer(b"ACGT-RYKMSWN", np.uint8)
 
@@ -314,7 +320,7 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
               budget_bytes: int = pa.DEFAULT_BUDGET_BYTES, chunk_bytes: int = CHUNK_BYTES, timings: Optional[dict] = None,
               adjust_direction: bool = False, orientation: Optional[list] = None, band=False, refine: int = 0,
               refinement: Optional[list] = None, progressive: bool = False, progression: Optional[list] = None,
-              max_leaves: Optional[int] = None, collapse: bool = False) -> List[MSA]:
+              max_leaves: Optional[int] = None, collapse: bool = False, device_tree: bool = False) -> List[MSA]:
     """loci: per locus its records as (title, sequence).  Returns the loci's centre-star MSAs (ids: the titles' first words,
     descriptions: the titles).  names: the loci's names for error messages (default: their indices).  timings: a dict that
     receives the wall seconds of the stages (orient, centre, pairs, merge: each ends at a download, so includes its kernels).
@@ -335,7 +341,13 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
     collapse: the spec's Collapse: every class of identical (oriented) sequences is aligned once and its row written for every
     member; the star MSAs are the same bytes, the progressive ones get equal rows for equal sequences.  timings also receives
     collapse_s, collapse_records, collapse_classes (the representatives, empty records included) and collapse_pairs (star) or
-    collapse_merges (progressive): the pair alignments and merges made.  False: nothing launches differently."""
+    collapse_merges (progressive): the pair alignments and merges made.  False: nothing launches differently.
+    device_tree: only with progressive (else a ValueError): the trees of the loci of three or more leaves by mprg_prog_tree, on the
+    tables mprg_prog_distances left on the device; the same merges, so the same MSAs.  timings also receives tree_device_loci.
+    False: nothing launches differently.  Either way timings receives tree_plan_s: the part of tree_s spent in _prog_plan on the
+    host (with device_tree the plan alone, without it the host's UPGMA too)."""
+    if device_tree and not progressive:
+        raise ValueError("device_tree: only with progressive")
     if not (isinstance(refine, (int, np.integer)) and not isinstance(refine, bool) and 0 <= refine <= REFINE_MAX):
         raise ValueError(f"refine: a number of rounds from 0 to {REFINE_MAX}, not {refine!r}")
     band = None if band is False or band is None else band      # from here on: None, True or pass 1's half-width
@@ -347,14 +359,15 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
     codes = [locus_codes(n, recs) for n, recs in zip(names, loci)]
     if progressive:
         return _progressive_msas(backend, loci, codes, names, budget_bytes, chunk_bytes, timings, adjust_direction, orientation, band,
-                                 int(refine), refinement, progression, PROG_MAX_LEAVES if max_leaves is None else int(max_leaves), bool(collapse))
+                                 int(refine), refinement, progression, PROG_MAX_LEAVES if max_leaves is None else int(max_leaves), bool(collapse),
+                                 bool(device_tree))
     return [m for lo, hi in _chunks(codes, chunk_bytes)
             for m in _star_chunk(backend, loci[lo:hi], codes[lo:hi], names[lo:hi], budget_bytes, timings, adjust_direction, orientation, band,
                                  int(refine), refinement, collapse=bool(collapse))]
 
 
 def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings, adjust_direction, orientation, band, refine, refinement,
-                      progression, max_leaves, collapse=False) -> List[MSA]:
+                      progression, max_leaves, collapse=False, device_tree=False) -> List[MSA]:
     """star_msas with progressive: the loci within the leaf limit through the progressive chunks, the others through the star
     chunks, the results (and what the caller's lists receive) back in the loci's order."""
     n_leaves = [sum(1 for c in cs if len(c)) for cs in codes]
@@ -368,7 +381,7 @@ def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings
             idx = sel[lo:hi]
             msas.extend(_star_chunk(be, [loci[l] for l in idx], sub[lo:hi], [names[l] for l in idx], budget_bytes, timings, adjust_direction,
                                     ori if orientation is not None else None, band, refine, ref if refinement is not None else None,
-                                    prog, pro, collapse))
+                                    prog, pro, collapse, device_tree and prog))
         if not prog:
             pro = [(n_leaves[l], 0, True) for l in sel]
         for k, l in enumerate(sel):
@@ -383,7 +396,7 @@ def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings
 
 
 def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direction=False, orientation=None, band=None, refine=0,
-                refinement=None, progressive=False, progression=None, collapse=False) -> List[MSA]:
+                refinement=None, progressive=False, progression=None, collapse=False, device_tree=False) -> List[MSA]:
     """One chunk: pack, optionally orient, optionally collapse, the star pass or the progressive one, optionally refine, collect."""
     laps = _Laps(timings)
     chunk = _pack(be, codes, names, [[t for t, _ in recs] for recs in loci])
@@ -393,7 +406,7 @@ def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direc
             orientation.extend(result)
         laps.lap("orient_s")
     classes = _collapse(be, chunk, laps) if collapse else None
-    text = (_progressive(be, chunk, budget_bytes, band, laps, progression, classes) if progressive else
+    text = (_progressive(be, chunk, budget_bytes, band, laps, progression, classes, device_tree) if progressive else
             _star_pass(be, chunk, budget_bytes, band, laps, classes))
     moved = {}
     if refine:
@@ -688,6 +701,24 @@ def _orient(be, chunk: Chunk, budget_bytes):
 
 
 # ---- progressive
+def _distances_launch(be, chunk: Chunk, d_seqs, grp):
+    """One mprg_prog_distances launch over the loci `grp` of a chunk: (m, each table's offset, the tables' words, the tables, nw
+    and the status words on the device, the work items)."""
+    lens, first = chunk.lens, chunk.first
+    m = chunk.counts[grp]
+    toff = exclusive_sum(m * m)
+    words = int((m * m).sum())
+    ltab = np.zeros((len(grp), LOCUS_FIELDS), np.int64)
+    ltab[:, 0], ltab[:, 1], ltab[:, 3] = first[grp], m, toff
+    work = np.stack([np.repeat(np.arange(len(grp)), m), _ranges(np.zeros(len(grp), np.int64), m)], 1).astype(np.int32)
+    d_loci, d_work = be.upload(ltab), be.upload(work)
+    d_shared, d_nw, d_status = be.zeros(4 * words), be.zeros(8 * len(lens)), be.empty(4 * len(work))
+    be.call("mprg_prog_distances", be.ptr(chunk.d_codes), chunk.codes_bytes, be.ptr(d_seqs), len(lens), be.ptr(d_loci), len(grp),
+            be.ptr(d_work), len(work), be.ptr(d_shared), words, be.ptr(d_nw), be.ptr(d_status), be.stream,
+            work=float((m * np.add.reduceat(lens, first)[grp]).sum() + 16384.0 * (m * m).sum()))
+    return m, toff, words, d_shared, d_nw, d_status, len(work)
+
+
 def _prog_shared(be, chunk: Chunk, sel, budget_bytes):
     """mprg_prog_distances over the loci `sel` of a chunk, in groups whose m x m tables fit budget_bytes: per locus (s as an
     (m, m) int64 array of which the part above the diagonal is filled, nw)."""
@@ -696,18 +727,8 @@ def _prog_shared(be, chunk: Chunk, sel, budget_bytes):
     d_seqs = be.upload(np.stack([chunk.seq_off, lens], 1).reshape(-1))
     for lo, hi in pa.budget_groups(4 * counts[sel] ** 2, budget_bytes):
         grp = sel[lo:hi]
-        m = counts[grp]
-        toff = exclusive_sum(m * m)
-        words = int((m * m).sum())
-        ltab = np.zeros((len(grp), LOCUS_FIELDS), np.int64)
-        ltab[:, 0], ltab[:, 1], ltab[:, 3] = first[grp], m, toff
-        work = np.stack([np.repeat(np.arange(len(grp)), m), _ranges(np.zeros(len(grp), np.int64), m)], 1).astype(np.int32)
-        d_loci, d_work = be.upload(ltab), be.upload(work)
-        d_shared, d_nw, d_status = be.zeros(4 * words), be.zeros(8 * len(lens)), be.empty(4 * len(work))
-        be.call("mprg_prog_distances", be.ptr(chunk.d_codes), chunk.codes_bytes, be.ptr(d_seqs), len(lens), be.ptr(d_loci), len(grp),
-                be.ptr(d_work), len(work), be.ptr(d_shared), words, be.ptr(d_nw), be.ptr(d_status), be.stream,
-                work=float((m * np.add.reduceat(lens, first)[grp]).sum() + 16384.0 * (m * m).sum()))
-        _check(be.download(d_status, np.int32, len(work)), "mprg_prog_distances", PG_STATUS)
+        m, toff, words, d_shared, d_nw, d_status, n_work = _distances_launch(be, chunk, d_seqs, grp)
+        _check(be.download(d_status, np.int32, n_work), "mprg_prog_distances", PG_STATUS)
         shared = be.download(d_shared, np.uint32, words).astype(np.int64)
         nw = be.download(d_nw, np.int64, len(lens))
         for k, l in enumerate(grp.tolist()):
@@ -719,6 +740,57 @@ def prog_shared(backend, codes: Sequence[Sequence[np.ndarray]], budget_bytes: in
     """mprg_prog_distances over the loci (per locus its gap-free code arrays): per locus (s, nw): s an (m, m) int64 array whose
     part above the diagonal holds the shared 6-mers of the records a < b, nw the records' valid windows."""
     got = _prog_shared(backend, _pack(backend, codes), np.arange(len(codes)), budget_bytes)
+    return [got[l] for l in range(len(codes))]
+
+
+def prog_tree_words(m):
+    """mprg_prog_tree's workspace need (int64 words) of a locus of m records."""
+    return m * (m + 2)
+
+
+def prog_tree_bytes(m):
+    """What a locus of m records holds on the device while its tree is built: the m x m table of shared 6-mers and the workspace."""
+    return 4 * m * m + 8 * prog_tree_words(m)
+
+
+def _prog_trees(be, chunk: Chunk, sel, budget_bytes, weights=None):
+    """The spec's Tree of the loci `sel` of a chunk on the device, in groups whose m x m tables and tree workspaces fit budget_bytes:
+    per group one mprg_prog_distances launch and one mprg_prog_tree launch over the tables it left on the device; the status words
+    and the merges are all that is downloaded.  Per locus its merges as prog_tree gives them.  weights: per record of the chunk's
+    tables how many times it counts (the spec's Collapse)."""
+    lens, first, counts = chunk.lens, chunk.first, chunk.counts
+    out = {}
+    d_seqs = be.upload(np.stack([chunk.seq_off, lens], 1).reshape(-1))
+    d_weights = None if weights is None else be.upload(np.asarray(weights, np.int32))
+    n_leaves = np.add.reduceat((lens > 0).astype(np.int64), first)
+    for lo, hi in pa.budget_groups(prog_tree_bytes(counts[sel]), budget_bytes):
+        grp = sel[lo:hi]
+        m, toff, words, d_shared, d_nw, d_status, n_work = _distances_launch(be, chunk, d_seqs, grp)
+        n_merges = np.maximum(n_leaves[grp] - 1, 0)
+        moff = 2 * exclusive_sum(n_merges)
+        ws_words = prog_tree_words(m)
+        ttab = np.stack([first[grp], m, toff, exclusive_sum(ws_words), moff], 1).astype(np.int64)
+        d_ttab, d_ws = be.upload(ttab), be.empty(8 * int(ws_words.sum()))
+        d_merges, d_tstatus = be.empty(8 * int(n_merges.sum())), be.empty(4 * len(grp))
+        be.call("mprg_prog_tree", be.ptr(d_shared), words, be.ptr(d_nw), be.ptr(d_seqs), len(lens), be.ptr(d_ttab), len(grp),
+                0 if d_weights is None else be.ptr(d_weights), be.ptr(d_ws), int(ws_words.sum()), be.ptr(d_merges), 2 * int(n_merges.sum()),
+                be.ptr(d_tstatus), be.stream, work=float((m * m).sum() * 24.0))
+        _check(be.download(d_status, np.int32, n_work), "mprg_prog_distances", PG_STATUS)
+        _check(be.download(d_tstatus, np.int32, len(grp)), "mprg_prog_tree", TREE_STATUS, "locus")
+        merges = be.download(d_merges, np.int32, 2 * int(n_merges.sum())).reshape(-1, 2)
+        for k, l in enumerate(grp.tolist()):
+            out[l] = [tuple(p) for p in merges[moff[k] // 2:moff[k] // 2 + n_merges[k]].tolist()]
+    return out
+
+
+def prog_trees(backend, codes: Sequence[Sequence[np.ndarray]], weights: Optional[Sequence[Sequence[int]]] = None,
+               budget_bytes: int = pa.DEFAULT_BUDGET_BYTES) -> List[List[Tuple[int, int]]]:
+    """mprg_prog_distances and mprg_prog_tree over the loci (per locus its gap-free code arrays; an empty one is no leaf): per locus
+    the spec's Tree as prog_tree gives it, the merges in order as (key(U), key(V)).  weights: per locus, per record, how many times
+    it counts (the spec's Collapse)."""
+    chunk = _pack(backend, codes)
+    flat = None if weights is None else np.concatenate([np.asarray(w, np.int64) for w in weights])
+    got = _prog_trees(backend, chunk, np.arange(len(codes)), budget_bytes, flat)
     return [got[l] for l in range(len(codes))]
 
 
@@ -770,23 +842,24 @@ def prog_tree(D: np.ndarray, leaves: Sequence[int], weights=None) -> List[Tuple[
     return merges
 
 
-def _prog_plan(lens, first, counts, shared, weights=None):
+def _prog_plan(lens, first, counts, shared, weights=None, merges=None):
     """What the spec's Tree decides for a chunk, from its tables and _prog_shared's of the loci of three or more leaves (two leaves
     have one tree); no device, no clock.  A leaf's node id is its record index, an inner node's counts on from the locus's records.
     Returns (per locus its leaves: the non-empty records; per round its merges (locus, y, x, parent), Y the child with more rows;
     per locus its root node; per locus the records of the root's rows in row order: Y's rows, then X's, at every node; per locus
     the progression tuple (leaves, rounds, False)).  weights: per record of the tables how many rows it stands for (the spec's
-    Collapse): the tree is the weighted one and Y the child with the larger weight sum."""
+    Collapse): the tree is the weighted one and Y the child with the larger weight sum.  merges: per locus of three or more
+    leaves its tree as _prog_trees gave it; `shared` is then not read."""
     leaves, by_round, roots, root_members, progression = [], {}, [], [], []
     for l in range(len(counts)):
         lv = np.nonzero(lens[first[l]:first[l] + counts[l]] > 0)[0].tolist()
         wl = None if weights is None else weights[first[l]:first[l] + counts[l]]
-        merges = ([(lv[0], lv[1])] if len(lv) == 2 else
-                  prog_tree(prog_distance_matrix(*shared[l]), lv, None if wl is None else wl[lv]) if len(lv) > 2 else [])
+        tree = ([(lv[0], lv[1])] if len(lv) == 2 else [] if len(lv) < 2 else merges[l] if merges is not None else
+                prog_tree(prog_distance_matrix(*shared[l]), lv, None if wl is None else wl[lv]))
         members = {a: [a] for a in lv}
         size = {a: 1 if wl is None else int(wl[a]) for a in lv}
         node_at, rnd, nxt = {a: a for a in lv}, {a: 0 for a in lv}, int(counts[l])
-        for u, v in merges:
+        for u, v in tree:
             a, b = node_at[u], node_at[v]                       # key(a) = u < v = key(b)
             y, x = (a, b) if size[a] >= size[b] else (b, a)
             members[nxt] = members.pop(y) + members.pop(x)
@@ -940,10 +1013,11 @@ def merge_profiles(backend, pairs: Sequence[Tuple[np.ndarray, np.ndarray]], budg
     return out
 
 
-def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression, classes: Optional[Classes] = None):
+def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression, classes: Optional[Classes] = None, device_tree=False):
     """The spec's Progressive over one chunk, on the (oriented) sequences in chunk.d_codes.  Returns what the star pass leaves: the
     device buffer of the MSAs' ASCII text, its bytes, each locus's offset in it and its width.  classes: the spec's Collapse: the
-    tree and the merges over the representatives with their weights, the root's rows written for every member."""
+    tree and the merges over the representatives with their weights, the root's rows written for every member.  device_tree: the
+    trees by mprg_prog_tree (_prog_trees) instead of prog_tree."""
     laps.lap()
     lens, first, counts = chunk.lens, chunk.first, chunk.counts
     n_leaves = np.add.reduceat((lens > 0).astype(np.int64), first)          # (every locus has a record)
@@ -959,9 +1033,19 @@ def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression,
         chunk = chunk._replace(lens=lens[keep], seq_off=chunk.seq_off[keep], first=exclusive_sum(kept), counts=kept)
         lens, first, counts, weights = chunk.lens, chunk.first, chunk.counts, classes.weight[keep]
         n_leaves = np.add.reduceat((lens > 0).astype(np.int64), first)
-    # the trees: distances on the device for the loci with three or more leaves (two leaves have one tree), UPGMA on the host
+    # the trees: distances on the device for the loci with three or more leaves (two leaves have one tree), UPGMA on the host or,
+    # with device_tree, on the device
     sel = np.nonzero(n_leaves >= 3)[0]
-    plan = _prog_plan(lens, first, counts, _prog_shared(be, chunk, sel, budget_bytes) if len(sel) else {}, weights)
+    if device_tree:
+        merges = _prog_trees(be, chunk, sel, budget_bytes, weights) if len(sel) else {}
+        add_to(laps.timings, "tree_device_loci", len(sel))
+        t0 = time.perf_counter()
+        plan = _prog_plan(lens, first, counts, None, weights, merges)
+    else:
+        shared = _prog_shared(be, chunk, sel, budget_bytes) if len(sel) else {}
+        t0 = time.perf_counter()
+        plan = _prog_plan(lens, first, counts, shared, weights)
+    add_to(laps.timings, "tree_plan_s", time.perf_counter() - t0)
     if progression is not None:
         progression.extend(plan[-1])
     laps.lap("tree_s")

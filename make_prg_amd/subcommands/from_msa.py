@@ -86,6 +86,11 @@ def register_parser(subparsers):
                         "same bytes from fewer pair alignments; with --progressive the tree has one weighted leaf per distinct "
                         "sequence, so equal sequences get equal rows (also after --refine), and a locus without duplicates keeps "
                         "its --progressive bytes.  Combines with --adjust-direction, --band, --refine and --progressive.  Off by default")
+    p.add_argument("--device-tree", dest="device_tree", action="store_true", default=False,
+                   help="(this implementation) with --unaligned --progressive: the guide trees of the loci of three or more leaves "
+                        "are built on the GPU too (csrc/k_prog_tree.inc: the same exact UPGMA with the same tie rule, weighted with "
+                        "--collapse-identical), on the distance tables where they are; only the merges come back.  The same bytes.  "
+                        "Off by default")
     p.set_defaults(func=run, check=check_options)
     return p
 
@@ -104,6 +109,8 @@ def check_options(args, parser):
         parser.error("--progressive needs --unaligned")
     if getattr(args, "collapse_identical", False) and not args.unaligned:
         parser.error("--collapse-identical needs --unaligned")
+    if getattr(args, "device_tree", False) and not getattr(args, "progressive", False):
+        parser.error("--device-tree needs --progressive")
     if getattr(args, "refine", None) is not None:
         if not args.unaligned:
             parser.error("--refine needs --unaligned")
@@ -605,15 +612,17 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
     progressive = bool(getattr(options, "progressive", False))
     progression = []
     collapse = bool(getattr(options, "collapse_identical", False))
+    device_tree = bool(getattr(options, "device_tree", False))
     for lo in range(0, len(mine), STAR_CHUNK):
         t0 = time.perf_counter()
         recs = [star_align.read_unaligned(f) for f in mine[lo:lo + STAR_CHUNK]]
         t1 = time.perf_counter()
         msas = star_align.star_msas(be, recs, names=loci[lo:lo + STAR_CHUNK], adjust_direction=adjust, orientation=orientation,
-                                    **(dict(band=True) if band else {}), **(dict(timings=counters) if band or collapse else {}),
+                                    **(dict(band=True) if band else {}), **(dict(timings=counters) if band or collapse or device_tree else {}),
                                     **(dict(collapse=True) if collapse else {}),
                                     **(dict(refine=refine, refinement=refinement) if refine else {}),
-                                    **(dict(progressive=True, progression=progression) if progressive else {}))
+                                    **(dict(progressive=True, progression=progression) if progressive else {}),
+                                    **(dict(device_tree=True) if device_tree else {}))
         t2 = time.perf_counter()
         for locus, m in zip(loci[lo:lo + STAR_CHUNK], msas):
             path = out_dir / f"{locus}.fa"
@@ -644,6 +653,8 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
         built = [(n, r) for n, r, star in progression if not star]
         logger.info(f"rank {rank}: --progressive: {len(built)} loci built, {sum(n - 1 for n, _ in built)} merges, "
                     f"{max((r for _, r in built), default=0)} rounds at most, {len(progression) - len(built)} loci left to the star pass")
+    if device_tree:
+        logger.info(f"rank {rank}: --device-tree: {counters.get('tree_device_loci', 0)} loci's trees built on the device")
     align_unaligned_inputs.timings = dict(read_s=t_read, align_s=t_align, write_s=t_write)
     return written
 

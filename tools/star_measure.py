@@ -23,7 +23,11 @@ prog_band_second_passes, prog_band_full_merges (sent to the full DP), prog_band_
 also gives collapse_s, collapse_records, collapse_classes and collapse_pairs or collapse_merges (the alignments made).  Every line
 gives dup_share: the share of the records whose sequence an earlier record of their locus has.
 `--dup FRACTION`: after a locus's sequences are made, each record but the first is replaced, with that probability, by a copy of
-an earlier record of the locus picked at random (seeded): loci with a known share of exact copies."""
+an earlier record of the locus picked at random (seeded): loci with a known share of exact copies.
+`--device-tree` (with --progressive): the guide trees on the device (`from_msa --unaligned --progressive --device-tree`); the line
+then also gives tree_device_loci.  Every --progressive line gives tree_plan_s, the part of tree_s spent on the host's plan (without
+--device-tree: the host's UPGMA and the plan).
+`--no-prg`: the PRG build over the MSAs written is left out (no prg_build_s): for runs that compare the alignment stages only."""
 import hashlib
 import json
 import os
@@ -58,6 +62,10 @@ objective = progressive or "--objective" in sys.argv
 diverged = int(sys.argv[sys.argv.index("--diverged") + 1]) if "--diverged" in sys.argv else 0
 collapse = "--collapse-identical" in sys.argv
 dup = float(sys.argv[sys.argv.index("--dup") + 1]) if "--dup" in sys.argv else 0.0
+device_tree = "--device-tree" in sys.argv
+if device_tree and not progressive:
+    sys.exit("--device-tree needs --progressive")
+prog_kw = dict(progressive=True, **(dict(device_tree=True) if device_tree else {})) if progressive else {}
 
 
 def diverged_seqs(seed):
@@ -100,7 +108,7 @@ try:
     files = sorted(src.iterdir())
     be = get_backend("runtime")
     sa.star_msas(be, [sa.read_unaligned(f) for f in files[:4]], adjust_direction=flip is not None, band=band, refine=refine,
-                 **(dict(progressive=True) if progressive else {}), **(dict(collapse=True) if collapse else {}))   # warm-up: first launches
+                 **prog_kw, **(dict(collapse=True) if collapse else {}))   # warm-up: first launches
     t0 = time.perf_counter()
     recs = [sa.read_unaligned(f) for f in files]
     t_read = time.perf_counter() - t0
@@ -110,7 +118,7 @@ try:
     refinement = []
     progression = []
     msas = sa.star_msas(be, recs, timings=timings, adjust_direction=flip is not None, orientation=orientation, band=band, refine=refine,
-                        refinement=refinement, **(dict(progressive=True, progression=progression) if progressive else {}),
+                        refinement=refinement, **(dict(prog_kw, progression=progression) if progressive else {}),
                         **(dict(collapse=True) if collapse else {}))
     t_star = time.perf_counter() - t0
     t0 = time.perf_counter()
@@ -138,7 +146,7 @@ try:
                      s_before=sum(s for _, s, _ in refinement), s_after=sum(s for _, _, s in refinement))
     if progressive:
         built = [(n, r) for n, r, star in progression if not star]
-        extra.update(progressive=True, loci_built=len(built), merges=sum(n - 1 for n, _ in built), max_rounds=max((r for _, r in built), default=0), mean_rounds=round(sum(r for _, r in built) / max(1, len(built)), 2),
+        extra.update(progressive=True, device_tree=device_tree, loci_built=len(built), merges=sum(n - 1 for n, _ in built), max_rounds=max((r for _, r in built), default=0), mean_rounds=round(sum(r for _, r in built) / max(1, len(built)), 2),
                      loci_left_to_star=len(progression) - len(built))
     if objective:
         import numpy as np
@@ -154,12 +162,14 @@ try:
     cells = sum(len(c) * len(cs[int(k)]) for cs, k in zip(codes, cent) for a, c in enumerate(cs) if a != int(k))
     opts = Namespace(input=str(msa_dir), suffix="", output_prefix=str(work / "out" / "prg"), alignment_format="fasta",
                      max_nesting=5, min_match_length=7, output_type=OutputType("a"), force=False, threads=16)
-    t0 = time.perf_counter()
-    from_msa._run(opts, None, None, 1, msa_files=written)
-    t_prg = time.perf_counter() - t0
+    t_prg = None
+    if "--no-prg" not in sys.argv:
+        t0 = time.perf_counter()
+        from_msa._run(opts, None, None, 1, msa_files=written)
+        t_prg = time.perf_counter() - t0
     print(json.dumps(dict(loci=n_loci, pairs=sum(len(r) - 1 for r in recs), residues=sum(len(s) for r in recs for _, s in r),
                           generate_s=round(t_gen, 2), read_s=round(t_read, 3), star_s=round(t_star, 3),
-                          **{k: round(v, 3) for k, v in timings.items()}, write_s=round(t_write, 3), prg_build_s=round(t_prg, 3),
+                          **{k: round(v, 3) for k, v in timings.items()}, write_s=round(t_write, 3), **({} if t_prg is None else dict(prg_build_s=round(t_prg, 3))),
                           dp_cells=cells, msa_md5=digest.hexdigest(), **extra)))
 finally:
     shutil.rmtree(work, ignore_errors=True)
