@@ -14,8 +14,10 @@
 //   on consecutive columns).  A cell's traceback is 4 bits, a lane packs eight steps per dword, so every store is a 256-byte
 //   row.  Lane 0 then walks the traceback back from (n, C) and writes the ops (reversed) and the score.
 //   The cell's recurrence (al_cell.inc) and the walk back (al_walk.inc) are written once for the four sweep kernels (this one,
-//   k_align_pairs_banded below, k_align_profile_pairs in k_prog.inc, k_align_profile_pairs_banded in k_prog_band.inc) and included
-//   as text: an inlined function body shared between kernels compiles them to other instructions (DESIGN.md §3a).
+//   k_align_pairs_banded below, k_align_profile_pairs in k_prog.inc, k_align_profile_pairs_banded in k_prog_band.inc), a column's
+//   counts (al_counts.inc) and its planes (al_planes.inc) once for the kernels that write profiles (k_align_profiles,
+//   k_prog_columns, k_prog_columns_weighted, and k_refine_profiles for the planes).  All are included as text: an inlined function
+//   body shared between kernels compiles them to other instructions, text that expands to the same tokens cannot (DESIGN.md §3a).
 // ---------------------------------------------------------------------------------------------------------------
 #define AL_THREADS 256
 #define AL_WAVES (AL_THREADS / 64)
@@ -33,18 +35,15 @@ KERNEL(k_align_profiles, const uint8_t *cells, const int64_t *leaves, const int3
   PAR_FOR(tt, 256) {
     const int c = wk[1] * 256 + (int)tt;
     if (c >= C) continue;
-    int cnt[5] = {0, 0, 0, 0, 0};
-    for (int r = 0; r < R; ++r) {
-      const unsigned code = cells[off + (long long)r * C + c];
-#pragma unroll
-      for (int q = 0; q < 5; ++q) cnt[q] += code == (unsigned)q;
-    }
-    const long long acgt = (long long)cnt[0] + cnt[1] + cnt[2] + cnt[3], gap = cnt[4];
+#define AL_CELL(r) cells[off + (long long)(r) * C + c]
+#define AL_WEIGHT(r) 1
+#include "al_counts.inc"
+#undef AL_CELL
+#undef AL_WEIGHT
+    const int pl_rows = R, pl_stride = C;
+    constexpr int kind = 0;                                  // (a leaf is a Y side)
     int32_t *o = profile + poff + c;
-#pragma unroll
-    for (int x = 0; x < 4; ++x) o[(long long)x * C] = (int32_t)(64 * (20 * cnt[x] - 9 * (acgt - cnt[x]) - 10 * gap) / R);
-    o[4LL * C] = (int32_t)(64 * (-10 * gap) / R);
-    o[5LL * C] = (int32_t)(64 * (-10 * ((long long)R - gap)) / R);
+#include "al_planes.inc"
   }
 }
 

@@ -1,7 +1,8 @@
 // ---------------------------------------------------------------------------------------------------------------
 // K-C  `from_msa --unaligned --collapse-identical` (make_prg_amd/from_msa/star_align.py holds the spec, "Collapse"; DESIGN.md
 //      §3b): the classes of identical sequences of a locus, and the column tables of a text whose rows count w times.
-//      Integers only.  Kernels of their own: every kernel of k_star.inc and k_prog.inc stays what it was.
+//      Integers only.  Kernels of their own, so that every kernel of k_star.inc and k_prog.inc stays what it was; what they have in
+//      common with those is one text, included in both (st_seqs_par.inc, pg_item.inc, al_counts.inc, al_planes.inc; DESIGN.md §3a).
 //
 // k_star_identical: one workgroup per locus, a wavefront per sequence (the wavefronts take the sequences round-robin), lanes on
 //   consecutive bytes.  A sequence's hash is the SUM over its positions of a mix of (position, code): a sum does not depend on
@@ -12,9 +13,9 @@
 //   earlier tile settled (rep[a] == a still), so rep[a] is the smallest equal b.  A locus of more than ID_TILE sequences costs
 //   one hash of a per earlier tile more; nothing is kept per sequence but rep itself: no scratch, any record count.
 //   The hash only filters: filter_bits of it are compared (0: every pair of equal length goes to the byte comparison).
-// k_prog_columns_weighted: k_prog_columns with row r counted weights[r] times and the divisor the weight sum: the planes of the
-//   text with every row written w_r times.  The workgroup first adds up the weights (every thread a stride of rows, a wave
-//   reduction, four partial sums through LDS) and refuses the item when one is below 1 or the sum is not the stated one.
+// k_prog_columns_weighted: k_prog_columns' texts (item fields, counts, planes) with row r counted weights[r] times and the divisor
+//   the weight sum: the planes of the text with every row written w_r times.  The workgroup first adds up the weights (every
+//   thread a stride of rows, wg_sum.inc) and refuses the item when one is below 1 or the sum is not the stated one.
 // ---------------------------------------------------------------------------------------------------------------
 #define ID_THREADS 256
 #define ID_WAVES (ID_THREADS / 64)
@@ -47,17 +48,7 @@ __global__ void __launch_bounds__(ID_THREADS) k_star_identical(const uint8_t *co
   const int64_t *L = loci + MPRG_ST_LOCUS_FIELDS * (long long)BLOCK_ID;
   const long long first = L[0], m = L[1];
   const bool ok = first >= 0 && m >= 0 && m <= 0x7fffffffLL && first <= n_seqs - m;
-  ONE_THREAD bad[0] = !ok;
-  BARRIER();
-  if (ok) {
-    int b = 0;
-    PAR_FOR(x, m) {
-      const long long off = seqs[2 * (first + x)], n = seqs[2 * (first + x) + 1];
-      b |= off < 0 || n < 0 || off > codes_bytes || n > codes_bytes - off;
-    }
-    if (b) ATOMIC_OR(&bad[0], 1);
-  }
-  BARRIER();
+#include "st_seqs_par.inc"
   ONE_THREAD status[BLOCK_ID] = bad[0] ? MPRG_ST_CENTRE_BAD : MPRG_ST_OK;
   if (bad[0]) return;                                        // (the whole workgroup; no rep written)
   PAR_FOR(x, m) rep[first + x] = (int32_t)x;
@@ -104,18 +95,14 @@ __global__ void __launch_bounds__(PG_THREADS) k_prog_columns_weighted(const int6
                                                                       int32_t *cols, long long cols_words, int32_t *status) {
   SHARED(long long, red, PG_WAVES);
   SHARED(int, low, 1);
-  const int32_t *wk = work + 2 * (long long)BLOCK_ID;
-  const long long it = wk[0], tile = wk[1];
   long long buf = 0, off = 0, R = 0, W = 0, kind = 0, coff = 0, woff = 0, S = 0;
-  int st = MPRG_PG_OK;
-  if (it < 0 || it >= n_items) st = MPRG_PG_BAD_ITEM;
-  else {
-    const int64_t *I = items + MPRG_PG_WITEM_FIELDS * it;
-    buf = I[0]; off = I[1]; R = I[2]; W = I[3]; kind = I[4]; coff = I[5]; woff = I[6]; S = I[7];
-    if (!pg_text_ok(bufs, n_bufs, buf, off, R, W) || tile < 0 || tile * 256 >= W || (kind != 0 && kind != 1) || woff < 0 ||
-        woff > weights_words || R > weights_words - woff || S < R || S > PG_MAX_ROWS) st = MPRG_PG_BAD_ITEM;
-    else if (coff < 0 || coff > cols_words || (6 + kind) * W > cols_words - coff) st = MPRG_PG_NO_SPACE;
-  }
+#define PG_ITEM_STRIDE MPRG_PG_WITEM_FIELDS
+#define PG_ITEM_READ_MORE woff = I[6]; S = I[7];
+#define PG_ITEM_ALSO_BAD woff < 0 || woff > weights_words || R > weights_words - woff || S < R || S > PG_MAX_ROWS
+#include "pg_item.inc"
+#undef PG_ITEM_STRIDE
+#undef PG_ITEM_READ_MORE
+#undef PG_ITEM_ALSO_BAD
   if (st != MPRG_PG_OK) {                                    // (the whole workgroup)
     if (threadIdx.x == 0) status[BLOCK_ID] = st;
     return;
@@ -127,37 +114,20 @@ __global__ void __launch_bounds__(PG_THREADS) k_prog_columns_weighted(const int6
   int below = 0;
   PAR_FOR(r, R) { const long long w = wt[r]; below |= w < 1; part += w; }
   if (below) ATOMIC_OR(&low[0], 1);
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d);
-  if (wave_lane() == 0) red[wave_id()] = part;
-  BARRIER();
-  long long sum = 0;
-  for (int w = 0; w < PG_WAVES; ++w) sum += red[w];
+#include "wg_sum.inc"
+  WG_TOTAL(sum, PG_WAVES);                                   // (every thread: st stays workgroup-uniform)
   if (low[0] || sum != S) st = MPRG_PG_BAD_ITEM;
   if (threadIdx.x == 0) status[BLOCK_ID] = st;
   if (st != MPRG_PG_OK) return;                              // (the whole workgroup)
   const long long c = tile * 256 + (long long)threadIdx.x;
   if (c >= W) return;
   const uint8_t *text = (const uint8_t *)(uintptr_t)bufs[2 * buf] + off;
-  int cnt[5] = {0, 0, 0, 0, 0};
-  for (long long r = 0; r < R; ++r) {
-    const unsigned code = text[r * W + c];
-    const int w = wt[r];
-#pragma unroll
-    for (int q = 0; q < 5; ++q) cnt[q] += code == (unsigned)q ? w : 0;
-  }
-  const long long acgt = (long long)cnt[0] + cnt[1] + cnt[2] + cnt[3], gap = cnt[4];
+#define AL_CELL(r) text[(r) * W + c]
+#define AL_WEIGHT(r) wt[r]
+#include "al_counts.inc"
+#undef AL_CELL
+#undef AL_WEIGHT
+  const long long pl_rows = S, pl_stride = W;                    // (the rows of the text with row r written w_r times)
   int32_t *o = cols + coff + c;
-  if (kind == 0) {
-#pragma unroll
-    for (int x = 0; x < 4; ++x) o[(long long)x * W] = (int32_t)(64 * (20 * cnt[x] - 9 * (acgt - cnt[x]) - 10 * gap) / S);
-    o[4LL * W] = (int32_t)(64 * (-10 * gap) / S);
-    o[5LL * W] = (int32_t)(64 * (-10 * (S - gap)) / S);
-  } else {
-#pragma unroll
-    for (int x = 0; x < 4; ++x) o[(long long)x * W] = cnt[x];
-    o[4LL * W] = (int32_t)(S - acgt - gap);
-    o[5LL * W] = (int32_t)gap;
-    o[6LL * W] = (int32_t)(64 * (-10 * (S - gap)) / S);
-  }
+#include "al_planes.inc"
 }

@@ -26,8 +26,8 @@
 // ---------------------------------------------------------------------------------------------------------------
 #define PG_THREADS 256
 #define PG_WAVES (PG_THREADS / 64)
-#define PG_BINS 4096
-#define PG_K 6
+#define PG_BINS ST_BINS                        // (a window is k_star.inc's: st_window.inc)
+#define PG_K ST_K
 #define PG_MAX_ROWS (1 << 20)                  // R_X up to here: pg_div stays exact and its operands stay in 32 bits
 
 __global__ void __launch_bounds__(PG_THREADS) k_prog_distances(const uint8_t *codes, long long codes_bytes, const int64_t *seqs,
@@ -47,38 +47,21 @@ __global__ void __launch_bounds__(PG_THREADS) k_prog_distances(const uint8_t *co
     ok = first >= 0 && m >= 1 && m <= 0x7fffffffLL && first <= n_seqs - m && a >= 0 && a < m && toff >= 0 && toff <= shared_words &&
          m <= (shared_words - toff) / m;
   }
-  ONE_THREAD bad[0] = !ok;
-  BARRIER();
-  if (ok) {
-    int b = 0;
-    PAR_FOR(x, m) {
-      const long long off = seqs[2 * (first + x)], n = seqs[2 * (first + x) + 1];
-      b |= off < 0 || n < 0 || off > codes_bytes || n > codes_bytes - off;
-    }
-    if (b) ATOMIC_OR(&bad[0], 1);
-  }
-  BARRIER();
+#include "st_seqs_par.inc"
   ONE_THREAD status[BLOCK_ID] = bad[0] ? MPRG_PG_BAD_ITEM : MPRG_PG_OK;
   if (bad[0]) return;                                        // (the whole workgroup)
   PAR_FOR(k, PG_BINS) ha[k] = 0;
   BARRIER();
   {
     const long long off = seqs[2 * (first + a)], n = seqs[2 * (first + a) + 1];
-    long long cnt = 0;
+    long long part = 0;
     PAR_FOR(w, n - (PG_K - 1)) {
-      unsigned k = 0;
-      bool v = true;
-#pragma unroll
-      for (int q = 0; q < PG_K; ++q) { const unsigned c = codes[off + w + q]; v = v && c < 4u; k = (k << 2) | (c & 3u); }
-      if (v) { ATOMIC_ADD(&ha[k], 1u); ++cnt; }
+#include "st_window.inc"
+      if (valid) { ATOMIC_ADD(&ha[k], 1u); ++part; }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d);
-    if (wave_lane() == 0) red[wave_id()] = cnt;
-    BARRIER();                                               // ha is read-only from here on
+#include "wg_sum.inc"                                        // (behind its barrier ha is read-only)
     ONE_THREAD {
-      long long s = 0;
-      for (int w = 0; w < PG_WAVES; ++w) s += red[w];
+      WG_TOTAL(s, PG_WAVES);
       nw[first + a] = s;
     }
   }
@@ -91,22 +74,15 @@ __global__ void __launch_bounds__(PG_THREADS) k_prog_distances(const uint8_t *co
     PAR_FOR(k, PG_BINS) hb[k] = 0;
     BARRIER();
     PAR_FOR(w, n - (PG_K - 1)) {
-      unsigned k = 0;
-      bool v = true;
-#pragma unroll
-      for (int q = 0; q < PG_K; ++q) { const unsigned c = codes[off + w + q]; v = v && c < 4u; k = (k << 2) | (c & 3u); }
-      if (v) ATOMIC_ADD(&hb[k], 1u);
+#include "st_window.inc"
+      if (valid) ATOMIC_ADD(&hb[k], 1u);
     }
     BARRIER();
     long long part = 0;
     PAR_FOR(k, PG_BINS) part += ha[k] < hb[k] ? ha[k] : hb[k];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d);
-    if (wave_lane() == 0) red[wave_id()] = part;
-    BARRIER();
+#include "wg_sum.inc"
     ONE_THREAD {
-      long long s = 0;
-      for (int w = 0; w < PG_WAVES; ++w) s += red[w];
+      WG_TOTAL(s, PG_WAVES);
       shared[toff + a * m + b] = (uint32_t)s;
     }                                                        // (red is written again only after the next two barriers)
   }
@@ -121,42 +97,27 @@ MPRG_DEV bool pg_text_ok(const int64_t *bufs, int n_bufs, long long buf, long lo
 
 __global__ void __launch_bounds__(PG_THREADS) k_prog_columns(const int64_t *bufs, int n_bufs, const int64_t *items, int n_items,
                                                              const int32_t *work, int32_t *cols, long long cols_words, int32_t *status) {
-  const int32_t *wk = work + 2 * (long long)BLOCK_ID;
-  const long long it = wk[0], tile = wk[1];
   long long buf = 0, off = 0, R = 0, W = 0, kind = 0, coff = 0;
-  int st = MPRG_PG_OK;
-  if (it < 0 || it >= n_items) st = MPRG_PG_BAD_ITEM;
-  else {
-    const int64_t *I = items + MPRG_PG_ITEM_FIELDS * it;
-    buf = I[0]; off = I[1]; R = I[2]; W = I[3]; kind = I[4]; coff = I[5];
-    if (!pg_text_ok(bufs, n_bufs, buf, off, R, W) || tile < 0 || tile * 256 >= W || (kind != 0 && kind != 1)) st = MPRG_PG_BAD_ITEM;
-    else if (coff < 0 || coff > cols_words || (6 + kind) * W > cols_words - coff) st = MPRG_PG_NO_SPACE;
-  }
+#define PG_ITEM_STRIDE MPRG_PG_ITEM_FIELDS
+#define PG_ITEM_READ_MORE
+#define PG_ITEM_ALSO_BAD false
+#include "pg_item.inc"
+#undef PG_ITEM_STRIDE
+#undef PG_ITEM_READ_MORE
+#undef PG_ITEM_ALSO_BAD
   if (threadIdx.x == 0) status[BLOCK_ID] = st;
   if (st != MPRG_PG_OK) return;                              // (the whole workgroup)
   const long long c = tile * 256 + (long long)threadIdx.x;
   if (c >= W) return;
   const uint8_t *text = (const uint8_t *)(uintptr_t)bufs[2 * buf] + off;
-  int cnt[5] = {0, 0, 0, 0, 0};
-  for (long long r = 0; r < R; ++r) {
-    const unsigned code = text[r * W + c];
-#pragma unroll
-    for (int q = 0; q < 5; ++q) cnt[q] += code == (unsigned)q;
-  }
-  const long long acgt = (long long)cnt[0] + cnt[1] + cnt[2] + cnt[3], gap = cnt[4];
+#define AL_CELL(r) text[(r) * W + c]
+#define AL_WEIGHT(r) 1
+#include "al_counts.inc"
+#undef AL_CELL
+#undef AL_WEIGHT
+  const long long pl_rows = R, pl_stride = W;
   int32_t *o = cols + coff + c;
-  if (kind == 0) {
-#pragma unroll
-    for (int x = 0; x < 4; ++x) o[(long long)x * W] = (int32_t)(64 * (20 * cnt[x] - 9 * (acgt - cnt[x]) - 10 * gap) / R);
-    o[4LL * W] = (int32_t)(64 * (-10 * gap) / R);
-    o[5LL * W] = (int32_t)(64 * (-10 * (R - gap)) / R);
-  } else {
-#pragma unroll
-    for (int x = 0; x < 4; ++x) o[(long long)x * W] = cnt[x];
-    o[4LL * W] = (int32_t)(R - acgt - gap);
-    o[5LL * W] = (int32_t)gap;
-    o[6LL * W] = (int32_t)(64 * (-10 * (R - gap)) / R);
-  }
+#include "al_planes.inc"
 }
 
 // C's truncating v / R for |v| <= 1 280 R, R <= PG_MAX_ROWS, as a multiplication and a shift: with s = ceil(log2 R) and

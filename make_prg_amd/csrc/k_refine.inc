@@ -101,12 +101,10 @@ __global__ void __launch_bounds__(RF_THREADS) k_refine_profiles(const uint8_t *t
 #pragma unroll
   for (int x = 0; x < 5; ++x) cnt[x] = in[(long long)x * W];
   cnt[0] -= ch == 'A'; cnt[1] -= ch == 'C'; cnt[2] -= ch == 'G'; cnt[3] -= ch == 'T'; cnt[4] -= ch == '-';
-  const long long Rm = R - 1, acgt = cnt[0] + cnt[1] + cnt[2] + cnt[3], gap = cnt[4];
+  const long long acgt = cnt[0] + cnt[1] + cnt[2] + cnt[3], gap = cnt[4], pl_rows = R - 1, pl_stride = W;
+  constexpr int kind = 0;                                    // (the MSA without the row is a Y side)
   int32_t *o = profile + poff + c;
-#pragma unroll
-  for (int x = 0; x < 4; ++x) o[(long long)x * W] = (int32_t)(64 * (20 * cnt[x] - 9 * (acgt - cnt[x]) - 10 * gap) / Rm);
-  o[4LL * W] = (int32_t)(64 * (-10 * gap) / Rm);
-  o[5LL * W] = (int32_t)(64 * (-10 * (Rm - gap)) / Rm);
+#include "al_planes.inc"
 }
 
 __global__ void __launch_bounds__(RF_THREADS) k_refine_scan(const int64_t *loci, int n_loci, long long text_bytes, const uint8_t *keep,

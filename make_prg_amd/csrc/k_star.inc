@@ -42,64 +42,9 @@ KERNEL(k_star_kmer_centre, const uint8_t *codes, long long codes_bytes, const in
   SHARED(uint32_t, hist, ST_BINS);
   SHARED(long long, red, ST_WAVES);
   SHARED(int, bad, 1);
-  const int64_t *L = loci + MPRG_ST_LOCUS_FIELDS * (long long)BLOCK_ID;
-  const long long first = L[0], m = L[1];
-  ONE_THREAD {
-    int b = first < 0 || m < 0 || first + m > n_seqs;
-    for (long long a = 0; !b && a < m; ++a) b = seqs[2 * (first + a)] < 0 || seqs[2 * (first + a) + 1] < 0 ||
-                                               seqs[2 * (first + a)] + seqs[2 * (first + a) + 1] > codes_bytes;
-    bad[0] = b;
-    if (b) centre[BLOCK_ID] = MPRG_ST_CENTRE_BAD;
-  }
-  BARRIER();
-  if (bad[0]) return;                                        // (the whole workgroup)
-  PAR_FOR(b, ST_BINS) tot[b] = 0;
-  BARRIER();
-  for (long long a = 0; a < m; ++a) {
-    const long long off = seqs[2 * (first + a)], n = seqs[2 * (first + a) + 1];
-    PAR_FOR(w, n - (ST_K - 1)) {
-      unsigned k = 0;
-      bool ok = true;
-#pragma unroll
-      for (int q = 0; q < ST_K; ++q) { const unsigned c = codes[off + w + q]; ok = ok && c < 4u; k = (k << 2) | (c & 3u); }
-      if (ok) ATOMIC_ADD(&tot[k], 1u);
-    }
-  }
-  BARRIER();
-  long long best = 0;
-  int best_a = -1;
-  for (long long a = 0; a < m; ++a) {
-    const long long off = seqs[2 * (first + a)], n = seqs[2 * (first + a) + 1];
-    PAR_FOR(b, ST_BINS) hist[b] = 0;
-    BARRIER();
-    PAR_FOR(w, n - (ST_K - 1)) {
-      unsigned k = 0;
-      bool ok = true;
-#pragma unroll
-      for (int q = 0; q < ST_K; ++q) { const unsigned c = codes[off + w + q]; ok = ok && c < 4u; k = (k << 2) | (c & 3u); }
-      if (ok) ATOMIC_ADD(&hist[k], 1u);
-    }
-    BARRIER();
-    long long part = 0;
-    PAR_FOR(w, n - (ST_K - 1)) {
-      unsigned k = 0;
-      bool ok = true;
-#pragma unroll
-      for (int q = 0; q < ST_K; ++q) { const unsigned c = codes[off + w + q]; ok = ok && c < 4u; k = (k << 2) | (c & 3u); }
-      if (ok) part += (long long)tot[k] - (long long)hist[k];
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d);
-    if (wave_lane() == 0) red[wave_id()] = part;
-    BARRIER();
-    ONE_THREAD {
-      long long s = 0;
-      for (int w = 0; w < ST_WAVES; ++w) s += red[w];
-      if (n > 0 && (best_a < 0 || s > best)) { best = s; best_a = (int)a; }
-    }
-    BARRIER();                                               // (hist and red are rewritten for the next sequence)
-  }
-  ONE_THREAD centre[BLOCK_ID] = best_a;                     // -1: every sequence is empty
+#define ST_BIN(k) (k)
+#include "st_centre.inc"
+#undef ST_BIN
 }
 
 // the strand-blind bin of a window: the smaller of its index and its reverse complement's
@@ -108,72 +53,18 @@ MPRG_DEV unsigned st_canonical(unsigned k) {
   return r < k ? r : k;
 }
 
-// k_star_kmer_centre with canonical bins.  A kernel of its own, not a shared body: k_star_kmer_centre's code stays what it was
-// (an inlined common body compiles it differently), so a run without --adjust-direction launches the same instructions as before.
+// k_star_kmer_centre with canonical bins.  A kernel of its own whose body is the same text (st_centre.inc), not a shared function:
+// an inlined common body compiles k_star_kmer_centre differently, the included text leaves both kernels the instructions they had
+// (DESIGN.md §3a), so a run without --adjust-direction launches what it always did.
 KERNEL(k_star_kmer_centre_canonical, const uint8_t *codes, long long codes_bytes, const int64_t *seqs, long long n_seqs,
        const int64_t *loci, int32_t *centre) {
   SHARED(uint32_t, tot, ST_BINS);
   SHARED(uint32_t, hist, ST_BINS);
   SHARED(long long, red, ST_WAVES);
   SHARED(int, bad, 1);
-  const int64_t *L = loci + MPRG_ST_LOCUS_FIELDS * (long long)BLOCK_ID;
-  const long long first = L[0], m = L[1];
-  ONE_THREAD {
-    int b = first < 0 || m < 0 || first + m > n_seqs;
-    for (long long a = 0; !b && a < m; ++a) b = seqs[2 * (first + a)] < 0 || seqs[2 * (first + a) + 1] < 0 ||
-                                               seqs[2 * (first + a)] + seqs[2 * (first + a) + 1] > codes_bytes;
-    bad[0] = b;
-    if (b) centre[BLOCK_ID] = MPRG_ST_CENTRE_BAD;
-  }
-  BARRIER();
-  if (bad[0]) return;                                        // (the whole workgroup)
-  PAR_FOR(b, ST_BINS) tot[b] = 0;
-  BARRIER();
-  for (long long a = 0; a < m; ++a) {
-    const long long off = seqs[2 * (first + a)], n = seqs[2 * (first + a) + 1];
-    PAR_FOR(w, n - (ST_K - 1)) {
-      unsigned k = 0;
-      bool ok = true;
-#pragma unroll
-      for (int q = 0; q < ST_K; ++q) { const unsigned c = codes[off + w + q]; ok = ok && c < 4u; k = (k << 2) | (c & 3u); }
-      if (ok) ATOMIC_ADD(&tot[st_canonical(k)], 1u);
-    }
-  }
-  BARRIER();
-  long long best = 0;
-  int best_a = -1;
-  for (long long a = 0; a < m; ++a) {
-    const long long off = seqs[2 * (first + a)], n = seqs[2 * (first + a) + 1];
-    PAR_FOR(b, ST_BINS) hist[b] = 0;
-    BARRIER();
-    PAR_FOR(w, n - (ST_K - 1)) {
-      unsigned k = 0;
-      bool ok = true;
-#pragma unroll
-      for (int q = 0; q < ST_K; ++q) { const unsigned c = codes[off + w + q]; ok = ok && c < 4u; k = (k << 2) | (c & 3u); }
-      if (ok) ATOMIC_ADD(&hist[st_canonical(k)], 1u);
-    }
-    BARRIER();
-    long long part = 0;
-    PAR_FOR(w, n - (ST_K - 1)) {
-      unsigned k = 0;
-      bool ok = true;
-#pragma unroll
-      for (int q = 0; q < ST_K; ++q) { const unsigned c = codes[off + w + q]; ok = ok && c < 4u; k = (k << 2) | (c & 3u); }
-      if (ok) { k = st_canonical(k); part += (long long)tot[k] - (long long)hist[k]; }
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d);
-    if (wave_lane() == 0) red[wave_id()] = part;
-    BARRIER();
-    ONE_THREAD {
-      long long s = 0;
-      for (int w = 0; w < ST_WAVES; ++w) s += red[w];
-      if (n > 0 && (best_a < 0 || s > best)) { best = s; best_a = (int)a; }
-    }
-    BARRIER();                                               // (hist and red are rewritten for the next sequence)
-  }
-  ONE_THREAD centre[BLOCK_ID] = best_a;                     // -1: every sequence is empty
+#define ST_BIN(k) st_canonical(k)
+#include "st_centre.inc"
+#undef ST_BIN
 }
 
 KERNEL(k_star_strand, const uint8_t *codes, long long codes_bytes, const int64_t *seqs, long long n_seqs, const int64_t *loci,
@@ -183,9 +74,9 @@ KERNEL(k_star_strand, const uint8_t *codes, long long codes_bytes, const int64_t
   const int64_t *L = loci + MPRG_ST_LOCUS_FIELDS * (long long)BLOCK_ID;
   const long long first = L[0], m = L[1], c = centre[BLOCK_ID];
   ONE_THREAD {
-    int b = first < 0 || m < 0 || first + m > n_seqs || c < 0 || c >= m;
-    for (long long a = 0; !b && a < m; ++a) b = seqs[2 * (first + a)] < 0 || seqs[2 * (first + a) + 1] < 0 ||
-                                               seqs[2 * (first + a)] + seqs[2 * (first + a) + 1] > codes_bytes;
+#define ST_ALSO_BAD c < 0 || c >= m
+#include "st_seqs_serial.inc"
+#undef ST_ALSO_BAD
     bad[0] = b;
     status[BLOCK_ID] = b ? MPRG_ST_CENTRE_BAD : MPRG_ST_OK;
   }
@@ -195,11 +86,8 @@ KERNEL(k_star_strand, const uint8_t *codes, long long codes_bytes, const int64_t
   {
     const long long off = seqs[2 * (first + c)], n = seqs[2 * (first + c) + 1];
     PAR_FOR(w, n - (ST_K - 1)) {
-      unsigned k = 0;
-      bool ok = true;
-#pragma unroll
-      for (int q = 0; q < ST_K; ++q) { const unsigned x = codes[off + w + q]; ok = ok && x < 4u; k = (k << 2) | (x & 3u); }
-      if (ok) ATOMIC_ADD(&href[k], 1u);
+#include "st_window.inc"
+      if (valid) ATOMIC_ADD(&href[k], 1u);
     }
   }
   BARRIER();                                                 // href is read-only from here on: no barrier, no LDS write below
@@ -207,11 +95,8 @@ KERNEL(k_star_strand, const uint8_t *codes, long long codes_bytes, const int64_t
     const long long off = seqs[2 * (first + a)], n = seqs[2 * (first + a) + 1];
     long long fwd = 0, rev = 0, nw = 0;
     for (long long w = wave_lane(); w < n - (ST_K - 1); w += WAVE) {
-      unsigned k = 0;
-      bool ok = true;
-#pragma unroll
-      for (int q = 0; q < ST_K; ++q) { const unsigned x = codes[off + w + q]; ok = ok && x < 4u; k = (k << 2) | (x & 3u); }
-      if (ok) { fwd += href[k]; rev += href[st_rc6(k)]; ++nw; }
+#include "st_window.inc"
+      if (valid) { fwd += href[k]; rev += href[st_rc6(k)]; ++nw; }
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) { fwd += __shfl_xor(fwd, d); rev += __shfl_xor(rev, d); nw += __shfl_xor(nw, d); }

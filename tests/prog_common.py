@@ -176,6 +176,69 @@ def check_tall_columns(be):
         assert min(int(v.min()) for v in want) < 0 < max(int(v.max()) for v in want)
 
 
+PLANE_ROWS, PLANE_WIDTHS = (1, 2, 3, 7), (1, 255, 256, 257)               # the widths: around k_prog_columns' 256-column tile
+
+
+@functools.lru_cache(maxsize=None)
+def plane_texts():
+    """16 texts of row strings over all twelve codes: an all-gap column, an all-ambiguity column and a column with one residue
+    among gaps (its numerators are negative and, for 3 and 7 rows, no multiples of R) in each of 255 columns or more; a text of
+    one column is one of the three in turn (all-gap, all-ambiguity, one residue, one residue: the last two have 3 and 7 rows)."""
+    rng = random.Random(23)
+    out = []
+    for k, R in enumerate(PLANE_ROWS):
+        for W in PLANE_WIDTHS:
+            t = [[rng.choice("ACGT-RYKMSWN") for _ in range(W)] for _ in range(R)]
+            special = (["-"] * R, [rng.choice("RYKMSWN") for _ in range(R)], ["-"] * (R // 2) + [rng.choice("ACGT")] + ["-"] * (R - R // 2 - 1))
+            for j, col in ((0, special[min(k, 2)]),) if W == 1 else ((W // 2, special[0]), (W - 1, special[1]), (0, special[2])):
+                for r in range(R):
+                    t[r][j] = col[r]
+            out.append(tuple("".join(r) for r in t))
+    return out
+
+
+def check_planes_agree(be):
+    """The four producers of planes on plane_texts: mprg_align_profiles, mprg_prog_columns kind 0 and the plain-Python profile are
+    equal, kind 1 equals the plain-Python X tables; mprg_prog_columns_weighted gives both with weights 1, and with weights 1..5 the
+    unweighted planes of the text with row r written w_r times; mprg_refine_profiles, for every row of every text of two rows or
+    more, gives mprg_align_profiles of the text without it."""
+    from tests import collapse_common as cc                              # (it imports this module)
+    from tests import collapse_ref as cr
+    from tests import refine_common as rc
+    texts = plane_texts()
+    assert {(len(t), len(t[0])) for t in texts} == {(R, W) for R in PLANE_ROWS for W in PLANE_WIDTHS}
+    assert all(64 * (9 + 10 * (R - 1)) % R for R in (3, 7))                # a base against one other base among gaps: -64 (9 + 10 (R - 1)) / R
+    mats = [codes(t) for t in texts]
+
+    def planes(got):
+        status, raw, items = got
+        assert not any(status)
+        cols = raw.view(np.int32)
+        return [cols[o:o + (6 + kind) * W].reshape(6 + kind, W) for _, _, _, W, kind, o, *_ in items]
+    plain = planes(cc._columns(be, mats))
+    for k, t in enumerate(texts):
+        P, Dc, cx, Ic = pr.column_tables(t, t)
+        want = np.array([[p[x] for p in P] for x in "ACGTN"] + [Dc])
+        assert (plain[k] == want).all() and (rc.align_profiles(be, t) == want).all(), (len(t), len(t[0]))
+        assert (plain[len(texts) + k] == np.array([[c[x] for c in cx] for x in ("A", "C", "G", "T", "amb", "-")] + [Ic])).all(), (len(t), len(t[0]))
+    ones = planes(cc._columns(be, mats, [np.ones(len(t), np.int64) for t in texts]))
+    assert all((a == b).all() for a, b in zip(ones, plain))
+    rng = np.random.default_rng(29)
+    weights = [rng.integers(1, 6, len(t)) for t in texts]
+    got = planes(cc._columns(be, mats, weights))
+    want = planes(cc._columns(be, [codes(cr.expanded(t, w.tolist())) for t, w in zip(texts, weights)]))
+    assert all((a == b).all() for a, b in zip(got, want)) and any(int(w.sum()) > len(w) for w in weights)
+    msas = [list(t) for t in texts if len(t) >= 2]
+    d_text, nbytes, toff, R, W = rc.upload_msas(be, msas)
+    rtab, d_counts, _, n_cols, _, _ = sa.refine_counts(be, d_text, nbytes, toff, R, W)
+    row_locus, row_in = np.repeat(np.arange(len(msas)), R), np.concatenate([np.arange(n) for n in R])
+    d_prof, poff, words = sa.refine_profiles(be, d_text, nbytes, rtab, d_counts, n_cols, row_locus, row_in)
+    prof = be.download(d_prof, np.int32, words)
+    for k, r, p in zip(row_locus.tolist(), row_in.tolist(), poff.tolist()):
+        m = msas[k]
+        assert (prof[p:p + 6 * len(m[0])].reshape(6, -1) == rc.align_profiles(be, m[:r] + m[r + 1:])).all(), (len(m), len(m[0]), r)
+
+
 def msa_loci():
     """Edge, special, random and the 18 table loci: balanced trees and caterpillars, one to several rounds."""
     return sr.edge_loci() + rr.special_loci() + sr.random_loci(3) + sr.random_loci(21, 20) + pr.table_loci()

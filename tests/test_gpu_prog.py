@@ -49,6 +49,10 @@ def test_columns_of_tall_texts(backend):
     pc.check_tall_columns(backend)
 
 
+def test_planes_agree(backend):
+    pc.check_planes_agree(backend)
+
+
 def test_msas_equal_the_spec(backend):
     pc.check_msas(backend)
 

@@ -118,6 +118,10 @@ def test_columns_of_tall_texts(emu):
     pc.check_tall_columns(emu)
 
 
+def test_planes_agree(emu):
+    pc.check_planes_agree(emu)
+
+
 def test_distances_equal_the_spec(emu):
     pc.check_distances(emu, sr.edge_loci() + rr.special_loci() + sr.random_loci(5, 25))
 
