@@ -306,6 +306,19 @@ int mprg_cluster_further_bounded(const uint8_t *arena, const int64_t *views, con
                                  const int32_t *work_cols, int n_work_cols, const int32_t *work_rows, int n_work_rows,
                                  int32_t *scratch, int32_t *out_further, const double *km_info, const uint8_t *gcodes, const int32_t *kinfo,
                                  long long max_rows, void *stream);
+/* mprg_cluster_further_bounded given mprg_ungap_dedupe's rep_g for the same `views` table (rep_g[row_off + i]: the smallest row
+ * position of the view whose gapped content is row i's; NULL: as mprg_cluster_further_bounded).  Rows of one gapped class share their
+ * distinct sequence — hence their cluster —, their symbol in every column and their distance to any string: each class is walked ONCE, by
+ * its representative (rep_g == own position), and counts with its size; the smallest tie-break key of a class is its representative's.
+ * out_further, assign and the majority strings are what the other two entry points give (integer counts: bit for bit).  Problems of more
+ * than MPRG_CF_ROWS rows take the same wide launch as there (every row), only their distance check leaves the copies out.  The
+ * one-workgroup form keeps 4 more bytes of LDS per row, so a few views just inside its bound go to the tiled launches instead.
+ * MPRG_CF_CLASSES=0 in the environment (read once at load): rep_g is ignored here and in mprg_forest_level. */
+int mprg_cluster_further_classes(const uint8_t *arena, const int64_t *views, const int32_t *rowidx, const int64_t *prob,
+                                 int n_probs, int k, const int32_t *d_of_row, const int32_t *labels, int32_t *assign,
+                                 const int32_t *work_cols, int n_work_cols, const int32_t *work_rows, int n_work_rows,
+                                 int32_t *scratch, int32_t *out_further, const double *km_info, const uint8_t *gcodes, const int32_t *kinfo,
+                                 long long max_rows, const int32_t *rep_g, void *stream);
 
 /* A11 + A10 + A12 as ONE launch per workgroup form — cluster_sequences.py:256-274, the whole loop
  *     while cluster_further(...): num_clusters += 1; KMeans(num_clusters).fit(X).predict(X); accept / revert

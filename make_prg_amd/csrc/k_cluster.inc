@@ -37,7 +37,18 @@ MPRG_DEV long long cf_lds_bytes(long long S, long long n, long long k) {
   const long long cp = (n + 3) & ~3LL;
   return ((S + 3) & ~3LL) + ((2 * S + 3) & ~3LL) + k * cp + S * cp;
 }
-MPRG_DEV bool cf_one_fits(long long S, long long n, long long k) { return S >= 1 && S < 65536 && n >= 1 && cf_lds_bytes(S, n, k) <= CFO_POOL; }
+// (cls: the launch was given rep_g — the one-workgroup form then keeps a class size and a list entry per row, 4 S bytes more)
+MPRG_DEV long long cf_lds_bytes_cls(long long S, long long n, long long k) { return cf_lds_bytes(S, n, k) + 4 * S; }
+MPRG_DEV bool cf_one_fits(long long S, long long n, long long k, bool cls = false) {
+  return S >= 1 && S < 65536 && n >= 1 && (cls ? cf_lds_bytes_cls(S, n, k) : cf_lds_bytes(S, n, k)) <= CFO_POOL;
+}
+// rep_g (optional, all three kernels; mprg_ungap_dedupe's table: the smallest row of the view with identical gapped content): rows of one
+// gapped class share their cluster, their symbol in every column and their distance to any string, so a class is counted ONCE, by its
+// representative (rep_g[i] == i) and with its size as weight; null: every row for itself
+MPRG_DEV int cf_rep(const int32_t *rep_g, long long i) {
+  const int r = rep_g ? rep_g[i] : (int)i;
+  return (unsigned)r > (unsigned)i ? (int)i : r;       // (a representative is the smallest row of its class: never beyond the row)
+}
 #ifndef CF_THREADS
 #define CF_THREADS 128                 // threads of a k_cluster_majority workgroup: a narrow problem offers k x columns ~ 100 items
 #endif
@@ -45,15 +56,17 @@ MPRG_DEV bool cf_one_fits(long long S, long long n, long long k) { return S >= 1
 // problem of more than CF_ROWS rows, which k_cluster_majority_big below takes); thread = (cluster,
 // column, slice of rows), the cluster's rows of the row-major copy walked in order (coalesced across the columns); per-thread
 // symbol counters live in LDS ([symbol][thread]: conflict-free).
+static_assert(12 * CF_THREADS >= CF_ROWS && (long long)CF_ROWS * CF_ROWS <= (1 << 20), "class sizes per row in `first`; key below 2^20, size above");
 KERNEL(k_cluster_majority, const uint8_t *arena, const int64_t *views, const int32_t *rowidx, const int64_t *prob_all,
        const int32_t *work, int k, const int32_t *d_of_row_all, const int32_t *labels_all, int32_t *assign_all,
-       const double *km_info, int32_t *scratch_all, const uint8_t *gcodes_all, const int32_t *kinfo, int one_form, DsCount dc) {
+       const double *km_info, int32_t *scratch_all, const uint8_t *gcodes_all, const int32_t *kinfo, int one_form, const int32_t *rep_g_all,
+       DsCount dc) {
   DS_GUARD(dc, 1);
   const int32_t *wk = work + 2 * (long long)BLOCK_ID;
   if (kinfo && kinfo[5 * (long long)wk[0] + 1] == 0) return;      // this problem sat the round out (k_kl_advance)
   const int64_t *P = prob_all + (long long)wk[0] * PF;
   const ViewD d = load_view(views, (int)P[0]);
-  if (one_form && cf_one_fits(d.n_rows, d.n_cols, k)) return;     // k_cluster_further_one's
+  if (one_form && cf_one_fits(d.n_rows, d.n_cols, k, rep_g_all != nullptr)) return;     // k_cluster_further_one's
   const int n = d.n_cols, S = d.n_rows, D = (int)P[1], tile = S > CF_ROWS ? CF_TILE_BIG : CF_TILE, c0 = wk[1] * tile;
   const int32_t *dor = d_of_row_all + d.row_off;
   const int32_t *labels = labels_all ? labels_all + P[10] : nullptr;      // null: one cluster holding every member
@@ -68,17 +81,23 @@ KERNEL(k_cluster_majority, const uint8_t *arena, const int64_t *views, const int
   if (S > CF_ROWS) return;                                        // k_cluster_majority_big's (the launch behind this one; 32-column tiles)
   // member rows bucketed by cluster once per workgroup (LDS): each cluster pass then touches only its own rows and can
   // keep several cell loads in flight.  Order inside a bucket is irrelevant: ties go to the smallest key.
+  // rep_g: only the representatives are filed; the class sizes add up in `first` (free until the passes below), one entry per row
+  const int32_t *rg = rep_g_all ? rep_g_all + d.row_off : nullptr;
   SHARED(int32_t, mrk, 2 * CF_ROWS);
   int32_t *mrow = mrk, *mkey = mrk + CF_ROWS;
   SHARED(int, coff, 16);
   SHARED(int, cfill, 16);
   PAR_FOR(q, 16) { coff[q] = 0; }
+  if (rg) { PAR_FOR(i, S) { first[i] = 0; } }
   BARRIER();
   PAR_FOR(i, S) {
     const int dd = dor[i];
     if (dd < 0) continue;
     const int cl = labels ? labels[dd] : 0;
-    if (cl >= 0 && cl < k) ATOMIC_ADD(coff + cl + 1, 1);
+    if (cl < 0 || cl >= k) continue;
+    const int r = cf_rep(rg, i);
+    if (r == (int)i) ATOMIC_ADD(coff + cl + 1, 1);
+    if (rg) ATOMIC_ADD(first + r, 1);
   }
   BARRIER();
   ONE_THREAD { for (int q = 1; q <= k; ++q) coff[q] += coff[q - 1]; for (int q = 0; q < k; ++q) cfill[q] = coff[q]; }
@@ -87,13 +106,15 @@ KERNEL(k_cluster_majority, const uint8_t *arena, const int64_t *views, const int
     const int dd = dor[i];
     if (dd < 0) continue;
     const int cl = labels ? labels[dd] : 0;
-    if (cl < 0 || cl >= k) continue;
+    if (cl < 0 || cl >= k || cf_rep(rg, i) != (int)i) continue;
     const int pos = ATOMIC_ADD(cfill + cl, 1);
     mrow[pos] = gcodes_all ? (int)i : view_row(d, rowidx, i);     // dense copy: rows by their position in the view
-    mkey[pos] = dd * S + i;              // the reference lists a cluster's rows by distinct sequence, then row (S <= CF_ROWS: 32 bits hold it)
+    // the reference lists a cluster's rows by distinct sequence, then row (S <= CF_ROWS: the key is below 2^20); above it the rows the entry counts for
+    mkey[pos] = (dd * S + (int)i) | ((rg ? first[i] : 1) << 20);
   }
   BARRIER();
-#define CF_COUNT(x, key) do { if ((x) < 12) { cnt[(x) * CF_THREADS + t] += 1; if ((key) < first[(x) * CF_THREADS + t]) first[(x) * CF_THREADS + t] = (key); } } while (0)
+#define CF_COUNT(x, kw) do { if ((x) < 12) { cnt[(x) * CF_THREADS + t] += (uint32_t)(kw) >> 20; const int32_t key_ = (kw) & 0xfffff; \
+                                             if (key_ < first[(x) * CF_THREADS + t]) first[(x) * CF_THREADS + t] = key_; } } while (0)
   // work item = (cluster, column of the tile, slice of the cluster's rows): clustered sub-alignments are a few dozen columns
   // wide, so columns alone would leave most of the workgroup idle while it walks the clusters — and, before the first
   // KMeans round (k = 1), every row of the view — one after the other.  Slices (only when all items fit one pass) count in
@@ -224,13 +245,14 @@ KERNEL(k_cluster_majority_big, const uint8_t *arena, const int64_t *views, const
 // row is farther than the one-reference-like threshold.
 KERNEL(k_cluster_hamming, const uint8_t *arena, const int64_t *views, const int32_t *rowidx, const int64_t *prob_all,
        const int32_t *work, const int32_t *d_of_row_all, const int32_t *labels_all, const int32_t *scratch_all,
-       int32_t *out_further, const uint8_t *gcodes_all, const int32_t *kinfo, int one_form_k, DsCount dc) {
+       int32_t *out_further, const uint8_t *gcodes_all, const int32_t *kinfo, int one_form_k, const int32_t *rep_g_all, DsCount dc) {
   DS_GUARD(dc, 1);
   const int32_t *wk = work + 2 * (long long)BLOCK_ID;
   if (kinfo && kinfo[5 * (long long)wk[0] + 1] == 0) return;
   const int64_t *P = prob_all + (long long)wk[0] * PF;
   const ViewD d = load_view(views, (int)P[0]);
-  if (one_form_k && cf_one_fits(d.n_rows, d.n_cols, one_form_k)) return;     // (one_form_k: the round's k when the one-workgroup form is on)
+  if (one_form_k && cf_one_fits(d.n_rows, d.n_cols, one_form_k, rep_g_all != nullptr)) return;     // (one_form_k: the round's k when the one-workgroup form is on)
+  const int32_t *rg = rep_g_all ? rep_g_all + d.row_off : nullptr;      // a row that is not its class's representative has nothing to decide
   const int n = d.n_cols, S = d.n_rows, chunk = cf_chunk_rows(n, S), r0 = wk[1] * chunk;
   const int32_t *dor = d_of_row_all + d.row_off;
   const int32_t *labels = labels_all ? labels_all + P[10] : nullptr;
@@ -246,7 +268,7 @@ KERNEL(k_cluster_hamming, const uint8_t *arena, const int64_t *views, const int3
       const int i = ib + (int)threadIdx.x / CFH_G;
       int stop = (gl == 0) ? *(volatile int32_t *)(out_further + wk[0]) : 0;
       stop = __shfl(stop, 0, CFH_G);
-      const int dd = (i < S && i < r0 + chunk) ? dor[i] : -1;
+      const int dd = (i < S && i < r0 + chunk && cf_rep(rg, i) == i) ? dor[i] : -1;
       const bool active = !stop && dd >= 0;             // (uniform per group; every lane runs the loop: its votes and shuffles are wave-wide)
       const int cl = (active && labels) ? labels[dd] : 0;
       const uint8_t *m = maj + (long long)cl * n;
@@ -281,7 +303,7 @@ KERNEL(k_cluster_hamming, const uint8_t *arena, const int64_t *views, const int3
   }
   PAR_FOR(t, chunk) {
     const int i = r0 + (int)t;
-    if (i >= S) continue;
+    if (i >= S || cf_rep(rg, i) != i) continue;
     const int dd = dor[i];
     if (dd < 0) continue;
     const int cl = labels ? labels[dd] : 0;

@@ -51,6 +51,12 @@ template <int FB> struct CfWords {
 #pragma unroll
     for (int q = 0; q < W; ++q) w[q] += sel == (unsigned)q ? inc : 0ull;
   }
+  MPRG_DEVM void addw(unsigned x, unsigned wgt) {        // the same for a row that stands for wgt identical rows
+    const unsigned long long inc = x < 12 ? (unsigned long long)wgt << (FB * (x % PER)) : 0ull;
+    const unsigned sel = x / PER;
+#pragma unroll
+    for (int q = 0; q < W; ++q) w[q] += sel == (unsigned)q ? inc : 0ull;
+  }
   MPRG_DEVM unsigned long long count(int s) const {      // s: compile-time after unrolling
     return (w[s / PER] >> (FB * (s % PER))) & ((FB == 32) ? 0xffffffffull : 0xffffull);
   }
@@ -172,12 +178,98 @@ KL_CF_FN bool cf_problem_fb(const int S, const int n, const int D, const int k, 
 // (cf_lds_bytes: k_cluster.inc)
 // OPT (mprg_cluster_further's one-workgroup launch only; the fused loops instantiate it without, unchanged): labels may be null — one
 // cluster holding every member, the k = 1 check — and assign may be null (the fit was not accepted: nothing to copy)
-template <bool OPT = false>
+// CLS (the same launch, given mprg_ungap_dedupe's rep_g: the smallest row of the view with identical gapped content): rows of one gapped
+// class share their distinct sequence — hence their cluster —, their symbol in every column and their distance to any string, so only
+// the REPRESENTATIVES (rep_g[i] == i) are listed, staged and walked, each counting for its class's size: a column's counts are sums of
+// class sizes, the tie-break's smallest key (distinct sequence, row) is a representative's — the smallest row of its class —, and
+// "some row is too far" is decided by the representatives.  A pan-genome view of ~100 rows holds ~16 such classes.  Tables: the row's
+// distinct-sequence index widens to 32 bits (class size in the high half, LDS atomics) and a 16-bit list of the representatives'
+// rows follows it: 4 S bytes more (cf_lds_bytes_cls); flag_s[1] counts the list.
+template <bool OPT = false, bool CLS = false>
 MPRG_DEV bool cf_problem_lds(const int S, const int n, const int D, const int k, const int32_t *dor, const int32_t *labels, int32_t *assign,
-                             const uint8_t *G, uint8_t *pool, int *flag_s) {
+                             const uint8_t *G, uint8_t *pool, int *flag_s, const int32_t *rep_g = nullptr) {
   typedef CfWords<16> Words;
   const int cpitch = u_pitch(n), cp = (n + 3) & ~3, cw4 = cp >> 2;
   uint8_t *mlab = pool;
+  if constexpr (CLS) {
+    uint32_t *dkw = (uint32_t *)(pool + ((S + 3) & ~3));
+    uint16_t *list = (uint16_t *)(dkw + S);
+    uint8_t *majs = (uint8_t *)list + ((2 * S + 3) & ~3);
+    uint8_t *cells = majs + k * cp;
+    if (assign) { PAR_FOR(q, D) { assign[q] = labels[q]; } }
+    PAR_FOR(i, S) { const int dd = dor[i]; mlab[i] = dd < 0 ? (uint8_t)255 : (!labels ? (uint8_t)0 : (uint8_t)labels[dd]); dkw[i] = (uint32_t)dd & 0xffffu; }
+    ONE_THREAD { flag_s[0] = 0; flag_s[1] = 0; }
+    BARRIER();
+    PAR_FOR(i, S) {
+      int r = rep_g[i];
+      if ((unsigned)r > (unsigned)i) r = (int)i;                       // (a representative is the smallest row of its class: never beyond the row)
+      atomicAdd(dkw + r, 0x10000u);
+      if (r == (int)i) list[atomicAdd(flag_s + 1, 1)] = (uint16_t)i;   // (any order: counts add, the smallest key wins, the flag only goes 0 -> 1)
+    }
+    BARRIER();
+    const int R = flag_s[1];
+    PAR_FOR(e, R * cw4) {                                              // representative j's cells at cells + j * cp
+      const int j = (int)((unsigned)e / (unsigned)cw4), w = (int)((unsigned)e % (unsigned)cw4);
+      *(uint32_t *)(cells + j * cp + 4 * w) = *(const uint32_t *)(G + (long long)list[j] * cpitch + 4 * w) & 0x0f0f0f0fu;
+    }
+    BARRIER();
+    PAR_FOR(item, k * n) {
+      const int cl = (int)((unsigned)item / (unsigned)n), c = (int)((unsigned)item % (unsigned)n);
+      Words cw;
+      cw.clear();
+      const uint8_t *col = cells + c;
+      int j = 0;
+      for (; j + 4 <= R; j += 4) {
+        unsigned ri[4], rc[4], wt[4], x[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { ri[q] = list[j + q]; x[q] = col[(j + q) * cp]; }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { rc[q] = mlab[ri[q]]; wt[q] = dkw[ri[q]] >> 16; }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) cw.addw(rc[q] == (unsigned)cl ? x[q] : 15u, wt[q]);
+      }
+      for (; j < R; ++j) { const int i = list[j]; cw.addw(mlab[i] == cl ? (unsigned)col[j * cp] : 15u, dkw[i] >> 16); }
+      unsigned long long best_n = 0;
+#pragma unroll
+      for (int s_ = 0; s_ < 12; ++s_) { const unsigned long long a = cw.count(s_); best_n = a > best_n ? a : best_n; }
+      unsigned tied = 0;
+#pragma unroll
+      for (int s_ = 0; s_ < 12; ++s_) if (cw.count(s_) == best_n) tied |= 1u << s_;
+      int best = __ffs(tied) - 1;
+      if (best_n > 0 && (tied & (tied - 1))) {                         // several symbols share the maximum: the one seen first wins
+        int best_key = 0x7fffffff;
+#pragma nounroll
+        for (int r = 0; r < R; ++r) {
+          const unsigned x = col[r * cp];
+          const int i = list[r];
+          if (mlab[i] != cl || !((tied >> x) & 1u)) continue;
+          const int key = (int)(dkw[i] & 0xffffu) * S + i;
+          if (key < best_key) { best_key = key; best = (int)x; }
+        }
+      }
+      majs[cl * cp + c] = (uint8_t)best;
+    }
+    BARRIER();
+    const int thresh = n < 5 ? 1 : (int)(0.2 * (double)n);
+    PAR_FOR(j, R) {
+      const int cl = mlab[list[j]];
+      if (cl == 255) continue;
+      const uint8_t *m = majs + cl * cp, *row = cells + j * cp;
+      int dist = 0;
+#pragma nounroll
+      for (int c = 0; c < n; c += 4) {
+        uint32_t v = *(const uint32_t *)(row + c) ^ *(const uint32_t *)(m + c);
+        if (c + 4 > n) v &= 0xffffffffu >> (8 * (c + 4 - n));
+        const uint32_t nz = (((v & 0x7f7f7f7fu) + 0x7f7f7f7fu) | v) & 0x80808080u;
+        dist += __popc(nz);
+      }
+      if (dist > thresh) flag_s[0] = 1;
+    }
+    BARRIER();
+    const bool further = flag_s[0] != 0;
+    BARRIER();
+    return further;
+  }
   uint16_t *dk = (uint16_t *)(pool + ((S + 3) & ~3));
   uint8_t *majs = (uint8_t *)dk + ((2 * S + 3) & ~3);
   uint8_t *cells = majs + k * cp;
@@ -444,18 +536,20 @@ __attribute__((amdgpu_flat_work_group_size(64, 1024), amdgpu_waves_per_eu(KM_WAV
 //      The two-launch kernels leave these problems alone (cf_one_fits, same rule on both sides).
 KERNEL(k_cluster_further_one, const int64_t *views, const int64_t *prob_all, int n_probs, int k, const int32_t *d_of_row_all,
        const int32_t *labels_all, int32_t *assign_all, const double *km_info, int32_t *out_further, const uint8_t *gcodes_all,
-       const int32_t *kinfo, DsCount dc) {
+       const int32_t *kinfo, const int32_t *rep_g_all, DsCount dc) {
   DS_GUARD(dc, 1);
   const int b = BLOCK_ID;
   if (kinfo && kinfo[5 * (long long)b + 1] == 0) return;          // this problem sat the round out (k_kl_advance)
   const int64_t *P = prob_all + (long long)b * PF;
   const ViewD d = load_view(views, (int)P[0]);
-  if (!cf_one_fits(d.n_rows, d.n_cols, k)) return;
+  if (!cf_one_fits(d.n_rows, d.n_cols, k, rep_g_all != nullptr)) return;
   __shared__ __attribute__((aligned(16))) uint8_t pool[CFO_POOL];
-  SHARED(int, flag, 1);
+  SHARED(int, flag, 2);                                           // 0 some row is too far, 1 representatives listed (rep_g)
   const int32_t *labels = labels_all ? labels_all + P[10] : nullptr;
   // accepted fit: its labels become the problem's assignment (a fit with fewer than k distinct labels is not: cluster_sequences.py:267-273)
   int32_t *assign = (labels && assign_all && (!km_info || km_info[8 * (long long)b + 3] >= (double)k)) ? assign_all + P[10] : nullptr;
-  const bool further = cf_problem_lds<true>(d.n_rows, d.n_cols, (int)P[1], k, d_of_row_all + d.row_off, labels, assign, gcodes_all + d.aux0, pool, flag);
+  const bool further = rep_g_all ? cf_problem_lds<true, true>(d.n_rows, d.n_cols, (int)P[1], k, d_of_row_all + d.row_off, labels, assign, gcodes_all + d.aux0,
+                                                              pool, flag, rep_g_all + d.row_off)
+                                 : cf_problem_lds<true>(d.n_rows, d.n_cols, (int)P[1], k, d_of_row_all + d.row_off, labels, assign, gcodes_all + d.aux0, pool, flag);
   ONE_THREAD { out_further[b] = further ? 1 : 0; }
 }

@@ -943,10 +943,11 @@ class ForestEngine(BatchEngine):
         be = self.be
         p = lambda b: (b if isinstance(b, int) else be.ptr(b)) if b is not None else None          # (a buffer, or an address inside one)
         # (no view has more rows than the forest's largest root: the launch that only tall problems need is left out below that)
-        be.call("mprg_cluster_further_bounded", be.ptr(self.d_arena), be.ptr(d_sub), be.ptr(self.d_pool), be.ptr(d_prob), n_probs, k,
+        # (rep_g: a class of identical gapped rows is walked once and counts with its size)
+        be.call("mprg_cluster_further_classes", be.ptr(self.d_arena), be.ptr(d_sub), be.ptr(self.d_pool), be.ptr(d_prob), n_probs, k,
                 be.ptr(dd["d_of_row"]), p(d_labels), p(d_assign), be.ptr(d_wc), n_wc, be.ptr(d_wr), n_wr, be.ptr(d_scratch),
-                be.ptr(d_further), p(d_info), be.ptr(dd["gcodes"]), p(d_kinfo), int(self.F[FI["MAX_ROWS"]]), be.stream, work=work,
-                label="mprg_cluster_further")
+                be.ptr(d_further), p(d_info), be.ptr(dd["gcodes"]), p(d_kinfo), int(self.F[FI["MAX_ROWS"]]), be.ptr(dd["rep_g"]), be.stream,
+                work=work, label="mprg_cluster_further")
         self.counters["launches"] += 2
 
     # ------------------------------------------------------------------------------------------------ host views of the tables
