@@ -36,7 +36,10 @@ enum {
 };
 enum { MPRG_CODE_GAP = 4, MPRG_CODE_N = 11, MPRG_N_CODES = 12 };
 enum { MPRG_IV_MATCH = 0, MPRG_IV_NONMATCH = 1 /* bit 0 of a triple's type word */,
-       MPRG_IV_PURE = 2 /* bit 1: match interval straight from the scan, view without N / ambiguity codes */ };
+       MPRG_IV_PURE = 2 /* bit 1: match interval straight from the scan, view without N / ambiguity codes */,
+       MPRG_IV_SELF = 4 /* bit 2: non-match interval of such a view (with rows, taken through the LDS paths) whose columns, as a view
+                         * of their own with the same rows, partition into exactly one non-match interval: themselves.  Bits 1 and 2
+                         * are hints for a host that recurses on the device; a reader of the interval's type masks `& 1` */ };
 /* per-view status bits written by mprg_partition */
 enum { MPRG_ST_PARTITION_ERROR = 1, MPRG_ST_ALL_N_SLICE = 2,
        MPRG_ST_BAD_LAUNCH = 4 /* a view of fused_list does not satisfy the fused launch shape: a host error, not a property of the data */ };
@@ -102,7 +105,12 @@ int mprg_compact_columns(const uint8_t *arena, const int64_t *views, const int32
  *      are SMALL — at most 512 rows and 1024 columns, rows x pitch <= 8192 bytes (pitch = columns rounded up to 4, +4
  *      if that is an even number of words), columns / max(min_match_length - 1, 1) + 4 <= 128 — and are handled by one
  *      workgroup each that holds the view's cells in LDS and computes their column masks and gap runs itself: they
- *      need NO work items in mprg_column_masks, none in work_rows here, and no scratch. */
+ *      need NO work items in mprg_column_masks, none in work_rows here, and no scratch.  With view_out set the lists may leave views out (the
+ *      forest's MPRG_NF_SELF nodes): no kernel visits such a view, it needs no column slots, and its n_iv, status and view_out
+ *      words must arrive ZEROED — the packed list's two launches read them for every view.
+ * type word of a triple: bit 0 MPRG_IV_NONMATCH; bit 1 MPRG_IV_PURE and bit 2 MPRG_IV_SELF are hints (see the enum); bit 2 is written
+ *      only by the paths that keep a view's non-match flags in LDS (every fused view; other views of at most 16 384 columns with
+ *      columns / max(min_match_length - 1, 1) + 4 <= 512): a wider view gives no hint. */
 int mprg_partition(const uint8_t *arena, const int64_t *views, const int32_t *rowidx, int n_views,
                    const uint32_t *mask, int min_match_length, const int32_t *work_rows, int n_work_rows,
                    uint32_t *maxrun, int32_t *stack, int32_t *ivflag, int32_t *iv, int32_t *n_iv, int32_t *status,
@@ -404,7 +412,9 @@ enum {
 enum { MPRG_KIND_LEAF = 0, MPRG_KIND_INTERVAL = 1, MPRG_KIND_CLUSTER = 2 };
 enum { MPRG_NF_PURE = 1 /* match interval of a view without N / ambiguity codes: a one-allele leaf, no kernel visits it */,
        MPRG_NF_SPECIAL = 2 /* its columns hold N or ambiguity codes */, MPRG_NF_FORCED = 4 /* tree root: never a cluster node */,
-       MPRG_NF_CAND = 8, MPRG_NF_DLEAF = 16, MPRG_NF_PQ = 32 };
+       MPRG_NF_CAND = 8, MPRG_NF_DLEAF = 16, MPRG_NF_PQ = 32,
+       MPRG_NF_SELF = 64 /* non-match interval whose own partition is known to be itself (MPRG_IV_SELF): it gets a view, but no column
+                          * slots, no place in the partition lists and no mask / gap-run work items; S2 takes one non-match interval */ };
 enum { MPRG_ASM_SIZE = 0, MPRG_ASM_PRE = 1 /* node id */, MPRG_ASM_SITE = 2, MPRG_ASM_TOTAL = 3, MPRG_ASM_START = 4,
        MPRG_ASM_NSEQ = 5, MPRG_ASM_ACHARS = 6, MPRG_ASM_JOB = 7, MPRG_ASM_FIELDS = 8 };
 enum { MPRG_FOREST_VALS_COLS = 16, MPRG_FOREST_HDR = 96 };
@@ -471,7 +481,8 @@ enum {
  * MPRG_FOREST_HDR words — block s at MPRG_DS_GLOBAL + (6 l + s) * MPRG_FOREST_HDR — that receive what the steps' headers hold
  * in the per-step form (frontier block: words 13 / 14 = first node / nodes of the level's frontier; sizes block: the
  * mprg_cluster_loop statistics, words 80 ..).  Buffers that must arrive zeroed: MPRG_F_MASK, _MAXRUN, _IVFLAG, _IVC, _X, _ASSIGN,
- * _KM_STATUS.  The clustering loop is the fused one (mprg_cluster_loop, forms MPRG_F_LOOP_FORMS). */
+ * _KM_STATUS, and _NIV, _STATUS, _VIEW_OUT (the views of MPRG_NF_SELF nodes: no partition kernel writes their words).  MPRG_F_FUSED_LIST
+ * and MPRG_F_OTHER_LIST are always set (the partition kernels go by the lists alone).  The clustering loop is the fused one (mprg_cluster_loop, forms MPRG_F_LOOP_FORMS). */
 enum { MPRG_DS_OVERFLOW = 0 /* 0, or 100 * (level + 1) + the step whose totals did not fit */, MPRG_DS_F0 = 1, MPRG_DS_N = 2,
        MPRG_DS_NNODES = 3, MPRG_DS_POOL_USED = 4, MPRG_DS_LEVEL = 5 /* levels enqueued so far */,
        MPRG_DS_NFAILED = 6 /* set when a view's partition failed (its locus is dropped: MPRG_F_FAILED, MPRG_F_ERR_FIRST) */, MPRG_DS_GLOBAL = 16,
@@ -490,13 +501,17 @@ int mprg_forest_state_rewind(int64_t *ds, long long n_words, long long level, vo
 int mprg_forest_state_init(int64_t *ds, long long n_words, long long n_roots, void *stream);
 /* S1  frontier -> views.  hdr: 0 views, 1 their columns, 2 their rows, 3 fused views, 4 other views, 5-9 mask work items for
  *     row chunks of 1024/512/256/128/64 rows, 10 gap-run row chunks, 11 cells, 12 cells of the other views.  The host picks MPRG_F_RPC_IDX from 5-9, allocates
- *     and calls _fill: views, view2node, fused / other lists, work items of mprg_column_masks and mprg_partition. */
+ *     and calls _fill: views, view2node, fused / other lists, work items of mprg_column_masks and mprg_partition.  A node with
+ *     MPRG_NF_SELF counts in 0, 2 and 11 only: a view, but no columns, no list, no work items (mprg_partition then gets lists that leave
+ *     views out, and zeroed n_iv / status / view_out). */
 int mprg_forest_frontier_count(const int64_t *F, void *stream);
 int mprg_forest_frontier_fill(const int64_t *F, void *stream);
 /* S2  after mprg_partition (view_out, iv_packed): status -> failed loci; leaf / multi-interval / clustering candidate.
  *     hdr: 0 children of multi-interval nodes, 1 selected views (candidates + leaves with several distinct rows), 2 their rows,
  *     3 bytes of their ungapped rows, 4 their columns, 5 row chunks of mprg_ungap_dedupe, 6 their cells.  _children: the child nodes
- *     (at MPRG_F_N_NODES on), the selected views' table `sub`, selnode, the dedupe work items. */
+ *     (at MPRG_F_N_NODES on), the selected views' table `sub`, selnode, the dedupe work items.  A node with MPRG_NF_SELF is taken as one
+ *     non-match interval without its view_out words being read; _children sets MPRG_NF_PURE / MPRG_NF_SELF on the children from bits
+ *     1 / 2 of their triples' type words (MPRG_IV_SELF=0 in the environment, read once at load: bit 2 is ignored). */
 int mprg_forest_classify(const int64_t *F, void *stream);
 int mprg_forest_children(const int64_t *F, void *stream);
 /* S3  after mprg_ungap_dedupe (summary): leaf alleles of the selected views; candidates that go on (recursion_tree.py:538-556).

@@ -435,6 +435,7 @@ _rt_thread = __import__("threading").local()          # .device: the HIP device 
 class _RtEvent:
     def __init__(self, lib, timing: bool):
         self.lib = lib
+        self._pid = os.getpid()
         self.h = lib.mprg_rt_event_create(int(timing))
         if not self.h:
             raise MprgError(f"event: {lib.mprg_last_error().decode()}")
@@ -451,7 +452,8 @@ class _RtEvent:
 
     def __del__(self):
         try:
-            self.lib.mprg_rt_event_destroy(self.h)
+            if self._pid == os.getpid():          # (a forked child owns nothing of its parent's runtime: see HipRuntimeBackend.close)
+                self.lib.mprg_rt_event_destroy(self.h)
         except Exception:
             pass
 
@@ -466,6 +468,7 @@ class HipRuntimeBackend(_Base):
         if not os.path.exists(lib_path):
             raise MprgError(f"{lib_path} not found: build it with `python __graft_entry__.py build` (hipcc, gfx950)")
         self._free = None
+        self._pid = os.getpid()
         self.lib = bind(ctypes.CDLL(lib_path))
         n = self.lib.mprg_rt_device_count()
         if n <= 0:
@@ -601,6 +604,12 @@ class HipRuntimeBackend(_Base):
         page-locked block, the streams destroyed.  Buffers still referenced by the caller must not be used afterwards (their
         blocks are NOT freed: they were never returned to the free lists).  Idempotent; also run when the backend is collected."""
         if self._free is None:
+            return
+        if getattr(self, "_pid", None) != os.getpid():
+            # a process forked from the one that made this backend (a pool of host workers): its collector may find the backend among
+            # the garbage it inherited, but the streams and blocks are the parent's — a HIP call here faults (the runtime is not
+            # initialised in the child).  Nothing to give back.
+            self._free = None
             return
         try:
             self._on_device()

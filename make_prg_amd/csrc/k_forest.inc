@@ -18,7 +18,7 @@
 #define KF_VC MPRG_FOREST_VALS_COLS      // columns of a step's count table
 #define KF_HDR MPRG_FOREST_HDR          // int64 words of a step's header
 enum { NF_PURE = MPRG_NF_PURE, NF_SPECIAL = MPRG_NF_SPECIAL, NF_FORCED = MPRG_NF_FORCED, NF_CAND = MPRG_NF_CAND, NF_DLEAF = MPRG_NF_DLEAF,
-       NF_PQ = MPRG_NF_PQ };
+       NF_PQ = MPRG_NF_PQ, NF_SELF = MPRG_NF_SELF };
 #define NODE(nodes, i) ((nodes) + (long long)(i) * MPRG_NODE_FIELDS)
 #define KF_GID ((long long)blockIdx.x * blockDim.x + threadIdx.x)
 #define KF_GRID(n) (unsigned)(((long long)(n) + 255) / 256)
@@ -221,6 +221,11 @@ KERNEL(k_ds_advance, int64_t *ds, const int64_t *classify_block, const int64_t *
 // ---- S1  the frontier's views ----------------------------------------------------------------------------------------
 // A frontier node that is a match interval straight from its parent's scan (NF_PURE) needs no kernel: for the same rows
 // every column is one plain base, so it is a one-allele leaf (recursion_tree.py:414-420 would find one match interval).
+// A frontier node that is a non-match interval whose own scan the parent's partition kernel has already run (NF_SELF, from
+// MPRG_IV_SELF) needs no partition: the result is the one non-match interval (0, columns - 1).  It still gets a view — k_lv_sub, the
+// row groups and everything after them read it — but no column slots, no place in the fused / other lists and no mask / gap-run work
+// items: columns 1, 3-10 and 12 do not count it, 0, 2 and 11 do.  No partition kernel writes its n_iv / status / view_out words: the
+// hosts hand those buffers over zeroed (k_pack_scan, k_pack_copy and k_lv_status read them for every view), k_lv_classify goes by the flag.
 // columns: 0 active, 1 columns, 2 rows, 3 fused, 4 other, 5-9 mask items for row chunks of 1024/512/256/128/64, 10 gap-run
 // row chunks, 11 cells, 12 cells of the other (non-fused) views
 MPRG_DEV bool kf_is_fused(long long S, long long n, int L, int enabled) {
@@ -236,10 +241,10 @@ KERNEL(k_fr_count, const int64_t *nodes, long long f0, long long n, int L, int f
   if (dc.ds) f0 = dc.ds[MPRG_DS_F0];
   const int64_t *nd = NODE(nodes, f0 + j);
   const KfRow v = KF_ROW(vals, n, j);
-  const bool active = !(nd[MPRG_N_FLAGS] & NF_PURE);
+  const bool active = !(nd[MPRG_N_FLAGS] & NF_PURE), part = active && !(nd[MPRG_N_FLAGS] & NF_SELF);
   const long long S = nd[MPRG_N_NROWS], nc = nd[MPRG_N_NCOLS];
-  const bool fused = active && kf_is_fused(S, nc, L, fused_enabled), other = active && !fused;
-  v[0] = active; v[1] = active ? nc : 0; v[2] = active ? S : 0; v[3] = fused; v[4] = other;
+  const bool fused = part && kf_is_fused(S, nc, L, fused_enabled), other = part && !fused;
+  v[0] = active; v[1] = part ? nc : 0; v[2] = active ? S : 0; v[3] = fused; v[4] = other;
   const long long lead = nd[MPRG_N_COL0] % 4, ntile = (nc + lead + CM_TILE_COLS - 1) / CM_TILE_COLS;
   for (int q = 0; q < 5; ++q) { const long long rpc = 1024 >> q; v[5 + q] = other ? ntile * ((S + rpc - 1) / rpc) : 0; }
   v[10] = other ? gr_items(S, nc) : 0;
@@ -262,6 +267,7 @@ KERNEL(k_fr_fill, int64_t *nodes, long long f0, long long n, int L, int fused_en
   o[0] = M[0]; o[1] = M[1]; o[2] = M[2]; o[3] = M[3]; o[4] = nd[MPRG_N_ROWS_OFF]; o[5] = S; o[6] = nd[MPRG_N_COL0]; o[7] = nc;
   o[8] = v[1]; o[9] = v[2]; o[10] = 0; o[11] = 0;
   view2node[vi] = f0 + j;
+  if (nd[MPRG_N_FLAGS] & NF_SELF) return;
   if (kf_is_fused(S, nc, L, fused_enabled)) { fused_list[v[3]] = (int32_t)vi; return; }
   other_list[v[4]] = (int32_t)vi;
   const long long lead = nd[MPRG_N_COL0] % 4, ntile = (nc + lead + CM_TILE_COLS - 1) / CM_TILE_COLS, rpc = 1024 >> rpc_idx;
@@ -298,7 +304,8 @@ KERNEL(k_lv_classify, int64_t *nodes, long long f0, long long n, int lvl, const 
   const KfRow v = KF_ROW(vals, n, j);
   long long n_iv = 1; int first_type = 0, has_star = 0, special = 0;
   const long long vi = nd[MPRG_N_AUX];
-  if (vi >= 0) {
+  if (nd[MPRG_N_FLAGS] & NF_SELF) { n_iv = 1; first_type = 1; has_star = 1; special = 0; }      // (no partition kernel ran: k_fr_count)
+  else if (vi >= 0) {
     const int32_t *o = view_out + 8 * vi;
     // a leaf's rows are its alleles unless every column is one plain base in ALL of them: a column of one base and N is a match
     // column (N never counts towards the consensus), yet the rows with N are left out (or no row is left: the host's expansion raises)
@@ -312,13 +319,14 @@ KERNEL(k_lv_classify, int64_t *nodes, long long f0, long long n, int lvl, const 
   nd[MPRG_N_KIND] = is_interval ? MPRG_KIND_INTERVAL : MPRG_KIND_LEAF;
   nd[MPRG_N_FIRST_CHILD] = -1; nd[MPRG_N_NCHILD] = 0; nd[MPRG_N_LVL] = lvl; nd[MPRG_N_REPS_OFF] = -1; nd[MPRG_N_NSEQ] = 1;
   nd[MPRG_N_ACHARS] = nc;
-  nd[MPRG_N_FLAGS] = (nd[MPRG_N_FLAGS] & (NF_PURE | NF_FORCED)) | (special ? NF_SPECIAL : 0) | (is_cand ? NF_CAND : 0) | (dleaf ? NF_DLEAF : 0);
+  nd[MPRG_N_FLAGS] = (nd[MPRG_N_FLAGS] & (NF_PURE | NF_FORCED | NF_SELF)) | (special ? NF_SPECIAL : 0) | (is_cand ? NF_CAND : 0) | (dleaf ? NF_DLEAF : 0);
   v[0] = is_interval ? n_iv : 0; v[1] = sel; v[2] = sel ? S : 0; v[3] = sel ? S * u_pitch((int)nc) : 0; v[4] = sel ? nc : 0;
   v[5] = sel ? ug_chunks(S, nc) : 0; v[6] = sel ? S * nc : 0;
 }
 // children of multi-interval nodes: one child per interval, same rows (recursion_tree.py:439-451); a wavefront per node
+// (iv_self = 0: the MPRG_IV_SELF hints are ignored, every non-match child is partitioned)
 KERNEL(k_lv_children, int64_t *nodes, long long f0, long long n, long long child_base, const int64_t *vals,
-       const int32_t *view_out, const int32_t *iv_packed, DsCount dc) {
+       const int32_t *view_out, const int32_t *iv_packed, int iv_self, DsCount dc) {
   const long long j = (long long)BLOCK_ID * (N_THREADS / WAVE) + wave_id();
   if (j >= ds_n(dc, n)) return;
   if (dc.ds) { f0 = dc.ds[MPRG_DS_F0]; child_base = dc.ds[MPRG_DS_NNODES]; }
@@ -333,7 +341,7 @@ KERNEL(k_lv_children, int64_t *nodes, long long f0, long long n, long long child
     c[MPRG_N_MSA] = nd[MPRG_N_MSA]; c[MPRG_N_PARENT] = f0 + j; c[MPRG_N_LEVEL] = nd[MPRG_N_LEVEL];
     c[MPRG_N_ROWS_OFF] = nd[MPRG_N_ROWS_OFF]; c[MPRG_N_NROWS] = nd[MPRG_N_NROWS];
     c[MPRG_N_COL0] = nd[MPRG_N_COL0] + tr[3 * e]; c[MPRG_N_NCOLS] = tr[3 * e + 1] - tr[3 * e] + 1;
-    c[MPRG_N_FLAGS] = (tr[3 * e + 2] & 2) ? NF_PURE : 0;
+    c[MPRG_N_FLAGS] = (tr[3 * e + 2] & MPRG_IV_PURE) ? NF_PURE : (((tr[3 * e + 2] & MPRG_IV_SELF) && iv_self) ? NF_SELF : 0);
     c[MPRG_N_KIND] = MPRG_KIND_LEAF; c[MPRG_N_FIRST_CHILD] = -1; c[MPRG_N_NCHILD] = 0; c[MPRG_N_LVL] = -1; c[MPRG_N_REPS_OFF] = -1;
     c[MPRG_N_NSEQ] = 1; c[MPRG_N_ACHARS] = c[MPRG_N_NCOLS]; c[MPRG_N_AUX] = -1;
   }

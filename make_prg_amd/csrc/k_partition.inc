@@ -78,6 +78,98 @@ MPRG_DEV int pt_next_switch(const uint32_t *bits, int i, int n, bool cur) {
   }
   return n;
 }
+// The scan's closing rule (interval_partition.py _add_interval :143-185): close the run [cs, ce] of kind cur_non when the scan reaches
+// column i (`end`: i is the view's width).  Stated once for the two scans that run it — the view's own (pt_phases, stacks in LDS /
+// global scratch) and the hint scan of a non-match interval's columns (pt_scan_is_self, the stacks' tops in registers).  The user
+// defines the stacks: nm / nn (entries), PUSH_M / PUSH_N (s, e), PT_POP_N (s, e out), PT_TOP_M_LEN, PT_DROP_M, PT_SHRINK_TOP_M (its
+// end one column back), PT_GROW_TOP_N (its end x columns on), and PT_GAP_AT_CE: the longest all-gap row stretch ending at column ce.
+#define PT_CLOSE_RUN()                                                                                                  \
+        bool cont = false;                                                                                              \
+        int ns = 0, ne = 0;                                                                                             \
+        if (!cur_non) {                                                                                                 \
+          if (ce - cs + 1 < L) {                       /* short match: absorbed by a non-match interval */              \
+            if (nn > 0) { PT_POP_N(ns, ne); ne += (ce - cs + 1) + 1; }                                                  \
+            else { ns = cs; ne = ce + 1; }                                                                              \
+            if (end) { ne -= 1; PUSH_N(ns, ne); }                                                                       \
+            cont = true;                                                                                                \
+          } else PUSH_M(cs, ce);                                                                                        \
+        } else {                                                                                                        \
+          bool pushed = false;                                                                                          \
+          if (nm > 0 && PT_GAP_AT_CE >= (uint32_t)(ce - cs + 1)) {   /* has_empty_sequence(alignment, (cs, ce)) */      \
+            const int lm = PT_TOP_M_LEN();                                                                              \
+            if (lm - 1 < L) {                                                                                           \
+              PT_DROP_M(); cs -= lm;                                                                                    \
+              if (nn > 0) { PT_GROW_TOP_N(ce - cs + 1); pushed = true; }                                                \
+            } else { PT_SHRINK_TOP_M(); cs -= 1; }                                                                      \
+          }                                                                                                             \
+          if (!pushed) PUSH_N(cs, ce);                                                                                  \
+        }
+// MPRG_IV_SELF: would columns s..e of this view, taken as a view of their own with the same rows, partition into exactly themselves —
+// no match interval, one non-match interval (0, e - s)?  The scan of those columns is RUN (same closing rule, same n < L branch):
+// their consensus is this view's (nmz: non-match bytes of this view's columns), and has_empty_sequence(a, b) asks for a row that is
+// all gaps from a to b, which does not depend on where a view starts (maxrun[b] >= b - a + 1, maxrun this view's).  Only the top
+// PT_SELF_STACK entries of either stack are kept, in registers; a push beyond them answers "no".  (That "no" is the scan's answer
+// too: a non-match run always starts where the top match interval ends, and a match interval that has stayed after the probe of the
+// run behind it stays for good — a later probe spans that run as well, or, after PT_SHRINK_TOP_M, a match column, where no row holds
+// a gap — and two non-match intervals on the stack have such a match interval between them: a third entry on either stack means a
+// match interval is in the result.)
+// The walk goes from switch to switch of the consensus.  run_start / run_gap (may be null): the view's run lists (pt_phases, by_runs)
+// — the next switch and the gap stretch at a run's end are then one LDS read each instead of a walk over the run's columns and a
+// read of global memory: a root view's longest non-match interval spans hundreds of columns, and its lane holds up the workgroup.
+#define PT_SELF_STACK 2
+struct PtTops { int s0, e0, s1, e1; };
+MPRG_DEV bool pt_scan_is_self(const uint8_t *nmz, const uint32_t *maxrun, int s, int e, int L, const uint16_t *run_start,
+                              const uint16_t *run_gap, int R, int n) {
+  if (e < s) return false;
+  if (e - s + 1 < L) {                                // (every column goes to one interval: non-match if any column is)
+    bool any = false;
+    for (int c = s; c <= e; ++c) any = any || nmz[c] != 0;
+    return any;
+  }
+  int r = 0;                                          // by runs: the run that holds column `at`
+  if (run_start) {
+    int hi = R;                                       // (run_start[0] == 0 <= s)
+    while (hi - r > 1) { const int mid = (r + hi) >> 1; if ((int)run_start[mid] <= s) r = mid; else hi = mid; }
+  }
+  PtTops Ms = {0, 0, 0, 0}, Ns = {0, 0, 0, 0};
+  int nm = 0, nn = 0;
+#define PT_SELF_PUSH(T, cnt, s_, e_) do { if (cnt >= PT_SELF_STACK) return false; T.s1 = T.s0; T.e1 = T.e0; T.s0 = (s_); T.e0 = (e_); ++cnt; } while (0)
+#define PT_SELF_POP(T, cnt) do { T.s0 = T.s1; T.e0 = T.e1; --cnt; } while (0)
+#define PUSH_M(s_, e_) PT_SELF_PUSH(Ms, nm, s_, e_)
+#define PUSH_N(s_, e_) PT_SELF_PUSH(Ns, nn, s_, e_)
+#define PT_POP_N(s_, e_) do { (s_) = Ns.s0; (e_) = Ns.e0; PT_SELF_POP(Ns, nn); } while (0)
+#define PT_TOP_M_LEN() (Ms.e0 - Ms.s0 + 1)
+#define PT_DROP_M() PT_SELF_POP(Ms, nm)
+#define PT_SHRINK_TOP_M() (Ms.e0 -= 1)
+#define PT_GROW_TOP_N(x_) (Ns.e0 += (x_))
+#define PT_GAP_AT_CE (whole_run ? (uint32_t)run_gap[r] : maxrun[ce])
+  int cs = s, at = s;                                 // the open run starts at cs; `at`: a column of the consensus run it ends with
+  bool cur_non = nmz[s] != 0;
+  for (;;) {
+    int i;                                            // the next switch: first column of the next consensus run
+    if (run_start) i = r + 1 < R ? (int)run_start[r + 1] : n;
+    else { i = at + 1; while (i <= e && (nmz[i] != 0) == cur_non) ++i; }
+    const bool whole_run = run_start != nullptr && i <= e + 1;      // (the columns end inside a consensus run: its gap stretch is not the list's)
+    if (i > e + 1) i = e + 1;
+    const int ce = i - 1;
+    const bool end = (i == e + 1);
+    PT_CLOSE_RUN()
+    if (end) break;
+    cs = cont ? ns : i;                               // (cont: the short match run and the non-match run behind it go on as one open run)
+    cur_non = !cur_non; at = i; ++r;
+  }
+#undef PT_SELF_PUSH
+#undef PT_SELF_POP
+#undef PUSH_M
+#undef PUSH_N
+#undef PT_POP_N
+#undef PT_TOP_M_LEN
+#undef PT_DROP_M
+#undef PT_SHRINK_TOP_M
+#undef PT_GROW_TOP_N
+#undef PT_GAP_AT_CE
+  return nm == 0 && nn == 1 && Ns.s0 == s && Ns.e0 == e;
+}
 // WV: the phases run by ONE wavefront on its own (k_partition_wave: several small views per workgroup): the loops stride the 64
 // lanes, what the workgroup forms settle with a barrier is a wavefront-scope fence (WAVE_SYNC), "one thread" is lane 0.
 template <bool FAST, bool CL, bool WV = false>
@@ -141,28 +233,12 @@ MPRG_DEV void pt_phases(const uint8_t *arena, const ViewD &d, const int32_t *row
     int nm = 0, nn = 0;
 #define PUSH_M(s, e) do { Ms[2 * nm] = (s); Ms[2 * nm + 1] = (e); ++nm; } while (0)
 #define PUSH_N(s, e) do { Ns[2 * nn] = (s); Ns[2 * nn + 1] = (e); ++nn; } while (0)
-    // close the run [cs, ce] of kind cur_non when the scan reaches column i (== n: the end); see the reference
-#define PT_CLOSE_RUN()                                                                                                  \
-        bool cont = false;                                                                                              \
-        int ns = 0, ne = 0;                                                                                             \
-        if (!cur_non) {                                                                                                 \
-          if (ce - cs + 1 < L) {                       /* short match: absorbed by a non-match interval */              \
-            if (nn > 0) { --nn; ns = Ns[2 * nn]; ne = Ns[2 * nn + 1] + (ce - cs + 1) + 1; }                             \
-            else { ns = cs; ne = ce + 1; }                                                                              \
-            if (end) { ne -= 1; PUSH_N(ns, ne); }                                                                       \
-            cont = true;                                                                                                \
-          } else PUSH_M(cs, ce);                                                                                        \
-        } else {                                                                                                        \
-          bool pushed = false;                                                                                          \
-          if (nm > 0 && PT_GAP_AT_CE >= (uint32_t)(ce - cs + 1)) {   /* has_empty_sequence(alignment, (cs, ce)) */      \
-            const int lm = Ms[2 * (nm - 1) + 1] - Ms[2 * (nm - 1)] + 1;                                                 \
-            if (lm - 1 < L) {                                                                                           \
-              --nm; cs -= lm;                                                                                           \
-              if (nn > 0) { Ns[2 * (nn - 1) + 1] += ce - cs + 1; pushed = true; }                                       \
-            } else { Ms[2 * (nm - 1) + 1] -= 1; cs -= 1; }                                                              \
-          }                                                                                                             \
-          if (!pushed) PUSH_N(cs, ce);                                                                                  \
-        }
+    // (PT_CLOSE_RUN's stacks: the arrays Ms / Ns)
+#define PT_POP_N(s_, e_) do { --nn; (s_) = Ns[2 * nn]; (e_) = Ns[2 * nn + 1]; } while (0)
+#define PT_TOP_M_LEN() (Ms[2 * (nm - 1) + 1] - Ms[2 * (nm - 1)] + 1)
+#define PT_DROP_M() (--nm)
+#define PT_SHRINK_TOP_M() (Ms[2 * (nm - 1) + 1] -= 1)
+#define PT_GROW_TOP_N(x_) (Ns[2 * (nn - 1) + 1] += (x_))
     if (n < L) {
       if (n > 0) {
         bool any = false;
@@ -218,7 +294,11 @@ MPRG_DEV void pt_phases(const uint8_t *arena, const ViewD &d, const int32_t *row
         else { cs = i; ce = i; cur_non = t; }
       }
     }
-#undef PT_CLOSE_RUN
+#undef PT_POP_N
+#undef PT_TOP_M_LEN
+#undef PT_DROP_M
+#undef PT_SHRINK_TOP_M
+#undef PT_GROW_TOP_N
     sh[1] = nm; sh[2] = nn;
   }
   P_BAR();
@@ -292,7 +372,18 @@ MPRG_DEV void pt_phases(const uint8_t *arena, const ViewD &d, const int32_t *row
   // retyping decision per non-match interval: 0 match (one distinct sequence without ambiguity codes), 1 non-match,
   // 3 non-match and every row of the slice contained N; an alignment without rows skips the test (:201-202)
 #define NTYPE(j) (d.n_rows > 0 ? (ref_row[j] == 0x7fffffff ? 3 : (flag_multi[j] == 0 ? 0 : 1)) : 1)
-  if (FAST) { P_FOR(j, nn) { ntype_s[j] = NTYPE(j); } P_BAR(); }
+  // FAST, a thread per non-match interval: + MPRG_IV_SELF where the interval stays a non-match interval of a view with rows and
+  // without N / ambiguity codes (what `pure` asks below) and the scan of its own columns gives the interval back (the non-match
+  // bytes are still in nmz_s: the triples overwrite them only below).  The child node then needs no partition (k_forest.inc S1).
+  if (FAST) {
+    const bool hint = !(sh[4] || sh[5]) && d.n_rows > 0;
+    P_FOR(j, nn) {
+      int ty = NTYPE(j);
+      if (hint && ty == 1 && Ns[2 * j] >= 0 && Ns[2 * j + 1] < n && pt_scan_is_self(nmz_s, maxrun, Ns[2 * j], Ns[2 * j + 1], L, by_runs ? run_start : nullptr, run_gap, by_runs ? sh[6] : 0, n)) ty |= MPRG_IV_SELF;
+      ntype_s[j] = ty;
+    }
+    P_BAR();
+  }
   P_ONE {
     const int nm = sh[1];
     int status = 0, cnt = 0, expect = 0, im = 0, in = 0;
@@ -306,8 +397,8 @@ MPRG_DEV void pt_phases(const uint8_t *arena, const ViewD &d, const int32_t *row
       else {
         s = Ns[2 * in]; e = Ns[2 * in + 1];
         const int ty = FAST ? ntype_s[in] : NTYPE(in);
-        if (ty == 3) status |= 2;
-        type = ty & 1;
+        if ((ty & 3) == 3) status |= 2;
+        type = ty & (1 | MPRG_IV_SELF);
         ++in;
       }
       if (s != expect || e < s || e >= n) { status |= 1; break; }

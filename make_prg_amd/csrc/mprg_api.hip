@@ -77,6 +77,9 @@ static const int g_pw_wave = [] { const char *e = getenv("MPRG_WAVE_VIEWS"); ret
 static const int g_cf_classes = [] { const char *e = getenv("MPRG_CF_CLASSES"); return (e && atoi(e) == 0) ? 0 : 1; }();
 // same row phase for the small views' wavefronts (k_rows_wave); MPRG_ROW_VIEWS=0: the launches of the wider views / k_dedupe_wave for them
 static const int g_row_views = [] { const char *e = getenv("MPRG_ROW_VIEWS"); return (e && atoi(e) == 0) ? 0 : 1; }();
+// mprg_forest_children: a non-match interval that its parent's partition kernel found to partition into itself (MPRG_IV_SELF) becomes a
+// node no partition kernel visits (MPRG_NF_SELF); MPRG_IV_SELF=0: the hint is ignored (the partition kernels still write it)
+static const int g_iv_self = [] { const char *e = getenv("MPRG_IV_SELF"); return (e && atoi(e) == 0) ? 0 : 1; }();
 #define RV_THREADS 128                 // k_rows_narrow: ~100 rows are the rule (256 threads: no faster); k_rows_narrow_s: one wavefront, two rows per lane
 #define RV_THREADS_S 64
 
@@ -153,7 +156,10 @@ static int d_partition(const uint8_t *arena, const int64_t *views, const int32_t
                        DsCount dc_other) {
   if (n_views <= 0) return 0;
   if (!fused_list && !other_list) { n_fused = 0; n_other = n_views; }
-  else if (n_fused < 0 || n_other < 0 || (!dc_views.ds && n_fused + n_other != n_views)) return fail("mprg_partition: the two view lists must cover the views");
+  // (with view_out the lists may leave views out — the forest's MPRG_NF_SELF nodes: no kernel here visits those, and the packed list takes
+  //  the n_iv / view_out words they arrived with, zeroed by the caller; a plain call's lists must cover the views)
+  else if (n_fused < 0 || n_other < 0 || (!dc_views.ds && (view_out ? (long long)n_fused + n_other > n_views : n_fused + n_other != n_views)))
+    return fail("mprg_partition: the two view lists must cover the views");
   else if ((n_fused > 0 && !fused_list) || (n_other > 0 && !other_list)) return fail("mprg_partition: a view list is missing");
   if (min_match_length < 1) return fail("mprg_partition: min_match_length must be positive");
   if (n_work_rows > 0) LAUNCH(k_gap_runs, n_work_rows, GR_ROWS, stream, arena, views, rowidx, work_rows, mask, maxrun, dc_rows);
@@ -806,7 +812,7 @@ static int kf_children(const int64_t *F, const KfStep &st, void *stream) {
   if (n <= 0) return 0;
   const DsCount dn = kf_dc(st, MPRG_DS_N);
   LAUNCH(k_lv_children, (n + 3) / 4, 256, stream, FP(int64_t, MPRG_F_NODES), (long long)F[MPRG_F_F0], n, (long long)F[MPRG_F_N_NODES],
-         FP(const int64_t, MPRG_F_VALS), FP(const int32_t, MPRG_F_VIEW_OUT), FP(const int32_t, MPRG_F_IV_PACKED), dn);
+         FP(const int64_t, MPRG_F_VALS), FP(const int32_t, MPRG_F_VIEW_OUT), FP(const int32_t, MPRG_F_IV_PACKED), g_iv_self, dn);
   if (F[MPRG_F_NSEL] > 0)
     LAUNCH(k_lv_sub, KF_GRID(n), 256, stream, FP(const int64_t, MPRG_F_NODES), (long long)F[MPRG_F_F0], n, FP(const int64_t, MPRG_F_VALS),
            FP(const int64_t, MPRG_F_VIEWS), FP(int64_t, MPRG_F_SUB), FP(int64_t, MPRG_F_SELNODE), FP(int32_t, MPRG_F_DD_WORK), dn);
@@ -974,13 +980,13 @@ int mprg_forest_level(const int64_t *F, void *stream) {
     if (C[MPRG_CAP_NOTHER] > 0 &&
         d_column_masks(arena, FP(const int64_t, MPRG_F_VIEWS), pool, FP(const int32_t, MPRG_F_MASK_WORK), (int)C[MPRG_CAP_ITEMS], 1024 >> rpc,
                        FP(uint32_t, MPRG_F_MASK), stream, slot(b0 + 5 + rpc)) != 0) return -1;
-    const bool lists = C[MPRG_CAP_NFUSED] > 0;
+    // (always by the lists k_fr_fill wrote: the views of MPRG_NF_SELF nodes are in neither, and no partition kernel may visit them)
+    if (!F[MPRG_F_FUSED_LIST] || !F[MPRG_F_OTHER_LIST]) return fail("mprg_forest_level: MPRG_F_FUSED_LIST / MPRG_F_OTHER_LIST are not set");
     if (d_partition(arena, FP(const int64_t, MPRG_F_VIEWS), pool, (int)cap_na, FP(const uint32_t, MPRG_F_MASK), Lm, FP(const int32_t, MPRG_F_GAP_WORK),
                     (int)C[MPRG_CAP_NGAP], FP(uint32_t, MPRG_F_MAXRUN), FP(int32_t, MPRG_F_STACK), FP(int32_t, MPRG_F_IVFLAG), FP(int32_t, MPRG_F_IV),
                     FP(int32_t, MPRG_F_NIV), FP(int32_t, MPRG_F_STATUS), FP(int32_t, MPRG_F_VIEW_OUT), FP(int32_t, MPRG_F_IV_PACKED),
-                    FP(int32_t, MPRG_F_IVC), lists ? FP(const int32_t, MPRG_F_FUSED_LIST) : nullptr, lists ? (int)C[MPRG_CAP_NFUSED] : 0,
-                    lists ? FP(const int32_t, MPRG_F_OTHER_LIST) : nullptr, lists ? (int)C[MPRG_CAP_NOTHER] : 0, stream, slot(b0 + 0), slot(b0 + 10),
-                    slot(b0 + 3), lists ? slot(b0 + 4) : slot(b0 + 0)) != 0) return -1;
+                    FP(int32_t, MPRG_F_IVC), FP(const int32_t, MPRG_F_FUSED_LIST), (int)C[MPRG_CAP_NFUSED], FP(const int32_t, MPRG_F_OTHER_LIST),
+                    (int)C[MPRG_CAP_NOTHER], stream, slot(b0 + 0), slot(b0 + 10), slot(b0 + 3), slot(b0 + 4)) != 0) return -1;
   }
   // ---- S2 classify, children of multi-interval nodes, the selected views
   int64_t *b1 = blk(MPRG_STEP_CLASSIFY);

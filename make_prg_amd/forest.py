@@ -208,6 +208,7 @@ class ForestEngine(BatchEngine):
         key = (root_levels.tobytes(), forced.tobytes())
         self._forest_begin(root_levels, forced, key)
         self._roots_args = (root_levels, forced, key)
+        self._pool_cache_used = -1          # (forest_tree_dump's host copy of the row pool: a new forest fills the pool in an order of its own)
         plan = getattr(self, "_plan", None)
         self._pending = None
         caps = None
@@ -566,7 +567,8 @@ class ForestEngine(BatchEngine):
         e, z = be.empty, be.zeros
         # the buffers that must arrive zeroed are places in ONE block: one fill per level instead of seven
         al = lambda x: (int(x) + 255) // 256 * 256
-        zsizes = dict(MASK=4 * tcols, MAXRUN=4 * tcols, IVFLAG=8 * tcols, IVC=4)
+        # (NIV, STATUS, VIEW_OUT: no partition kernel writes the words of a view whose node is NF_SELF, the level's later kernels read them)
+        zsizes = dict(MASK=4 * tcols, MAXRUN=4 * tcols, IVFLAG=8 * tcols, IVC=4, NIV=4 * na, STATUS=4 * na, VIEW_OUT=32 * na)
         if P:
             zsizes.update(KM_STATUS=4 * P, ASSIGN=4 * lo, X=8 * xd)
         zoff, ztotal = {}, 0
@@ -577,8 +579,7 @@ class ForestEngine(BatchEngine):
         zbase = be.ptr(zslab)
         self._alive["ZSLAB"] = zslab
         bufs = dict(VIEWS=e(8 * VF * na), VIEW2NODE=e(8 * na), FUSED_LIST=e(4 * n_fused), OTHER_LIST=e(4 * n_other), MASK_WORK=e(12 * n_items),
-                    GAP_WORK=e(8 * n_gap), VIEW_OUT=e(32 * na), IV_PACKED=e(12 * tcols), STACK=e(16 * tcols),
-                    IV=e(12 * tcols), NIV=e(4 * na), STATUS=e(4 * na),
+                    GAP_WORK=e(8 * n_gap), IV_PACKED=e(12 * tcols), STACK=e(16 * tcols), IV=e(12 * tcols),
                     SUB=e(8 * VF * nsel), SELNODE=e(8 * nsel), DD_WORK=e(8 * n_dd))
         caps = {CAP_TCOLS: tcols, CAP_NFUSED: n_fused, CAP_NOTHER: n_other, CAP_ITEMS: n_items, CAP_NGAP: n_gap, CAP_SROWS: srows, CAP_UBYTES: ubytes,
                 CAP_SCOLS: scols, CAP_NDD: n_dd, CAP_WC: n_wc, CAP_WR: n_wr, CAP_TABLE: table_bytes, CAP_FLAG: flag_bytes, CAP_LO: lo, CAP_XD: xd,
@@ -635,15 +636,16 @@ class ForestEngine(BatchEngine):
         self._set(VIEWS=d_views, VIEW2NODE=d_v2n, FUSED_LIST=d_fl, OTHER_LIST=d_ol, MASK_WORK=d_mw, RPC_IDX=rpc_idx, GAP_WORK=d_gw,
                   N_VIEWS=na)
         self._step("frontier_fill")
-        d_vout, d_ivp = be.empty(32 * na), be.empty(12 * total_cols)
+        # (zeroed: the views of NF_SELF nodes are in neither list, no partition kernel writes their words, the packed list and S2 read them)
+        d_vout, d_ivp = be.zeros(32 * na), be.empty(12 * total_cols)
         if na:
             d_mask = be.zeros(4 * total_cols)
             if n_other:
                 be.call("mprg_column_masks", be.ptr(self.d_arena), be.ptr(d_views), be.ptr(self.d_pool), be.ptr(d_mw), n_items,
                         1024 >> rpc_idx, be.ptr(d_mask), be.stream, work=cells_other)
             d_maxrun, d_stack, d_ivflag = be.zeros(4 * total_cols), be.empty(16 * total_cols), be.zeros(8 * total_cols)
-            d_iv, d_niv, d_status, d_ivc = be.empty(12 * total_cols), be.empty(4 * na), be.empty(4 * na), be.zeros(4)
-            lists = (be.ptr(d_fl), n_fused, be.ptr(d_ol), n_other) if n_fused else (None, 0, None, 0)
+            d_iv, d_niv, d_status, d_ivc = be.empty(12 * total_cols), be.zeros(4 * na), be.zeros(4 * na), be.zeros(4)
+            lists = (be.ptr(d_fl), n_fused, be.ptr(d_ol), n_other)
             be.call("mprg_partition", be.ptr(self.d_arena), be.ptr(d_views), be.ptr(self.d_pool), na, be.ptr(d_mask), L,
                     be.ptr(d_gw), n_gap, be.ptr(d_maxrun), be.ptr(d_stack), be.ptr(d_ivflag), be.ptr(d_iv), be.ptr(d_niv),
                     be.ptr(d_status), be.ptr(d_vout), be.ptr(d_ivp), be.ptr(d_ivc), *lists, be.stream, work=cells)
