@@ -798,6 +798,38 @@ int mprg_prog_tree(const uint32_t *shared, long long shared_words, const int64_t
                    const int64_t *loci, int n_loci, const int32_t *weights, int64_t *workspace, long long workspace_words,
                    int32_t *merges, long long merges_words, int32_t *status, void *stream);
 
+/* `--progressive --refine-tree`: a progressive MSA cut at a guide-tree edge, the two halves realigned as profiles (the spec:
+ * star_align.py, "Tree refinement").  Texts and bufs are mprg_prog_columns'.
+ * mprg_tree_split: items: n_items x MPRG_TS_ITEM_FIELDS int64 {buffer, offset of the R x W text in it, R >= 2, W >= 1, offset of
+ *   the text's R side bytes in `sides` (0: the row belongs to Y, 1: to X), offset of the item's output in `out`, offset of its W
+ *   columns in `flags` (uint8, n_cols long), offset of its ceil(W / 256) + 1 entries in `tiles` (pairs of int32, n_tiles pairs
+ *   long)}.  work: n_work x 2 int32 {item, 256-column tile}: every tile of every item must be in it, once (an item of which a tile is
+ *   missing is split from counts nobody wrote: its widths and texts are then undefined, though never outside the item's output;
+ *   with an empty work table every item gets MPRG_PG_BAD_ITEM).  flags and tiles are workspace: no need to initialise them, their
+ *   contents afterwards are not part of the interface.
+ *   Y's rows, in the text's order, over the columns in which one of them is not '-' (in order), row-major as an R_Y x W_Y text at
+ *   the item's output offset; directly behind it X's R_X x W_X text likewise.  R W output bytes always suffice.
+ *   widths[2 item], widths[2 item + 1] (int64) receive W_Y, W_X.  With them the two texts are sides {buffer, offset, R, W} for
+ *   mprg_prog_columns(_weighted), the DP calls and mprg_prog_rows.  `out` must not overlap a text.
+ *   status: n_items int32: MPRG_PG_OK; MPRG_PG_BAD_ITEM (the text, the side bytes, the flags or the tile entries outside their
+ *   buffer, R < 2, a side byte above 1, a side without rows or without a kept column); MPRG_PG_NO_SPACE (R_Y W_Y + R_X W_X bytes
+ *   at the output offset do not fit out_bytes).  With any status but MPRG_PG_OK the item writes neither widths nor output.
+ *   Three launches: a workgroup per (item, tile), a wavefront per item, a workgroup per (item, tile); no LDS beyond a few words.
+ * mprg_tree_objective: items: n_items x MPRG_TS_OBJ_FIELDS int64 {buffer, offset of the R x W text in it, R >= 1, W >= 1, offset
+ *   of the text's R weights in `weights` (int32 elements, weights_words long), their sum, E >= 0}.  work as above.  sums[item]
+ *   (int64, ZEROED by the caller) receives mprg_refine_counts' objective S of the MSA that holds row r weights[r] times and E
+ *   all-gap rows more (ambiguity codes score as there; every run of '-' of every row counted), added up over the item's tiles by
+ *   64-bit integer atomics: all of an item's tiles must be in `work`, once.
+ *   status: n_work int32: MPRG_PG_OK, or MPRG_PG_BAD_ITEM (an index, a tile, the text or the weights outside their table or
+ *   buffer, a weight below 1, a sum that is not the stated one, sum + E above 2^20 or (sum + E)^2 W above 2^58: S would not fit
+ *   int64): nothing else written. */
+enum { MPRG_TS_ITEM_FIELDS = 8, MPRG_TS_OBJ_FIELDS = 7 };
+int mprg_tree_split(const int64_t *bufs, int n_bufs, const int64_t *items, int n_items, const int32_t *work, int n_work,
+                    const uint8_t *sides, long long sides_bytes, uint8_t *flags, long long n_cols, int32_t *tiles, long long n_tiles,
+                    uint8_t *out, long long out_bytes, int64_t *widths, int32_t *status, void *stream);
+int mprg_tree_objective(const int64_t *bufs, int n_bufs, const int64_t *items, int n_items, const int32_t *work, int n_work,
+                        const int32_t *weights, long long weights_words, int64_t *sums, int32_t *status, void *stream);
+
 /* (f)-1 output encoders, HOST functions (host pointers), one pass over a PRG string as PrgBuilder emits it.
  * reference make_prg/utils/prg_encoder.py:44-91 and make_prg/utils/gfa.py:16-109.
  * mprg_prg_encode_host: out[n] receives the uint32 stream (A C G T -> 1 2 3 4, markers as integers, the closing

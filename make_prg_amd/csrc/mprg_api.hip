@@ -24,6 +24,7 @@
 #include "k_prog_band.inc"
 #include "k_collapse.inc"
 #include "k_prog_tree.inc"
+#include "k_tree_refine.inc"
 #include "host_encoders.inc"
 #include "host_batch.inc"
 
@@ -760,6 +761,32 @@ int mprg_prog_tree(const uint32_t *shared, long long shared_words, const int64_t
   LAUNCH(k_prog_tree, n_loci, PG_THREADS, stream, shared, shared_words, nw, seqs, n_seqs, loci, weights, workspace, workspace_words,
          merges, merges_words, status);      // a workgroup per locus
   return check_launch("k_prog_tree");
+}
+
+int mprg_tree_split(const int64_t *bufs, int n_bufs, const int64_t *items, int n_items, const int32_t *work, int n_work,
+                    const uint8_t *sides, long long sides_bytes, uint8_t *flags, long long n_cols, int32_t *tiles, long long n_tiles,
+                    uint8_t *out, long long out_bytes, int64_t *widths, int32_t *status, void *stream) {
+  if (n_items <= 0) return 0;
+  if (n_work > 0) {
+    LAUNCH(k_tree_split_flags, n_work, TS_THREADS, stream, bufs, n_bufs, items, n_items, work, sides, sides_bytes, flags, n_cols, tiles,
+           n_tiles);
+    const int rc = check_launch("k_tree_split_flags");
+    if (rc) return rc;
+  }
+  LAUNCH(k_tree_split_scan, (n_items + TS_WAVES - 1) / TS_WAVES, TS_THREADS, stream, bufs, n_bufs, items, n_items, sides, sides_bytes,
+         n_cols, tiles, n_tiles, out_bytes, widths, status, n_work > 0 ? 1 : 0);      // a wavefront per item
+  const int rc = check_launch("k_tree_split_scan");
+  if (rc || n_work <= 0) return rc;
+  LAUNCH(k_tree_split_rows, n_work, TS_THREADS, stream, bufs, n_bufs, items, n_items, work, sides, sides_bytes, flags, n_cols, tiles,
+         n_tiles, widths, status, out);
+  return check_launch("k_tree_split_rows");
+}
+
+int mprg_tree_objective(const int64_t *bufs, int n_bufs, const int64_t *items, int n_items, const int32_t *work, int n_work,
+                        const int32_t *weights, long long weights_words, int64_t *sums, int32_t *status, void *stream) {
+  if (n_work <= 0) return 0;
+  LAUNCH(k_tree_objective, n_work, TS_THREADS, stream, bufs, n_bufs, items, n_items, work, weights, weights_words, sums, status);
+  return check_launch("k_tree_objective");
 }
 
 // ---- the recursion forest on the device (k_forest.inc); F: host array of MPRG_F_FIELDS int64 ------------------------------

@@ -16,6 +16,10 @@ With `--collapse-identical` the records of a locus whose (oriented) sequences ar
 once, with the class size as an integer weight; every member gets its representative's row (Collapse below; kernels in
 csrc/k_collapse.inc, C ABI: mprg_star_identical / mprg_prog_columns_weighted).
 
+With `--refine-tree` (and `--progressive`) the progressive MSA is then cut at the edges of its guide tree, one after the other, and the
+two halves realigned as profiles; a realignment is kept if it raises the objective (Tree refinement below; kernels in
+csrc/k_tree_refine.inc, C ABI: mprg_tree_split / mprg_tree_objective).
+
 It is NOT MAFFT.  PRGs built from these alignments differ from PRGs built from a MAFFT alignment of the same sequences.
 
 Spec (the kernels and tests/star_ref.py follow it bit for bit)
@@ -176,6 +180,44 @@ reverse-complemented copy of it fall into one class.
             with the representatives only (the distance tables cover them alone), with the weights beside them; the last
             mprg_prog_rows launch names the representative's root row as the source of every member's output row.
 
+Tree refinement (only with progressive and refine_tree = N > 0; integers only; tests/treerefine_ref.py states it in plain Python;
+kernels: csrc/k_tree_refine.inc, C ABI: mprg_tree_split / mprg_tree_objective).  Progressive never looks back at a merge, and
+Refinement's second look is one row against all others; a locus of two or three sub-families carries its errors on the tree's inner
+edges, clade against clade.  Here the tree is cut at an edge, the two halves are realigned as profiles, and the result is kept if
+the objective rises.
+  Where.    After the last merge of Progressive, on the root's text: one row per leaf (with collapse one row per class, with the
+            class weights), before the rows are put into input order.  adjust_direction has run before it, refine runs after it,
+            unchanged, on the text that results.
+  Which loci.  Those built progressively with 4 <= m <= TREE_REFINE_MAX_LEAVES = 512 leaves (with fewer no edge has two leaves on
+            either side).  The cap is a cost constant: a pass costs about as many DP cells as the whole progressive stage, and its
+            steps are sequential per locus.  A locus above it keeps its progressive MSA and is reported.
+  Steps.    The tree's merges are numbered t = 0 .. m - 2 in the order UPGMA made them (prog_tree's and mprg_prog_tree's order);
+            L_t is the set of leaves under node t.  The steps of a locus are the nodes t = 0 .. m - 3, ascending, with
+            m - |L_t| >= 2.  If both children of the root are inner nodes they cut the same split: the one with the smaller t is
+            left out, so the root's split comes last.
+  A step    on the current MSA A (rows = leaves, weights w, all 1 without collapse): G = L_t, G' the other leaves.  A_G: G's rows
+            over the columns in which one of them is not '-', columns in order, rows in the order they have in A; A_G' likewise.
+            Y is the side with the larger weight sum, on equal sums the side that holds the locus's lowest leaf index; X the
+            other.  The merge is exactly Progressive's "Merge of a node's two children" with Collapse's weights: the same planes,
+            DP and ties.  A': Y's rows, then X's, over the ops; it has no all-gap column by construction.
+  Objective.  Refinement's S of the locus's OUTPUT MSA: every row counts w_r times and the locus's E empty records count as all-gap
+            rows.  R = sum w + E; c_x is summed over the weights, g over the weights plus E; runs = sum w_r runs(row r) + E.  So it
+            is the number mprg_refine_counts gives for the MSA as written.
+  Acceptance.  A' replaces A only if S(A') > S(A).  A pass visits all steps in order, each on the MSA the accepted steps before it
+            left.  A locus takes up to N passes; a pass without an accepted step ends its refinement.
+  Limit.    A step with W_X + W_Y >= 10^6, or whose full-DP traceback exceeds the workspace budget, is skipped and counts as
+            refused; skipped steps are reported.  The run never fails on a locus that the progressive pass built.
+  With band the merges go through _prog_pairs' certified two passes: the same bytes.
+  Promised (tested): every row with its gaps removed is its input sequence; no column is all gaps; S never falls; a locus all of
+            whose steps are refused has its progressive bytes; with collapse equal sequences get equal rows; band and device_tree
+            give the same bytes.
+  Host side (_tree_refine, between _prog_rounds and _prog_output): step s of every locus of the chunk that still has a step s
+            goes together: one mprg_tree_split launch into a buffer of the step's own, one download of the widths and status
+            words (20 bytes per item), _prog_groups / _prog_pairs on the two halves as ordinary sides, mprg_prog_rows into a new
+            text buffer per group, one mprg_tree_objective launch, one download of S (8 bytes per item).  The host keeps per
+            locus its row order (Y's leaves, then X's) and where its current text is; a buffer is dropped when no locus points to
+            it.  No MSA text leaves the device during the stage.
+
 Progressive, host side: per chunk the distances in launches whose m x m tables fit budget_bytes (loci of three or more leaves), D
 and the tree per locus in NumPy / Python integers (prog_tree: a float64 quotient only shortlists, the choice is exact).  A node's
 round is 1 + the larger of its children's rounds.  With device_tree the tree is built on the device instead (csrc/k_prog_tree.inc):
@@ -238,6 +280,10 @@ PG_BAND_PAIR_FIELDS = 8                   # MPRG_PG_BAND_PAIR_FIELDS
 PG_WITEM_FIELDS = 8                       # MPRG_PG_WITEM_FIELDS
 PG_TREE_FIELDS = 5                        # MPRG_PG_TREE_FIELDS
 PROG_BAND_W0 = 64                         # pass 1's half-width of a banded merge (what was tried)
+TS_ITEM_FIELDS, TS_OBJ_FIELDS = 8, 7      # MPRG_TS_ITEM_FIELDS, MPRG_TS_OBJ_FIELDS
+TREE_REFINE_MAX_LEAVES = 512              # the spec's cost cap of a tree-refined locus
+TREE_REFINE_MIN_LEAVES = 4                # below it no step leaves two leaves on either side
+TREE_REFINE_DEFAULT, TREE_REFINE_MAX = 1, 4   # passes of `--refine-tree` alone, and the most it takes
 PG_STATUS = {1: "an index, a tile or a source range outside its table or buffer", 2: "ops, widths and cells that do not fit each other",
              3: "the output outside its buffer"}
 TREE_STATUS = {1: "a range outside its buffer, a leaf's weight below 1 or a weight sum above 4 096", 3: "the workspace outside its buffer"}
@@ -320,7 +366,8 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
               budget_bytes: int = pa.DEFAULT_BUDGET_BYTES, chunk_bytes: int = CHUNK_BYTES, timings: Optional[dict] = None,
               adjust_direction: bool = False, orientation: Optional[list] = None, band=False, refine: int = 0,
               refinement: Optional[list] = None, progressive: bool = False, progression: Optional[list] = None,
-              max_leaves: Optional[int] = None, collapse: bool = False, device_tree: bool = False) -> List[MSA]:
+              max_leaves: Optional[int] = None, collapse: bool = False, device_tree: bool = False, refine_tree: Optional[int] = None,
+              tree_refinement: Optional[list] = None, tree_refine_max_leaves: int = TREE_REFINE_MAX_LEAVES) -> List[MSA]:
     """loci: per locus its records as (title, sequence).  Returns the loci's centre-star MSAs (ids: the titles' first words,
     descriptions: the titles).  names: the loci's names for error messages (default: their indices).  timings: a dict that
     receives the wall seconds of the stages (orient, centre, pairs, merge: each ends at a download, so includes its kernels).
@@ -345,9 +392,19 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
     device_tree: only with progressive (else a ValueError): the trees of the loci of three or more leaves by mprg_prog_tree, on the
     tables mprg_prog_distances left on the device; the same merges, so the same MSAs.  timings also receives tree_device_loci.
     False: nothing launches differently.  Either way timings receives tree_plan_s: the part of tree_s spent in _prog_plan on the
-    host (with device_tree the plan alone, without it the host's UPGMA too)."""
+    host (with device_tree the plan alone, without it the host's UPGMA too).
+    refine_tree: only with progressive (else a ValueError): N, the passes of the spec's Tree refinement (1 to TREE_REFINE_MAX), on
+    the loci built progressively with 4 to tree_refine_max_leaves leaves; before the rows go into input order, so before refine.
+    None: nothing launches differently.  tree_refinement: a list that then receives per locus (steps tried: every step visited,
+    accepted, skipped: the spec's Limit, S before, S after), None for a locus left to the star pass.  timings also receives
+    tree_refine_s and tree_refine_loci, tree_refine_steps, tree_refine_accepted, tree_refine_skipped, tree_refine_above_cap."""
     if device_tree and not progressive:
         raise ValueError("device_tree: only with progressive")
+    if refine_tree is not None:
+        if not progressive:
+            raise ValueError("refine_tree: only with progressive")
+        if not (isinstance(refine_tree, (int, np.integer)) and not isinstance(refine_tree, bool) and 1 <= refine_tree <= TREE_REFINE_MAX):
+            raise ValueError(f"refine_tree: a number of passes from 1 to {TREE_REFINE_MAX}, not {refine_tree!r}")
     if not (isinstance(refine, (int, np.integer)) and not isinstance(refine, bool) and 0 <= refine <= REFINE_MAX):
         raise ValueError(f"refine: a number of rounds from 0 to {REFINE_MAX}, not {refine!r}")
     band = None if band is False or band is None else band      # from here on: None, True or pass 1's half-width
@@ -360,44 +417,49 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
     if progressive:
         return _progressive_msas(backend, loci, codes, names, budget_bytes, chunk_bytes, timings, adjust_direction, orientation, band,
                                  int(refine), refinement, progression, PROG_MAX_LEAVES if max_leaves is None else int(max_leaves), bool(collapse),
-                                 bool(device_tree))
+                                 bool(device_tree), int(refine_tree or 0), tree_refinement, int(tree_refine_max_leaves))
     return [m for lo, hi in _chunks(codes, chunk_bytes)
             for m in _star_chunk(backend, loci[lo:hi], codes[lo:hi], names[lo:hi], budget_bytes, timings, adjust_direction, orientation, band,
                                  int(refine), refinement, collapse=bool(collapse))]
 
 
 def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings, adjust_direction, orientation, band, refine, refinement,
-                      progression, max_leaves, collapse=False, device_tree=False) -> List[MSA]:
+                      progression, max_leaves, collapse=False, device_tree=False, refine_tree=0, tree_refinement=None,
+                      tree_max_leaves=TREE_REFINE_MAX_LEAVES) -> List[MSA]:
     """star_msas with progressive: the loci within the leaf limit through the progressive chunks, the others through the star
     chunks, the results (and what the caller's lists receive) back in the loci's order."""
     n_leaves = [sum(1 for c in cs if len(c)) for cs in codes]
     out = [None] * len(loci)
-    got = {k: [None] * len(loci) for k in ("orientation", "refinement", "progression")}
+    got = {k: [None] * len(loci) for k in ("orientation", "refinement", "progression", "tree_refinement")}
     for prog in (True, False):
         sel = [l for l in range(len(loci)) if (n_leaves[l] <= max_leaves) == prog]
         sub = [codes[l] for l in sel]
-        ori, ref, pro, msas = [], [], [], []
+        ori, ref, pro, tre, msas = [], [], [], [], []
         for lo, hi in _chunks(sub, chunk_bytes):
             idx = sel[lo:hi]
             msas.extend(_star_chunk(be, [loci[l] for l in idx], sub[lo:hi], [names[l] for l in idx], budget_bytes, timings, adjust_direction,
                                     ori if orientation is not None else None, band, refine, ref if refinement is not None else None,
-                                    prog, pro, collapse, device_tree and prog))
+                                    prog, pro, collapse, device_tree and prog, refine_tree if prog else 0,
+                                    tre if tree_refinement is not None else None, tree_max_leaves))
         if not prog:
             pro = [(n_leaves[l], 0, True) for l in sel]
         for k, l in enumerate(sel):
             out[l] = msas[k]
-            for key, vals in (("orientation", ori), ("refinement", ref), ("progression", pro)):
+            for key, vals in (("orientation", ori), ("refinement", ref), ("progression", pro), ("tree_refinement", tre)):
                 if vals:
                     got[key][l] = vals[k]
-    for key, dest in (("orientation", orientation), ("refinement", refinement), ("progression", progression)):
+    for key, dest in (("orientation", orientation), ("refinement", refinement), ("progression", progression),
+                      ("tree_refinement", tree_refinement)):
         if dest is not None:
             dest.extend(got[key])
     return out
 
 
 def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direction=False, orientation=None, band=None, refine=0,
-                refinement=None, progressive=False, progression=None, collapse=False, device_tree=False) -> List[MSA]:
-    """One chunk: pack, optionally orient, optionally collapse, the star pass or the progressive one, optionally refine, collect."""
+                refinement=None, progressive=False, progression=None, collapse=False, device_tree=False, refine_tree=0,
+                tree_refinement=None, tree_max_leaves=TREE_REFINE_MAX_LEAVES) -> List[MSA]:
+    """One chunk: pack, optionally orient, optionally collapse, the star pass or the progressive one (with its tree refinement),
+    optionally refine, collect."""
     laps = _Laps(timings)
     chunk = _pack(be, codes, names, [[t for t, _ in recs] for recs in loci])
     if adjust_direction:
@@ -406,7 +468,8 @@ def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direc
             orientation.extend(result)
         laps.lap("orient_s")
     classes = _collapse(be, chunk, laps) if collapse else None
-    text = (_progressive(be, chunk, budget_bytes, band, laps, progression, classes, device_tree) if progressive else
+    text = (_progressive(be, chunk, budget_bytes, band, laps, progression, classes, device_tree, refine_tree, tree_refinement,
+                         tree_max_leaves) if progressive else
             _star_pass(be, chunk, budget_bytes, band, laps, classes))
     moved = {}
     if refine:
@@ -847,10 +910,11 @@ def _prog_plan(lens, first, counts, shared, weights=None, merges=None):
     have one tree); no device, no clock.  A leaf's node id is its record index, an inner node's counts on from the locus's records.
     Returns (per locus its leaves: the non-empty records; per round its merges (locus, y, x, parent), Y the child with more rows;
     per locus its root node; per locus the records of the root's rows in row order: Y's rows, then X's, at every node; per locus
-    the progression tuple (leaves, rounds, False)).  weights: per record of the tables how many rows it stands for (the spec's
-    Collapse): the tree is the weighted one and Y the child with the larger weight sum.  merges: per locus of three or more
-    leaves its tree as _prog_trees gave it; `shared` is then not read."""
-    leaves, by_round, roots, root_members, progression = [], {}, [], [], []
+    its tree: the merges (key(U), key(V)) in the order UPGMA made them; per locus the progression tuple (leaves, rounds, False)).
+    weights: per record of the tables how many rows it stands for (the spec's Collapse): the tree is the weighted one and Y the
+    child with the larger weight sum.  merges: per locus of three or more leaves its tree as _prog_trees gave it; `shared` is then
+    not read."""
+    leaves, by_round, roots, root_members, trees, progression = [], {}, [], [], [], []
     for l in range(len(counts)):
         lv = np.nonzero(lens[first[l]:first[l] + counts[l]] > 0)[0].tolist()
         wl = None if weights is None else weights[first[l]:first[l] + counts[l]]
@@ -871,8 +935,9 @@ def _prog_plan(lens, first, counts, shared, weights=None, merges=None):
         leaves.append(lv)
         roots.append(node_at[lv[0]])
         root_members.append(members[roots[-1]])
+        trees.append(tree)
         progression.append((len(lv), rnd[roots[-1]], False))
-    return leaves, by_round, roots, root_members, progression
+    return leaves, by_round, roots, root_members, trees, progression
 
 
 def _prog_w0(band):
@@ -1013,11 +1078,13 @@ def merge_profiles(backend, pairs: Sequence[Tuple[np.ndarray, np.ndarray]], budg
     return out
 
 
-def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression, classes: Optional[Classes] = None, device_tree=False):
+def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression, classes: Optional[Classes] = None, device_tree=False,
+                 refine_tree=0, tree_refinement=None, max_leaves=None):
     """The spec's Progressive over one chunk, on the (oriented) sequences in chunk.d_codes.  Returns what the star pass leaves: the
     device buffer of the MSAs' ASCII text, its bytes, each locus's offset in it and its width.  classes: the spec's Collapse: the
     tree and the merges over the representatives with their weights, the root's rows written for every member.  device_tree: the
-    trees by mprg_prog_tree (_prog_trees) instead of prog_tree."""
+    trees by mprg_prog_tree (_prog_trees) instead of prog_tree.  refine_tree: the passes of the spec's Tree refinement on the
+    roots' texts before they are written out (0: none); tree_refinement receives its tuples, max_leaves is its cap."""
     laps.lap()
     lens, first, counts = chunk.lens, chunk.first, chunk.counts
     n_leaves = np.add.reduceat((lens > 0).astype(np.int64), first)          # (every locus has a record)
@@ -1049,22 +1116,53 @@ def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression,
     if progression is not None:
         progression.extend(plan[-1])
     laps.lap("tree_s")
-    text = _prog_rounds(be, chunk, plan, budget_bytes, band, laps.timings, weights, expand)
+    bufs, live, where = _prog_rounds(be, chunk, plan, budget_bytes, band, laps.timings, weights)
+    laps.lap("progressive_s")
+    order = plan[3]
+    if refine_tree:
+        order, result = _tree_refine(be, chunk, plan, bufs, live, where, weights, refine_tree, max_leaves, budget_bytes, band, laps.timings)
+        if tree_refinement is not None:
+            tree_refinement.extend(result)
+        laps.lap("tree_refine_s")
+    text = _prog_output(be, chunk, plan[2], order, bufs, where, expand)
     laps.lap("progressive_s")
     return text
 
 
-def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters, weights=None, expand=None):
+def _prog_parents(be, d_bufs, n_bufs, Xg, Yg, d_ops, ops_bytes, ops_off, count):
+    """The texts of a group of merges (Xg, Yg: the sides' {buffer, offset, R, W}; the ops as _prog_pairs left them) into a new
+    buffer, one mprg_prog_rows launch: Y's rows, then X's, each through the merge's ops.  Returns (the buffer, its bytes, each
+    parent's offset in it, its rows; its width is the op count)."""
+    RY, RX = Yg[:, 2], Xg[:, 2]
+    R = RY + RX
+    poff = exclusive_sum(R * count)
+    new_bytes = int((R * count).sum())
+    rows = np.zeros((int(R.sum()), PG_ROW_FIELDS), np.int64)
+    of = np.repeat(np.arange(len(R)), R)
+    rank = np.arange(len(rows)) - np.repeat(exclusive_sum(R), R)
+    is_x = rank >= RY[of]
+    src = np.where(is_x[:, None], Xg[of], Yg[of])
+    rows[:, 0] = src[:, 0]
+    rows[:, 1] = src[:, 1] + (rank - np.where(is_x, RY[of], 0)) * src[:, 3]
+    rows[:, 2], rows[:, 3], rows[:, 4], rows[:, 5] = src[:, 3], ops_off[of], count[of], is_x
+    rows[:, 6], rows[:, 7] = poff[of] + rank * count[of], count[of]
+    d_rows, d_new, d_status = be.upload(rows), be.empty(new_bytes), be.empty(4 * len(rows))
+    be.call("mprg_prog_rows", be.ptr(d_bufs), n_bufs, be.ptr(d_ops), ops_bytes, be.ptr(d_rows), len(rows), be.ptr(d_new), new_bytes,
+            0, be.ptr(d_status), be.stream, work=float(2 * new_bytes))
+    _check(be.download(d_status, np.int32, len(rows)), "mprg_prog_rows", PG_STATUS)
+    return d_new, new_bytes, poff, R
+
+
+def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters, weights=None):
     """_progressive's device part: the plan's rounds (every node of a round, over all loci of the chunk, in one set of launches
-    per budget group), then the roots' rows in input order.
+    per budget group).  Returns (bufs, live, where) as the last round left them: of every locus only its root is in where.
     The texts' lifetime: bufs[b] is (buffer, bytes) of text buffer b, 0 the chunk's code buffer (the leaves); where[locus, node]
     is (b, offset, rows, width) of a node not yet merged; live[b] counts the nodes of where in b.  A group's parents go into a
     buffer of their own; a buffer (but 0) is dropped when its last node has been merged into a parent.
-    weights, expand (the spec's Collapse): the chunk's tables hold the representatives only, weights per record of them; rw[locus,
-    node] then is the weights of the node's rows.  expand: (records per locus, each locus's first record, per record its
-    representative's index in the chunk's tables) of the output: every record gets its representative's row."""
-    lens, seq_off, first, counts, n_loci = chunk.lens, chunk.seq_off, chunk.first, chunk.counts, chunk.n_loci
-    leaves, by_round, root, root_members, _ = plan
+    weights (the spec's Collapse): the chunk's tables hold the representatives only, weights per record of them; rw[locus, node]
+    then is the weights of the node's rows."""
+    lens, seq_off, first, n_loci = chunk.lens, chunk.seq_off, chunk.first, chunk.n_loci
+    leaves, by_round = plan[:2]
     bufs, live = [(chunk.d_codes, chunk.codes_bytes)], [0]
     where = {(l, a): (0, int(seq_off[first[l] + a]), 1, int(lens[first[l] + a])) for l in range(n_loci) for a in leaves[l]}
     rw = {} if weights is None else {(l, a): weights[first[l] + a:first[l] + a + 1] for l in range(n_loci) for a in leaves[l]}
@@ -1087,24 +1185,7 @@ def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters, weights=N
                 wg = ([rw[todo[k][0], todo[k][2]] for k in grp.tolist()], [rw[todo[k][0], todo[k][1]] for k in grp.tolist()])
                 add_to(counters, "collapse_merges", len(grp))
             d_ops, ops_bytes, ops_off, count, _ = _prog_pairs(be, d_bufs, len(bufs), Xg, Yg, band, budget_bytes, counters, wg)
-            RY, RX = Yg[:, 2], Xg[:, 2]
-            R = RY + RX
-            poff = exclusive_sum(R * count)
-            new_bytes = int((R * count).sum())
-            # the parents' rows: Y's, then X's, each through the merge's ops
-            rows = np.zeros((int(R.sum()), PG_ROW_FIELDS), np.int64)
-            of = np.repeat(np.arange(len(grp)), R)
-            rank = np.arange(len(rows)) - np.repeat(exclusive_sum(R), R)
-            is_x = rank >= RY[of]
-            src = np.where(is_x[:, None], Xg[of], Yg[of])
-            rows[:, 0] = src[:, 0]
-            rows[:, 1] = src[:, 1] + (rank - np.where(is_x, RY[of], 0)) * src[:, 3]
-            rows[:, 2], rows[:, 3], rows[:, 4], rows[:, 5] = src[:, 3], ops_off[of], count[of], is_x
-            rows[:, 6], rows[:, 7] = poff[of] + rank * count[of], count[of]
-            d_rows, d_new, d_status = be.upload(rows), be.empty(new_bytes), be.empty(4 * len(rows))
-            be.call("mprg_prog_rows", be.ptr(d_bufs), len(bufs), be.ptr(d_ops), ops_bytes, be.ptr(d_rows), len(rows), be.ptr(d_new), new_bytes,
-                    0, be.ptr(d_status), be.stream, work=float(2 * new_bytes))
-            _check(be.download(d_status, np.int32, len(rows)), "mprg_prog_rows", PG_STATUS)
+            d_new, new_bytes, poff, R = _prog_parents(be, d_bufs, len(bufs), Xg, Yg, d_ops, ops_bytes, ops_off, count)
             bufs.append((d_new, new_bytes))
             live.append(len(grp))
             for i, k in enumerate(grp.tolist()):
@@ -1114,7 +1195,15 @@ def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters, weights=N
                     rw[l, parent] = np.concatenate([rw.pop((l, y)), rw.pop((l, x))])
                 merged(l, y)
                 merged(l, x)
-    # the roots' rows into input order, as ASCII; an empty record is a row of '-'
+    return bufs, live, where
+
+
+def _prog_output(be, chunk: Chunk, root, root_members, bufs, where, expand=None):
+    """The roots' rows into input order, as ASCII; an empty record is a row of '-': one more mprg_prog_rows launch.  root_members:
+    per locus the records of the root's rows, in row order.  expand (the spec's Collapse): (records per locus, each locus's first
+    record, per record its representative's index in the chunk's tables) of the output: every record gets its representative's
+    row.  Returns what the star pass leaves: (the buffer, its bytes, each locus's offset in it, its width)."""
+    first, counts, n_loci = chunk.first, chunk.counts, chunk.n_loci
     W = np.array([where[l, root[l]][3] for l in range(n_loci)], np.int64)
     o_counts, o_first, slot = (counts, first, None) if expand is None else expand
     base = exclusive_sum(o_counts * W)
@@ -1140,6 +1229,164 @@ def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters, weights=N
             be.ptr(d_status), be.stream, work=float(2 * out_bytes))
     _check(be.download(d_status, np.int32, len(rows)), "mprg_prog_rows", PG_STATUS)
     return d_out, out_bytes, base, W
+
+
+# ---- tree refinement
+def tree_steps(merges: Sequence[Tuple[int, int]]) -> List[np.ndarray]:
+    """The spec's Steps of a tree given as prog_tree's merges: per step G = L_t, the leaves under node t (ascending)."""
+    m = len(merges) + 1
+    at, under, kids = {}, [], []
+    for t, (u, v) in enumerate(merges):
+        a, b = at.get(u, -1), at.get(v, -1)                      # (-1: a leaf)
+        kids.append((a, b))
+        under.append((under[a] if a >= 0 else [u]) + (under[b] if b >= 0 else [v]))
+        at[u] = t
+    twin = min(kids[-1]) if m >= 3 and min(kids[-1]) >= 0 else -1     # both children of the root are inner nodes: one split
+    return [np.array(sorted(under[t]), np.int64) for t in range(m - 2) if m - len(under[t]) >= 2 and t != twin]
+
+
+def tree_split(be, d_bufs, n_bufs: int, texts: np.ndarray, sides: Sequence[np.ndarray]):
+    """mprg_tree_split: texts (n, 4) int64 {buffer, offset, R, W}, per text its side bytes (0: Y, 1: X).  One launch into a new
+    buffer, the widths and the status words downloaded: (the buffer, its bytes, each item's offset in it, the widths (n, 2):
+    W_Y, W_X).  Y's text is at the item's offset, X's R_Y W_Y bytes behind it."""
+    n = len(texts)
+    R, W = texts[:, 2], texts[:, 3]
+    tiles = -(-W // 256) + 1
+    ooff, out_bytes, n_cols, n_tiles = exclusive_sum(R * W), int((R * W).sum()), int(W.sum()), int(tiles.sum())
+    items = np.stack([texts[:, 0], texts[:, 1], R, W, exclusive_sum(R), ooff, exclusive_sum(W), exclusive_sum(tiles)], 1).astype(np.int64)
+    work = _tile_work(W)
+    flat = np.concatenate(sides).astype(np.uint8)
+    d_items, d_work, d_sides = be.upload(items), be.upload(work), be.upload(flat)
+    d_flags, d_tiles, d_out, d_got = be.empty(n_cols), be.empty(8 * n_tiles), be.empty(out_bytes), be.empty(20 * n)
+    be.call("mprg_tree_split", be.ptr(d_bufs), n_bufs, be.ptr(d_items), n, be.ptr(d_work), len(work), be.ptr(d_sides), len(flat),
+            be.ptr(d_flags), n_cols, be.ptr(d_tiles), n_tiles, be.ptr(d_out), out_bytes, be.ptr(d_got), be.ptr(d_got) + 16 * n, be.stream,
+            work=float(3 * out_bytes))
+    got = be.download(d_got, np.uint8, 20 * n)                  # {W_Y, W_X} per item, then the status words
+    _check(got[16 * n:].view(np.int32), "mprg_tree_split", PG_STATUS)
+    return d_out, out_bytes, ooff, got[:16 * n].view(np.int64).reshape(-1, 2).copy()
+
+
+def tree_objective(be, d_bufs, n_bufs: int, texts: np.ndarray, weights: Sequence[np.ndarray], empty: np.ndarray) -> np.ndarray:
+    """mprg_tree_objective: the spec's Objective of texts (n, 4) int64 {buffer, offset, R, W} whose rows count weights[k][r] times,
+    with empty[k] all-gap rows more; one launch, S per text downloaded."""
+    n = len(texts)
+    flat = np.concatenate(weights).astype(np.int32)
+    items = np.zeros((n, TS_OBJ_FIELDS), np.int64)
+    items[:, :4], items[:, 4], items[:, 5], items[:, 6] = texts, exclusive_sum(texts[:, 2]), [int(w.sum()) for w in weights], empty
+    work = _tile_work(items[:, 3])
+    d_items, d_work, d_weights = be.upload(items), be.upload(work), be.upload(flat)
+    d_sums, d_status = be.zeros(8 * n), be.empty(4 * len(work))
+    be.call("mprg_tree_objective", be.ptr(d_bufs), n_bufs, be.ptr(d_items), n, be.ptr(d_work), len(work), be.ptr(d_weights), len(flat),
+            be.ptr(d_sums), be.ptr(d_status), be.stream, work=float((items[:, 2] * items[:, 3]).sum()))
+    _check(be.download(d_status, np.int32, len(work)), "mprg_tree_objective", PG_STATUS)
+    return be.download(d_sums, np.int64, n)
+
+
+def _tree_step_fits(WX, WY, budget_words):
+    """The spec's Limit of a step: the full DP can take it (the int32 score limit) within the workspace budget (with or without band:
+    a merge the band does not help goes to the full DP)."""
+    return (WX + WY < pa.MAX_LEN) & (pa.workspace_words_v(WX, WY) <= budget_words)
+
+
+def _tree_refine(be, chunk: Chunk, plan, bufs, live, where, weights, passes, max_leaves, budget_bytes, band, counters):
+    """The spec's Tree refinement over one chunk, on the roots' texts as _prog_rounds left them (bufs, live, where: its state, kept
+    up here: where[locus, root] names the locus's current text, a buffer is dropped when nothing points to it; weights: per
+    record of the chunk's tables, the spec's Collapse).  Step s of every locus that still has one goes together: one split launch,
+    the widths downloaded, the merges in _prog_groups' groups through _prog_pairs and _prog_parents, one objective launch, S
+    downloaded.  Returns (per locus the records of its text's rows in row order, per locus (steps tried, accepted, skipped, S
+    before, S after))."""
+    first, counts, n_loci = chunk.first, chunk.counts, chunk.n_loci
+    leaves, root, trees = plan[0], plan[2], plan[4]
+    order = [np.array(x, np.int64) for x in plan[3]]
+    wl = [np.ones(int(counts[l]), np.int64) if weights is None else weights[first[l]:first[l] + counts[l]] for l in range(n_loci)]
+    empty = np.array([counts[l] - len(leaves[l]) for l in range(n_loci)], np.int64)
+    budget_words = max(64, int(budget_bytes) // 4)
+
+    def add_buf(buf, nbytes):
+        """The buffer's index in bufs: a dropped buffer's place if there is one."""
+        b = next((i for i in range(1, len(bufs)) if bufs[i][0] is None), len(bufs))
+        if b == len(bufs):
+            bufs.append(None)
+            live.append(0)
+        bufs[b], live[b] = (buf, nbytes), 0
+        return b
+
+    def drop_unused(bs):
+        for b in bs:
+            if b and not live[b]:
+                bufs[b] = (None, 0)
+
+    S = tree_objective(be, _bufs_table(be, bufs), len(bufs), np.array([where[l, root[l]] for l in range(n_loci)], np.int64),
+                       [wl[l][order[l]] for l in range(n_loci)], empty)
+    out = [[0, 0, 0, int(S[l]), int(S[l])] for l in range(n_loci)]
+    n_lv = np.array([len(x) for x in leaves], np.int64)
+    add_to(counters, "tree_refine_above_cap", int((n_lv > max_leaves).sum()))
+    steps = {}                                                  # per refinable locus, per step: is the record a leaf of G?
+    for l in np.nonzero((n_lv >= TREE_REFINE_MIN_LEAVES) & (n_lv <= max_leaves))[0].tolist():
+        groups = tree_steps(trees[l])
+        steps[l] = np.zeros((len(groups), int(counts[l])), bool)
+        for s, g in enumerate(groups):
+            steps[l][s, g] = True
+    active = [l for l in steps if len(steps[l])]
+    add_to(counters, "tree_refine_loci", len(active))
+    for _ in range(passes):
+        moved = set()
+        for s in range(max((len(steps[l]) for l in active), default=0)):
+            its = [l for l in active if s < len(steps[l])]
+            n = len(its)
+            # the sides: Y the heavier of G and the rest, on equal weight sums the one with the locus's lowest leaf
+            sides = []
+            for l in its:
+                o = order[l]
+                in_g, w = steps[l][s][o], wl[l][o]
+                wg, wo = int(w[in_g].sum()), int(w[~in_g].sum())
+                g_is_y = wg > wo or (wg == wo and bool(in_g[np.argmin(o)]))
+                sides.append((in_g != g_is_y).astype(np.uint8))
+            texts = np.array([where[l, root[l]] for l in its], np.int64)
+            d_split, split_bytes, soff, widths = tree_split(be, _bufs_table(be, bufs), len(bufs), texts, sides)
+            RY = np.array([int((sd == 0).sum()) for sd in sides], np.int64)
+            WY, WX = widths[:, 0], widths[:, 1]
+            b = add_buf(d_split, split_bytes)
+            Y = np.stack([np.full(n, b), soff, RY, WY], 1).astype(np.int64)
+            X = np.stack([np.full(n, b), soff + RY * WY, texts[:, 2] - RY, WX], 1).astype(np.int64)
+            fits = _tree_step_fits(WX, WY, budget_words)           # (a step beyond the limit is skipped: it counts as refused)
+            sel = np.nonzero(fits)[0]
+            new, made = {}, [b]
+            for grp in _prog_groups(X[sel, 3], Y[sel, 3], budget_bytes, band):
+                g = sel[grp]
+                d_bufs = _bufs_table(be, bufs)
+                wg = None
+                if weights is not None:
+                    wg = ([wl[its[k]][order[its[k]][sides[k] == 1]] for k in g.tolist()], [wl[its[k]][order[its[k]][sides[k] == 0]] for k in g.tolist()])
+                d_ops, ops_bytes, ops_off, count, _ = _prog_pairs(be, d_bufs, len(bufs), X[g], Y[g], band, budget_bytes, counters, wg)
+                d_new, new_bytes, poff, R = _prog_parents(be, d_bufs, len(bufs), X[g], Y[g], d_ops, ops_bytes, ops_off, count)
+                made.append(add_buf(d_new, new_bytes))
+                for i, k in enumerate(g.tolist()):
+                    new[k] = (made[-1], int(poff[i]), int(R[i]), int(count[i]))
+            ks = sorted(new)
+            rows2 = {k: np.concatenate([order[its[k]][sides[k] == 0], order[its[k]][sides[k] == 1]]) for k in ks}     # Y's rows, then X's
+            S2 = (tree_objective(be, _bufs_table(be, bufs), len(bufs), np.array([new[k] for k in ks], np.int64),
+                                 [wl[its[k]][rows2[k]] for k in ks], empty[[its[k] for k in ks]]) if ks else [])
+            for k in range(n):
+                out[its[k]][0] += 1
+                out[its[k]][2] += int(not fits[k])
+            for k, s2 in zip(ks, S2):
+                l = its[k]
+                if int(s2) > out[l][4]:                             # accepted: the locus's text is the new one
+                    old = where[l, root[l]][0]
+                    live[old] -= 1
+                    live[new[k][0]] += 1
+                    where[l, root[l]], order[l] = new[k], rows2[k]
+                    out[l][1], out[l][4] = out[l][1] + 1, int(s2)
+                    moved.add(l)
+                    made.append(old)
+            drop_unused(made)
+        active = [l for l in active if l in moved]
+        if not active:
+            break
+    for key, i in (("tree_refine_steps", 0), ("tree_refine_accepted", 1), ("tree_refine_skipped", 2)):
+        add_to(counters, key, sum(o[i] for o in out))
+    return [o.tolist() for o in order], [tuple(o) for o in out]
 
 
 # ---- refinement

@@ -91,6 +91,17 @@ def register_parser(subparsers):
                         "are built on the GPU too (csrc/k_prog_tree.inc: the same exact UPGMA with the same tie rule, weighted with "
                         "--collapse-identical), on the distance tables where they are; only the merges come back.  The same bytes.  "
                         "Off by default")
+    from ..from_msa import star_align                   # (its constants: the parser states them, it launches nothing)
+    p.add_argument("--refine-tree", dest="refine_tree", action="store", type=int, nargs="?", const=star_align.TREE_REFINE_DEFAULT, default=None,
+                   metavar="N",
+                   help=f"(this implementation) with --unaligned --progressive: after the last merge every locus of "
+                        f"{star_align.TREE_REFINE_MIN_LEAVES} to {star_align.TREE_REFINE_MAX_LEAVES} leaves gets up to N passes "
+                        f"(1-{star_align.TREE_REFINE_MAX}; --refine-tree alone: {star_align.TREE_REFINE_DEFAULT}) of tree-dependent "
+                        "refinement on the GPU: the MSA is cut at "
+                        "an edge of its guide tree, the two halves are realigned as profiles, and the result is kept only if it "
+                        "raises the locus's sum-of-pairs objective (star_align.py, Tree refinement), so a locus no step improves "
+                        "keeps its --progressive bytes.  --refine runs after it, --band and --device-tree give the same bytes, with "
+                        "--collapse-identical equal sequences keep equal rows.  Off by default")
     p.set_defaults(func=run, check=check_options)
     return p
 
@@ -111,6 +122,12 @@ def check_options(args, parser):
         parser.error("--collapse-identical needs --unaligned")
     if getattr(args, "device_tree", False) and not getattr(args, "progressive", False):
         parser.error("--device-tree needs --progressive")
+    if getattr(args, "refine_tree", None) is not None:
+        if not getattr(args, "progressive", False):
+            parser.error("--refine-tree needs --progressive")
+        from ..from_msa import star_align
+        if not 1 <= args.refine_tree <= star_align.TREE_REFINE_MAX:
+            parser.error(f"--refine-tree takes 1 to {star_align.TREE_REFINE_MAX} passes, not {args.refine_tree}")
     if getattr(args, "refine", None) is not None:
         if not args.unaligned:
             parser.error("--refine needs --unaligned")
@@ -613,16 +630,19 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
     progression = []
     collapse = bool(getattr(options, "collapse_identical", False))
     device_tree = bool(getattr(options, "device_tree", False))
+    refine_tree = int(getattr(options, "refine_tree", None) or 0)
+    tree_refinement = []
     for lo in range(0, len(mine), STAR_CHUNK):
         t0 = time.perf_counter()
         recs = [star_align.read_unaligned(f) for f in mine[lo:lo + STAR_CHUNK]]
         t1 = time.perf_counter()
         msas = star_align.star_msas(be, recs, names=loci[lo:lo + STAR_CHUNK], adjust_direction=adjust, orientation=orientation,
-                                    **(dict(band=True) if band else {}), **(dict(timings=counters) if band or collapse or device_tree else {}),
+                                    **(dict(band=True) if band else {}), **(dict(timings=counters) if band or collapse or device_tree or refine_tree else {}),
                                     **(dict(collapse=True) if collapse else {}),
                                     **(dict(refine=refine, refinement=refinement) if refine else {}),
                                     **(dict(progressive=True, progression=progression) if progressive else {}),
-                                    **(dict(device_tree=True) if device_tree else {}))
+                                    **(dict(device_tree=True) if device_tree else {}),
+                                    **(dict(refine_tree=refine_tree, tree_refinement=tree_refinement) if refine_tree else {}))
         t2 = time.perf_counter()
         for locus, m in zip(loci[lo:lo + STAR_CHUNK], msas):
             path = out_dir / f"{locus}.fa"
@@ -643,6 +663,11 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
         logger.info(f"rank {rank}: --progressive --band: {counters.get('prog_band_merges', 0)} merges, "
                     f"{counters.get('prog_band_second_passes', 0)} second passes, {counters.get('prog_band_full_merges', 0)} sent to the "
                     f"full DP, {counters.get('prog_band_cells', 0)} of {counters.get('prog_band_full_cells', 0)} DP cells computed")
+    if refine_tree:
+        logger.info(f"rank {rank}: --refine-tree {refine_tree}: {sum(1 for t in tree_refinement if t and t[1])} loci refined, "
+                    f"{counters.get('tree_refine_steps', 0)} steps tried, {counters.get('tree_refine_accepted', 0)} accepted, "
+                    f"{counters.get('tree_refine_skipped', 0)} skipped, {counters.get('tree_refine_above_cap', 0)} loci above the cap of "
+                    f"{star_align.TREE_REFINE_MAX_LEAVES} leaves")
     if refine:
         logger.info(f"rank {rank}: --refine {refine}: {sum(1 for a, _, _ in refinement if a)} loci refined, "
                     f"{sum(a for a, _, _ in refinement)} rounds accepted, {sum(1 for a, _, _ in refinement if not a)} loci left as the star MSA")

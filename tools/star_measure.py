@@ -27,6 +27,9 @@ an earlier record of the locus picked at random (seeded): loci with a known shar
 `--device-tree` (with --progressive): the guide trees on the device (`from_msa --unaligned --progressive --device-tree`); the line
 then also gives tree_device_loci.  Every --progressive line gives tree_plan_s, the part of tree_s spent on the host's plan (without
 --device-tree: the host's UPGMA and the plan).
+`--refine-tree [N]` (with --progressive): tree-dependent refinement (`from_msa --unaligned --progressive --refine-tree`; N passes,
+default 1); the line then also gives tree_refine_s, the loci with a step, the steps tried, accepted and skipped, the loci above the
+cap, the loci changed and the total objective S before and after the stage.
 `--no-prg`: the PRG build over the MSAs written is left out (no prg_build_s): for runs that compare the alignment stages only."""
 import hashlib
 import json
@@ -65,7 +68,14 @@ dup = float(sys.argv[sys.argv.index("--dup") + 1]) if "--dup" in sys.argv else 0
 device_tree = "--device-tree" in sys.argv
 if device_tree and not progressive:
     sys.exit("--device-tree needs --progressive")
-prog_kw = dict(progressive=True, **(dict(device_tree=True) if device_tree else {})) if progressive else {}
+refine_tree = None
+if "--refine-tree" in sys.argv:
+    nxt = sys.argv[sys.argv.index("--refine-tree") + 1:][:1]
+    refine_tree = int(nxt[0]) if nxt and nxt[0].isdigit() else sa.TREE_REFINE_DEFAULT
+    if not progressive:
+        sys.exit("--refine-tree needs --progressive")
+prog_kw = dict(progressive=True, **(dict(device_tree=True) if device_tree else {}),
+               **(dict(refine_tree=refine_tree) if refine_tree else {})) if progressive else {}
 
 
 def diverged_seqs(seed):
@@ -117,8 +127,10 @@ try:
     orientation = []
     refinement = []
     progression = []
+    tree_refinement = []
     msas = sa.star_msas(be, recs, timings=timings, adjust_direction=flip is not None, orientation=orientation, band=band, refine=refine,
                         refinement=refinement, **(dict(prog_kw, progression=progression) if progressive else {}),
+                        **(dict(tree_refinement=tree_refinement) if refine_tree else {}),
                         **(dict(collapse=True) if collapse else {}))
     t_star = time.perf_counter() - t0
     t0 = time.perf_counter()
@@ -148,6 +160,10 @@ try:
         built = [(n, r) for n, r, star in progression if not star]
         extra.update(progressive=True, device_tree=device_tree, loci_built=len(built), merges=sum(n - 1 for n, _ in built), max_rounds=max((r for _, r in built), default=0), mean_rounds=round(sum(r for _, r in built) / max(1, len(built)), 2),
                      loci_left_to_star=len(progression) - len(built))
+    if refine_tree:
+        done = [t for t in tree_refinement if t]
+        extra.update(refine_tree=refine_tree, tree_loci_changed=sum(1 for t in done if t[1]), tree_s_before=sum(t[3] for t in done),
+                     tree_s_after=sum(t[4] for t in done))
     if objective:
         import numpy as np
         s_total = 0
