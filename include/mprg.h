@@ -798,6 +798,19 @@ int mprg_prog_tree(const uint32_t *shared, long long shared_words, const int64_t
                    const int64_t *loci, int n_loci, const int32_t *weights, int64_t *workspace, long long workspace_words,
                    int32_t *merges, long long merges_words, int32_t *status, void *stream);
 
+/* `--progressive --collapse-identical --large-loci --device-tree`: the same tree for weight sums up to 2^20 (the spec: star_align.py,
+ * "Large loci").
+ * mprg_prog_tree_wide: mprg_prog_tree's arguments, tables, merges, workspace need and status codes; the same merges wherever
+ *   mprg_prog_tree builds a locus.  What differs is the bound: a leaf's weight from 1 to 2^20, a locus's weight sum at most
+ *   2^20 = 1 048 576 and at most 4 096 leaves; a weight below 1, a weight sum above 2^20 or more than 4 096 leaves is
+ *   MPRG_PG_BAD_ITEM, nothing else written.  With |U| + |V| <= 2^20 a sum of w_a w_b D(a, b) is at most 2^54 and stays int64, a
+ *   denominator |U| |V| is at most 2^38 and is held in 64 bits, and the cross products, at most 2^92, are compared in 128 bits:
+ *   integers only, exact.  Multiplying every weight of a locus by a constant does not change its merges.  One workgroup per locus,
+ *   8.2 KB of LDS. */
+int mprg_prog_tree_wide(const uint32_t *shared, long long shared_words, const int64_t *nw, const int64_t *seqs, long long n_seqs,
+                        const int64_t *loci, int n_loci, const int32_t *weights, int64_t *workspace, long long workspace_words,
+                        int32_t *merges, long long merges_words, int32_t *status, void *stream);
+
 /* `--progressive --refine-tree`: a progressive MSA cut at a guide-tree edge, the two halves realigned as profiles (the spec:
  * star_align.py, "Tree refinement").  Texts and bufs are mprg_prog_columns'.
  * mprg_tree_split: items: n_items x MPRG_TS_ITEM_FIELDS int64 {buffer, offset of the R x W text in it, R >= 2, W >= 1, offset of

@@ -123,6 +123,8 @@ SIGNATURES = {
                                            ctypes.c_longlong, c_void_p, c_void_p]),
     "mprg_prog_tree": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, c_void_p,
                                ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
+    "mprg_prog_tree_wide": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, c_void_p,
+                                    ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
     "mprg_tree_split": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong,
                                 c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p]),
     "mprg_tree_objective": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_void_p,

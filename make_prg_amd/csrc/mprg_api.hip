@@ -24,6 +24,7 @@
 #include "k_prog_band.inc"
 #include "k_collapse.inc"
 #include "k_prog_tree.inc"
+#include "k_prog_tree_wide.inc"
 #include "k_tree_refine.inc"
 #include "host_encoders.inc"
 #include "host_batch.inc"
@@ -761,6 +762,15 @@ int mprg_prog_tree(const uint32_t *shared, long long shared_words, const int64_t
   LAUNCH(k_prog_tree, n_loci, PG_THREADS, stream, shared, shared_words, nw, seqs, n_seqs, loci, weights, workspace, workspace_words,
          merges, merges_words, status);      // a workgroup per locus
   return check_launch("k_prog_tree");
+}
+
+int mprg_prog_tree_wide(const uint32_t *shared, long long shared_words, const int64_t *nw, const int64_t *seqs, long long n_seqs,
+                        const int64_t *loci, int n_loci, const int32_t *weights, int64_t *workspace, long long workspace_words,
+                        int32_t *merges, long long merges_words, int32_t *status, void *stream) {
+  if (n_loci <= 0) return 0;
+  LAUNCH(k_prog_tree_wide, n_loci, PG_THREADS, stream, shared, shared_words, nw, seqs, n_seqs, loci, weights, workspace,
+         workspace_words, merges, merges_words, status);      // a workgroup per locus
+  return check_launch("k_prog_tree_wide");
 }
 
 int mprg_tree_split(const int64_t *bufs, int n_bufs, const int64_t *items, int n_items, const int32_t *work, int n_work,

@@ -20,6 +20,10 @@ With `--refine-tree` (and `--progressive`) the progressive MSA is then cut at th
 two halves realigned as profiles; a realignment is kept if it raises the objective (Tree refinement below; kernels in
 csrc/k_tree_refine.inc, C ABI: mprg_tree_split / mprg_tree_objective).
 
+With `--large-loci` (and `--progressive --collapse-identical`) the leaf limit of the progressive pass counts classes, not records: a
+locus of up to 2^20 records over at most 4 096 distinct sequences is built progressively (Large loci below; kernel:
+csrc/k_prog_tree_wide.inc, C ABI: mprg_prog_tree_wide).
+
 It is NOT MAFFT.  PRGs built from these alignments differ from PRGs built from a MAFFT alignment of the same sequences.
 
 Spec (the kernels and tests/star_ref.py follow it bit for bit)
@@ -167,7 +171,7 @@ reverse-complemented copy of it fall into one class.
             representatives only.  The tree is exact UPGMA, as above, with |U| = sum of w over U's leaves and dist(U, V) = sum over a
             in U, b in V of w_a w_b D(a, b) / (|U| |V|), compared by cross-multiplication; keys and the tie rule are unchanged.  A
             locus with more than PROG_MAX_LEAVES non-empty RECORDS (not classes) still gets the star MSA and is reported: the 2^60
-            bound stays where it is.  The merge of a node's two children takes Y as the child with the larger weight sum, on equal
+            bound stays where it is (Large loci below counts classes instead).  The merge of a node's two children takes Y as the child with the larger weight sum, on equal
             sums the one with the lower key.  Every count, P, Dc, Ic and R_X are those Progressive gives for the node's matrix with
             row r written w_r times; R is the weight sum (mprg_prog_columns_weighted; the DP kernels, the band certificate and
             pg_div work on such profiles as they are: a weighted sum is a sum of R_X terms).  A node's text holds one row per
@@ -179,6 +183,34 @@ reverse-complemented copy of it fall into one class.
             words; the star pass and the progressive one take the class tables.  The progressive pass runs on the chunk's tables
             with the representatives only (the distance tables cover them alone), with the weights beside them; the last
             mprg_prog_rows launch names the representative's root row as the source of every member's output row.
+
+Large loci (only with progressive, collapse and large_loci; integers only; tests/large_ref.py states it in plain Python; kernel:
+csrc/k_prog_tree_wide.inc, C ABI: mprg_prog_tree_wide).  Progressive counts its leaf limit in records, so a core gene of 20 000 genomes
+with forty alleles gets the star MSA although its tree has forty leaves.  Here the limit counts leaves.
+  Constant. PROG_MAX_RECORDS = 2^20 = 1 048 576: PG_MAX_ROWS, the weight sum up to which mprg_prog_columns_weighted, pg_div, the DP
+            kernels, the band certificate, mprg_prog_rows and mprg_tree_objective are specified.
+  Rule.     A locus is built progressively iff its number of leaves, Collapse's classes of non-empty records (counted after
+            Orientation when adjust_direction is on), is at most max_leaves (PROG_MAX_LEAVES unless given) AND its number of
+            records, empty ones included, is at most max_records (PROG_MAX_RECORDS unless given).  Any other locus gets what it
+            gets today: the star MSA, byte for byte what collapse alone gives, and (non-empty records, 0, True) in progression.
+  Unchanged.  Tree, Merge and Output are Collapse's: the weighted UPGMA with its keys and tie rule, Y the child with the larger
+            weight sum, every record its representative's row.  Only the bound moves.
+  Bound.    With |U| + |V| <= 2^20: |U| |V| <= 2^38, a sum over a in U, b in V of w_a w_b D(a, b) <= 65 536 |U| |V| <= 2^54, and a single
+            entry w_a w_b D(a, b) is below 2^56 whatever the two weights (<= 2^54 for two leaves of one locus).  So the sums stay in
+            int64, a denominator needs more than 32 bits, and a cross product, at most 2^92, needs 128: mprg_prog_tree_wide
+            compares in unsigned 128-bit integers, the host's prog_tree in Python integers.
+  Never fails.  The run never fails on a locus the star pass aligns.  A later stage with a bound of its own that such a locus
+            cannot meet skips it and reports that by its own Limit rule: Tree refinement leaves out a locus with
+            (weight sum + E)^2 W > 2^58 (mprg_tree_objective's bound) and a locus above its leaf cap.
+  Promised (tested): a locus of at most max_leaves records gives the bytes it gives without large_loci; multiplying every weight of
+            a tree by a constant does not change the tree; band, device_tree and the host tree give the same bytes; equal sequences
+            get equal rows; every row with its gaps removed is its input sequence.
+  Host side: the classes exist only after _orient and _collapse, inside a chunk, so the decision is made there: the loci of more
+            than max_records records go to the star chunks beforehand, every other locus to a progressive chunk, which counts
+            classes per locus from Collapse's own table and, where some locus is over max_leaves, runs the star pass over those and
+            the progressive pass over the others, both on the chunk's code buffer and class table (_star_chunk_parts).  With
+            device_tree the loci whose weight sum exceeds PROG_MAX_LEAVES form budget groups of their own, whose distances launch is
+            followed by mprg_prog_tree_wide; all others go to mprg_prog_tree as before.
 
 Tree refinement (only with progressive and refine_tree = N > 0; integers only; tests/treerefine_ref.py states it in plain Python;
 kernels: csrc/k_tree_refine.inc, C ABI: mprg_tree_split / mprg_tree_objective).  Progressive never looks back at a merge, and
@@ -274,6 +306,7 @@ RF_LOCUS_FIELDS, RF_ROW_FIELDS = 4, 3     # MPRG_RF_LOCUS_FIELDS, MPRG_RF_ROW_FI
 RF_STATUS = {1: "a locus's ranges outside the buffers", 2: "a row or tile out of range", 3: "the profile or the output outside its buffer"}
 REFINE_DEFAULT, REFINE_MAX = 2, 16        # rounds of `--refine` alone, and the most it takes
 PROG_MAX_LEAVES = 4096                    # the spec's leaf limit of a progressive locus
+PROG_MAX_RECORDS = 1 << 20                # the spec's record limit of a large locus (Large loci): PG_MAX_ROWS of csrc/k_prog.inc
 PROG_SCALE = 1 << 16                      # D = PROG_SCALE - floor(PROG_SCALE s / m)
 PG_ITEM_FIELDS, PG_PAIR_FIELDS, PG_ROW_FIELDS = 6, 6, 8   # MPRG_PG_ITEM_FIELDS, MPRG_PG_PAIR_FIELDS, MPRG_PG_ROW_FIELDS
 PG_BAND_PAIR_FIELDS = 8                   # MPRG_PG_BAND_PAIR_FIELDS
@@ -287,6 +320,8 @@ TREE_REFINE_DEFAULT, TREE_REFINE_MAX = 1, 4   # passes of `--refine-tree` alone,
 PG_STATUS = {1: "an index, a tile or a source range outside its table or buffer", 2: "ops, widths and cells that do not fit each other",
              3: "the output outside its buffer"}
 TREE_STATUS = {1: "a range outside its buffer, a leaf's weight below 1 or a weight sum above 4 096", 3: "the workspace outside its buffer"}
+WIDE_TREE_STATUS = {1: "a range outside its buffer, a leaf's weight below 1, a weight sum above 2^20 or more than 4 096 leaves",
+                    3: "the workspace outside its buffer"}
 _GAP = ord("-")
 _ASCII = np.frombuffer(b"ACGT-RYKMSWN", np.uint8)
 
@@ -367,7 +402,8 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
               adjust_direction: bool = False, orientation: Optional[list] = None, band=False, refine: int = 0,
               refinement: Optional[list] = None, progressive: bool = False, progression: Optional[list] = None,
               max_leaves: Optional[int] = None, collapse: bool = False, device_tree: bool = False, refine_tree: Optional[int] = None,
-              tree_refinement: Optional[list] = None, tree_refine_max_leaves: int = TREE_REFINE_MAX_LEAVES) -> List[MSA]:
+              tree_refinement: Optional[list] = None, tree_refine_max_leaves: int = TREE_REFINE_MAX_LEAVES, large_loci: bool = False,
+              max_records: Optional[int] = None) -> List[MSA]:
     """loci: per locus its records as (title, sequence).  Returns the loci's centre-star MSAs (ids: the titles' first words,
     descriptions: the titles).  names: the loci's names for error messages (default: their indices).  timings: a dict that
     receives the wall seconds of the stages (orient, centre, pairs, merge: each ends at a download, so includes its kernels).
@@ -397,9 +433,20 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
     the loci built progressively with 4 to tree_refine_max_leaves leaves; before the rows go into input order, so before refine.
     None: nothing launches differently.  tree_refinement: a list that then receives per locus (steps tried: every step visited,
     accepted, skipped: the spec's Limit, S before, S after), None for a locus left to the star pass.  timings also receives
-    tree_refine_s and tree_refine_loci, tree_refine_steps, tree_refine_accepted, tree_refine_skipped, tree_refine_above_cap."""
+    tree_refine_s and tree_refine_loci, tree_refine_steps, tree_refine_accepted, tree_refine_skipped, tree_refine_above_cap
+    (and tree_refine_over_bound: loci left out because mprg_tree_objective's bound on rows^2 W does not hold for them).
+    large_loci: only with progressive and collapse (else a ValueError): the spec's Large loci: a locus is built progressively iff
+    its classes of non-empty records number at most max_leaves and its records at most max_records (PROG_MAX_RECORDS unless
+    given); the others get the star MSA and (non-empty records, 0, True) in progression, as without it.  With device_tree the
+    trees of the loci whose records exceed PROG_MAX_LEAVES are built by mprg_prog_tree_wide.  timings also receives large_loci (the
+    loci of more than max_leaves non-empty records built progressively), large_records (their records) and large_fallbacks (the
+    loci over either limit).  False: nothing launches or computes differently."""
     if device_tree and not progressive:
         raise ValueError("device_tree: only with progressive")
+    if large_loci and not (progressive and collapse):
+        raise ValueError("large_loci: only with progressive and collapse")
+    if max_records is not None and not (large_loci and 0 <= int(max_records) <= PROG_MAX_RECORDS):
+        raise ValueError(f"max_records: only with large_loci, and at most {PROG_MAX_RECORDS}, not {max_records!r}")
     if refine_tree is not None:
         if not progressive:
             raise ValueError("refine_tree: only with progressive")
@@ -417,7 +464,8 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
     if progressive:
         return _progressive_msas(backend, loci, codes, names, budget_bytes, chunk_bytes, timings, adjust_direction, orientation, band,
                                  int(refine), refinement, progression, PROG_MAX_LEAVES if max_leaves is None else int(max_leaves), bool(collapse),
-                                 bool(device_tree), int(refine_tree or 0), tree_refinement, int(tree_refine_max_leaves))
+                                 bool(device_tree), int(refine_tree or 0), tree_refinement, int(tree_refine_max_leaves),
+                                 (PROG_MAX_RECORDS if max_records is None else int(max_records)) if large_loci else None)
     return [m for lo, hi in _chunks(codes, chunk_bytes)
             for m in _star_chunk(backend, loci[lo:hi], codes[lo:hi], names[lo:hi], budget_bytes, timings, adjust_direction, orientation, band,
                                  int(refine), refinement, collapse=bool(collapse))]
@@ -425,14 +473,17 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
 
 def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings, adjust_direction, orientation, band, refine, refinement,
                       progression, max_leaves, collapse=False, device_tree=False, refine_tree=0, tree_refinement=None,
-                      tree_max_leaves=TREE_REFINE_MAX_LEAVES) -> List[MSA]:
+                      tree_max_leaves=TREE_REFINE_MAX_LEAVES, max_records=None) -> List[MSA]:
     """star_msas with progressive: the loci within the leaf limit through the progressive chunks, the others through the star
-    chunks, the results (and what the caller's lists receive) back in the loci's order."""
+    chunks, the results (and what the caller's lists receive) back in the loci's order.  max_records (the spec's Large loci; None:
+    without it): only the loci of more records go to the star chunks here; the progressive chunks count every locus's classes
+    once Collapse has made them and send those above max_leaves through the star pass themselves."""
     n_leaves = [sum(1 for c in cs if len(c)) for cs in codes]
     out = [None] * len(loci)
     got = {k: [None] * len(loci) for k in ("orientation", "refinement", "progression", "tree_refinement")}
+    limits = None if max_records is None else (max_leaves, max_records)
     for prog in (True, False):
-        sel = [l for l in range(len(loci)) if (n_leaves[l] <= max_leaves) == prog]
+        sel = [l for l in range(len(loci)) if (n_leaves[l] <= max_leaves if limits is None else len(codes[l]) <= max_records) == prog]
         sub = [codes[l] for l in sel]
         ori, ref, pro, tre, msas = [], [], [], [], []
         for lo, hi in _chunks(sub, chunk_bytes):
@@ -440,7 +491,7 @@ def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings
             msas.extend(_star_chunk(be, [loci[l] for l in idx], sub[lo:hi], [names[l] for l in idx], budget_bytes, timings, adjust_direction,
                                     ori if orientation is not None else None, band, refine, ref if refinement is not None else None,
                                     prog, pro, collapse, device_tree and prog, refine_tree if prog else 0,
-                                    tre if tree_refinement is not None else None, tree_max_leaves))
+                                    tre if tree_refinement is not None else None, tree_max_leaves, limits if prog else None))
         if not prog:
             pro = [(n_leaves[l], 0, True) for l in sel]
         for k, l in enumerate(sel):
@@ -448,6 +499,11 @@ def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings
             for key, vals in (("orientation", ori), ("refinement", ref), ("progression", pro), ("tree_refinement", tre)):
                 if vals:
                     got[key][l] = vals[k]
+    if limits is not None:
+        built = [l for l in range(len(loci)) if n_leaves[l] > max_leaves and not got["progression"][l][2]]
+        add_to(timings, "large_loci", len(built))
+        add_to(timings, "large_records", sum(len(codes[l]) for l in built))
+        add_to(timings, "large_fallbacks", sum(1 for p in got["progression"] if p[2]))
     for key, dest in (("orientation", orientation), ("refinement", refinement), ("progression", progression),
                       ("tree_refinement", tree_refinement)):
         if dest is not None:
@@ -457,9 +513,10 @@ def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings
 
 def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direction=False, orientation=None, band=None, refine=0,
                 refinement=None, progressive=False, progression=None, collapse=False, device_tree=False, refine_tree=0,
-                tree_refinement=None, tree_max_leaves=TREE_REFINE_MAX_LEAVES) -> List[MSA]:
+                tree_refinement=None, tree_max_leaves=TREE_REFINE_MAX_LEAVES, limits=None) -> List[MSA]:
     """One chunk: pack, optionally orient, optionally collapse, the star pass or the progressive one (with its tree refinement),
-    optionally refine, collect."""
+    optionally refine, collect.  limits (the spec's Large loci; only with progressive and collapse): (max_leaves, max_records): the
+    loci with more classes of non-empty records, or more records, go through the star pass."""
     laps = _Laps(timings)
     chunk = _pack(be, codes, names, [[t for t, _ in recs] for recs in loci])
     if adjust_direction:
@@ -468,6 +525,52 @@ def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direc
             orientation.extend(result)
         laps.lap("orient_s")
     classes = _collapse(be, chunk, laps) if collapse else None
+    if limits is not None:
+        n_classes = np.add.reduceat(((classes.weight > 0) & (chunk.lens > 0)).astype(np.int64), chunk.first)
+        build = (n_classes <= limits[0]) & (chunk.counts <= limits[1])
+        if not build.all():
+            return _star_chunk_parts(be, chunk, classes, build, budget_bytes, laps, band, refine, refinement, progression, device_tree,
+                                     refine_tree, tree_refinement, tree_max_leaves)
+    return _star_chunk_rest(be, chunk, classes, budget_bytes, laps, band, refine, refinement, progressive, progression, device_tree,
+                            refine_tree, tree_refinement, tree_max_leaves)
+
+
+def _star_chunk_parts(be, chunk: Chunk, classes, build, budget_bytes, laps, band, refine, refinement, progression, device_tree,
+                      refine_tree, tree_refinement, tree_max_leaves) -> List[MSA]:
+    """_star_chunk behind Collapse for a chunk of which only the loci `build` (a bool per locus) are built progressively (the spec's
+    Large loci): those as one chunk through the progressive pass, the others as one through the star pass, both over the same code
+    buffer and the classes already made; the MSAs, and what the caller's lists receive, back in the chunk's order."""
+    n_filled = np.add.reduceat((chunk.lens > 0).astype(np.int64), chunk.first)
+    msas, ref, pro, tre = ([None] * chunk.n_loci for _ in range(4))
+    for prog in (True, False):
+        sel = np.nonzero(build == prog)[0]
+        if not len(sel):
+            continue
+        rec = _ranges(chunk.first[sel], chunk.counts[sel])      # the part's records in the chunk's table, and its own tables
+        at = np.full(len(chunk.lens), -1, np.int64)
+        at[rec] = np.arange(len(rec))
+        part = chunk._replace(names=[chunk.names[l] for l in sel], titles=[chunk.titles[l] for l in sel], codes=[chunk.codes[l] for l in sel],
+                              lens=chunk.lens[rec], seq_off=chunk.seq_off[rec], first=exclusive_sum(chunk.counts[sel]), counts=chunk.counts[sel])
+        got = [[], [], []]
+        out = _star_chunk_rest(be, part, Classes(at[classes.rep[rec]], classes.weight[rec]), budget_bytes, laps, band, refine, got[0], prog,
+                               got[1], device_tree and prog, refine_tree if prog else 0, got[2], tree_max_leaves)
+        if not prog:
+            got[1] = [(int(n_filled[l]), 0, True) for l in sel]
+        for k, l in enumerate(sel.tolist()):
+            msas[l] = out[k]
+            for dest, vals in zip((ref, pro, tre), got):
+                if vals:
+                    dest[l] = vals[k]
+    for dest, vals, wanted in ((refinement, ref, refine), (progression, pro, True), (tree_refinement, tre, refine_tree)):
+        if dest is not None and wanted:
+            dest.extend(vals)
+    return msas
+
+
+def _star_chunk_rest(be, chunk: Chunk, classes, budget_bytes, laps, band, refine, refinement, progressive, progression, device_tree,
+                     refine_tree, tree_refinement, tree_max_leaves) -> List[MSA]:
+    """_star_chunk behind Collapse: the star pass or the progressive one (with its tree refinement), optionally refine, collect."""
+    timings = laps.timings
     text = (_progressive(be, chunk, budget_bytes, band, laps, progression, classes, device_tree, refine_tree, tree_refinement,
                          tree_max_leaves) if progressive else
             _star_pass(be, chunk, budget_bytes, band, laps, classes))
@@ -820,14 +923,21 @@ def _prog_trees(be, chunk: Chunk, sel, budget_bytes, weights=None):
     """The spec's Tree of the loci `sel` of a chunk on the device, in groups whose m x m tables and tree workspaces fit budget_bytes:
     per group one mprg_prog_distances launch and one mprg_prog_tree launch over the tables it left on the device; the status words
     and the merges are all that is downloaded.  Per locus its merges as prog_tree gives them.  weights: per record of the chunk's
-    tables how many times it counts (the spec's Collapse)."""
+    tables how many times it counts (the spec's Collapse).  The loci whose weight sum exceeds PROG_MAX_LEAVES (the spec's Large
+    loci) form groups of their own, whose trees mprg_prog_tree_wide builds."""
     lens, first, counts = chunk.lens, chunk.first, chunk.counts
     out = {}
     d_seqs = be.upload(np.stack([chunk.seq_off, lens], 1).reshape(-1))
     d_weights = None if weights is None else be.upload(np.asarray(weights, np.int32))
     n_leaves = np.add.reduceat((lens > 0).astype(np.int64), first)
-    for lo, hi in pa.budget_groups(prog_tree_bytes(counts[sel]), budget_bytes):
-        grp = sel[lo:hi]
+    # the spec's Large loci: a locus whose weight sum exceeds mprg_prog_tree's bound goes to mprg_prog_tree_wide, in groups (and so
+    # in launches) of such loci alone; without one nothing launches differently
+    wsum = n_leaves if weights is None else np.add.reduceat(np.where(lens > 0, np.asarray(weights, np.int64), 0), first)
+    wide = wsum[sel] > PROG_MAX_LEAVES
+    groups = [(part[lo:hi], entry, table)
+              for part, entry, table in ((sel[~wide], "mprg_prog_tree", TREE_STATUS), (sel[wide], "mprg_prog_tree_wide", WIDE_TREE_STATUS))
+              if len(part) for lo, hi in pa.budget_groups(prog_tree_bytes(counts[part]), budget_bytes)]
+    for grp, entry, table in groups:
         m, toff, words, d_shared, d_nw, d_status, n_work = _distances_launch(be, chunk, d_seqs, grp)
         n_merges = np.maximum(n_leaves[grp] - 1, 0)
         moff = 2 * exclusive_sum(n_merges)
@@ -835,11 +945,11 @@ def _prog_trees(be, chunk: Chunk, sel, budget_bytes, weights=None):
         ttab = np.stack([first[grp], m, toff, exclusive_sum(ws_words), moff], 1).astype(np.int64)
         d_ttab, d_ws = be.upload(ttab), be.empty(8 * int(ws_words.sum()))
         d_merges, d_tstatus = be.empty(8 * int(n_merges.sum())), be.empty(4 * len(grp))
-        be.call("mprg_prog_tree", be.ptr(d_shared), words, be.ptr(d_nw), be.ptr(d_seqs), len(lens), be.ptr(d_ttab), len(grp),
+        be.call(entry, be.ptr(d_shared), words, be.ptr(d_nw), be.ptr(d_seqs), len(lens), be.ptr(d_ttab), len(grp),
                 0 if d_weights is None else be.ptr(d_weights), be.ptr(d_ws), int(ws_words.sum()), be.ptr(d_merges), 2 * int(n_merges.sum()),
                 be.ptr(d_tstatus), be.stream, work=float((m * m).sum() * 24.0))
         _check(be.download(d_status, np.int32, n_work), "mprg_prog_distances", PG_STATUS)
-        _check(be.download(d_tstatus, np.int32, len(grp)), "mprg_prog_tree", TREE_STATUS, "locus")
+        _check(be.download(d_tstatus, np.int32, len(grp)), entry, table, "locus")
         merges = be.download(d_merges, np.int32, 2 * int(n_merges.sum())).reshape(-1, 2)
         for k, l in enumerate(grp.tolist()):
             out[l] = [tuple(p) for p in merges[moff[k] // 2:moff[k] // 2 + n_merges[k]].tolist()]
@@ -850,7 +960,8 @@ def prog_trees(backend, codes: Sequence[Sequence[np.ndarray]], weights: Optional
                budget_bytes: int = pa.DEFAULT_BUDGET_BYTES) -> List[List[Tuple[int, int]]]:
     """mprg_prog_distances and mprg_prog_tree over the loci (per locus its gap-free code arrays; an empty one is no leaf): per locus
     the spec's Tree as prog_tree gives it, the merges in order as (key(U), key(V)).  weights: per locus, per record, how many times
-    it counts (the spec's Collapse)."""
+    it counts (the spec's Collapse); a locus whose weights add up to more than PROG_MAX_LEAVES, up to PROG_MAX_RECORDS, is built by
+    mprg_prog_tree_wide (the spec's Large loci)."""
     chunk = _pack(backend, codes)
     flat = None if weights is None else np.concatenate([np.asarray(w, np.int64) for w in weights])
     got = _prog_trees(backend, chunk, np.arange(len(codes)), budget_bytes, flat)
@@ -882,6 +993,9 @@ def prog_tree(D: np.ndarray, leaves: Sequence[int], weights=None) -> List[Tuple[
     Q[iu] = S[iu]
     if weights is not None:                                     # S: sums of w_a w_b D(a, b); a cluster's size: its weight sum
         size = np.asarray(weights, np.int64).copy()            # (Q stays D: the quotient of w_a w_b D(a, b) by w_a w_b)
+        # int64 up to the spec's Large loci: sum w <= 2^20, so w_a w_b <= 2^38 off the diagonal and 2^40 on it (where D = 0), an
+        # entry w_a w_b D <= 2^54, a sum between two clusters <= 65 536 |U| |V| <= 2^54 and size[u] * size[v] <= 2^38; the cross
+        # products (up to 2^92) are made in Python integers
         S = S * np.outer(size, size)
     merges = []
     for _ in range(n - 1):
@@ -1316,13 +1430,21 @@ def _tree_refine(be, chunk: Chunk, plan, bufs, live, where, weights, passes, max
             if b and not live[b]:
                 bufs[b] = (None, 0)
 
-    S = tree_objective(be, _bufs_table(be, bufs), len(bufs), np.array([where[l, root[l]] for l in range(n_loci)], np.int64),
-                       [wl[l][order[l]] for l in range(n_loci)], empty)
+    # mprg_tree_objective's bound, rows^2 W <= 2^58: only a locus of the spec's Large loci can miss it (4 096 rows do not, below the
+    # DP's 10^6 columns); it is left out of the stage and reported with no step and S = 0
+    in_bound = np.array([(int(wl[l][order[l]].sum()) + int(empty[l])) ** 2 * where[l, root[l]][3] <= 1 << 58 for l in range(n_loci)], bool)
+    if not in_bound.all():
+        add_to(counters, "tree_refine_over_bound", int((~in_bound).sum()))
+    known = np.nonzero(in_bound)[0].tolist()
+    S = np.zeros(n_loci, np.int64)
+    if known:
+        S[known] = tree_objective(be, _bufs_table(be, bufs), len(bufs), np.array([where[l, root[l]] for l in known], np.int64),
+                                  [wl[l][order[l]] for l in known], empty[known])
     out = [[0, 0, 0, int(S[l]), int(S[l])] for l in range(n_loci)]
     n_lv = np.array([len(x) for x in leaves], np.int64)
     add_to(counters, "tree_refine_above_cap", int((n_lv > max_leaves).sum()))
     steps = {}                                                  # per refinable locus, per step: is the record a leaf of G?
-    for l in np.nonzero((n_lv >= TREE_REFINE_MIN_LEAVES) & (n_lv <= max_leaves))[0].tolist():
+    for l in np.nonzero((n_lv >= TREE_REFINE_MIN_LEAVES) & (n_lv <= max_leaves) & in_bound)[0].tolist():
         groups = tree_steps(trees[l])
         steps[l] = np.zeros((len(groups), int(counts[l])), bool)
         for s, g in enumerate(groups):

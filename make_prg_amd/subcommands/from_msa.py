@@ -77,7 +77,8 @@ def register_parser(subparsers):
                    help="(this implementation) with --unaligned: every locus's MSA is built progressively on the GPU instead of "
                         "centre-star: an exact UPGMA guide tree from 6-mer distances, then profile-profile merges up the tree "
                         "(star_align.py, Progressive); NOT MAFFT.  --adjust-direction runs first, --refine afterwards, --band computes "
-                        "the merges (and the refinement's realignments) over certified bands, the same bytes; a locus of more than 4096 non-empty records gets the centre-star MSA.  "
+                        "the merges (and the refinement's realignments) over certified bands, the same bytes; a locus of more than 4096 non-empty records gets the centre-star MSA "
+                        "(with --collapse-identical --large-loci: of more than 4096 distinct sequences, or more than 1048576 records).  "
                         "Off by default")
     p.add_argument("--collapse-identical", dest="collapse_identical", action="store_true", default=False,
                    help="(this implementation) with --unaligned: the records of a locus whose sequences are identical (after "
@@ -91,6 +92,12 @@ def register_parser(subparsers):
                         "are built on the GPU too (csrc/k_prog_tree.inc: the same exact UPGMA with the same tie rule, weighted with "
                         "--collapse-identical), on the distance tables where they are; only the merges come back.  The same bytes.  "
                         "Off by default")
+    p.add_argument("--large-loci", dest="large_loci", action="store_true", default=False,
+                   help="(this implementation) with --unaligned --progressive --collapse-identical: the leaf limit of --progressive "
+                        "counts distinct sequences, not records: a locus of up to 1048576 records over at most 4096 distinct non-empty "
+                        "sequences is built progressively (star_align.py, Large loci; with --device-tree its tree by "
+                        "csrc/k_prog_tree_wide.inc, which compares the averages in 128-bit integers); a locus over either limit gets the "
+                        "centre-star MSA as before, and a locus of at most 4096 records keeps its bytes.  Off by default")
     from ..from_msa import star_align                   # (its constants: the parser states them, it launches nothing)
     p.add_argument("--refine-tree", dest="refine_tree", action="store", type=int, nargs="?", const=star_align.TREE_REFINE_DEFAULT, default=None,
                    metavar="N",
@@ -122,6 +129,11 @@ def check_options(args, parser):
         parser.error("--collapse-identical needs --unaligned")
     if getattr(args, "device_tree", False) and not getattr(args, "progressive", False):
         parser.error("--device-tree needs --progressive")
+    if getattr(args, "large_loci", False):
+        if not getattr(args, "progressive", False):
+            parser.error("--large-loci needs --progressive")
+        if not getattr(args, "collapse_identical", False):
+            parser.error("--large-loci needs --collapse-identical")
     if getattr(args, "refine_tree", None) is not None:
         if not getattr(args, "progressive", False):
             parser.error("--refine-tree needs --progressive")
@@ -632,6 +644,7 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
     device_tree = bool(getattr(options, "device_tree", False))
     refine_tree = int(getattr(options, "refine_tree", None) or 0)
     tree_refinement = []
+    large_loci = bool(getattr(options, "large_loci", False))
     for lo in range(0, len(mine), STAR_CHUNK):
         t0 = time.perf_counter()
         recs = [star_align.read_unaligned(f) for f in mine[lo:lo + STAR_CHUNK]]
@@ -642,6 +655,7 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
                                     **(dict(refine=refine, refinement=refinement) if refine else {}),
                                     **(dict(progressive=True, progression=progression) if progressive else {}),
                                     **(dict(device_tree=True) if device_tree else {}),
+                                    **(dict(large_loci=True) if large_loci else {}),
                                     **(dict(refine_tree=refine_tree, tree_refinement=tree_refinement) if refine_tree else {}))
         t2 = time.perf_counter()
         for locus, m in zip(loci[lo:lo + STAR_CHUNK], msas):
@@ -680,6 +694,9 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
                     f"{max((r for _, r in built), default=0)} rounds at most, {len(progression) - len(built)} loci left to the star pass")
     if device_tree:
         logger.info(f"rank {rank}: --device-tree: {counters.get('tree_device_loci', 0)} loci's trees built on the device")
+    if large_loci:
+        logger.info(f"rank {rank}: --large-loci: {counters.get('large_loci', 0)} loci of more than {star_align.PROG_MAX_LEAVES} records built "
+                    f"progressively ({counters.get('large_records', 0)} records), {counters.get('large_fallbacks', 0)} over a limit")
     align_unaligned_inputs.timings = dict(read_s=t_read, align_s=t_align, write_s=t_write)
     return written
 

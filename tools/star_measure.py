@@ -30,6 +30,10 @@ then also gives tree_device_loci.  Every --progressive line gives tree_plan_s, t
 `--refine-tree [N]` (with --progressive): tree-dependent refinement (`from_msa --unaligned --progressive --refine-tree`; N passes,
 default 1); the line then also gives tree_refine_s, the loci with a step, the steps tried, accepted and skipped, the loci above the
 cap, the loci changed and the total objective S before and after the stage.
+`--records N` (with --diverged A): loci of many records over few alleles: every locus has N records, each of the locus's A diverged
+sequences once and then seeded picks among them, shuffled: the pan-genome core gene `--large-loci` is for.
+`--large-loci` (with --progressive --collapse-identical): the leaf limit counts distinct sequences (`from_msa --unaligned
+--progressive --collapse-identical --large-loci`); the line then also gives large_loci, large_records and large_fallbacks.
 `--no-prg`: the PRG build over the MSAs written is left out (no prg_build_s): for runs that compare the alignment stages only."""
 import hashlib
 import json
@@ -74,7 +78,13 @@ if "--refine-tree" in sys.argv:
     refine_tree = int(nxt[0]) if nxt and nxt[0].isdigit() else sa.TREE_REFINE_DEFAULT
     if not progressive:
         sys.exit("--refine-tree needs --progressive")
-prog_kw = dict(progressive=True, **(dict(device_tree=True) if device_tree else {}),
+records = int(sys.argv[sys.argv.index("--records") + 1]) if "--records" in sys.argv else 0
+if records and not diverged:
+    sys.exit("--records needs --diverged")
+large_loci = "--large-loci" in sys.argv
+if large_loci and not (progressive and collapse):
+    sys.exit("--large-loci needs --progressive and --collapse-identical")
+prog_kw = dict(progressive=True, **(dict(device_tree=True) if device_tree else {}), **(dict(large_loci=True) if large_loci else {}),
                **(dict(refine_tree=refine_tree) if refine_tree else {})) if progressive else {}
 
 
@@ -104,6 +114,10 @@ try:
     rng, flipped = random.Random(1), []
     for seed in range(n_loci):
         seqs = diverged_seqs(seed) if diverged else [r.decode().replace("-", "") for r in synth_rows(seed, *config_shape("C", seed))]
+        if records:
+            rrng = random.Random(2000003 + seed)
+            seqs = seqs + [rrng.choice(seqs) for _ in range(records - len(seqs))]
+            rrng.shuffle(seqs)
         if dup:
             drng = random.Random(1000003 + seed)
             for i in range(1, len(seqs)):
@@ -159,7 +173,7 @@ try:
     if progressive:
         built = [(n, r) for n, r, star in progression if not star]
         extra.update(progressive=True, device_tree=device_tree, loci_built=len(built), merges=sum(n - 1 for n, _ in built), max_rounds=max((r for _, r in built), default=0), mean_rounds=round(sum(r for _, r in built) / max(1, len(built)), 2),
-                     loci_left_to_star=len(progression) - len(built))
+                     loci_left_to_star=len(progression) - len(built), **(dict(large_loci_flag=True) if large_loci else {}))
     if refine_tree:
         done = [t for t in tree_refinement if t]
         extra.update(refine_tree=refine_tree, tree_loci_changed=sum(1 for t in done if t[1]), tree_s_before=sum(t[3] for t in done),
