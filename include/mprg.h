@@ -843,6 +843,28 @@ int mprg_tree_split(const int64_t *bufs, int n_bufs, const int64_t *items, int n
 int mprg_tree_objective(const int64_t *bufs, int n_bufs, const int64_t *items, int n_items, const int32_t *work, int n_work,
                         const int32_t *weights, long long weights_words, int64_t *sums, int32_t *status, void *stream);
 
+/* `--progressive --retree`: the guide tree rebuilt from the progressive MSA (the spec: star_align.py, "Retree").
+ * Texts and bufs are mprg_prog_columns'.
+ * mprg_prog_identities: items: n_items x MPRG_PI_ITEM_FIELDS int64 {buffer, offset of the R x W text in it, R >= 1, W >= 1, offset
+ *   of the item's R entries in `leaf` (int32 elements, leaf_words long), first, m, offset of the locus's m x m table in `shared`
+ *   (uint32 elements, shared_words long)}.  Row r of the text is record leaf[offset + r] of the locus, 0 <= . < m; `first` is the
+ *   locus's first sequence, an index into nw (int64, n_seqs long).  work: n_work x 2 int32 {item, row block q}: the rows
+ *   q B .. min(R, (q + 1) B) - 1 with B = MPRG_PI_BLOCK_ROWS; every block of every item once.
+ *   With nw'_r the number of cells of row r that are A, C, G or T (codes 0..3) and s'(r, r') the number of columns in which both
+ *   rows hold the same code and that code is 0..3 ('-' against '-', two equal ambiguity codes and N against N are no match): for
+ *   every row r of the block nw[first + leaf[r]] = nw'_r, and for every later row r' > r of the text, with a = leaf[r] and
+ *   b = leaf[r'], shared[table + min(a, b) m + max(a, b)] = s'(r, r').  So every pair is written once, by one workgroup, without
+ *   atomics, and s' <= min(nw'_a, nw'_b): the table and nw are what mprg_prog_tree(_wide) and star_align.prog_distance_matrix take
+ *   from mprg_prog_distances.  The diagonal, the part below it, and the rows, columns and nw entries of records that are not in
+ *   `leaf` are not written.  Two rows of an item with the same leaf index are the caller's error: the writes stay inside the table.
+ *   status: n_work int32: MPRG_PG_OK, or MPRG_PG_BAD_ITEM (an index, a block or the text outside its table or buffer, the leaf
+ *   entries outside leaf_words, a leaf index outside [0, m), first .. first + m outside n_seqs, the table outside shared_words):
+ *   nothing else written.  One workgroup per work item, 32 KB of LDS. */
+enum { MPRG_PI_ITEM_FIELDS = 8, MPRG_PI_BLOCK_ROWS = 16 };
+int mprg_prog_identities(const int64_t *bufs, int n_bufs, const int64_t *items, int n_items, const int32_t *work, int n_work,
+                         const int32_t *leaf, long long leaf_words, uint32_t *shared, long long shared_words, int64_t *nw,
+                         long long n_seqs, int32_t *status, void *stream);
+
 /* (f)-1 output encoders, HOST functions (host pointers), one pass over a PRG string as PrgBuilder emits it.
  * reference make_prg/utils/prg_encoder.py:44-91 and make_prg/utils/gfa.py:16-109.
  * mprg_prg_encode_host: out[n] receives the uint32 stream (A C G T -> 1 2 3 4, markers as integers, the closing

@@ -26,6 +26,7 @@
 #include "k_prog_tree.inc"
 #include "k_prog_tree_wide.inc"
 #include "k_tree_refine.inc"
+#include "k_prog_retree.inc"
 #include "host_encoders.inc"
 #include "host_batch.inc"
 
@@ -797,6 +798,15 @@ int mprg_tree_objective(const int64_t *bufs, int n_bufs, const int64_t *items, i
   if (n_work <= 0) return 0;
   LAUNCH(k_tree_objective, n_work, TS_THREADS, stream, bufs, n_bufs, items, n_items, work, weights, weights_words, sums, status);
   return check_launch("k_tree_objective");
+}
+
+int mprg_prog_identities(const int64_t *bufs, int n_bufs, const int64_t *items, int n_items, const int32_t *work, int n_work,
+                         const int32_t *leaf, long long leaf_words, uint32_t *shared, long long shared_words, int64_t *nw,
+                         long long n_seqs, int32_t *status, void *stream) {
+  if (n_work <= 0) return 0;
+  LAUNCH(k_prog_identities, n_work, PI_THREADS, stream, bufs, n_bufs, items, n_items, work, leaf, leaf_words, shared, shared_words, nw,
+         n_seqs, status);      // a workgroup per (item, row block)
+  return check_launch("k_prog_identities");
 }
 
 // ---- the recursion forest on the device (k_forest.inc); F: host array of MPRG_F_FIELDS int64 ------------------------------

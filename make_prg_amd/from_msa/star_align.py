@@ -24,6 +24,10 @@ With `--large-loci` (and `--progressive --collapse-identical`) the leaf limit of
 locus of up to 2^20 records over at most 4 096 distinct sequences is built progressively (Large loci below; kernel:
 csrc/k_prog_tree_wide.inc, C ABI: mprg_prog_tree_wide).
 
+With `--retree` (and `--progressive`) the guide tree is rebuilt from the progressive MSA itself, from the identities of its rows, and
+the locus is aligned again up the new tree; the new MSA is kept if it raises the objective (Retree below; kernel:
+csrc/k_prog_retree.inc, C ABI: mprg_prog_identities).
+
 It is NOT MAFFT.  PRGs built from these alignments differ from PRGs built from a MAFFT alignment of the same sequences.
 
 Spec (the kernels and tests/star_ref.py follow it bit for bit)
@@ -250,6 +254,48 @@ the objective rises.
             locus its row order (Y's leaves, then X's) and where its current text is; a buffer is dropped when no locus points to
             it.  No MSA text leaves the device during the stage.
 
+Retree (only with progressive and retree = N > 0; integers only; tests/retree_ref.py states it in plain Python; kernel:
+csrc/k_prog_retree.inc, C ABI: mprg_prog_identities).  The guide tree is built once, from 6-mer distances, which say little about how
+two sequences align and saturate on diverged sub-families; Tree refinement only re-cuts the edges of that same tree.  Here the
+distances are taken a second time, from the MSA the first tree built, a new tree is built from them and the locus aligned again
+(MAFFT's --retree 2, MUSCLE's stage 2, Clustal Omega's --iter).
+  Where.    After the last merge of Progressive, on the root's text: one row per leaf (with collapse one row per class, with the
+            class weights), before Tree refinement, before the rows are put into input order and before refine.  adjust_direction
+            has run before it.
+  Which loci.  Those built progressively with 3 or more leaves (two leaves have one tree).  A locus for which mprg_tree_objective's
+            bound does not hold ((weight sum + E)^2 W > 2^58) is left out and reported ("bound"), as Tree refinement does.  The run
+            never fails on a locus the progressive pass built.
+  Distance. Rows a and b are the leaves' rows of the current MSA A.  nw'_a: the cells of row a that are A, C, G or T (cell codes
+            0..3).  s'(a, b): the columns in which both rows hold the same code and that code is 0..3; '-' against '-' is no match,
+            nor are two equal ambiguity codes or N against N.  D'(a, b) = 65 536 - floor(65 536 s' / min(nw'_a, nw'_b)), and 65 536
+            when the minimum is 0.  So s' <= min(nw'_a, nw'_b): a table of s above the diagonal and a vector nw, exactly what
+            prog_distance_matrix, mprg_prog_tree and mprg_prog_tree_wide take from mprg_prog_distances; they are used unchanged.
+            It is the identity over the shorter sequence, and was chosen for that reason: the same shape, scale and bounds as
+            Progressive's D, so the tree code, its 2^60 (2^92) bounds and its tie rule need nothing new.
+  Tree.     Progressive's Tree on D'; Collapse's weighted tree when there are weights: exact, the same keys and tie rule; on the
+            host, or with device_tree on the device, a locus whose weight sum exceeds 4 096 by mprg_prog_tree_wide.
+  Iteration.  Up to N times per locus: (1) D' from the current MSA, and the tree T' on it.  (2) If T' has the same merge list as
+            the tree that built the current MSA the locus stops ("same"): no merge is run, a rebuild would reproduce the bytes.
+            (3) Otherwise the MSA A' is built from the leaves up T': Merge, the choice of Y and X and the row order are
+            Progressive's (Collapse's with weights).  (4) A' replaces A only if S(A') > S(A); otherwise the locus keeps A and stops
+            ("refused").  S is Tree refinement's Objective: rows count w_r times, the locus's E empty records as all-gap rows.
+  Limit.    A merge of the rebuild that Tree refinement's Limit would skip (W_X + W_Y >= 10^6, or a full-DP traceback beyond the
+            workspace budget) ends the locus's retree with the MSA it has ("limit").
+  Afterwards.  Tree refinement, if asked for, runs on the accepted MSA with the accepted tree's merges and row order; progression
+            reports the leaves and rounds of the tree that built the MSA that is written.
+  Promised (tested): every row with its gaps removed is its input sequence; no column is all gaps; S never falls; a locus that
+            stops "same" or "refused" at its first iteration has its progressive bytes; band, device_tree and the host tree give
+            the same bytes; with collapse equal sequences get equal rows and a locus without copies gets the bytes it gets without
+            collapse; with large_loci the large loci go through it like any other.
+  Host side (_retree, between _prog_rounds and _tree_refine): one mprg_tree_objective launch for S of the first MSAs; then per
+            iteration all loci of the chunk that are still iterating go together: in _prog_trees' budget groups (prog_tree_bytes)
+            one mprg_prog_identities launch into tables laid out as _distances_launch lays them out (PI_BLOCK_ROWS = 16 rows a
+            work item), and with device_tree mprg_prog_tree(_wide) over the tables where they are (the merges and the status words
+            come back), without it the tables downloaded and prog_tree(prog_distance_matrix(...)) on the host; _prog_plan for the
+            loci whose tree changed; _prog_rounds for those loci alone, from the leaves in buffer 0, into new text buffers; one
+            mprg_tree_objective launch, 8 bytes of S per locus downloaded.  The old root's buffer is dropped when the new MSA is
+            accepted, the new one when it is refused (_prog_rounds' live counts).  No MSA text leaves the device during the stage.
+
 Progressive, host side: per chunk the distances in launches whose m x m tables fit budget_bytes (loci of three or more leaves), D
 and the tree per locus in NumPy / Python integers (prog_tree: a float64 quotient only shortlists, the choice is exact).  A node's
 round is 1 + the larger of its children's rounds.  With device_tree the tree is built on the device instead (csrc/k_prog_tree.inc):
@@ -317,6 +363,8 @@ TS_ITEM_FIELDS, TS_OBJ_FIELDS = 8, 7      # MPRG_TS_ITEM_FIELDS, MPRG_TS_OBJ_FIE
 TREE_REFINE_MAX_LEAVES = 512              # the spec's cost cap of a tree-refined locus
 TREE_REFINE_MIN_LEAVES = 4                # below it no step leaves two leaves on either side
 TREE_REFINE_DEFAULT, TREE_REFINE_MAX = 1, 4   # passes of `--refine-tree` alone, and the most it takes
+PI_ITEM_FIELDS, PI_BLOCK_ROWS = 8, 16         # MPRG_PI_ITEM_FIELDS, MPRG_PI_BLOCK_ROWS
+RETREE_DEFAULT, RETREE_MAX = 1, 4             # rebuilds of `--retree` alone, and the most it takes
 PG_STATUS = {1: "an index, a tile or a source range outside its table or buffer", 2: "ops, widths and cells that do not fit each other",
              3: "the output outside its buffer"}
 TREE_STATUS = {1: "a range outside its buffer, a leaf's weight below 1 or a weight sum above 4 096", 3: "the workspace outside its buffer"}
@@ -403,7 +451,7 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
               refinement: Optional[list] = None, progressive: bool = False, progression: Optional[list] = None,
               max_leaves: Optional[int] = None, collapse: bool = False, device_tree: bool = False, refine_tree: Optional[int] = None,
               tree_refinement: Optional[list] = None, tree_refine_max_leaves: int = TREE_REFINE_MAX_LEAVES, large_loci: bool = False,
-              max_records: Optional[int] = None) -> List[MSA]:
+              max_records: Optional[int] = None, retree: Optional[int] = None, retreeing: Optional[list] = None) -> List[MSA]:
     """loci: per locus its records as (title, sequence).  Returns the loci's centre-star MSAs (ids: the titles' first words,
     descriptions: the titles).  names: the loci's names for error messages (default: their indices).  timings: a dict that
     receives the wall seconds of the stages (orient, centre, pairs, merge: each ends at a download, so includes its kernels).
@@ -440,7 +488,13 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
     given); the others get the star MSA and (non-empty records, 0, True) in progression, as without it.  With device_tree the
     trees of the loci whose records exceed PROG_MAX_LEAVES are built by mprg_prog_tree_wide.  timings also receives large_loci (the
     loci of more than max_leaves non-empty records built progressively), large_records (their records) and large_fallbacks (the
-    loci over either limit).  False: nothing launches or computes differently."""
+    loci over either limit).  False: nothing launches or computes differently.
+    retree: only with progressive (else a ValueError): N, the rebuilds of the spec's Retree (1 to RETREE_MAX), on the loci built
+    progressively with 3 or more leaves; behind the last merge, so before refine_tree and refine.  None: nothing launches or
+    computes differently.  retreeing: a list that then receives per locus (iterations run, accepted, why it stopped: "same",
+    "refused", "limit", "bound", or None when every iteration was accepted or the locus has fewer than 3 leaves, S before, S after),
+    None for a locus left to the star pass.  timings also receives retree_s and retree_loci, retree_rebuilds, retree_accepted,
+    retree_same_tree, retree_refused, retree_over_bound."""
     if device_tree and not progressive:
         raise ValueError("device_tree: only with progressive")
     if large_loci and not (progressive and collapse):
@@ -452,6 +506,11 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
             raise ValueError("refine_tree: only with progressive")
         if not (isinstance(refine_tree, (int, np.integer)) and not isinstance(refine_tree, bool) and 1 <= refine_tree <= TREE_REFINE_MAX):
             raise ValueError(f"refine_tree: a number of passes from 1 to {TREE_REFINE_MAX}, not {refine_tree!r}")
+    if retree is not None:
+        if not progressive:
+            raise ValueError("retree: only with progressive")
+        if not (isinstance(retree, (int, np.integer)) and not isinstance(retree, bool) and 1 <= retree <= RETREE_MAX):
+            raise ValueError(f"retree: a number of rebuilds from 1 to {RETREE_MAX}, not {retree!r}")
     if not (isinstance(refine, (int, np.integer)) and not isinstance(refine, bool) and 0 <= refine <= REFINE_MAX):
         raise ValueError(f"refine: a number of rounds from 0 to {REFINE_MAX}, not {refine!r}")
     band = None if band is False or band is None else band      # from here on: None, True or pass 1's half-width
@@ -465,7 +524,8 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
         return _progressive_msas(backend, loci, codes, names, budget_bytes, chunk_bytes, timings, adjust_direction, orientation, band,
                                  int(refine), refinement, progression, PROG_MAX_LEAVES if max_leaves is None else int(max_leaves), bool(collapse),
                                  bool(device_tree), int(refine_tree or 0), tree_refinement, int(tree_refine_max_leaves),
-                                 (PROG_MAX_RECORDS if max_records is None else int(max_records)) if large_loci else None)
+                                 (PROG_MAX_RECORDS if max_records is None else int(max_records)) if large_loci else None, int(retree or 0),
+                                 retreeing)
     return [m for lo, hi in _chunks(codes, chunk_bytes)
             for m in _star_chunk(backend, loci[lo:hi], codes[lo:hi], names[lo:hi], budget_bytes, timings, adjust_direction, orientation, band,
                                  int(refine), refinement, collapse=bool(collapse))]
@@ -473,30 +533,31 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
 
 def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings, adjust_direction, orientation, band, refine, refinement,
                       progression, max_leaves, collapse=False, device_tree=False, refine_tree=0, tree_refinement=None,
-                      tree_max_leaves=TREE_REFINE_MAX_LEAVES, max_records=None) -> List[MSA]:
+                      tree_max_leaves=TREE_REFINE_MAX_LEAVES, max_records=None, retree=0, retreeing=None) -> List[MSA]:
     """star_msas with progressive: the loci within the leaf limit through the progressive chunks, the others through the star
     chunks, the results (and what the caller's lists receive) back in the loci's order.  max_records (the spec's Large loci; None:
     without it): only the loci of more records go to the star chunks here; the progressive chunks count every locus's classes
     once Collapse has made them and send those above max_leaves through the star pass themselves."""
     n_leaves = [sum(1 for c in cs if len(c)) for cs in codes]
     out = [None] * len(loci)
-    got = {k: [None] * len(loci) for k in ("orientation", "refinement", "progression", "tree_refinement")}
+    got = {k: [None] * len(loci) for k in ("orientation", "refinement", "progression", "tree_refinement", "retreeing")}
     limits = None if max_records is None else (max_leaves, max_records)
     for prog in (True, False):
         sel = [l for l in range(len(loci)) if (n_leaves[l] <= max_leaves if limits is None else len(codes[l]) <= max_records) == prog]
         sub = [codes[l] for l in sel]
-        ori, ref, pro, tre, msas = [], [], [], [], []
+        ori, ref, pro, tre, ret, msas = [], [], [], [], [], []
         for lo, hi in _chunks(sub, chunk_bytes):
             idx = sel[lo:hi]
             msas.extend(_star_chunk(be, [loci[l] for l in idx], sub[lo:hi], [names[l] for l in idx], budget_bytes, timings, adjust_direction,
                                     ori if orientation is not None else None, band, refine, ref if refinement is not None else None,
                                     prog, pro, collapse, device_tree and prog, refine_tree if prog else 0,
-                                    tre if tree_refinement is not None else None, tree_max_leaves, limits if prog else None))
+                                    tre if tree_refinement is not None else None, tree_max_leaves, limits if prog else None,
+                                    retree if prog else 0, ret if retreeing is not None else None))
         if not prog:
             pro = [(n_leaves[l], 0, True) for l in sel]
         for k, l in enumerate(sel):
             out[l] = msas[k]
-            for key, vals in (("orientation", ori), ("refinement", ref), ("progression", pro), ("tree_refinement", tre)):
+            for key, vals in (("orientation", ori), ("refinement", ref), ("progression", pro), ("tree_refinement", tre), ("retreeing", ret)):
                 if vals:
                     got[key][l] = vals[k]
     if limits is not None:
@@ -505,7 +566,7 @@ def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings
         add_to(timings, "large_records", sum(len(codes[l]) for l in built))
         add_to(timings, "large_fallbacks", sum(1 for p in got["progression"] if p[2]))
     for key, dest in (("orientation", orientation), ("refinement", refinement), ("progression", progression),
-                      ("tree_refinement", tree_refinement)):
+                      ("tree_refinement", tree_refinement), ("retreeing", retreeing)):
         if dest is not None:
             dest.extend(got[key])
     return out
@@ -513,7 +574,7 @@ def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings
 
 def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direction=False, orientation=None, band=None, refine=0,
                 refinement=None, progressive=False, progression=None, collapse=False, device_tree=False, refine_tree=0,
-                tree_refinement=None, tree_max_leaves=TREE_REFINE_MAX_LEAVES, limits=None) -> List[MSA]:
+                tree_refinement=None, tree_max_leaves=TREE_REFINE_MAX_LEAVES, limits=None, retree=0, retreeing=None) -> List[MSA]:
     """One chunk: pack, optionally orient, optionally collapse, the star pass or the progressive one (with its tree refinement),
     optionally refine, collect.  limits (the spec's Large loci; only with progressive and collapse): (max_leaves, max_records): the
     loci with more classes of non-empty records, or more records, go through the star pass."""
@@ -530,18 +591,18 @@ def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direc
         build = (n_classes <= limits[0]) & (chunk.counts <= limits[1])
         if not build.all():
             return _star_chunk_parts(be, chunk, classes, build, budget_bytes, laps, band, refine, refinement, progression, device_tree,
-                                     refine_tree, tree_refinement, tree_max_leaves)
+                                     refine_tree, tree_refinement, tree_max_leaves, retree, retreeing)
     return _star_chunk_rest(be, chunk, classes, budget_bytes, laps, band, refine, refinement, progressive, progression, device_tree,
-                            refine_tree, tree_refinement, tree_max_leaves)
+                            refine_tree, tree_refinement, tree_max_leaves, retree, retreeing)
 
 
 def _star_chunk_parts(be, chunk: Chunk, classes, build, budget_bytes, laps, band, refine, refinement, progression, device_tree,
-                      refine_tree, tree_refinement, tree_max_leaves) -> List[MSA]:
+                      refine_tree, tree_refinement, tree_max_leaves, retree=0, retreeing=None) -> List[MSA]:
     """_star_chunk behind Collapse for a chunk of which only the loci `build` (a bool per locus) are built progressively (the spec's
     Large loci): those as one chunk through the progressive pass, the others as one through the star pass, both over the same code
     buffer and the classes already made; the MSAs, and what the caller's lists receive, back in the chunk's order."""
     n_filled = np.add.reduceat((chunk.lens > 0).astype(np.int64), chunk.first)
-    msas, ref, pro, tre = ([None] * chunk.n_loci for _ in range(4))
+    msas, ref, pro, tre, ret = ([None] * chunk.n_loci for _ in range(5))
     for prog in (True, False):
         sel = np.nonzero(build == prog)[0]
         if not len(sel):
@@ -551,28 +612,28 @@ def _star_chunk_parts(be, chunk: Chunk, classes, build, budget_bytes, laps, band
         at[rec] = np.arange(len(rec))
         part = chunk._replace(names=[chunk.names[l] for l in sel], titles=[chunk.titles[l] for l in sel], codes=[chunk.codes[l] for l in sel],
                               lens=chunk.lens[rec], seq_off=chunk.seq_off[rec], first=exclusive_sum(chunk.counts[sel]), counts=chunk.counts[sel])
-        got = [[], [], []]
+        got = [[], [], [], []]
         out = _star_chunk_rest(be, part, Classes(at[classes.rep[rec]], classes.weight[rec]), budget_bytes, laps, band, refine, got[0], prog,
-                               got[1], device_tree and prog, refine_tree if prog else 0, got[2], tree_max_leaves)
+                               got[1], device_tree and prog, refine_tree if prog else 0, got[2], tree_max_leaves, retree if prog else 0, got[3])
         if not prog:
             got[1] = [(int(n_filled[l]), 0, True) for l in sel]
         for k, l in enumerate(sel.tolist()):
             msas[l] = out[k]
-            for dest, vals in zip((ref, pro, tre), got):
+            for dest, vals in zip((ref, pro, tre, ret), got):
                 if vals:
                     dest[l] = vals[k]
-    for dest, vals, wanted in ((refinement, ref, refine), (progression, pro, True), (tree_refinement, tre, refine_tree)):
+    for dest, vals, wanted in ((refinement, ref, refine), (progression, pro, True), (tree_refinement, tre, refine_tree), (retreeing, ret, retree)):
         if dest is not None and wanted:
             dest.extend(vals)
     return msas
 
 
 def _star_chunk_rest(be, chunk: Chunk, classes, budget_bytes, laps, band, refine, refinement, progressive, progression, device_tree,
-                     refine_tree, tree_refinement, tree_max_leaves) -> List[MSA]:
+                     refine_tree, tree_refinement, tree_max_leaves, retree=0, retreeing=None) -> List[MSA]:
     """_star_chunk behind Collapse: the star pass or the progressive one (with its tree refinement), optionally refine, collect."""
     timings = laps.timings
     text = (_progressive(be, chunk, budget_bytes, band, laps, progression, classes, device_tree, refine_tree, tree_refinement,
-                         tree_max_leaves) if progressive else
+                         tree_max_leaves, retree, retreeing) if progressive else
             _star_pass(be, chunk, budget_bytes, band, laps, classes))
     moved = {}
     if refine:
@@ -925,35 +986,52 @@ def _prog_trees(be, chunk: Chunk, sel, budget_bytes, weights=None):
     and the merges are all that is downloaded.  Per locus its merges as prog_tree gives them.  weights: per record of the chunk's
     tables how many times it counts (the spec's Collapse).  The loci whose weight sum exceeds PROG_MAX_LEAVES (the spec's Large
     loci) form groups of their own, whose trees mprg_prog_tree_wide builds."""
-    lens, first, counts = chunk.lens, chunk.first, chunk.counts
+    lens, first = chunk.lens, chunk.first
     out = {}
     d_seqs = be.upload(np.stack([chunk.seq_off, lens], 1).reshape(-1))
     d_weights = None if weights is None else be.upload(np.asarray(weights, np.int32))
     n_leaves = np.add.reduceat((lens > 0).astype(np.int64), first)
     # the spec's Large loci: a locus whose weight sum exceeds mprg_prog_tree's bound goes to mprg_prog_tree_wide, in groups (and so
     # in launches) of such loci alone; without one nothing launches differently
-    wsum = n_leaves if weights is None else np.add.reduceat(np.where(lens > 0, np.asarray(weights, np.int64), 0), first)
-    wide = wsum[sel] > PROG_MAX_LEAVES
-    groups = [(part[lo:hi], entry, table)
-              for part, entry, table in ((sel[~wide], "mprg_prog_tree", TREE_STATUS), (sel[wide], "mprg_prog_tree_wide", WIDE_TREE_STATUS))
-              if len(part) for lo, hi in pa.budget_groups(prog_tree_bytes(counts[part]), budget_bytes)]
-    for grp, entry, table in groups:
+    for grp, entry, table in _tree_groups(chunk, sel, budget_bytes, weights):
         m, toff, words, d_shared, d_nw, d_status, n_work = _distances_launch(be, chunk, d_seqs, grp)
-        n_merges = np.maximum(n_leaves[grp] - 1, 0)
-        moff = 2 * exclusive_sum(n_merges)
-        ws_words = prog_tree_words(m)
-        ttab = np.stack([first[grp], m, toff, exclusive_sum(ws_words), moff], 1).astype(np.int64)
-        d_ttab, d_ws = be.upload(ttab), be.empty(8 * int(ws_words.sum()))
-        d_merges, d_tstatus = be.empty(8 * int(n_merges.sum())), be.empty(4 * len(grp))
-        be.call(entry, be.ptr(d_shared), words, be.ptr(d_nw), be.ptr(d_seqs), len(lens), be.ptr(d_ttab), len(grp),
-                0 if d_weights is None else be.ptr(d_weights), be.ptr(d_ws), int(ws_words.sum()), be.ptr(d_merges), 2 * int(n_merges.sum()),
-                be.ptr(d_tstatus), be.stream, work=float((m * m).sum() * 24.0))
+        launched = _tree_launch(be, chunk, grp, entry, d_seqs, d_weights, n_leaves, toff, words, d_shared, d_nw)
         _check(be.download(d_status, np.int32, n_work), "mprg_prog_distances", PG_STATUS)
-        _check(be.download(d_tstatus, np.int32, len(grp)), entry, table, "locus")
-        merges = be.download(d_merges, np.int32, 2 * int(n_merges.sum())).reshape(-1, 2)
-        for k, l in enumerate(grp.tolist()):
-            out[l] = [tuple(p) for p in merges[moff[k] // 2:moff[k] // 2 + n_merges[k]].tolist()]
+        out.update(_tree_merges(be, grp, entry, table, *launched))
     return out
+
+
+def _tree_groups(chunk: Chunk, sel, budget_bytes, weights=None):
+    """_prog_trees' groups of the loci `sel`: (the group's loci, the entry point that builds their trees, its status texts)."""
+    n_leaves = np.add.reduceat((chunk.lens > 0).astype(np.int64), chunk.first)
+    wsum = n_leaves if weights is None else np.add.reduceat(np.where(chunk.lens > 0, np.asarray(weights, np.int64), 0), chunk.first)
+    wide = wsum[sel] > PROG_MAX_LEAVES
+    return [(part[lo:hi], entry, table)
+            for part, entry, table in ((sel[~wide], "mprg_prog_tree", TREE_STATUS), (sel[wide], "mprg_prog_tree_wide", WIDE_TREE_STATUS))
+            if len(part) for lo, hi in pa.budget_groups(prog_tree_bytes(chunk.counts[part]), budget_bytes)]
+
+
+def _tree_launch(be, chunk: Chunk, grp, entry, d_seqs, d_weights, n_leaves, toff, words, d_shared, d_nw):
+    """One mprg_prog_tree(_wide) launch over the tables of the loci `grp` where a launch left them on the device: what
+    _tree_merges downloads."""
+    m = chunk.counts[grp]
+    n_merges = np.maximum(n_leaves[grp] - 1, 0)
+    moff = 2 * exclusive_sum(n_merges)
+    ws_words = prog_tree_words(m)
+    ttab = np.stack([chunk.first[grp], m, toff, exclusive_sum(ws_words), moff], 1).astype(np.int64)
+    d_ttab, d_ws = be.upload(ttab), be.empty(8 * int(ws_words.sum()))
+    d_merges, d_tstatus = be.empty(8 * int(n_merges.sum())), be.empty(4 * len(grp))
+    be.call(entry, be.ptr(d_shared), words, be.ptr(d_nw), be.ptr(d_seqs), len(chunk.lens), be.ptr(d_ttab), len(grp),
+            0 if d_weights is None else be.ptr(d_weights), be.ptr(d_ws), int(ws_words.sum()), be.ptr(d_merges), 2 * int(n_merges.sum()),
+            be.ptr(d_tstatus), be.stream, work=float((m * m).sum() * 24.0))
+    return d_tstatus, d_merges, n_merges, moff
+
+
+def _tree_merges(be, grp, entry, table, d_tstatus, d_merges, n_merges, moff):
+    """The status words and the merges of a _tree_launch, downloaded: per locus its merges as prog_tree gives them."""
+    _check(be.download(d_tstatus, np.int32, len(grp)), entry, table, "locus")
+    merges = be.download(d_merges, np.int32, 2 * int(n_merges.sum())).reshape(-1, 2)
+    return {l: [tuple(p) for p in merges[moff[k] // 2:moff[k] // 2 + n_merges[k]].tolist()] for k, l in enumerate(grp.tolist())}
 
 
 def prog_trees(backend, codes: Sequence[Sequence[np.ndarray]], weights: Optional[Sequence[Sequence[int]]] = None,
@@ -1193,12 +1271,14 @@ def merge_profiles(backend, pairs: Sequence[Tuple[np.ndarray, np.ndarray]], budg
 
 
 def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression, classes: Optional[Classes] = None, device_tree=False,
-                 refine_tree=0, tree_refinement=None, max_leaves=None):
+                 refine_tree=0, tree_refinement=None, max_leaves=None, retree=0, retreeing=None):
     """The spec's Progressive over one chunk, on the (oriented) sequences in chunk.d_codes.  Returns what the star pass leaves: the
     device buffer of the MSAs' ASCII text, its bytes, each locus's offset in it and its width.  classes: the spec's Collapse: the
     tree and the merges over the representatives with their weights, the root's rows written for every member.  device_tree: the
     trees by mprg_prog_tree (_prog_trees) instead of prog_tree.  refine_tree: the passes of the spec's Tree refinement on the
-    roots' texts before they are written out (0: none); tree_refinement receives its tuples, max_leaves is its cap."""
+    roots' texts before they are written out (0: none); tree_refinement receives its tuples, max_leaves is its cap.  retree: the
+    rebuilds of the spec's Retree, in front of that (0: none); retreeing receives its tuples, progression then the tuples of the
+    trees that built the texts that are written."""
     laps.lap()
     lens, first, counts = chunk.lens, chunk.first, chunk.counts
     n_leaves = np.add.reduceat((lens > 0).astype(np.int64), first)          # (every locus has a record)
@@ -1227,11 +1307,16 @@ def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression,
         t0 = time.perf_counter()
         plan = _prog_plan(lens, first, counts, shared, weights)
     add_to(laps.timings, "tree_plan_s", time.perf_counter() - t0)
-    if progression is not None:
-        progression.extend(plan[-1])
     laps.lap("tree_s")
     bufs, live, where = _prog_rounds(be, chunk, plan, budget_bytes, band, laps.timings, weights)
     laps.lap("progressive_s")
+    if retree:
+        plan, result = _retree(be, chunk, plan, bufs, live, where, weights, retree, budget_bytes, band, device_tree, laps.timings)
+        if retreeing is not None:
+            retreeing.extend(result)
+        laps.lap("retree_s")
+    if progression is not None:
+        progression.extend(plan[-1])
     order = plan[3]
     if refine_tree:
         order, result = _tree_refine(be, chunk, plan, bufs, live, where, weights, refine_tree, max_leaves, budget_bytes, band, laps.timings)
@@ -1267,14 +1352,16 @@ def _prog_parents(be, d_bufs, n_bufs, Xg, Yg, d_ops, ops_bytes, ops_off, count):
     return d_new, new_bytes, poff, R
 
 
-def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters, weights=None):
+def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters, weights=None, beyond=None):
     """_progressive's device part: the plan's rounds (every node of a round, over all loci of the chunk, in one set of launches
     per budget group).  Returns (bufs, live, where) as the last round left them: of every locus only its root is in where.
     The texts' lifetime: bufs[b] is (buffer, bytes) of text buffer b, 0 the chunk's code buffer (the leaves); where[locus, node]
     is (b, offset, rows, width) of a node not yet merged; live[b] counts the nodes of where in b.  A group's parents go into a
     buffer of their own; a buffer (but 0) is dropped when its last node has been merged into a parent.
     weights (the spec's Collapse): the chunk's tables hold the representatives only, weights per record of them; rw[locus, node]
-    then is the weights of the node's rows."""
+    then is the weights of the node's rows.
+    beyond (the spec's Retree): a set that receives the loci with a merge beyond Tree refinement's Limit (_tree_step_fits) instead
+    of an error: such a locus takes no further merge and none of its nodes stays in where."""
     lens, seq_off, first, n_loci = chunk.lens, chunk.seq_off, chunk.first, chunk.n_loci
     leaves, by_round = plan[:2]
     bufs, live = [(chunk.d_codes, chunk.codes_bytes)], [0]
@@ -1289,6 +1376,16 @@ def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters, weights=N
             bufs[b] = (None, 0)
 
     for _, todo in sorted(by_round.items()):
+        if beyond is not None:
+            todo = [t for t in todo if t[0] not in beyond]
+            fits = _tree_step_fits(np.array([where[l, x][3] for l, _, x, _ in todo], np.int64),
+                                   np.array([where[l, y][3] for l, y, _, _ in todo], np.int64), max(64, int(budget_bytes) // 4))
+            beyond.update(t[0] for t, ok in zip(todo, fits.tolist()) if not ok)
+            for key in [key for key in where if key[0] in beyond]:
+                merged(*key)
+            todo = [t for t in todo if t[0] not in beyond]
+            if not todo:
+                continue
         Y = np.array([where[l, y] for l, y, _, _ in todo], np.int64)
         X = np.array([where[l, x] for l, _, x, _ in todo], np.int64)
         for grp in _prog_groups(X[:, 3], Y[:, 3], budget_bytes, band):
@@ -1343,6 +1440,165 @@ def _prog_output(be, chunk: Chunk, root, root_members, bufs, where, expand=None)
             be.ptr(d_status), be.stream, work=float(2 * out_bytes))
     _check(be.download(d_status, np.int32, len(rows)), "mprg_prog_rows", PG_STATUS)
     return d_out, out_bytes, base, W
+
+
+def _add_buf(bufs, live, buf, nbytes):
+    """The buffer's index in _prog_rounds' bufs: a dropped buffer's place if there is one."""
+    b = next((i for i in range(1, len(bufs)) if bufs[i][0] is None), len(bufs))
+    if b == len(bufs):
+        bufs.append(None)
+        live.append(0)
+    bufs[b], live[b] = (buf, nbytes), 0
+    return b
+
+
+def _drop_unused(bufs, live, bs):
+    for b in bs:
+        if b and not live[b]:
+            bufs[b] = (None, 0)
+
+
+# ---- retree
+def _identities_launch(be, d_bufs, n_bufs: int, texts: np.ndarray, leaf: Sequence[np.ndarray], first: np.ndarray, m: np.ndarray, n_seqs: int):
+    """One mprg_prog_identities launch: texts (n, 4) int64 {buffer, offset, R, W}, per text the record of each of its rows (an index
+    within its locus), per text its locus's first sequence and sequence count m.  The tables are laid out as _distances_launch lays
+    them out.  Returns (each table's offset, the tables' words, the tables, nw and the status words on the device, the work items)."""
+    n = len(texts)
+    R = texts[:, 2]
+    toff, words = exclusive_sum(m * m), int((m * m).sum())
+    items = np.stack([texts[:, 0], texts[:, 1], R, texts[:, 3], exclusive_sum(R), first, m, toff], 1).astype(np.int64)
+    blocks = -(-R // PI_BLOCK_ROWS)
+    work = np.stack([np.repeat(np.arange(n), blocks), _ranges(np.zeros(n, np.int64), blocks)], 1).astype(np.int32)
+    flat = np.concatenate(leaf).astype(np.int32)
+    d_items, d_work, d_leaf = be.upload(items), be.upload(work), be.upload(flat)
+    d_shared, d_nw, d_status = be.zeros(4 * words), be.zeros(8 * n_seqs), be.empty(4 * len(work))
+    be.call("mprg_prog_identities", be.ptr(d_bufs), n_bufs, be.ptr(d_items), n, be.ptr(d_work), len(work), be.ptr(d_leaf), len(flat),
+            be.ptr(d_shared), words, be.ptr(d_nw), n_seqs, be.ptr(d_status), be.stream, work=float((R * R * texts[:, 3]).sum() / 2.0))
+    return toff, words, d_shared, d_nw, d_status, len(work)
+
+
+def prog_identities(backend, texts: Sequence[np.ndarray], leaf: Optional[Sequence[Sequence[int]]] = None, m: Optional[Sequence[int]] = None):
+    """mprg_prog_identities on texts (per item an R x W matrix of cell codes), one launch: per item (s, nw): s an (m, m) int64 array
+    whose part above the diagonal holds s' of the records a < b, nw the records' nw' (the spec's Retree, Distance).  leaf: per item
+    the record of each row (default: row r is record r); m: per item its locus's records (default: R).  What no row stands for is 0."""
+    be = backend
+    mats = [np.ascontiguousarray(t, np.uint8) for t in texts]
+    off = exclusive_sum(np.array([t.size for t in mats], np.int64))
+    flat = np.concatenate([t.reshape(-1) for t in mats])
+    tab = np.array([[0, off[k], *t.shape] for k, t in enumerate(mats)], np.int64).reshape(-1, 4)
+    leaf = [np.arange(len(t)) for t in mats] if leaf is None else [np.asarray(x, np.int64) for x in leaf]
+    m = np.array([len(t) for t in mats] if m is None else m, np.int64)
+    first = exclusive_sum(m)
+    d_text = be.upload(flat)
+    toff, words, d_shared, d_nw, d_status, n_work = _identities_launch(be, _bufs_table(be, [(d_text, len(flat))]), 1, tab, leaf, first, m, int(m.sum()))
+    _check(be.download(d_status, np.int32, n_work), "mprg_prog_identities", PG_STATUS)
+    shared, nw = be.download(d_shared, np.uint32, words).astype(np.int64), be.download(d_nw, np.int64, int(m.sum()))
+    return [(shared[toff[k]:toff[k] + m[k] * m[k]].reshape(int(m[k]), int(m[k])), nw[first[k]:first[k] + m[k]]) for k in range(len(mats))]
+
+
+def _retree_trees(be, chunk: Chunk, sel, texts, order, bufs, weights, budget_bytes, device_tree):
+    """The spec's Retree, Distance and Tree, for the loci `sel` of a chunk: texts[l] {buffer, offset, R, W} is the locus's current
+    MSA, order[l] the records of its rows.  In _prog_trees' groups: one mprg_prog_identities launch, then with device_tree the tree
+    launch over the tables where they are (the merges and the status words come back), without it the tables downloaded and
+    prog_tree on the host.  Per locus its merges as prog_tree gives them."""
+    lens, first, counts = chunk.lens, chunk.first, chunk.counts
+    out = {}
+    n_leaves = np.add.reduceat((lens > 0).astype(np.int64), first)
+    d_seqs = be.upload(np.stack([chunk.seq_off, lens], 1).reshape(-1)) if device_tree else None
+    d_weights = None if weights is None or not device_tree else be.upload(np.asarray(weights, np.int32))
+    for grp, entry, table in _tree_groups(chunk, sel, budget_bytes, weights if device_tree else None):
+        loci = grp.tolist()
+        toff, words, d_shared, d_nw, d_status, n_work = _identities_launch(
+            be, _bufs_table(be, bufs), len(bufs), np.array([texts[l] for l in loci], np.int64), [order[l] for l in loci], first[grp], counts[grp],
+            len(lens))
+        if device_tree:
+            launched = _tree_launch(be, chunk, grp, entry, d_seqs, d_weights, n_leaves, toff, words, d_shared, d_nw)
+            _check(be.download(d_status, np.int32, n_work), "mprg_prog_identities", PG_STATUS)
+            out.update(_tree_merges(be, grp, entry, table, *launched))
+            continue
+        _check(be.download(d_status, np.int32, n_work), "mprg_prog_identities", PG_STATUS)
+        shared = be.download(d_shared, np.uint32, words).astype(np.int64)
+        nw = be.download(d_nw, np.int64, len(lens))
+        for k, l in enumerate(loci):
+            mk, rec = int(counts[l]), slice(first[l], first[l] + counts[l])
+            lv = np.nonzero(lens[rec] > 0)[0]
+            out[l] = prog_tree(prog_distance_matrix(shared[toff[k]:toff[k] + mk * mk].reshape(mk, mk), nw[rec]), lv,
+                               None if weights is None else weights[rec][lv])
+    return out
+
+
+def _retree(be, chunk: Chunk, plan, bufs, live, where, weights, rebuilds, budget_bytes, band, device_tree, counters):
+    """The spec's Retree over one chunk, on the roots' texts as _prog_rounds left them (bufs, live, where: its state, kept up here
+    as _tree_refine keeps it up).  Per iteration all loci that are still iterating go together: the identities and the trees
+    (_retree_trees), _prog_plan and _prog_rounds for the loci whose tree changed, from the leaves, into buffers of their own, one
+    objective launch, S downloaded; the text that loses goes with its buffer.  Returns (the plan with the accepted trees, their
+    row orders and progression tuples in place of the first ones, per locus (iterations, accepted, why it stopped, S before, S
+    after))."""
+    lens, first, counts, n_loci = chunk.lens, chunk.first, chunk.counts, chunk.n_loci
+    leaves, root = plan[0], plan[2]
+    order, trees, progression = [np.array(x, np.int64) for x in plan[3]], list(plan[4]), list(plan[5])
+    wl = [np.ones(int(counts[l]), np.int64) if weights is None else weights[first[l]:first[l] + counts[l]] for l in range(n_loci)]
+    empty = np.array([counts[l] - len(leaves[l]) for l in range(n_loci)], np.int64)
+    # mprg_tree_objective's bound, as in _tree_refine: a locus that misses it is left out and reported
+    in_bound = np.array([(int(wl[l][order[l]].sum()) + int(empty[l])) ** 2 * where[l, root[l]][3] <= 1 << 58 for l in range(n_loci)], bool)
+    add_to(counters, "retree_over_bound", int((~in_bound).sum()))
+    known = np.nonzero(in_bound)[0].tolist()
+    S = np.zeros(n_loci, np.int64)
+    if known:
+        S[known] = tree_objective(be, _bufs_table(be, bufs), len(bufs), np.array([where[l, root[l]] for l in known], np.int64),
+                                  [wl[l][order[l]] for l in known], empty[known])
+    out = [[0, 0, None if in_bound[l] else "bound", int(S[l]), int(S[l])] for l in range(n_loci)]
+    active = [l for l in known if len(leaves[l]) >= 3]
+    add_to(counters, "retree_loci", len(active))
+    for _ in range(rebuilds):
+        if not active:
+            break
+        merges = _retree_trees(be, chunk, np.array(active, np.int64), {l: where[l, root[l]] for l in active}, order, bufs, weights, budget_bytes,
+                               device_tree)
+        for l in active:
+            out[l][0] += 1
+            if merges[l] == trees[l]:                           # a rebuild would reproduce the bytes
+                out[l][2] = "same"
+        todo = [l for l in active if out[l][2] is None]
+        add_to(counters, "retree_same_tree", len(active) - len(todo))
+        add_to(counters, "retree_rebuilds", len(todo))
+        active = []
+        if not todo:
+            break
+        # the rebuild: the changed loci as a chunk of their own over the same tables, from the leaves in buffer 0
+        part = chunk._replace(first=first[todo], counts=counts[todo])
+        plan2 = _prog_plan(lens, part.first, part.counts, None, weights, [merges[l] for l in todo])
+        beyond = set()
+        bufs2, live2, where2 = _prog_rounds(be, part, plan2, budget_bytes, band, counters, weights, beyond)
+        made, new = {}, {}
+        for k, l in enumerate(todo):
+            if k in beyond:
+                out[l][2] = "limit"
+                continue
+            b, off, R, W = where2[k, plan2[2][k]]
+            if b not in made:
+                made[b] = _add_buf(bufs, live, *bufs2[b])
+            new[l] = (made[b], off, R, W, k)
+        ks = sorted(new)
+        S2 = (tree_objective(be, _bufs_table(be, bufs), len(bufs), np.array([new[l][:4] for l in ks], np.int64),
+                             [wl[l][np.array(plan2[3][new[l][4]], np.int64)] for l in ks], empty[ks]) if ks else [])
+        used = list(made.values())
+        for l, s2 in zip(ks, S2):
+            k = new[l][4]
+            if int(s2) > out[l][4]:                             # accepted: the locus's text is the new one, its tree the new tree
+                old = where[l, root[l]][0]
+                live[old] -= 1
+                live[new[l][0]] += 1
+                where[l, root[l]], order[l], trees[l], progression[l] = new[l][:4], np.array(plan2[3][k], np.int64), merges[l], plan2[5][k]
+                out[l][1], out[l][4] = out[l][1] + 1, int(s2)
+                used.append(old)
+                active.append(l)
+            else:
+                out[l][2] = "refused"
+        _drop_unused(bufs, live, used)
+    add_to(counters, "retree_accepted", sum(o[1] for o in out))
+    add_to(counters, "retree_refused", sum(o[2] == "refused" for o in out))
+    return (leaves, plan[1], root, [o.tolist() for o in order], trees, progression), [tuple(o) for o in out]
 
 
 # ---- tree refinement
@@ -1417,18 +1673,10 @@ def _tree_refine(be, chunk: Chunk, plan, bufs, live, where, weights, passes, max
     budget_words = max(64, int(budget_bytes) // 4)
 
     def add_buf(buf, nbytes):
-        """The buffer's index in bufs: a dropped buffer's place if there is one."""
-        b = next((i for i in range(1, len(bufs)) if bufs[i][0] is None), len(bufs))
-        if b == len(bufs):
-            bufs.append(None)
-            live.append(0)
-        bufs[b], live[b] = (buf, nbytes), 0
-        return b
+        return _add_buf(bufs, live, buf, nbytes)
 
     def drop_unused(bs):
-        for b in bs:
-            if b and not live[b]:
-                bufs[b] = (None, 0)
+        _drop_unused(bufs, live, bs)
 
     # mprg_tree_objective's bound, rows^2 W <= 2^58: only a locus of the spec's Large loci can miss it (4 096 rows do not, below the
     # DP's 10^6 columns); it is left out of the stage and reported with no step and S = 0

@@ -109,6 +109,14 @@ def register_parser(subparsers):
                         "raises the locus's sum-of-pairs objective (star_align.py, Tree refinement), so a locus no step improves "
                         "keeps its --progressive bytes.  --refine runs after it, --band and --device-tree give the same bytes, with "
                         "--collapse-identical equal sequences keep equal rows.  Off by default")
+    p.add_argument("--retree", dest="retree", action="store", type=int, nargs="?", const=star_align.RETREE_DEFAULT, default=None, metavar="N",
+                   help="(this implementation) with --unaligned --progressive: after the last merge every locus of 3 or more leaves gets "
+                        f"up to N rebuilds (1-{star_align.RETREE_MAX}; --retree alone: {star_align.RETREE_DEFAULT}) of its guide tree on "
+                        "the GPU: pairwise identities over the shorter sequence are taken from the rows of the MSA (all pairs, "
+                        "csrc/k_prog_retree.inc), a new tree is built from them and the locus is aligned again up that tree; the new "
+                        "MSA is kept only if it raises the locus's sum-of-pairs objective (star_align.py, Retree), so a locus whose "
+                        "tree comes out the same or whose rebuild is refused keeps its --progressive bytes.  --refine-tree and "
+                        "--refine run after it, --band and --device-tree give the same bytes.  Off by default")
     p.set_defaults(func=run, check=check_options)
     return p
 
@@ -140,6 +148,12 @@ def check_options(args, parser):
         from ..from_msa import star_align
         if not 1 <= args.refine_tree <= star_align.TREE_REFINE_MAX:
             parser.error(f"--refine-tree takes 1 to {star_align.TREE_REFINE_MAX} passes, not {args.refine_tree}")
+    if getattr(args, "retree", None) is not None:
+        if not getattr(args, "progressive", False):
+            parser.error("--retree needs --progressive")
+        from ..from_msa import star_align
+        if not 1 <= args.retree <= star_align.RETREE_MAX:
+            parser.error(f"--retree takes 1 to {star_align.RETREE_MAX} rebuilds, not {args.retree}")
     if getattr(args, "refine", None) is not None:
         if not args.unaligned:
             parser.error("--refine needs --unaligned")
@@ -645,18 +659,20 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
     refine_tree = int(getattr(options, "refine_tree", None) or 0)
     tree_refinement = []
     large_loci = bool(getattr(options, "large_loci", False))
+    retree = int(getattr(options, "retree", None) or 0)
     for lo in range(0, len(mine), STAR_CHUNK):
         t0 = time.perf_counter()
         recs = [star_align.read_unaligned(f) for f in mine[lo:lo + STAR_CHUNK]]
         t1 = time.perf_counter()
         msas = star_align.star_msas(be, recs, names=loci[lo:lo + STAR_CHUNK], adjust_direction=adjust, orientation=orientation,
-                                    **(dict(band=True) if band else {}), **(dict(timings=counters) if band or collapse or device_tree or refine_tree else {}),
+                                    **(dict(band=True) if band else {}), **(dict(timings=counters) if band or collapse or device_tree or refine_tree or retree else {}),
                                     **(dict(collapse=True) if collapse else {}),
                                     **(dict(refine=refine, refinement=refinement) if refine else {}),
                                     **(dict(progressive=True, progression=progression) if progressive else {}),
                                     **(dict(device_tree=True) if device_tree else {}),
                                     **(dict(large_loci=True) if large_loci else {}),
-                                    **(dict(refine_tree=refine_tree, tree_refinement=tree_refinement) if refine_tree else {}))
+                                    **(dict(refine_tree=refine_tree, tree_refinement=tree_refinement) if refine_tree else {}),
+                                    **(dict(retree=retree) if retree else {}))
         t2 = time.perf_counter()
         for locus, m in zip(loci[lo:lo + STAR_CHUNK], msas):
             path = out_dir / f"{locus}.fa"
@@ -677,6 +693,10 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
         logger.info(f"rank {rank}: --progressive --band: {counters.get('prog_band_merges', 0)} merges, "
                     f"{counters.get('prog_band_second_passes', 0)} second passes, {counters.get('prog_band_full_merges', 0)} sent to the "
                     f"full DP, {counters.get('prog_band_cells', 0)} of {counters.get('prog_band_full_cells', 0)} DP cells computed")
+    if retree:
+        logger.info(f"rank {rank}: --retree {retree}: {counters.get('retree_rebuilds', 0)} loci rebuilt, "
+                    f"{counters.get('retree_accepted', 0)} accepted, {counters.get('retree_same_tree', 0)} same tree, "
+                    f"{counters.get('retree_refused', 0)} refused")
     if refine_tree:
         logger.info(f"rank {rank}: --refine-tree {refine_tree}: {sum(1 for t in tree_refinement if t and t[1])} loci refined, "
                     f"{counters.get('tree_refine_steps', 0)} steps tried, {counters.get('tree_refine_accepted', 0)} accepted, "

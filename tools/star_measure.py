@@ -30,6 +30,9 @@ then also gives tree_device_loci.  Every --progressive line gives tree_plan_s, t
 `--refine-tree [N]` (with --progressive): tree-dependent refinement (`from_msa --unaligned --progressive --refine-tree`; N passes,
 default 1); the line then also gives tree_refine_s, the loci with a step, the steps tried, accepted and skipped, the loci above the
 cap, the loci changed and the total objective S before and after the stage.
+`--retree [N]` (with --progressive): the guide tree rebuilt from the MSA (`from_msa --unaligned --progressive --retree`; N rebuilds,
+default 1); the line then also gives retree_s, the loci iterated, rebuilt, accepted, refused and with the same tree, the loci changed
+and the total objective S before and after the stage.
 `--records N` (with --diverged A): loci of many records over few alleles: every locus has N records, each of the locus's A diverged
 sequences once and then seeded picks among them, shuffled: the pan-genome core gene `--large-loci` is for.
 `--large-loci` (with --progressive --collapse-identical): the leaf limit counts distinct sequences (`from_msa --unaligned
@@ -78,6 +81,12 @@ if "--refine-tree" in sys.argv:
     refine_tree = int(nxt[0]) if nxt and nxt[0].isdigit() else sa.TREE_REFINE_DEFAULT
     if not progressive:
         sys.exit("--refine-tree needs --progressive")
+retree = None
+if "--retree" in sys.argv:
+    nxt = sys.argv[sys.argv.index("--retree") + 1:][:1]
+    retree = int(nxt[0]) if nxt and nxt[0].isdigit() else sa.RETREE_DEFAULT
+    if not progressive:
+        sys.exit("--retree needs --progressive")
 records = int(sys.argv[sys.argv.index("--records") + 1]) if "--records" in sys.argv else 0
 if records and not diverged:
     sys.exit("--records needs --diverged")
@@ -85,7 +94,7 @@ large_loci = "--large-loci" in sys.argv
 if large_loci and not (progressive and collapse):
     sys.exit("--large-loci needs --progressive and --collapse-identical")
 prog_kw = dict(progressive=True, **(dict(device_tree=True) if device_tree else {}), **(dict(large_loci=True) if large_loci else {}),
-               **(dict(refine_tree=refine_tree) if refine_tree else {})) if progressive else {}
+               **(dict(refine_tree=refine_tree) if refine_tree else {}), **(dict(retree=retree) if retree else {})) if progressive else {}
 
 
 def diverged_seqs(seed):
@@ -142,9 +151,10 @@ try:
     refinement = []
     progression = []
     tree_refinement = []
+    retreeing = []
     msas = sa.star_msas(be, recs, timings=timings, adjust_direction=flip is not None, orientation=orientation, band=band, refine=refine,
                         refinement=refinement, **(dict(prog_kw, progression=progression) if progressive else {}),
-                        **(dict(tree_refinement=tree_refinement) if refine_tree else {}),
+                        **(dict(tree_refinement=tree_refinement) if refine_tree else {}), **(dict(retreeing=retreeing) if retree else {}),
                         **(dict(collapse=True) if collapse else {}))
     t_star = time.perf_counter() - t0
     t0 = time.perf_counter()
@@ -178,6 +188,10 @@ try:
         done = [t for t in tree_refinement if t]
         extra.update(refine_tree=refine_tree, tree_loci_changed=sum(1 for t in done if t[1]), tree_s_before=sum(t[3] for t in done),
                      tree_s_after=sum(t[4] for t in done))
+    if retree:
+        done = [t for t in retreeing if t]
+        extra.update(retree=retree, retree_loci_changed=sum(1 for t in done if t[1]), retree_s_before=sum(t[3] for t in done),
+                     retree_s_after=sum(t[4] for t in done))
     if objective:
         import numpy as np
         s_total = 0
