@@ -865,6 +865,29 @@ int mprg_prog_identities(const int64_t *bufs, int n_bufs, const int64_t *items, 
                          const int32_t *leaf, long long leaf_words, uint32_t *shared, long long shared_words, int64_t *nw,
                          long long n_seqs, int32_t *status, void *stream);
 
+/* `--progressive --seq-weights`: a weight per leaf from the guide tree (the spec: star_align.py, "Sequence weights").
+ * mprg_prog_leaf_weights: shared, shared_words, nw, seqs, n_seqs, loci (n_loci x MPRG_PG_TREE_FIELDS) and weights are
+ *   mprg_prog_tree's: the tables where mprg_prog_distances or mprg_prog_identities left them (only b > a of a table is read), the
+ *   leaves' multiplicities m_a (null: 1 each).  merges, merges_words: the locus's L - 1 merges {key(U), key(V)} at its merges offset,
+ *   as mprg_prog_tree(_wide) writes them (the offset must be even).  With D as mprg_prog_tree states it, per merge t of clusters U, V:
+ *   N_t = sum of m_a m_b D(a, b) over a in U, b in V, |U| = sum of m_a, H_t = N_t / (|U| |V|) (truncating; a leaf has H = 0); the
+ *   edge above a node c with parent t has len(c) = max(H_t - H_c, 0) and n_c = the multiplicity sum below c;
+ *   c_a = sum over the nodes c on the path from leaf a (inclusive) to the root (exclusive) of (256 len(c) m_a) / n_c;
+ *   M = the largest c_a of the locus; q_a = 1 if M = 0, else 1 + (255 c_a) / M, so 1 <= q_a <= 256.
+ *   heights (int32, merges_words / 2 long): heights[offset / 2 + t] = H_t.  raw (int64) and q (int32), n_seqs long each:
+ *   raw[first + a] = c_a, q[first + a] = q_a; a record that is no leaf gets 0 in both.  Any valid merge list is taken, UPGMA's or
+ *   not (the max is the clamp of a height that falls).  L = 1: q = 1; L = 0: zeros; no merge is read.
+ *   The workspace need of a locus is 6 m int64 words, whatever L is.
+ *   status: n_loci int32: MPRG_PG_OK; MPRG_PG_BAD_ITEM (mprg_prog_tree's range clauses, an odd merges offset, a leaf's multiplicity
+ *   below 1, a multiplicity sum above 2^20, more than 4 096 leaves: nothing else written.  Also for a merge whose keys are not two
+ *   live clusters with key(U) < key(V), a leaf's nw below 0 or an s(a, b) between leaves above min(nw_a, nw_b) > 0: the locus's
+ *   workspace may have been written, heights, raw and q are not); MPRG_PG_NO_SPACE (the workspace need outside workspace_words:
+ *   nothing else written).  One workgroup per locus, a few words of LDS; every pair of leaves is read once. */
+int mprg_prog_leaf_weights(const uint32_t *shared, long long shared_words, const int64_t *nw, const int64_t *seqs, long long n_seqs,
+                           const int64_t *loci, int n_loci, const int32_t *weights, int64_t *workspace, long long workspace_words,
+                           const int32_t *merges, long long merges_words, int32_t *heights, int64_t *raw, int32_t *q, int32_t *status,
+                           void *stream);
+
 /* (f)-1 output encoders, HOST functions (host pointers), one pass over a PRG string as PrgBuilder emits it.
  * reference make_prg/utils/prg_encoder.py:44-91 and make_prg/utils/gfa.py:16-109.
  * mprg_prg_encode_host: out[n] receives the uint32 stream (A C G T -> 1 2 3 4, markers as integers, the closing

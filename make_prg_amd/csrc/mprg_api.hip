@@ -27,6 +27,7 @@
 #include "k_prog_tree_wide.inc"
 #include "k_tree_refine.inc"
 #include "k_prog_retree.inc"
+#include "k_prog_weights.inc"
 #include "host_encoders.inc"
 #include "host_batch.inc"
 
@@ -807,6 +808,16 @@ int mprg_prog_identities(const int64_t *bufs, int n_bufs, const int64_t *items, 
   LAUNCH(k_prog_identities, n_work, PI_THREADS, stream, bufs, n_bufs, items, n_items, work, leaf, leaf_words, shared, shared_words, nw,
          n_seqs, status);      // a workgroup per (item, row block)
   return check_launch("k_prog_identities");
+}
+
+int mprg_prog_leaf_weights(const uint32_t *shared, long long shared_words, const int64_t *nw, const int64_t *seqs, long long n_seqs,
+                           const int64_t *loci, int n_loci, const int32_t *weights, int64_t *workspace, long long workspace_words,
+                           const int32_t *merges, long long merges_words, int32_t *heights, int64_t *raw, int32_t *q, int32_t *status,
+                           void *stream) {
+  if (n_loci <= 0) return 0;
+  LAUNCH(k_prog_leaf_weights, n_loci, PG_THREADS, stream, shared, shared_words, nw, seqs, n_seqs, loci, weights, workspace,
+         workspace_words, merges, merges_words, heights, raw, q, status);      // a workgroup per locus
+  return check_launch("k_prog_leaf_weights");
 }
 
 // ---- the recursion forest on the device (k_forest.inc); F: host array of MPRG_F_FIELDS int64 ------------------------------

@@ -28,6 +28,9 @@ With `--retree` (and `--progressive`) the guide tree is rebuilt from the progres
 the locus is aligned again up the new tree; the new MSA is kept if it raises the objective (Retree below; kernel:
 csrc/k_prog_retree.inc, C ABI: mprg_prog_identities).
 
+With `--seq-weights` (and `--progressive`) every leaf of the guide tree gets a weight from the tree, its share of the edges above it,
+and counts that often in every merge (Sequence weights below; kernel: csrc/k_prog_weights.inc, C ABI: mprg_prog_leaf_weights).
+
 It is NOT MAFFT.  PRGs built from these alignments differ from PRGs built from a MAFFT alignment of the same sequences.
 
 Spec (the kernels and tests/star_ref.py follow it bit for bit)
@@ -127,7 +130,7 @@ a guide tree, profile against profile.  It replaces Centre, Pairs and Merge; Inp
             same score).  |sum| <= 1 280 R_X, so the division is a multiplication and a shift on the device (k_prog.inc, pg_div).
   Output.   The root's rows in input order, the empty records as all-gap rows, titles unchanged.
   Not promised.  Identical input sequences need not give identical rows (two different sequences can have D = 0 and merge between
-            them).  No sequence weighting.  It is not MAFFT.  adjust_direction runs first, on the records; refine runs afterwards,
+            them).  No sequence weighting unless seq_weights asks for it (Sequence weights below).  It is not MAFFT.  adjust_direction runs first, on the records; refine runs afterwards,
             on the progressive MSA's text on the device, unchanged.  With band the merges run over certified bands (below) and
             the realignments of refine over theirs: the same bytes.
   Invariants (tested): every row with its gaps removed is its input sequence; no column is all gaps.
@@ -296,6 +299,45 @@ distances are taken a second time, from the MSA the first tree built, a new tree
             mprg_tree_objective launch, 8 bytes of S per locus downloaded.  The old root's buffer is dropped when the new MSA is
             accepted, the new one when it is refused (_prog_rounds' live counts).  No MSA text leaves the device during the stage.
 
+Sequence weights (only with progressive and seq_weights; integers only; tests/weights_ref.py states it in plain Python; kernel:
+csrc/k_prog_weights.inc, C ABI: mprg_prog_leaf_weights).  At a merge every row of a profile counts once, so an over-sampled clade
+outvotes a rare sub-family wherever the two are joined (with collapse: a class of 6 000 copies counts 6 000 times).  A leaf's weight
+is the tree length it does not share with its relatives (ClustalW's scheme), so a crowded clade counts about as much as a lonely one.
+  Per locus, over what the tree was built from: the leaves (non-empty records; with collapse the class representatives) and their
+            multiplicities m_a (1 without collapse), the distances D(a, b) the tree was built on (Progressive's 6-mer D, or
+            Retree's D' for a rebuilt tree), and the tree's merges in order, as (key(U), key(V)).
+  Heights.  For the inner node t that merges clusters U and V: N_t = sum over a in U, b in V of m_a m_b D(a, b); |U| = sum of m_a
+            over U; H_t = floor(N_t / (|U| |V|)).  A leaf has H = 0.  Under Large loci's limits N_t <= 2^54, the divisor <= 2^38,
+            H_t <= 65 536.
+  Edges.    The edge above a node c with parent t has len(c) = max(H_t - H_c, 0) and n_c = the multiplicity sum of the leaves
+            below c.  UPGMA's own trees never need the clamp (average linkage has no inversions and the floor is monotone;
+            tests/weights_ref.py's loci show none); the kernel accepts any valid merge list.
+  Raw weight.  c_a = sum over the nodes c on the path from leaf a (inclusive) to the root (exclusive) of
+            floor(256 len(c) m_a / n_c).  The numerator is at most 2^44, and c_a <= 2^24.  With collapse this is the weight of the
+            whole class: m_a records, each with its share.
+  Weight.   M = max_a c_a.  q_a = 1 if M = 0, else 1 + floor(255 c_a / M).  So 1 <= q_a <= 256 and the sum over at most 4 096 leaves
+            is at most 2^20: exactly what mprg_prog_columns_weighted, pg_div and PG_MAX_ROWS accept.
+  Merge.    Progressive's merge through Collapse's weighted column tables, with the row of leaf a counting q_a times on both
+            sides; R_Y and R_X are the q sums.
+  Nothing else changes: the tree, the choice of Y (rows, or with collapse the multiplicity sum, then the lower key), the rounds and
+            the output order, Collapse's expansion, and the objective S, which stays the sum of pairs over records and
+            multiplicities, never over q.
+  Two facts (tested): multiplying every q of a locus by a constant changes no plane and no score ((64 k v) / (k R) truncates like
+            (64 v) / R, and the same holds for X's counts); so, without collapse, a locus whose leaves all get the same q keeps
+            its progressive bytes, and a locus of fewer than 3 leaves needs no weights at all (two leaves always get equal q).
+  With      adjust_direction first; band, device_tree and a small budget_bytes give the same bytes; collapse and large_loci as
+            above (equal sequences still get equal rows); retree: the pass up a rebuilt tree uses the weights from that tree and
+            from D', acceptance by S as before; refine_tree: a step's realignment counts every row with the q of the tree that
+            built the accepted MSA, acceptance by S with multiplicities as before; refine runs afterwards, unchanged and unweighted.
+  The flag promises the stated weights, not a higher S: S counts every record equally, and moves either way by fractions of a percent.
+  Host side: a stage in _progressive after the plan.  With device_tree the weights launch joins each group's launches in
+            _prog_trees (the tables and the merges are still on the device); with the host's tree the group's tables are computed
+            again by _distances_launch and the merges uploaded (the tables are never weighted on the host).  Only q (4 bytes a
+            record) and the status words come back.  _prog_rounds, _tree_refine and _retree take q as a second per-record array,
+            the alignment weights, beside the multiplicities, which keep their role in the plan, the expansion and S;
+            _retree_trees launches the weights over the identity tables it already has on the device.  leaf_weights is the same
+            statement in Python integers.
+
 Progressive, host side: per chunk the distances in launches whose m x m tables fit budget_bytes (loci of three or more leaves), D
 and the tree per locus in NumPy / Python integers (prog_tree: a float64 quotient only shortlists, the choice is exact).  A node's
 round is 1 + the larger of its children's rounds.  With device_tree the tree is built on the device instead (csrc/k_prog_tree.inc):
@@ -365,11 +407,14 @@ TREE_REFINE_MIN_LEAVES = 4                # below it no step leaves two leaves o
 TREE_REFINE_DEFAULT, TREE_REFINE_MAX = 1, 4   # passes of `--refine-tree` alone, and the most it takes
 PI_ITEM_FIELDS, PI_BLOCK_ROWS = 8, 16         # MPRG_PI_ITEM_FIELDS, MPRG_PI_BLOCK_ROWS
 RETREE_DEFAULT, RETREE_MAX = 1, 4             # rebuilds of `--retree` alone, and the most it takes
+SEQ_WEIGHT_UNIT = 256                         # the spec's Sequence weights: the scale of a raw weight, and the largest q
 PG_STATUS = {1: "an index, a tile or a source range outside its table or buffer", 2: "ops, widths and cells that do not fit each other",
              3: "the output outside its buffer"}
 TREE_STATUS = {1: "a range outside its buffer, a leaf's weight below 1 or a weight sum above 4 096", 3: "the workspace outside its buffer"}
 WIDE_TREE_STATUS = {1: "a range outside its buffer, a leaf's weight below 1, a weight sum above 2^20 or more than 4 096 leaves",
                     3: "the workspace outside its buffer"}
+WEIGHTS_STATUS = {1: "a range outside its buffer, a multiplicity below 1, a multiplicity sum above 2^20, more than 4 096 leaves, a merge list "
+                     "that is no tree over the leaves, or a table entry out of bounds", 3: "the workspace outside its buffer"}
 _GAP = ord("-")
 _ASCII = np.frombuffer(b"ACGT-RYKMSWN", np.uint8)
 
@@ -451,7 +496,8 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
               refinement: Optional[list] = None, progressive: bool = False, progression: Optional[list] = None,
               max_leaves: Optional[int] = None, collapse: bool = False, device_tree: bool = False, refine_tree: Optional[int] = None,
               tree_refinement: Optional[list] = None, tree_refine_max_leaves: int = TREE_REFINE_MAX_LEAVES, large_loci: bool = False,
-              max_records: Optional[int] = None, retree: Optional[int] = None, retreeing: Optional[list] = None) -> List[MSA]:
+              max_records: Optional[int] = None, retree: Optional[int] = None, retreeing: Optional[list] = None,
+              seq_weights: bool = False) -> List[MSA]:
     """loci: per locus its records as (title, sequence).  Returns the loci's centre-star MSAs (ids: the titles' first words,
     descriptions: the titles).  names: the loci's names for error messages (default: their indices).  timings: a dict that
     receives the wall seconds of the stages (orient, centre, pairs, merge: each ends at a download, so includes its kernels).
@@ -494,9 +540,16 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
     computes differently.  retreeing: a list that then receives per locus (iterations run, accepted, why it stopped: "same",
     "refused", "limit", "bound", or None when every iteration was accepted or the locus has fewer than 3 leaves, S before, S after),
     None for a locus left to the star pass.  timings also receives retree_s and retree_loci, retree_rebuilds, retree_accepted,
-    retree_same_tree, retree_refused, retree_over_bound."""
+    retree_same_tree, retree_refused, retree_over_bound.
+    seq_weights: only with progressive (else a ValueError): the spec's Sequence weights: every leaf of a locus of three or more
+    leaves counts q times (1 to 256) in the merges, in the rebuilds of retree and in the realignments of refine_tree.  timings also
+    receives seq_weight_loci (the loci weighted), seq_weight_min_q (the smallest q of any leaf) and seq_weight_s (the stage's wall
+    seconds: its launches and downloads; on the host's tree the second distances launches too).  False: nothing launches, uploads
+    or downloads differently."""
     if device_tree and not progressive:
         raise ValueError("device_tree: only with progressive")
+    if seq_weights and not progressive:
+        raise ValueError("seq_weights: only with progressive")
     if large_loci and not (progressive and collapse):
         raise ValueError("large_loci: only with progressive and collapse")
     if max_records is not None and not (large_loci and 0 <= int(max_records) <= PROG_MAX_RECORDS):
@@ -525,7 +578,7 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
                                  int(refine), refinement, progression, PROG_MAX_LEAVES if max_leaves is None else int(max_leaves), bool(collapse),
                                  bool(device_tree), int(refine_tree or 0), tree_refinement, int(tree_refine_max_leaves),
                                  (PROG_MAX_RECORDS if max_records is None else int(max_records)) if large_loci else None, int(retree or 0),
-                                 retreeing)
+                                 retreeing, bool(seq_weights))
     return [m for lo, hi in _chunks(codes, chunk_bytes)
             for m in _star_chunk(backend, loci[lo:hi], codes[lo:hi], names[lo:hi], budget_bytes, timings, adjust_direction, orientation, band,
                                  int(refine), refinement, collapse=bool(collapse))]
@@ -533,7 +586,7 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
 
 def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings, adjust_direction, orientation, band, refine, refinement,
                       progression, max_leaves, collapse=False, device_tree=False, refine_tree=0, tree_refinement=None,
-                      tree_max_leaves=TREE_REFINE_MAX_LEAVES, max_records=None, retree=0, retreeing=None) -> List[MSA]:
+                      tree_max_leaves=TREE_REFINE_MAX_LEAVES, max_records=None, retree=0, retreeing=None, seq_weights=False) -> List[MSA]:
     """star_msas with progressive: the loci within the leaf limit through the progressive chunks, the others through the star
     chunks, the results (and what the caller's lists receive) back in the loci's order.  max_records (the spec's Large loci; None:
     without it): only the loci of more records go to the star chunks here; the progressive chunks count every locus's classes
@@ -552,7 +605,7 @@ def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings
                                     ori if orientation is not None else None, band, refine, ref if refinement is not None else None,
                                     prog, pro, collapse, device_tree and prog, refine_tree if prog else 0,
                                     tre if tree_refinement is not None else None, tree_max_leaves, limits if prog else None,
-                                    retree if prog else 0, ret if retreeing is not None else None))
+                                    retree if prog else 0, ret if retreeing is not None else None, seq_weights and prog))
         if not prog:
             pro = [(n_leaves[l], 0, True) for l in sel]
         for k, l in enumerate(sel):
@@ -574,7 +627,7 @@ def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings
 
 def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direction=False, orientation=None, band=None, refine=0,
                 refinement=None, progressive=False, progression=None, collapse=False, device_tree=False, refine_tree=0,
-                tree_refinement=None, tree_max_leaves=TREE_REFINE_MAX_LEAVES, limits=None, retree=0, retreeing=None) -> List[MSA]:
+                tree_refinement=None, tree_max_leaves=TREE_REFINE_MAX_LEAVES, limits=None, retree=0, retreeing=None, seq_weights=False) -> List[MSA]:
     """One chunk: pack, optionally orient, optionally collapse, the star pass or the progressive one (with its tree refinement),
     optionally refine, collect.  limits (the spec's Large loci; only with progressive and collapse): (max_leaves, max_records): the
     loci with more classes of non-empty records, or more records, go through the star pass."""
@@ -591,13 +644,13 @@ def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direc
         build = (n_classes <= limits[0]) & (chunk.counts <= limits[1])
         if not build.all():
             return _star_chunk_parts(be, chunk, classes, build, budget_bytes, laps, band, refine, refinement, progression, device_tree,
-                                     refine_tree, tree_refinement, tree_max_leaves, retree, retreeing)
+                                     refine_tree, tree_refinement, tree_max_leaves, retree, retreeing, seq_weights)
     return _star_chunk_rest(be, chunk, classes, budget_bytes, laps, band, refine, refinement, progressive, progression, device_tree,
-                            refine_tree, tree_refinement, tree_max_leaves, retree, retreeing)
+                            refine_tree, tree_refinement, tree_max_leaves, retree, retreeing, seq_weights)
 
 
 def _star_chunk_parts(be, chunk: Chunk, classes, build, budget_bytes, laps, band, refine, refinement, progression, device_tree,
-                      refine_tree, tree_refinement, tree_max_leaves, retree=0, retreeing=None) -> List[MSA]:
+                      refine_tree, tree_refinement, tree_max_leaves, retree=0, retreeing=None, seq_weights=False) -> List[MSA]:
     """_star_chunk behind Collapse for a chunk of which only the loci `build` (a bool per locus) are built progressively (the spec's
     Large loci): those as one chunk through the progressive pass, the others as one through the star pass, both over the same code
     buffer and the classes already made; the MSAs, and what the caller's lists receive, back in the chunk's order."""
@@ -614,7 +667,8 @@ def _star_chunk_parts(be, chunk: Chunk, classes, build, budget_bytes, laps, band
                               lens=chunk.lens[rec], seq_off=chunk.seq_off[rec], first=exclusive_sum(chunk.counts[sel]), counts=chunk.counts[sel])
         got = [[], [], [], []]
         out = _star_chunk_rest(be, part, Classes(at[classes.rep[rec]], classes.weight[rec]), budget_bytes, laps, band, refine, got[0], prog,
-                               got[1], device_tree and prog, refine_tree if prog else 0, got[2], tree_max_leaves, retree if prog else 0, got[3])
+                               got[1], device_tree and prog, refine_tree if prog else 0, got[2], tree_max_leaves, retree if prog else 0, got[3],
+                               seq_weights and prog)
         if not prog:
             got[1] = [(int(n_filled[l]), 0, True) for l in sel]
         for k, l in enumerate(sel.tolist()):
@@ -629,11 +683,11 @@ def _star_chunk_parts(be, chunk: Chunk, classes, build, budget_bytes, laps, band
 
 
 def _star_chunk_rest(be, chunk: Chunk, classes, budget_bytes, laps, band, refine, refinement, progressive, progression, device_tree,
-                     refine_tree, tree_refinement, tree_max_leaves, retree=0, retreeing=None) -> List[MSA]:
+                     refine_tree, tree_refinement, tree_max_leaves, retree=0, retreeing=None, seq_weights=False) -> List[MSA]:
     """_star_chunk behind Collapse: the star pass or the progressive one (with its tree refinement), optionally refine, collect."""
     timings = laps.timings
     text = (_progressive(be, chunk, budget_bytes, band, laps, progression, classes, device_tree, refine_tree, tree_refinement,
-                         tree_max_leaves, retree, retreeing) if progressive else
+                         tree_max_leaves, retree, retreeing, seq_weights) if progressive else
             _star_pass(be, chunk, budget_bytes, band, laps, classes))
     moved = {}
     if refine:
@@ -980,12 +1034,18 @@ def prog_tree_bytes(m):
     return 4 * m * m + 8 * prog_tree_words(m)
 
 
-def _prog_trees(be, chunk: Chunk, sel, budget_bytes, weights=None):
+def prog_weights_words(m):
+    """mprg_prog_leaf_weights' workspace need (int64 words) of a locus of m records."""
+    return 6 * m
+
+
+def _prog_trees(be, chunk: Chunk, sel, budget_bytes, weights=None, seq_weights: Optional["_LeafWeights"] = None):
     """The spec's Tree of the loci `sel` of a chunk on the device, in groups whose m x m tables and tree workspaces fit budget_bytes:
     per group one mprg_prog_distances launch and one mprg_prog_tree launch over the tables it left on the device; the status words
     and the merges are all that is downloaded.  Per locus its merges as prog_tree gives them.  weights: per record of the chunk's
     tables how many times it counts (the spec's Collapse).  The loci whose weight sum exceeds PROG_MAX_LEAVES (the spec's Large
-    loci) form groups of their own, whose trees mprg_prog_tree_wide builds."""
+    loci) form groups of their own, whose trees mprg_prog_tree_wide builds.  seq_weights (the spec's Sequence weights): every group
+    is followed by an mprg_prog_leaf_weights launch over the same tables and the merges where the tree launch left them."""
     lens, first = chunk.lens, chunk.first
     out = {}
     d_seqs = be.upload(np.stack([chunk.seq_off, lens], 1).reshape(-1))
@@ -996,9 +1056,127 @@ def _prog_trees(be, chunk: Chunk, sel, budget_bytes, weights=None):
     for grp, entry, table in _tree_groups(chunk, sel, budget_bytes, weights):
         m, toff, words, d_shared, d_nw, d_status, n_work = _distances_launch(be, chunk, d_seqs, grp)
         launched = _tree_launch(be, chunk, grp, entry, d_seqs, d_weights, n_leaves, toff, words, d_shared, d_nw)
+        if seq_weights is not None:
+            seq_weights.launch(grp, d_seqs, d_weights, toff, words, d_shared, d_nw, *launched[1:])
         _check(be.download(d_status, np.int32, n_work), "mprg_prog_distances", PG_STATUS)
         out.update(_tree_merges(be, grp, entry, table, *launched))
     return out
+
+
+class _LeafWeights:
+    """The spec's Sequence weights of a chunk on the device: q and raw per record of the chunk's tables, one pair of buffers for all
+    launches; launch() is one mprg_prog_leaf_weights launch over a group's tables and merges where they are; q() downloads the
+    status words of the launches and q, nothing else."""
+
+    def __init__(self, be, chunk: Chunk):
+        self.be, self.chunk, self.pending, self.groups, self.spent = be, chunk, [], [], 0.0
+        self.n_leaves = np.add.reduceat((chunk.lens > 0).astype(np.int64), chunk.first)
+        self.d_q, self.d_raw = be.zeros(4 * len(chunk.lens)), be.zeros(8 * len(chunk.lens))
+
+    def launch(self, grp, d_seqs, d_weights, toff, words, d_shared, d_nw, d_merges, n_merges, moff):
+        be, chunk = self.be, self.chunk
+        t0 = time.perf_counter()
+        m = chunk.counts[grp]
+        ws_words = prog_weights_words(m)
+        ttab = np.stack([chunk.first[grp], m, toff, exclusive_sum(ws_words), moff], 1).astype(np.int64)
+        total = int(n_merges.sum())
+        d_ttab, d_ws = be.upload(ttab), be.empty(8 * int(ws_words.sum()))
+        d_heights, d_status = be.empty(4 * total), be.empty(4 * len(grp))
+        be.call("mprg_prog_leaf_weights", be.ptr(d_shared), words, be.ptr(d_nw), be.ptr(d_seqs), len(chunk.lens), be.ptr(d_ttab), len(grp),
+                0 if d_weights is None else be.ptr(d_weights), be.ptr(d_ws), int(ws_words.sum()), be.ptr(d_merges), 2 * total,
+                be.ptr(d_heights), be.ptr(self.d_raw), be.ptr(self.d_q), be.ptr(d_status), be.stream,
+                work=float((self.n_leaves[grp] ** 2).sum() * 8.0))
+        self.pending.append((d_status, len(grp), d_heights))
+        self.groups.append(grp.tolist())
+        self.spent += time.perf_counter() - t0
+
+    def upload_and_launch(self, grp, trees, d_seqs, d_weights, toff, words, d_shared, d_nw):
+        """launch() for merges made on the host: trees[l], the merges of every locus of grp, uploaded."""
+        n_merges = np.array([len(trees[l]) for l in grp.tolist()], np.int64)
+        flat = np.array([p for l in grp.tolist() for p in trees[l]], np.int32).reshape(-1)
+        self.launch(grp, d_seqs, d_weights, toff, words, d_shared, d_nw, self.be.upload(flat), n_merges, 2 * exclusive_sum(n_merges))
+
+    def q(self) -> np.ndarray:
+        t0 = time.perf_counter()
+        for d_status, n, _ in self.pending:
+            _check(self.be.download(d_status, np.int32, n), "mprg_prog_leaf_weights", WEIGHTS_STATUS, "locus")
+        self.pending = []
+        got = self.be.download(self.d_q, np.int32, len(self.chunk.lens)).astype(np.int64)
+        self.spent += time.perf_counter() - t0
+        return got
+
+
+def _prog_weights(be, chunk: Chunk, sel, trees, budget_bytes, weights=None) -> "_LeafWeights":
+    """The spec's Sequence weights of the loci `sel` whose trees were built on the host: in groups whose tables fit budget_bytes the
+    distances launch again (the tables are not kept on the device, and never weighted on the host), the merges uploaded, one
+    mprg_prog_leaf_weights launch."""
+    lw = _LeafWeights(be, chunk)
+    t0 = time.perf_counter()
+    d_seqs = be.upload(np.stack([chunk.seq_off, chunk.lens], 1).reshape(-1))
+    d_weights = None if weights is None else be.upload(np.asarray(weights, np.int32))
+    checks = []
+    for lo, hi in pa.budget_groups(4 * chunk.counts[sel] ** 2 + 8 * prog_weights_words(chunk.counts[sel]), budget_bytes):
+        grp = sel[lo:hi]
+        m, toff, words, d_shared, d_nw, d_status, n_work = _distances_launch(be, chunk, d_seqs, grp)
+        lw.upload_and_launch(grp, trees, d_seqs, d_weights, toff, words, d_shared, d_nw)
+        checks.append((d_status, n_work))
+    for d_status, n_work in checks:
+        _check(be.download(d_status, np.int32, n_work), "mprg_prog_distances", PG_STATUS)
+    lw.spent = time.perf_counter() - t0                         # (the distances launches are the stage's here)
+    return lw
+
+
+def prog_leaf_weights(backend, codes: Sequence[Sequence[np.ndarray]], merges: Sequence[Sequence[Tuple[int, int]]],
+                      weights: Optional[Sequence[Sequence[int]]] = None, budget_bytes: int = pa.DEFAULT_BUDGET_BYTES):
+    """mprg_prog_distances and mprg_prog_leaf_weights over the loci (per locus its gap-free code arrays; an empty one is no leaf) and
+    their trees (per locus the merges in order as (key(U), key(V)), as prog_trees and prog_tree give them): per locus the spec's
+    Sequence weights as (heights per merge, raw per record, q per record), what leaf_weights gives from D; a record that is no leaf
+    has 0 in raw and q.  weights: per locus, per record, its multiplicity (the spec's Collapse)."""
+    be = backend
+    chunk = _pack(be, codes)
+    flat = None if weights is None else np.concatenate([np.asarray(w, np.int64) for w in weights])
+    lw = _prog_weights(be, chunk, np.arange(len(codes)), list(merges), budget_bytes, flat)
+    heights = [be.download(d_heights, np.int32, sum(len(merges[l]) for l in grp)) for grp, d_heights in
+               zip(lw.groups, [p[2] for p in lw.pending])]
+    q = lw.q()
+    raw = be.download(lw.d_raw, np.int64, len(chunk.lens))
+    out = [None] * len(codes)
+    for grp, h in zip(lw.groups, heights):
+        at = 0
+        for l in grp:
+            rec = slice(int(chunk.first[l]), int(chunk.first[l] + chunk.counts[l]))
+            out[l] = (h[at:at + len(merges[l])].astype(np.int64), raw[rec].copy(), q[rec].copy())
+            at += len(merges[l])
+    return out
+
+
+def leaf_weights(D, leaves: Sequence[int], merges: Sequence[Tuple[int, int]], weights=None):
+    """The spec's Sequence weights in Python integers: D[a][b] the distances the tree was built on, leaves (ascending indices into
+    D), merges the tree as prog_tree gives it, weights per leaf its multiplicity (default 1).  Returns (heights per merge, raw per
+    leaf, q per leaf)."""
+    lv = [int(a) for a in leaves]
+    mult = {a: 1 if weights is None else int(w) for a, w in zip(lv, lv if weights is None else weights)}
+    live = {a: (None, [a], mult[a]) for a in lv}              # per key: its cluster's node (None: a leaf), leaves, multiplicity sum
+    heights, par, lpar, below = [], {}, {}, {}
+    for t, (u, v) in enumerate(merges):
+        (nu, mu, su), (nv, mv, sv) = live[u], live.pop(v)
+        heights.append(sum(mult[a] * mult[b] * int(D[a][b]) for a in mu for b in mv) // (su * sv))
+        for key, node in ((u, nu), (v, nv)):
+            if node is None:
+                lpar[key] = t
+            else:
+                par[node] = t
+        below[t] = su + sv
+        live[u] = (t, mu + mv, su + sv)
+    raw = []
+    for a in lv:
+        c, h, n, t = 0, 0, mult[a], lpar.get(a)
+        while t is not None:
+            c += (SEQ_WEIGHT_UNIT * max(heights[t] - h, 0) * mult[a]) // n
+            h, n, t = heights[t], below[t], par.get(t)
+        raw.append(c)
+    top = max(raw, default=0)
+    return heights, raw, [1 if top == 0 else 1 + ((SEQ_WEIGHT_UNIT - 1) * c) // top for c in raw]
 
 
 def _tree_groups(chunk: Chunk, sel, budget_bytes, weights=None):
@@ -1270,15 +1448,24 @@ def merge_profiles(backend, pairs: Sequence[Tuple[np.ndarray, np.ndarray]], budg
     return out
 
 
+def _seq_weight_counters(counters, n_loci, q, spent):
+    """The spec's Sequence weights in the counters: the loci weighted, the smallest q of any leaf, the stage's wall seconds."""
+    add_to(counters, "seq_weight_loci", int(n_loci))
+    add_to(counters, "seq_weight_s", float(spent))
+    if counters is not None and len(q):
+        counters["seq_weight_min_q"] = min(int(counters.get("seq_weight_min_q", SEQ_WEIGHT_UNIT)), int(q.min()))
+
+
 def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression, classes: Optional[Classes] = None, device_tree=False,
-                 refine_tree=0, tree_refinement=None, max_leaves=None, retree=0, retreeing=None):
+                 refine_tree=0, tree_refinement=None, max_leaves=None, retree=0, retreeing=None, seq_weights=False):
     """The spec's Progressive over one chunk, on the (oriented) sequences in chunk.d_codes.  Returns what the star pass leaves: the
     device buffer of the MSAs' ASCII text, its bytes, each locus's offset in it and its width.  classes: the spec's Collapse: the
     tree and the merges over the representatives with their weights, the root's rows written for every member.  device_tree: the
     trees by mprg_prog_tree (_prog_trees) instead of prog_tree.  refine_tree: the passes of the spec's Tree refinement on the
     roots' texts before they are written out (0: none); tree_refinement receives its tuples, max_leaves is its cap.  retree: the
     rebuilds of the spec's Retree, in front of that (0: none); retreeing receives its tuples, progression then the tuples of the
-    trees that built the texts that are written."""
+    trees that built the texts that are written.  seq_weights: the spec's Sequence weights: q per leaf from the trees, after the
+    plan, as the rows' weights in every merge."""
     laps.lap()
     lens, first, counts = chunk.lens, chunk.first, chunk.counts
     n_leaves = np.add.reduceat((lens > 0).astype(np.int64), first)          # (every locus has a record)
@@ -1297,8 +1484,9 @@ def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression,
     # the trees: distances on the device for the loci with three or more leaves (two leaves have one tree), UPGMA on the host or,
     # with device_tree, on the device
     sel = np.nonzero(n_leaves >= 3)[0]
+    lw = _LeafWeights(be, chunk) if seq_weights and device_tree and len(sel) else None
     if device_tree:
-        merges = _prog_trees(be, chunk, sel, budget_bytes, weights) if len(sel) else {}
+        merges = _prog_trees(be, chunk, sel, budget_bytes, weights, lw) if len(sel) else {}
         add_to(laps.timings, "tree_device_loci", len(sel))
         t0 = time.perf_counter()
         plan = _prog_plan(lens, first, counts, None, weights, merges)
@@ -1308,10 +1496,20 @@ def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression,
         plan = _prog_plan(lens, first, counts, shared, weights)
     add_to(laps.timings, "tree_plan_s", time.perf_counter() - t0)
     laps.lap("tree_s")
-    bufs, live, where = _prog_rounds(be, chunk, plan, budget_bytes, band, laps.timings, weights)
+    # the spec's Sequence weights: q per leaf of the loci that have a tree (fewer than three leaves need none: their q are equal)
+    align = None
+    if seq_weights:
+        align = np.ones(len(lens), np.int64)
+        if len(sel):
+            lw = lw if device_tree else _prog_weights(be, chunk, sel, plan[4], budget_bytes, weights)
+            rec = _ranges(first[sel], counts[sel])
+            align[rec] = np.maximum(lw.q()[rec], 1)            # (an empty record has no row: its entry is never read)
+            _seq_weight_counters(laps.timings, len(sel), align[rec][lens[rec] > 0], lw.spent)
+        laps.lap("tree_s")
+    bufs, live, where = _prog_rounds(be, chunk, plan, budget_bytes, band, laps.timings, weights, align=align)
     laps.lap("progressive_s")
     if retree:
-        plan, result = _retree(be, chunk, plan, bufs, live, where, weights, retree, budget_bytes, band, device_tree, laps.timings)
+        plan, result = _retree(be, chunk, plan, bufs, live, where, weights, retree, budget_bytes, band, device_tree, laps.timings, align)
         if retreeing is not None:
             retreeing.extend(result)
         laps.lap("retree_s")
@@ -1319,7 +1517,8 @@ def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression,
         progression.extend(plan[-1])
     order = plan[3]
     if refine_tree:
-        order, result = _tree_refine(be, chunk, plan, bufs, live, where, weights, refine_tree, max_leaves, budget_bytes, band, laps.timings)
+        order, result = _tree_refine(be, chunk, plan, bufs, live, where, weights, refine_tree, max_leaves, budget_bytes, band, laps.timings,
+                                     align)
         if tree_refinement is not None:
             tree_refinement.extend(result)
         laps.lap("tree_refine_s")
@@ -1352,7 +1551,7 @@ def _prog_parents(be, d_bufs, n_bufs, Xg, Yg, d_ops, ops_bytes, ops_off, count):
     return d_new, new_bytes, poff, R
 
 
-def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters, weights=None, beyond=None):
+def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters, weights=None, beyond=None, align=None):
     """_progressive's device part: the plan's rounds (every node of a round, over all loci of the chunk, in one set of launches
     per budget group).  Returns (bufs, live, where) as the last round left them: of every locus only its root is in where.
     The texts' lifetime: bufs[b] is (buffer, bytes) of text buffer b, 0 the chunk's code buffer (the leaves); where[locus, node]
@@ -1361,12 +1560,15 @@ def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters, weights=N
     weights (the spec's Collapse): the chunk's tables hold the representatives only, weights per record of them; rw[locus, node]
     then is the weights of the node's rows.
     beyond (the spec's Retree): a set that receives the loci with a merge beyond Tree refinement's Limit (_tree_step_fits) instead
-    of an error: such a locus takes no further merge and none of its nodes stays in where."""
+    of an error: such a locus takes no further merge and none of its nodes stays in where.
+    align (the spec's Sequence weights): per record of the chunk's tables the weight q its row has in a merge, in place of the
+    multiplicities, which keep their role in the plan."""
     lens, seq_off, first, n_loci = chunk.lens, chunk.seq_off, chunk.first, chunk.n_loci
     leaves, by_round = plan[:2]
     bufs, live = [(chunk.d_codes, chunk.codes_bytes)], [0]
     where = {(l, a): (0, int(seq_off[first[l] + a]), 1, int(lens[first[l] + a])) for l in range(n_loci) for a in leaves[l]}
-    rw = {} if weights is None else {(l, a): weights[first[l] + a:first[l] + a + 1] for l in range(n_loci) for a in leaves[l]}
+    row_w = weights if align is None else align
+    rw = {} if row_w is None else {(l, a): row_w[first[l] + a:first[l] + a + 1] for l in range(n_loci) for a in leaves[l]}
 
     def merged(l, node):
         """The node has gone into its parent: its buffer goes with its last node."""
@@ -1392,8 +1594,9 @@ def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters, weights=N
             d_bufs = _bufs_table(be, bufs)
             Xg, Yg = X[grp], Y[grp]
             wg = None
-            if weights is not None:
+            if row_w is not None:
                 wg = ([rw[todo[k][0], todo[k][2]] for k in grp.tolist()], [rw[todo[k][0], todo[k][1]] for k in grp.tolist()])
+            if weights is not None:
                 add_to(counters, "collapse_merges", len(grp))
             d_ops, ops_bytes, ops_off, count, _ = _prog_pairs(be, d_bufs, len(bufs), Xg, Yg, band, budget_bytes, counters, wg)
             d_new, new_bytes, poff, R = _prog_parents(be, d_bufs, len(bufs), Xg, Yg, d_ops, ops_bytes, ops_off, count)
@@ -1402,7 +1605,7 @@ def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters, weights=N
             for i, k in enumerate(grp.tolist()):
                 l, y, x, parent = todo[k]
                 where[l, parent] = (len(bufs) - 1, int(poff[i]), int(R[i]), int(count[i]))
-                if weights is not None:
+                if row_w is not None:
                     rw[l, parent] = np.concatenate([rw.pop((l, y)), rw.pop((l, x))])
                 merged(l, y)
                 merged(l, x)
@@ -1496,16 +1699,19 @@ def prog_identities(backend, texts: Sequence[np.ndarray], leaf: Optional[Sequenc
     return [(shared[toff[k]:toff[k] + m[k] * m[k]].reshape(int(m[k]), int(m[k])), nw[first[k]:first[k] + m[k]]) for k in range(len(mats))]
 
 
-def _retree_trees(be, chunk: Chunk, sel, texts, order, bufs, weights, budget_bytes, device_tree):
+def _retree_trees(be, chunk: Chunk, sel, texts, order, bufs, weights, budget_bytes, device_tree, seq_weights=None):
     """The spec's Retree, Distance and Tree, for the loci `sel` of a chunk: texts[l] {buffer, offset, R, W} is the locus's current
     MSA, order[l] the records of its rows.  In _prog_trees' groups: one mprg_prog_identities launch, then with device_tree the tree
     launch over the tables where they are (the merges and the status words come back), without it the tables downloaded and
-    prog_tree on the host.  Per locus its merges as prog_tree gives them."""
+    prog_tree on the host.  Per locus its merges as prog_tree gives them.  seq_weights (a _LeafWeights; the spec's Sequence
+    weights): every group's trees (uploaded, where the host built them) go through mprg_prog_leaf_weights over the group's
+    identity tables, which are still on the device."""
     lens, first, counts = chunk.lens, chunk.first, chunk.counts
     out = {}
     n_leaves = np.add.reduceat((lens > 0).astype(np.int64), first)
-    d_seqs = be.upload(np.stack([chunk.seq_off, lens], 1).reshape(-1)) if device_tree else None
-    d_weights = None if weights is None or not device_tree else be.upload(np.asarray(weights, np.int32))
+    on_device = device_tree or seq_weights is not None
+    d_seqs = be.upload(np.stack([chunk.seq_off, lens], 1).reshape(-1)) if on_device else None
+    d_weights = None if weights is None or not on_device else be.upload(np.asarray(weights, np.int32))
     for grp, entry, table in _tree_groups(chunk, sel, budget_bytes, weights if device_tree else None):
         loci = grp.tolist()
         toff, words, d_shared, d_nw, d_status, n_work = _identities_launch(
@@ -1513,6 +1719,8 @@ def _retree_trees(be, chunk: Chunk, sel, texts, order, bufs, weights, budget_byt
             len(lens))
         if device_tree:
             launched = _tree_launch(be, chunk, grp, entry, d_seqs, d_weights, n_leaves, toff, words, d_shared, d_nw)
+            if seq_weights is not None:
+                seq_weights.launch(grp, d_seqs, d_weights, toff, words, d_shared, d_nw, *launched[1:])
             _check(be.download(d_status, np.int32, n_work), "mprg_prog_identities", PG_STATUS)
             out.update(_tree_merges(be, grp, entry, table, *launched))
             continue
@@ -1524,16 +1732,19 @@ def _retree_trees(be, chunk: Chunk, sel, texts, order, bufs, weights, budget_byt
             lv = np.nonzero(lens[rec] > 0)[0]
             out[l] = prog_tree(prog_distance_matrix(shared[toff[k]:toff[k] + mk * mk].reshape(mk, mk), nw[rec]), lv,
                                None if weights is None else weights[rec][lv])
+        if seq_weights is not None:
+            seq_weights.upload_and_launch(grp, out, d_seqs, d_weights, toff, words, d_shared, d_nw)
     return out
 
 
-def _retree(be, chunk: Chunk, plan, bufs, live, where, weights, rebuilds, budget_bytes, band, device_tree, counters):
+def _retree(be, chunk: Chunk, plan, bufs, live, where, weights, rebuilds, budget_bytes, band, device_tree, counters, align=None):
     """The spec's Retree over one chunk, on the roots' texts as _prog_rounds left them (bufs, live, where: its state, kept up here
     as _tree_refine keeps it up).  Per iteration all loci that are still iterating go together: the identities and the trees
     (_retree_trees), _prog_plan and _prog_rounds for the loci whose tree changed, from the leaves, into buffers of their own, one
     objective launch, S downloaded; the text that loses goes with its buffer.  Returns (the plan with the accepted trees, their
     row orders and progression tuples in place of the first ones, per locus (iterations, accepted, why it stopped, S before, S
-    after))."""
+    after)).  align (the spec's Sequence weights): per record its q; a rebuild runs with the q of the rebuilt tree on D', and an
+    accepted locus's entries of align are replaced by them, in place."""
     lens, first, counts, n_loci = chunk.lens, chunk.first, chunk.counts, chunk.n_loci
     leaves, root = plan[0], plan[2]
     order, trees, progression = [np.array(x, np.int64) for x in plan[3]], list(plan[4]), list(plan[5])
@@ -1553,8 +1764,14 @@ def _retree(be, chunk: Chunk, plan, bufs, live, where, weights, rebuilds, budget
     for _ in range(rebuilds):
         if not active:
             break
+        lw = None if align is None else _LeafWeights(be, chunk)
         merges = _retree_trees(be, chunk, np.array(active, np.int64), {l: where[l, root[l]] for l in active}, order, bufs, weights, budget_bytes,
-                               device_tree)
+                               device_tree, lw)
+        align2 = None
+        if lw is not None:                                      # every active locus's q on the tree just built
+            align2, rec = align.copy(), _ranges(first[active], counts[active])
+            align2[rec] = np.maximum(lw.q()[rec], 1)
+            _seq_weight_counters(counters, 0, align2[rec][lens[rec] > 0], lw.spent)
         for l in active:
             out[l][0] += 1
             if merges[l] == trees[l]:                           # a rebuild would reproduce the bytes
@@ -1569,7 +1786,7 @@ def _retree(be, chunk: Chunk, plan, bufs, live, where, weights, rebuilds, budget
         part = chunk._replace(first=first[todo], counts=counts[todo])
         plan2 = _prog_plan(lens, part.first, part.counts, None, weights, [merges[l] for l in todo])
         beyond = set()
-        bufs2, live2, where2 = _prog_rounds(be, part, plan2, budget_bytes, band, counters, weights, beyond)
+        bufs2, live2, where2 = _prog_rounds(be, part, plan2, budget_bytes, band, counters, weights, beyond, align2)
         made, new = {}, {}
         for k, l in enumerate(todo):
             if k in beyond:
@@ -1591,6 +1808,8 @@ def _retree(be, chunk: Chunk, plan, bufs, live, where, weights, rebuilds, budget
                 live[new[l][0]] += 1
                 where[l, root[l]], order[l], trees[l], progression[l] = new[l][:4], np.array(plan2[3][k], np.int64), merges[l], plan2[5][k]
                 out[l][1], out[l][4] = out[l][1] + 1, int(s2)
+                if align is not None:
+                    align[first[l]:first[l] + counts[l]] = align2[first[l]:first[l] + counts[l]]
                 used.append(old)
                 active.append(l)
             else:
@@ -1658,17 +1877,19 @@ def _tree_step_fits(WX, WY, budget_words):
     return (WX + WY < pa.MAX_LEN) & (pa.workspace_words_v(WX, WY) <= budget_words)
 
 
-def _tree_refine(be, chunk: Chunk, plan, bufs, live, where, weights, passes, max_leaves, budget_bytes, band, counters):
+def _tree_refine(be, chunk: Chunk, plan, bufs, live, where, weights, passes, max_leaves, budget_bytes, band, counters, align=None):
     """The spec's Tree refinement over one chunk, on the roots' texts as _prog_rounds left them (bufs, live, where: its state, kept
     up here: where[locus, root] names the locus's current text, a buffer is dropped when nothing points to it; weights: per
     record of the chunk's tables, the spec's Collapse).  Step s of every locus that still has one goes together: one split launch,
     the widths downloaded, the merges in _prog_groups' groups through _prog_pairs and _prog_parents, one objective launch, S
     downloaded.  Returns (per locus the records of its text's rows in row order, per locus (steps tried, accepted, skipped, S
-    before, S after))."""
+    before, S after)).  align (the spec's Sequence weights): per record the q its row has in a realignment, in place of the
+    multiplicities, which keep the choice of Y and the objective."""
     first, counts, n_loci = chunk.first, chunk.counts, chunk.n_loci
     leaves, root, trees = plan[0], plan[2], plan[4]
     order = [np.array(x, np.int64) for x in plan[3]]
     wl = [np.ones(int(counts[l]), np.int64) if weights is None else weights[first[l]:first[l] + counts[l]] for l in range(n_loci)]
+    al = wl if align is None else [align[first[l]:first[l] + counts[l]] for l in range(n_loci)]
     empty = np.array([counts[l] - len(leaves[l]) for l in range(n_loci)], np.int64)
     budget_words = max(64, int(budget_bytes) // 4)
 
@@ -1726,8 +1947,8 @@ def _tree_refine(be, chunk: Chunk, plan, bufs, live, where, weights, passes, max
                 g = sel[grp]
                 d_bufs = _bufs_table(be, bufs)
                 wg = None
-                if weights is not None:
-                    wg = ([wl[its[k]][order[its[k]][sides[k] == 1]] for k in g.tolist()], [wl[its[k]][order[its[k]][sides[k] == 0]] for k in g.tolist()])
+                if weights is not None or align is not None:
+                    wg = ([al[its[k]][order[its[k]][sides[k] == 1]] for k in g.tolist()], [al[its[k]][order[its[k]][sides[k] == 0]] for k in g.tolist()])
                 d_ops, ops_bytes, ops_off, count, _ = _prog_pairs(be, d_bufs, len(bufs), X[g], Y[g], band, budget_bytes, counters, wg)
                 d_new, new_bytes, poff, R = _prog_parents(be, d_bufs, len(bufs), X[g], Y[g], d_ops, ops_bytes, ops_off, count)
                 made.append(add_buf(d_new, new_bytes))

@@ -117,6 +117,14 @@ def register_parser(subparsers):
                         "MSA is kept only if it raises the locus's sum-of-pairs objective (star_align.py, Retree), so a locus whose "
                         "tree comes out the same or whose rebuild is refused keeps its --progressive bytes.  --refine-tree and "
                         "--refine run after it, --band and --device-tree give the same bytes.  Off by default")
+    p.add_argument("--seq-weights", dest="seq_weights", action="store_true", default=False,
+                   help="(this implementation) with --unaligned --progressive: every leaf of a guide tree gets a weight from 1 to 256, "
+                        "its share of the tree's edge lengths (ClustalW's scheme in integers; node heights from the tree's own "
+                        "distances on the GPU, csrc/k_prog_weights.inc), and counts that often in every profile merge, so an "
+                        "over-sampled clade counts about as much as a lonely one (star_align.py, Sequence weights).  The tree, the "
+                        "row order and the objective are unchanged; with --collapse-identical a class's weight replaces its size in "
+                        "the merges.  --retree and --refine-tree use the weights of the tree that built the MSA, --refine runs "
+                        "after it unweighted, --band and --device-tree give the same bytes.  Off by default")
     p.set_defaults(func=run, check=check_options)
     return p
 
@@ -154,6 +162,8 @@ def check_options(args, parser):
         from ..from_msa import star_align
         if not 1 <= args.retree <= star_align.RETREE_MAX:
             parser.error(f"--retree takes 1 to {star_align.RETREE_MAX} rebuilds, not {args.retree}")
+    if getattr(args, "seq_weights", False) and not getattr(args, "progressive", False):
+        parser.error("--seq-weights needs --progressive")
     if getattr(args, "refine", None) is not None:
         if not args.unaligned:
             parser.error("--refine needs --unaligned")
@@ -660,19 +670,21 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
     tree_refinement = []
     large_loci = bool(getattr(options, "large_loci", False))
     retree = int(getattr(options, "retree", None) or 0)
+    seq_weights = bool(getattr(options, "seq_weights", False))
     for lo in range(0, len(mine), STAR_CHUNK):
         t0 = time.perf_counter()
         recs = [star_align.read_unaligned(f) for f in mine[lo:lo + STAR_CHUNK]]
         t1 = time.perf_counter()
         msas = star_align.star_msas(be, recs, names=loci[lo:lo + STAR_CHUNK], adjust_direction=adjust, orientation=orientation,
-                                    **(dict(band=True) if band else {}), **(dict(timings=counters) if band or collapse or device_tree or refine_tree or retree else {}),
+                                    **(dict(band=True) if band else {}), **(dict(timings=counters) if band or collapse or device_tree or refine_tree or retree or seq_weights else {}),
                                     **(dict(collapse=True) if collapse else {}),
                                     **(dict(refine=refine, refinement=refinement) if refine else {}),
                                     **(dict(progressive=True, progression=progression) if progressive else {}),
                                     **(dict(device_tree=True) if device_tree else {}),
                                     **(dict(large_loci=True) if large_loci else {}),
                                     **(dict(refine_tree=refine_tree, tree_refinement=tree_refinement) if refine_tree else {}),
-                                    **(dict(retree=retree) if retree else {}))
+                                    **(dict(retree=retree) if retree else {}),
+                                    **(dict(seq_weights=True) if seq_weights else {}))
         t2 = time.perf_counter()
         for locus, m in zip(loci[lo:lo + STAR_CHUNK], msas):
             path = out_dir / f"{locus}.fa"
@@ -693,6 +705,9 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
         logger.info(f"rank {rank}: --progressive --band: {counters.get('prog_band_merges', 0)} merges, "
                     f"{counters.get('prog_band_second_passes', 0)} second passes, {counters.get('prog_band_full_merges', 0)} sent to the "
                     f"full DP, {counters.get('prog_band_cells', 0)} of {counters.get('prog_band_full_cells', 0)} DP cells computed")
+    if seq_weights:
+        logger.info(f"rank {rank}: --seq-weights: {counters.get('seq_weight_loci', 0)} loci weighted, "
+                    f"smallest weight {counters.get('seq_weight_min_q', 1)}")
     if retree:
         logger.info(f"rank {rank}: --retree {retree}: {counters.get('retree_rebuilds', 0)} loci rebuilt, "
                     f"{counters.get('retree_accepted', 0)} accepted, {counters.get('retree_same_tree', 0)} same tree, "

@@ -37,6 +37,10 @@ and the total objective S before and after the stage.
 sequences once and then seeded picks among them, shuffled: the pan-genome core gene `--large-loci` is for.
 `--large-loci` (with --progressive --collapse-identical): the leaf limit counts distinct sequences (`from_msa --unaligned
 --progressive --collapse-identical --large-loci`); the line then also gives large_loci, large_records and large_fallbacks.
+`--seq-weights` (with --progressive): tree weights (`from_msa --unaligned --progressive --seq-weights`); the line then also gives
+seq_weight_s (the stage's wall seconds: its launches and downloads; without --device-tree the distances launched again too),
+seq_weight_loci, seq_weight_min_q, and, from an untimed run of the same loci without the flag afterwards, seq_weight_loci_changed
+(the loci whose MSA differs) and s_total_unweighted beside s_total.
 `--no-prg`: the PRG build over the MSAs written is left out (no prg_build_s): for runs that compare the alignment stages only."""
 import hashlib
 import json
@@ -87,6 +91,9 @@ if "--retree" in sys.argv:
     retree = int(nxt[0]) if nxt and nxt[0].isdigit() else sa.RETREE_DEFAULT
     if not progressive:
         sys.exit("--retree needs --progressive")
+seq_weights = "--seq-weights" in sys.argv
+if seq_weights and not progressive:
+    sys.exit("--seq-weights needs --progressive")
 records = int(sys.argv[sys.argv.index("--records") + 1]) if "--records" in sys.argv else 0
 if records and not diverged:
     sys.exit("--records needs --diverged")
@@ -94,7 +101,21 @@ large_loci = "--large-loci" in sys.argv
 if large_loci and not (progressive and collapse):
     sys.exit("--large-loci needs --progressive and --collapse-identical")
 prog_kw = dict(progressive=True, **(dict(device_tree=True) if device_tree else {}), **(dict(large_loci=True) if large_loci else {}),
-               **(dict(refine_tree=refine_tree) if refine_tree else {}), **(dict(retree=retree) if retree else {})) if progressive else {}
+               **(dict(refine_tree=refine_tree) if refine_tree else {}), **(dict(retree=retree) if retree else {}),
+               **(dict(seq_weights=True) if seq_weights else {})) if progressive else {}
+
+
+def objective_total(be, msas):
+    """The objective S of the MSAs, summed over the loci (mprg_refine_counts over their text)."""
+    import numpy as np
+    s_total = 0
+    for lo in range(0, len(msas), 64):
+        part = msas[lo:lo + 64]
+        R, W = np.array([m.data.shape[0] for m in part], np.int64), np.array([m.data.shape[1] for m in part], np.int64)
+        toff = np.concatenate([[0], np.cumsum(R * W)[:-1]]).astype(np.int64)
+        text = np.concatenate([np.ascontiguousarray(m.data).reshape(-1) for m in part])
+        s_total += int(sa.refine_counts(be, be.upload(text), len(text), toff, R, W)[4].sum())
+    return s_total
 
 
 def diverged_seqs(seed):
@@ -193,15 +214,12 @@ try:
         extra.update(retree=retree, retree_loci_changed=sum(1 for t in done if t[1]), retree_s_before=sum(t[3] for t in done),
                      retree_s_after=sum(t[4] for t in done))
     if objective:
-        import numpy as np
-        s_total = 0
-        for lo in range(0, len(msas), 64):
-            part = msas[lo:lo + 64]
-            R, W = np.array([m.data.shape[0] for m in part], np.int64), np.array([m.data.shape[1] for m in part], np.int64)
-            toff = np.concatenate([[0], np.cumsum(R * W)[:-1]]).astype(np.int64)
-            text = np.concatenate([np.ascontiguousarray(m.data).reshape(-1) for m in part])
-            s_total += int(sa.refine_counts(be, be.upload(text), len(text), toff, R, W)[4].sum())
-        extra.update(s_total=s_total)
+        extra.update(s_total=objective_total(be, msas))
+    if seq_weights:
+        plain = sa.star_msas(be, recs, adjust_direction=flip is not None, band=band, refine=refine, **dict(prog_kw, seq_weights=False),
+                             **(dict(collapse=True) if collapse else {}))
+        extra.update(seq_weights=True, seq_weight_loci_changed=sum(1 for a, b in zip(msas, plain) if sa.msa_fasta(a) != sa.msa_fasta(b)),
+                     s_total_unweighted=objective_total(be, plain))
     cent = sa.centres(be, codes)
     cells = sum(len(c) * len(cs[int(k)]) for cs, k in zip(codes, cent) for a, c in enumerate(cs) if a != int(k))
     opts = Namespace(input=str(msa_dir), suffix="", output_prefix=str(work / "out" / "prg"), alignment_format="fasta",
