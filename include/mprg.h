@@ -605,6 +605,27 @@ int mprg_align_pairs_banded(const int32_t *profile, const int64_t *leaves, int n
                             int n_pairs, int32_t *workspace, long long workspace_words, uint8_t *ops, long long ops_bytes, int32_t *out,
                             void *stream);
 
+/* `from_msa --unaligned --progressive --pair-distances`: the scores of mprg_align_pairs / mprg_align_pairs_banded alone, no traceback
+ * and no ops, for guide trees from all pairs of a locus (the spec: make_prg_amd/from_msa/star_align.py, "Pair distances"; DESIGN.md
+ * §3b).  profile, leaves, seqs are mprg_align_pairs'; leaves of any R.
+ * mprg_align_pair_scores: pairs: n_pairs x MPRG_AL_SCORE_PAIR_FIELDS int64 {leaf, offset of the sequence's cell codes in `seqs`, its
+ *   length n >= 0, workspace offset (int32 words, a multiple of 64), dst}.  A pair needs ceil(2 (C + 1) / 64) * 64 words of
+ *   `workspace` (the row between two 64-residue strips) and nothing else.  out: n_pairs x 2 int32 {status, score}, the score
+ *   mprg_align_pairs gives the pair.  Where dst >= 0, table[dst] = max(score, 0) >> 6 as well (uint32; `table` has table_words
+ *   elements): an entry of the tables mprg_prog_tree reads.  status: mprg_align_pairs'; MPRG_AL_NO_SPACE also for dst >=
+ *   table_words; with any status but MPRG_AL_OK the score is 0 and the table is not written.  A pair is one wavefront.
+ * mprg_align_pair_scores_banded: pairs: n_pairs x MPRG_AL_SCORE_BAND_PAIR_FIELDS int64, the five fields, then dlo and dhi as
+ *   mprg_align_pairs_banded takes them (the same MPRG_AL_BAD_INPUT for a band without (0, 0) or (n, C)).  With dlo' = max(dlo, -n),
+ *   dhi' = min(dhi, C) a pair needs ceil(2 (dhi' - dlo' + 1) / 64) * 64 words.  The score is mprg_align_pairs_banded's: the full
+ *   DP's exactly when the certificate holds; a later launch over a wider band overwrites out and table[dst] of its pair. */
+enum { MPRG_AL_SCORE_PAIR_FIELDS = 5, MPRG_AL_SCORE_BAND_PAIR_FIELDS = 7 };
+int mprg_align_pair_scores(const int32_t *profile, const int64_t *leaves, int n_leaves, const uint8_t *seqs, const int64_t *pairs,
+                           int n_pairs, int32_t *workspace, long long workspace_words, uint32_t *table, long long table_words, int32_t *out,
+                           void *stream);
+int mprg_align_pair_scores_banded(const int32_t *profile, const int64_t *leaves, int n_leaves, const uint8_t *seqs, const int64_t *pairs,
+                                  int n_pairs, int32_t *workspace, long long workspace_words, uint32_t *table, long long table_words,
+                                  int32_t *out, void *stream);
+
 /* `from_msa --unaligned`: centre-star MSAs of unaligned loci (the spec: make_prg_amd/from_msa/star_align.py).
  * Not MAFFT: no reference function is replaced.  The pairs are mprg_align_pairs' (the centre as a 1-row leaf).
  * codes: the loci's sequences as cell codes (ACGT-RYKMSWN -> 0..11, no gaps), codes_bytes long.  seqs: n_seqs x 2 int64

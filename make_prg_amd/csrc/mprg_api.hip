@@ -18,6 +18,7 @@
 #include "k_emit.inc"
 #include "k_forest.inc"
 #include "k_align.inc"
+#include "k_align_scores.inc"
 #include "k_star.inc"
 #include "k_refine.inc"
 #include "k_prog.inc"
@@ -610,6 +611,24 @@ int mprg_align_pairs_banded(const int32_t *profile, const int64_t *leaves, int n
   LAUNCH(k_align_pairs_banded, (n_pairs + AL_WAVES - 1) / AL_WAVES, AL_THREADS, stream, profile, leaves, n_leaves, seqs, pairs, n_pairs,
          workspace, workspace_words, ops, ops_bytes, out);      // a wavefront per pair
   return check_launch("k_align_pairs_banded");
+}
+
+int mprg_align_pair_scores(const int32_t *profile, const int64_t *leaves, int n_leaves, const uint8_t *seqs, const int64_t *pairs,
+                           int n_pairs, int32_t *workspace, long long workspace_words, uint32_t *table, long long table_words, int32_t *out,
+                           void *stream) {
+  if (n_pairs <= 0) return 0;
+  LAUNCH(k_align_scores, (n_pairs + AL_WAVES - 1) / AL_WAVES, AL_THREADS, stream, profile, leaves, n_leaves, seqs, pairs, n_pairs,
+         workspace, workspace_words, table, table_words, out);      // a wavefront per pair
+  return check_launch("k_align_scores");
+}
+
+int mprg_align_pair_scores_banded(const int32_t *profile, const int64_t *leaves, int n_leaves, const uint8_t *seqs, const int64_t *pairs,
+                                  int n_pairs, int32_t *workspace, long long workspace_words, uint32_t *table, long long table_words,
+                                  int32_t *out, void *stream) {
+  if (n_pairs <= 0) return 0;
+  LAUNCH(k_align_scores_banded, (n_pairs + AL_WAVES - 1) / AL_WAVES, AL_THREADS, stream, profile, leaves, n_leaves, seqs, pairs, n_pairs,
+         workspace, workspace_words, table, table_words, out);      // a wavefront per pair
+  return check_launch("k_align_scores_banded");
 }
 
 int mprg_star_centres(const uint8_t *codes, long long codes_bytes, const int64_t *seqs, long long n_seqs, const int64_t *loci,

@@ -31,6 +31,10 @@ csrc/k_prog_retree.inc, C ABI: mprg_prog_identities).
 With `--seq-weights` (and `--progressive`) every leaf of the guide tree gets a weight from the tree, its share of the edges above it,
 and counts that often in every merge (Sequence weights below; kernel: csrc/k_prog_weights.inc, C ABI: mprg_prog_leaf_weights).
 
+With `--pair-distances` (and `--progressive`) the first guide tree is built from the scores of the pair DP over all pairs of a locus's
+leaves instead of from 6-mer counts (Pair distances below; kernels: csrc/k_align_scores.inc, C ABI: mprg_align_pair_scores /
+mprg_align_pair_scores_banded).
+
 It is NOT MAFFT.  PRGs built from these alignments differ from PRGs built from a MAFFT alignment of the same sequences.
 
 Spec (the kernels and tests/star_ref.py follow it bit for bit)
@@ -338,6 +342,42 @@ is the tree length it does not share with its relatives (ClustalW's scheme), so 
             _retree_trees launches the weights over the identity tables it already has on the device.  leaf_weights is the same
             statement in Python integers.
 
+Pair distances (only with progressive and pair_distances; integers only; tests/pairdist_ref.py states it in plain Python; kernels:
+csrc/k_align_scores.inc, C ABI: mprg_align_pair_scores / mprg_align_pair_scores_banded).  Progressive's 6-mer distances saturate: two
+records that differ at one base in five share almost no 6-mer, so on a locus of diverged sub-families nearly every D sits near 65 536
+and UPGMA's tie rule decides the tree, not the data.  Here the first tree comes from the scores of the pair DP over all pairs of
+leaves (ClustalW's pairwise mode, MAFFT's --globalpair).
+  Leaves.   Progressive's: the non-empty records, with collapse the class representatives, after Orientation.
+  Score.    For leaves a < b (table indices) score(a, b) is the score of profile_align.py's DP of sequence a against sequence b as a
+            1-row leaf: its formulas, its int32 arithmetic, end gaps charged.  Three facts of two sequences against each other
+            (tested): score(a, b) = score(b, a), because a residue against a gap costs -640 on either side and a run -704 on
+            either; every score is a multiple of 64 (one row: no division leaves a remainder); score <= 1 280 min(acgt_a, acgt_b),
+            acgt the cells with code 0..3, because only an equal ACGT pair scores above 0.
+  Tables.   s''(a, b) = max(score(a, b), 0) / 64, nw''_a = 20 acgt_a, D''(a, b) = 65 536 - floor(65 536 s'' / min(nw''_a, nw''_b)),
+            and 65 536 when the minimum is 0.  So 0 <= s'' <= min(nw''): a table of s'' above the diagonal beside a vector nw'', the
+            shape and the bounds of what _distances_launch leaves, so prog_distance_matrix, prog_tree, mprg_prog_tree,
+            mprg_prog_tree_wide and mprg_prog_leaf_weights, with their 2^60 and 2^92 bounds, are used unchanged.  A pair with an
+            empty record is not run: its entry is 0 and the record's nw'' is 0.
+  Which loci.  Those built progressively with 3 to PAIR_DIST_MAX_LEAVES = 512 leaves.  The cap is a cost constant, like
+            TREE_REFINE_MAX_LEAVES: a locus costs m (m - 1) / 2 pair DPs.  A locus above it is reported as "cap", a locus with a pair
+            of n + C >= 10^6 as "limit"; both get Progressive's 6-mer tree.  The run never fails on a locus the progressive pass
+            builds without the flag.
+  Nothing else changes: Merge, Y and X, the rounds, the output order and the objective S.  collapse: the tree is the weighted one
+            over the representatives.  large_loci: the wide tree kernel on the same tables.  device_tree: the tables stay on the
+            device.  seq_weights: the heights come from D'', the distances the tree was built on.  retree: its D' replaces D'' for
+            a rebuilt tree, as it replaces D without the flag; "same" compares with the tree that built the current MSA.
+            refine_tree, refine, adjust_direction: unchanged.  band: the scores come over certified bands (profile_align.py,
+            "Band": band_plan and certified_widths unchanged, SB and m from mprg_align_bounds) and are the same scores.
+  The flag promises these distances, not a higher S.
+  Host side (_pair_scores_launch, in place of _distances_launch for these loci): per group of loci one mprg_align_profiles launch
+            over the leaves as 1-row texts where they lie in the code buffer, with band one mprg_align_bounds launch, then the
+            pairs longest first through mprg_align_pair_scores in launches whose row buffers (8 (C + 1) bytes a pair) fit
+            budget_bytes; with band pass 1 at BAND_W0, pass 2 for the pairs with w* > w0, the full form for a pair whose band spans
+            the columns anyway.  The kernels write s'' into the group's tables themselves; {status, score} (8 bytes a pair) and,
+            with band, the bounds are all that comes back; nw'' is counted on the host from the code arrays it holds and uploaded
+            (8 bytes a record).  A locus's pair scores are computed once per run: on the host's tree with seq_weights the tables
+            _prog_shared downloaded are kept and uploaded for the weights launch (_PairTables).
+
 Progressive, host side: per chunk the distances in launches whose m x m tables fit budget_bytes (loci of three or more leaves), D
 and the tree per locus in NumPy / Python integers (prog_tree: a float64 quotient only shortlists, the choice is exact).  A node's
 round is 1 + the larger of its children's rounds.  With device_tree the tree is built on the device instead (csrc/k_prog_tree.inc):
@@ -408,6 +448,10 @@ TREE_REFINE_DEFAULT, TREE_REFINE_MAX = 1, 4   # passes of `--refine-tree` alone,
 PI_ITEM_FIELDS, PI_BLOCK_ROWS = 8, 16         # MPRG_PI_ITEM_FIELDS, MPRG_PI_BLOCK_ROWS
 RETREE_DEFAULT, RETREE_MAX = 1, 4             # rebuilds of `--retree` alone, and the most it takes
 SEQ_WEIGHT_UNIT = 256                         # the spec's Sequence weights: the scale of a raw weight, and the largest q
+AL_SCORE_PAIR_FIELDS, AL_SCORE_BAND_PAIR_FIELDS = 5, 7   # MPRG_AL_SCORE_PAIR_FIELDS, MPRG_AL_SCORE_BAND_PAIR_FIELDS
+PAIR_DIST_MAX_LEAVES = 512                    # the spec's cost cap of a locus whose tree comes from pair scores: m (m - 1) / 2 pair DPs
+PAIR_DIST_MATCH = 20                          # nw'' = 20 acgt: 1 280 / 64, the most a cell of either sequence can add to s''
+PAIR_DIST_MIN_LEAVES = 3                      # two leaves have one tree
 PG_STATUS = {1: "an index, a tile or a source range outside its table or buffer", 2: "ops, widths and cells that do not fit each other",
              3: "the output outside its buffer"}
 TREE_STATUS = {1: "a range outside its buffer, a leaf's weight below 1 or a weight sum above 4 096", 3: "the workspace outside its buffer"}
@@ -497,7 +541,8 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
               max_leaves: Optional[int] = None, collapse: bool = False, device_tree: bool = False, refine_tree: Optional[int] = None,
               tree_refinement: Optional[list] = None, tree_refine_max_leaves: int = TREE_REFINE_MAX_LEAVES, large_loci: bool = False,
               max_records: Optional[int] = None, retree: Optional[int] = None, retreeing: Optional[list] = None,
-              seq_weights: bool = False) -> List[MSA]:
+              seq_weights: bool = False, pair_distances: bool = False, pair_distancing: Optional[list] = None,
+              pair_dist_max_leaves: int = PAIR_DIST_MAX_LEAVES) -> List[MSA]:
     """loci: per locus its records as (title, sequence).  Returns the loci's centre-star MSAs (ids: the titles' first words,
     descriptions: the titles).  names: the loci's names for error messages (default: their indices).  timings: a dict that
     receives the wall seconds of the stages (orient, centre, pairs, merge: each ends at a download, so includes its kernels).
@@ -545,11 +590,20 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
     leaves counts q times (1 to 256) in the merges, in the rebuilds of retree and in the realignments of refine_tree.  timings also
     receives seq_weight_loci (the loci weighted), seq_weight_min_q (the smallest q of any leaf) and seq_weight_s (the stage's wall
     seconds: its launches and downloads; on the host's tree the second distances launches too).  False: nothing launches, uploads
-    or downloads differently."""
+    or downloads differently.
+    pair_distances: only with progressive (else a ValueError): the spec's Pair distances: the first tree of every locus built
+    progressively with 3 to pair_dist_max_leaves leaves (PAIR_DIST_MAX_LEAVES unless given) comes from the DP scores of all its
+    pairs of leaves.  pair_distancing: a list that then receives per locus (leaves, pairs run, how: "pairs", "cap", "limit", or None
+    for fewer than 3 leaves), None for a locus left to the star pass.  timings also receives pair_dist_s (part of tree_s, and with
+    seq_weights on the host's tree of its second lap), pair_dist_loci, pair_dist_pairs, pair_dist_cells, pair_dist_above_cap,
+    pair_dist_limit, and with band pair_dist_second_passes and pair_dist_full_pairs.  False: nothing launches, uploads or
+    downloads differently."""
     if device_tree and not progressive:
         raise ValueError("device_tree: only with progressive")
     if seq_weights and not progressive:
         raise ValueError("seq_weights: only with progressive")
+    if pair_distances and not progressive:
+        raise ValueError("pair_distances: only with progressive")
     if large_loci and not (progressive and collapse):
         raise ValueError("large_loci: only with progressive and collapse")
     if max_records is not None and not (large_loci and 0 <= int(max_records) <= PROG_MAX_RECORDS):
@@ -578,7 +632,7 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
                                  int(refine), refinement, progression, PROG_MAX_LEAVES if max_leaves is None else int(max_leaves), bool(collapse),
                                  bool(device_tree), int(refine_tree or 0), tree_refinement, int(tree_refine_max_leaves),
                                  (PROG_MAX_RECORDS if max_records is None else int(max_records)) if large_loci else None, int(retree or 0),
-                                 retreeing, bool(seq_weights))
+                                 retreeing, bool(seq_weights), int(pair_dist_max_leaves) if pair_distances else None, pair_distancing)
     return [m for lo, hi in _chunks(codes, chunk_bytes)
             for m in _star_chunk(backend, loci[lo:hi], codes[lo:hi], names[lo:hi], budget_bytes, timings, adjust_direction, orientation, band,
                                  int(refine), refinement, collapse=bool(collapse))]
@@ -586,31 +640,34 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
 
 def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings, adjust_direction, orientation, band, refine, refinement,
                       progression, max_leaves, collapse=False, device_tree=False, refine_tree=0, tree_refinement=None,
-                      tree_max_leaves=TREE_REFINE_MAX_LEAVES, max_records=None, retree=0, retreeing=None, seq_weights=False) -> List[MSA]:
+                      tree_max_leaves=TREE_REFINE_MAX_LEAVES, max_records=None, retree=0, retreeing=None, seq_weights=False,
+                      pair_dist=None, pair_distancing=None) -> List[MSA]:
     """star_msas with progressive: the loci within the leaf limit through the progressive chunks, the others through the star
     chunks, the results (and what the caller's lists receive) back in the loci's order.  max_records (the spec's Large loci; None:
     without it): only the loci of more records go to the star chunks here; the progressive chunks count every locus's classes
     once Collapse has made them and send those above max_leaves through the star pass themselves."""
     n_leaves = [sum(1 for c in cs if len(c)) for cs in codes]
     out = [None] * len(loci)
-    got = {k: [None] * len(loci) for k in ("orientation", "refinement", "progression", "tree_refinement", "retreeing")}
+    got = {k: [None] * len(loci) for k in ("orientation", "refinement", "progression", "tree_refinement", "retreeing", "pair_distancing")}
     limits = None if max_records is None else (max_leaves, max_records)
     for prog in (True, False):
         sel = [l for l in range(len(loci)) if (n_leaves[l] <= max_leaves if limits is None else len(codes[l]) <= max_records) == prog]
         sub = [codes[l] for l in sel]
-        ori, ref, pro, tre, ret, msas = [], [], [], [], [], []
+        ori, ref, pro, tre, ret, pdi, msas = [], [], [], [], [], [], []
         for lo, hi in _chunks(sub, chunk_bytes):
             idx = sel[lo:hi]
             msas.extend(_star_chunk(be, [loci[l] for l in idx], sub[lo:hi], [names[l] for l in idx], budget_bytes, timings, adjust_direction,
                                     ori if orientation is not None else None, band, refine, ref if refinement is not None else None,
                                     prog, pro, collapse, device_tree and prog, refine_tree if prog else 0,
                                     tre if tree_refinement is not None else None, tree_max_leaves, limits if prog else None,
-                                    retree if prog else 0, ret if retreeing is not None else None, seq_weights and prog))
+                                    retree if prog else 0, ret if retreeing is not None else None, seq_weights and prog,
+                                    pair_dist if prog else None, pdi if pair_distancing is not None else None))
         if not prog:
             pro = [(n_leaves[l], 0, True) for l in sel]
         for k, l in enumerate(sel):
             out[l] = msas[k]
-            for key, vals in (("orientation", ori), ("refinement", ref), ("progression", pro), ("tree_refinement", tre), ("retreeing", ret)):
+            for key, vals in (("orientation", ori), ("refinement", ref), ("progression", pro), ("tree_refinement", tre), ("retreeing", ret),
+                              ("pair_distancing", pdi)):
                 if vals:
                     got[key][l] = vals[k]
     if limits is not None:
@@ -619,7 +676,7 @@ def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings
         add_to(timings, "large_records", sum(len(codes[l]) for l in built))
         add_to(timings, "large_fallbacks", sum(1 for p in got["progression"] if p[2]))
     for key, dest in (("orientation", orientation), ("refinement", refinement), ("progression", progression),
-                      ("tree_refinement", tree_refinement), ("retreeing", retreeing)):
+                      ("tree_refinement", tree_refinement), ("retreeing", retreeing), ("pair_distancing", pair_distancing)):
         if dest is not None:
             dest.extend(got[key])
     return out
@@ -627,7 +684,8 @@ def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings
 
 def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direction=False, orientation=None, band=None, refine=0,
                 refinement=None, progressive=False, progression=None, collapse=False, device_tree=False, refine_tree=0,
-                tree_refinement=None, tree_max_leaves=TREE_REFINE_MAX_LEAVES, limits=None, retree=0, retreeing=None, seq_weights=False) -> List[MSA]:
+                tree_refinement=None, tree_max_leaves=TREE_REFINE_MAX_LEAVES, limits=None, retree=0, retreeing=None, seq_weights=False,
+                pair_dist=None, pair_distancing=None) -> List[MSA]:
     """One chunk: pack, optionally orient, optionally collapse, the star pass or the progressive one (with its tree refinement),
     optionally refine, collect.  limits (the spec's Large loci; only with progressive and collapse): (max_leaves, max_records): the
     loci with more classes of non-empty records, or more records, go through the star pass."""
@@ -644,18 +702,19 @@ def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direc
         build = (n_classes <= limits[0]) & (chunk.counts <= limits[1])
         if not build.all():
             return _star_chunk_parts(be, chunk, classes, build, budget_bytes, laps, band, refine, refinement, progression, device_tree,
-                                     refine_tree, tree_refinement, tree_max_leaves, retree, retreeing, seq_weights)
+                                     refine_tree, tree_refinement, tree_max_leaves, retree, retreeing, seq_weights, pair_dist, pair_distancing)
     return _star_chunk_rest(be, chunk, classes, budget_bytes, laps, band, refine, refinement, progressive, progression, device_tree,
-                            refine_tree, tree_refinement, tree_max_leaves, retree, retreeing, seq_weights)
+                            refine_tree, tree_refinement, tree_max_leaves, retree, retreeing, seq_weights, pair_dist, pair_distancing)
 
 
 def _star_chunk_parts(be, chunk: Chunk, classes, build, budget_bytes, laps, band, refine, refinement, progression, device_tree,
-                      refine_tree, tree_refinement, tree_max_leaves, retree=0, retreeing=None, seq_weights=False) -> List[MSA]:
+                      refine_tree, tree_refinement, tree_max_leaves, retree=0, retreeing=None, seq_weights=False, pair_dist=None,
+                      pair_distancing=None) -> List[MSA]:
     """_star_chunk behind Collapse for a chunk of which only the loci `build` (a bool per locus) are built progressively (the spec's
     Large loci): those as one chunk through the progressive pass, the others as one through the star pass, both over the same code
     buffer and the classes already made; the MSAs, and what the caller's lists receive, back in the chunk's order."""
     n_filled = np.add.reduceat((chunk.lens > 0).astype(np.int64), chunk.first)
-    msas, ref, pro, tre, ret = ([None] * chunk.n_loci for _ in range(5))
+    msas, ref, pro, tre, ret, pdi = ([None] * chunk.n_loci for _ in range(6))
     for prog in (True, False):
         sel = np.nonzero(build == prog)[0]
         if not len(sel):
@@ -665,29 +724,31 @@ def _star_chunk_parts(be, chunk: Chunk, classes, build, budget_bytes, laps, band
         at[rec] = np.arange(len(rec))
         part = chunk._replace(names=[chunk.names[l] for l in sel], titles=[chunk.titles[l] for l in sel], codes=[chunk.codes[l] for l in sel],
                               lens=chunk.lens[rec], seq_off=chunk.seq_off[rec], first=exclusive_sum(chunk.counts[sel]), counts=chunk.counts[sel])
-        got = [[], [], [], []]
+        got = [[], [], [], [], []]
         out = _star_chunk_rest(be, part, Classes(at[classes.rep[rec]], classes.weight[rec]), budget_bytes, laps, band, refine, got[0], prog,
                                got[1], device_tree and prog, refine_tree if prog else 0, got[2], tree_max_leaves, retree if prog else 0, got[3],
-                               seq_weights and prog)
+                               seq_weights and prog, pair_dist if prog else None, got[4])
         if not prog:
             got[1] = [(int(n_filled[l]), 0, True) for l in sel]
         for k, l in enumerate(sel.tolist()):
             msas[l] = out[k]
-            for dest, vals in zip((ref, pro, tre, ret), got):
+            for dest, vals in zip((ref, pro, tre, ret, pdi), got):
                 if vals:
                     dest[l] = vals[k]
-    for dest, vals, wanted in ((refinement, ref, refine), (progression, pro, True), (tree_refinement, tre, refine_tree), (retreeing, ret, retree)):
+    for dest, vals, wanted in ((refinement, ref, refine), (progression, pro, True), (tree_refinement, tre, refine_tree), (retreeing, ret, retree),
+                               (pair_distancing, pdi, pair_dist is not None)):
         if dest is not None and wanted:
             dest.extend(vals)
     return msas
 
 
 def _star_chunk_rest(be, chunk: Chunk, classes, budget_bytes, laps, band, refine, refinement, progressive, progression, device_tree,
-                     refine_tree, tree_refinement, tree_max_leaves, retree=0, retreeing=None, seq_weights=False) -> List[MSA]:
+                     refine_tree, tree_refinement, tree_max_leaves, retree=0, retreeing=None, seq_weights=False, pair_dist=None,
+                     pair_distancing=None) -> List[MSA]:
     """_star_chunk behind Collapse: the star pass or the progressive one (with its tree refinement), optionally refine, collect."""
     timings = laps.timings
     text = (_progressive(be, chunk, budget_bytes, band, laps, progression, classes, device_tree, refine_tree, tree_refinement,
-                         tree_max_leaves, retree, retreeing, seq_weights) if progressive else
+                         tree_max_leaves, retree, retreeing, seq_weights, pair_dist, pair_distancing) if progressive else
             _star_pass(be, chunk, budget_bytes, band, laps, classes))
     moved = {}
     if refine:
@@ -1000,20 +1061,158 @@ def _distances_launch(be, chunk: Chunk, d_seqs, grp):
     return m, toff, words, d_shared, d_nw, d_status, len(work)
 
 
-def _prog_shared(be, chunk: Chunk, sel, budget_bytes):
+def _acgt(chunk: Chunk) -> np.ndarray:
+    """Per record of the chunk's tables the cells with code 0..3, from the code arrays the host holds (reverse-complementing a
+    record does not change the number)."""
+    return np.array([int((c < 4).sum()) for cs in chunk.codes for c in cs], np.int64)
+
+
+def _pair_scores_launch(be, chunk: Chunk, d_seqs, grp, band=None, counters=None, acgt=None, budget_bytes=pa.DEFAULT_BUDGET_BYTES):
+    """The spec's Pair distances over the loci `grp` of a chunk: what _distances_launch returns, the tables s'' and nw'' in its layout,
+    so _prog_shared, _prog_trees and _prog_weights take either source.  One mprg_align_profiles launch over the group's leaves as
+    1-row texts, with band one mprg_align_bounds launch, then the pairs a < b of every locus (sequence a against leaf b), longest
+    first, through mprg_align_pair_scores in launches whose row buffers fit budget_bytes; with band the spec's two passes
+    (profile_align.band_plan, certified_widths) through mprg_align_pair_scores_banded and the full form for the rest, a later pass
+    overwriting the pair's entry.  {status, score} per pair and, with band, the bounds are all that comes back.  acgt: per record
+    of the chunk's tables its ACGT cells (default: counted from chunk.codes); nw'' = 20 acgt is uploaded.  counters receives
+    pair_dist_pairs, pair_dist_cells and with band pair_dist_second_passes, pair_dist_full_pairs.  The status words returned are
+    a single zero: every pair's status has been checked here."""
+    lens, first = chunk.lens, chunk.first
+    m = chunk.counts[grp]
+    toff = exclusive_sum(m * m)
+    words = int((m * m).sum())
+    acgt = _acgt(chunk) if acgt is None else np.asarray(acgt, np.int64)
+    d_shared, d_nw, d_status = be.zeros(4 * words), be.upload(PAIR_DIST_MATCH * acgt), be.zeros(4)
+    # the leaves: the group's non-empty records, each a 1-row text where it lies in the code buffer
+    rec = _ranges(first[grp], m)
+    lrec = rec[lens[rec] > 0]
+    C = lens[lrec]
+    leaf_at = np.full(len(lens), -1, np.int64)
+    leaf_at[lrec] = np.arange(len(lrec))
+    pa_, pb_, dst = [], [], []
+    for k, l in enumerate(grp.tolist()):
+        lv = np.nonzero(lens[first[l]:first[l] + m[k]] > 0)[0]
+        ia, ib = np.triu_indices(len(lv), 1)
+        pa_.append(first[l] + lv[ia])
+        pb_.append(first[l] + lv[ib])
+        dst.append(toff[k] + lv[ia] * m[k] + lv[ib])
+    pa_, pb_, dst = (np.concatenate(x).astype(np.int64) if x else np.zeros(0, np.int64) for x in (pa_, pb_, dst))
+    n_pairs = len(pa_)
+    if not n_pairs:
+        return m, toff, words, d_shared, d_nw, d_status, 1
+    pn, pc, pl = lens[pa_], lens[pb_], leaf_at[pb_]
+    k = np.nonzero(pn + pc >= pa.MAX_LEN)[0]
+    if len(k):
+        raise StarAlignError(f"a pair of {pn[k[0]]} residues against {pc[k[0]]} columns: n + C must stay below {pa.MAX_LEN}")
+    prof_off = exclusive_sum(6 * C)
+    d_leaves = be.upload(np.stack([chunk.seq_off[lrec], np.ones(len(lrec), np.int64), C, prof_off], 1).astype(np.int64))
+    work = _tile_work(C)
+    d_work, d_prof = be.upload(work), be.empty(4 * int((6 * C).sum()))
+    be.call("mprg_align_profiles", be.ptr(chunk.d_codes), be.ptr(d_leaves), be.ptr(d_work), len(work), be.ptr(d_prof), be.stream,
+            work=float(C.sum()))
+    soff = chunk.seq_off[pa_]
+    score = np.zeros(n_pairs, np.int64)
+    pending = []                                                # (pairs, call, the launch's {status, score}): in launch order
+
+    def launches(call, idx, wordsv, dlo=None, dhi=None):
+        for sel, ws_off, used in pa.budget_launches(idx, wordsv, budget_bytes, StarAlignError, "pair", pn, pc):
+            band_cols = () if dlo is None else (dlo[sel], dhi[sel])
+            d_pairs = be.upload(np.stack([pl[sel], soff[sel], pn[sel], ws_off, dst[sel], *band_cols], 1).astype(np.int64))
+            d_ws, d_out = be.empty(4 * used), be.empty(8 * len(sel))
+            be.call(call, be.ptr(d_prof), be.ptr(d_leaves), len(lrec), be.ptr(chunk.d_codes), be.ptr(d_pairs), len(sel), be.ptr(d_ws), used,
+                    be.ptr(d_shared), words, be.ptr(d_out), be.stream, work=pa.sweep_work(pn[sel], pc[sel], *band_cols))
+            pending.append((sel, call, d_out))
+
+    def collect():
+        for sel, call, d_out in pending:                         # in launch order: a later pass's result replaces pass 1's
+            res = be.download(d_out, np.int32, 2 * len(sel)).reshape(-1, 2)
+            bad = np.nonzero(res[:, 0])[0]
+            if len(bad):
+                raise StarAlignError(f"{call}: {pa.STATUS.get(int(res[bad[0], 0]), int(res[bad[0], 0]))}")
+            score[sel] = res[:, 1]
+        pending.clear()
+    need = (2 * (pc + 1) + 63) // 64 * 64
+    w0 = None if band is None or band is False else pa.BAND_W0 if band is True else int(band)
+    if w0 is None:
+        launches("mprg_align_pair_scores", np.argsort(-((pn + 1) * pc), kind="stable"), need)
+        collect()
+        cells = int((pn * pc).sum())
+    else:
+        if w0 < 0:
+            raise StarAlignError("band: a negative half-width")
+        d_bounds = be.empty(16 * len(lrec))
+        be.call("mprg_align_bounds", be.ptr(d_prof), be.ptr(d_leaves), len(lrec), be.ptr(d_bounds), be.stream, work=float((6 * C).sum()))
+        bounds = be.download(d_bounds, np.int64, 2 * len(lrec)).reshape(-1, 2)
+        SB, mn = bounds[pl, 0], bounds[pl, 1]
+
+        def band_need(dlo, dhi):
+            return (2 * (dhi - dlo + 1) + 63) // 64 * 64
+
+        def pass1(firstp, dlo, dhi):
+            launches("mprg_align_pair_scores_banded", firstp, band_need(dlo, dhi), dlo, dhi)
+            collect()
+            return pa.certified_widths(pn, pc, SB, mn, score)
+        second, rest, dlo, dhi, counts = pa.band_plan(pn, pc, w0, pass1)
+        launches("mprg_align_pair_scores_banded", second, band_need(dlo, dhi), dlo, dhi)
+        launches("mprg_align_pair_scores", rest, need)
+        collect()
+        cells = int(counts[3])
+        add_to(counters, "pair_dist_second_passes", int(counts[1]))
+        add_to(counters, "pair_dist_full_pairs", int(counts[2]))
+    add_to(counters, "pair_dist_pairs", n_pairs)
+    add_to(counters, "pair_dist_cells", cells)
+    return m, toff, words, d_shared, d_nw, d_status, 1
+
+
+class _PairTables:
+    """The spec's Pair distances as a source of tables for _prog_shared, _prog_trees and _prog_weights: called like
+    _distances_launch.  keep: the tables _prog_shared downloads are kept per locus, and a group all of whose loci are kept is
+    uploaded, not launched again (the host's tree with seq_weights: a locus's pair scores are computed once per run)."""
+
+    def __init__(self, band, counters, acgt, budget_bytes, keep=False):
+        self.band, self.counters, self.acgt, self.budget_bytes = band, counters, acgt, budget_bytes
+        self.cache, self.spent = ({} if keep else None), 0.0
+
+    def __call__(self, be, chunk: Chunk, d_seqs, grp):
+        t0 = time.perf_counter()
+        if self.cache is not None and all(l in self.cache for l in grp.tolist()):
+            m = chunk.counts[grp]
+            flat = np.concatenate([self.cache[l] for l in grp.tolist()]).astype(np.uint32)
+            got = (m, exclusive_sum(m * m), int((m * m).sum()), be.upload(flat), be.upload(PAIR_DIST_MATCH * self.acgt), be.zeros(4), 1)
+        else:
+            got = _pair_scores_launch(be, chunk, d_seqs, grp, self.band, self.counters, self.acgt, self.budget_bytes)
+        self.spent += time.perf_counter() - t0
+        return got
+
+
+def prog_pair_tables(backend, codes: Sequence[Sequence[np.ndarray]], band=None, budget_bytes: int = pa.DEFAULT_BUDGET_BYTES,
+                     counters: Optional[dict] = None):
+    """The spec's Pair distances over the loci (per locus its gap-free code arrays; an empty one is no leaf): per locus (s'', nw''):
+    s'' an (m, m) int64 array whose part above the diagonal holds max(score(a, b), 0) / 64 of the records a < b, nw'' = 20 acgt per
+    record (0 for an empty one).  band: None, True or pass 1's half-width: the same tables over certified bands."""
+    chunk = _pack(backend, codes)
+    got = _prog_shared(backend, chunk, np.arange(len(codes)), budget_bytes,
+                       _PairTables(band, counters, _acgt(chunk), budget_bytes))
+    return [got[l] for l in range(len(codes))]
+
+
+def _prog_shared(be, chunk: Chunk, sel, budget_bytes, tables=None):
     """mprg_prog_distances over the loci `sel` of a chunk, in groups whose m x m tables fit budget_bytes: per locus (s as an
-    (m, m) int64 array of which the part above the diagonal is filled, nw)."""
+    (m, m) int64 array of which the part above the diagonal is filled, nw).  tables: another source of the tables, called like
+    _distances_launch (the spec's Pair distances)."""
     lens, first, counts = chunk.lens, chunk.first, chunk.counts
     out = {}
     d_seqs = be.upload(np.stack([chunk.seq_off, lens], 1).reshape(-1))
     for lo, hi in pa.budget_groups(4 * counts[sel] ** 2, budget_bytes):
         grp = sel[lo:hi]
-        m, toff, words, d_shared, d_nw, d_status, n_work = _distances_launch(be, chunk, d_seqs, grp)
+        m, toff, words, d_shared, d_nw, d_status, n_work = (tables or _distances_launch)(be, chunk, d_seqs, grp)
         _check(be.download(d_status, np.int32, n_work), "mprg_prog_distances", PG_STATUS)
         shared = be.download(d_shared, np.uint32, words).astype(np.int64)
         nw = be.download(d_nw, np.int64, len(lens))
         for k, l in enumerate(grp.tolist()):
             out[l] = (shared[toff[k]:toff[k] + m[k] * m[k]].reshape(int(m[k]), int(m[k])), nw[first[l]:first[l] + counts[l]])
+            if getattr(tables, "cache", None) is not None:
+                tables.cache[l] = shared[toff[k]:toff[k] + m[k] * m[k]]
     return out
 
 
@@ -1039,13 +1238,14 @@ def prog_weights_words(m):
     return 6 * m
 
 
-def _prog_trees(be, chunk: Chunk, sel, budget_bytes, weights=None, seq_weights: Optional["_LeafWeights"] = None):
+def _prog_trees(be, chunk: Chunk, sel, budget_bytes, weights=None, seq_weights: Optional["_LeafWeights"] = None, tables=None):
     """The spec's Tree of the loci `sel` of a chunk on the device, in groups whose m x m tables and tree workspaces fit budget_bytes:
     per group one mprg_prog_distances launch and one mprg_prog_tree launch over the tables it left on the device; the status words
     and the merges are all that is downloaded.  Per locus its merges as prog_tree gives them.  weights: per record of the chunk's
     tables how many times it counts (the spec's Collapse).  The loci whose weight sum exceeds PROG_MAX_LEAVES (the spec's Large
     loci) form groups of their own, whose trees mprg_prog_tree_wide builds.  seq_weights (the spec's Sequence weights): every group
-    is followed by an mprg_prog_leaf_weights launch over the same tables and the merges where the tree launch left them."""
+    is followed by an mprg_prog_leaf_weights launch over the same tables and the merges where the tree launch left them.  tables:
+    another source of the tables, called like _distances_launch (the spec's Pair distances)."""
     lens, first = chunk.lens, chunk.first
     out = {}
     d_seqs = be.upload(np.stack([chunk.seq_off, lens], 1).reshape(-1))
@@ -1054,7 +1254,7 @@ def _prog_trees(be, chunk: Chunk, sel, budget_bytes, weights=None, seq_weights: 
     # the spec's Large loci: a locus whose weight sum exceeds mprg_prog_tree's bound goes to mprg_prog_tree_wide, in groups (and so
     # in launches) of such loci alone; without one nothing launches differently
     for grp, entry, table in _tree_groups(chunk, sel, budget_bytes, weights):
-        m, toff, words, d_shared, d_nw, d_status, n_work = _distances_launch(be, chunk, d_seqs, grp)
+        m, toff, words, d_shared, d_nw, d_status, n_work = (tables or _distances_launch)(be, chunk, d_seqs, grp)
         launched = _tree_launch(be, chunk, grp, entry, d_seqs, d_weights, n_leaves, toff, words, d_shared, d_nw)
         if seq_weights is not None:
             seq_weights.launch(grp, d_seqs, d_weights, toff, words, d_shared, d_nw, *launched[1:])
@@ -1106,23 +1306,24 @@ class _LeafWeights:
         return got
 
 
-def _prog_weights(be, chunk: Chunk, sel, trees, budget_bytes, weights=None) -> "_LeafWeights":
+def _prog_weights(be, chunk: Chunk, sel, trees, budget_bytes, weights=None, tables=None, lw=None) -> "_LeafWeights":
     """The spec's Sequence weights of the loci `sel` whose trees were built on the host: in groups whose tables fit budget_bytes the
     distances launch again (the tables are not kept on the device, and never weighted on the host), the merges uploaded, one
-    mprg_prog_leaf_weights launch."""
-    lw = _LeafWeights(be, chunk)
-    t0 = time.perf_counter()
+    mprg_prog_leaf_weights launch.  tables: another source of the tables, called like _distances_launch (the spec's Pair distances);
+    lw: the chunk's _LeafWeights when an earlier call made one."""
+    lw = _LeafWeights(be, chunk) if lw is None else lw
+    t0, before = time.perf_counter(), lw.spent
     d_seqs = be.upload(np.stack([chunk.seq_off, chunk.lens], 1).reshape(-1))
     d_weights = None if weights is None else be.upload(np.asarray(weights, np.int32))
     checks = []
     for lo, hi in pa.budget_groups(4 * chunk.counts[sel] ** 2 + 8 * prog_weights_words(chunk.counts[sel]), budget_bytes):
         grp = sel[lo:hi]
-        m, toff, words, d_shared, d_nw, d_status, n_work = _distances_launch(be, chunk, d_seqs, grp)
+        m, toff, words, d_shared, d_nw, d_status, n_work = (tables or _distances_launch)(be, chunk, d_seqs, grp)
         lw.upload_and_launch(grp, trees, d_seqs, d_weights, toff, words, d_shared, d_nw)
         checks.append((d_status, n_work))
     for d_status, n_work in checks:
         _check(be.download(d_status, np.int32, n_work), "mprg_prog_distances", PG_STATUS)
-    lw.spent = time.perf_counter() - t0                         # (the distances launches are the stage's here)
+    lw.spent = before + time.perf_counter() - t0                # (the distances launches are the stage's here)
     return lw
 
 
@@ -1448,6 +1649,28 @@ def merge_profiles(backend, pairs: Sequence[Tuple[np.ndarray, np.ndarray]], budg
     return out
 
 
+def _pair_dist_how(chunk: Chunk, n_leaves, cap: int) -> list:
+    """The spec's Pair distances, Which loci: per locus of the chunk "pairs", "cap" (more leaves than the cap), "limit" (a pair with
+    n + C >= 10^6: the two longest leaves decide) or None (fewer than 3 leaves)."""
+    how = []
+    for l in range(chunk.n_loci):
+        ln = np.sort(chunk.lens[chunk.first[l]:chunk.first[l] + chunk.counts[l]])
+        how.append(None if n_leaves[l] < PAIR_DIST_MIN_LEAVES else "cap" if n_leaves[l] > cap else
+                   "limit" if int(ln[-1] + ln[-2]) >= pa.MAX_LEN else "pairs")
+    return how
+
+
+def _pair_dist_report(counters, pair_distancing, how, n_leaves, spent, band=None):
+    """The spec's Pair distances in the counters and in the caller's list: per locus (leaves, pairs run, how)."""
+    add_to(counters, "pair_dist_s", float(spent))
+    for key in ("pair_dist_pairs", "pair_dist_cells") + (("pair_dist_second_passes", "pair_dist_full_pairs") if band is not None else ()):
+        add_to(counters, key, 0)
+    for key, word in (("pair_dist_loci", "pairs"), ("pair_dist_above_cap", "cap"), ("pair_dist_limit", "limit")):
+        add_to(counters, key, sum(1 for h in how if h == word))
+    if pair_distancing is not None:
+        pair_distancing.extend((int(n), int(n) * (int(n) - 1) // 2 if h == "pairs" else 0, h) for n, h in zip(n_leaves, how))
+
+
 def _seq_weight_counters(counters, n_loci, q, spent):
     """The spec's Sequence weights in the counters: the loci weighted, the smallest q of any leaf, the stage's wall seconds."""
     add_to(counters, "seq_weight_loci", int(n_loci))
@@ -1457,7 +1680,8 @@ def _seq_weight_counters(counters, n_loci, q, spent):
 
 
 def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression, classes: Optional[Classes] = None, device_tree=False,
-                 refine_tree=0, tree_refinement=None, max_leaves=None, retree=0, retreeing=None, seq_weights=False):
+                 refine_tree=0, tree_refinement=None, max_leaves=None, retree=0, retreeing=None, seq_weights=False, pair_dist=None,
+                 pair_distancing=None):
     """The spec's Progressive over one chunk, on the (oriented) sequences in chunk.d_codes.  Returns what the star pass leaves: the
     device buffer of the MSAs' ASCII text, its bytes, each locus's offset in it and its width.  classes: the spec's Collapse: the
     tree and the merges over the representatives with their weights, the root's rows written for every member.  device_tree: the
@@ -1465,9 +1689,11 @@ def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression,
     roots' texts before they are written out (0: none); tree_refinement receives its tuples, max_leaves is its cap.  retree: the
     rebuilds of the spec's Retree, in front of that (0: none); retreeing receives its tuples, progression then the tuples of the
     trees that built the texts that are written.  seq_weights: the spec's Sequence weights: q per leaf from the trees, after the
-    plan, as the rows' weights in every merge."""
+    plan, as the rows' weights in every merge.  pair_dist: the spec's Pair distances: its leaf cap (None: without it);
+    pair_distancing receives its tuples."""
     laps.lap()
     lens, first, counts = chunk.lens, chunk.first, chunk.counts
+    acgt = _acgt(chunk) if pair_dist is not None else None
     n_leaves = np.add.reduceat((lens > 0).astype(np.int64), first)          # (every locus has a record)
     for l in np.nonzero(n_leaves == 0)[0]:
         raise StarAlignError(f"locus {chunk.names[l]}: every sequence is empty")
@@ -1480,18 +1706,33 @@ def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression,
         expand = (counts, first, slot[classes.rep])
         chunk = chunk._replace(lens=lens[keep], seq_off=chunk.seq_off[keep], first=exclusive_sum(kept), counts=kept)
         lens, first, counts, weights = chunk.lens, chunk.first, chunk.counts, classes.weight[keep]
+        acgt = None if acgt is None else acgt[keep]
         n_leaves = np.add.reduceat((lens > 0).astype(np.int64), first)
     # the trees: distances on the device for the loci with three or more leaves (two leaves have one tree), UPGMA on the host or,
     # with device_tree, on the device
     sel = np.nonzero(n_leaves >= 3)[0]
+    # the spec's Pair distances: the loci of `sel` within the cap and the DP's limit take their tables from the pair scores, the
+    # others (and every locus without the flag) from the 6-mer counts; parts: (loci, the source of their tables)
+    parts = [(sel, None)]
+    if pair_dist is not None:
+        how = _pair_dist_how(chunk, n_leaves, int(pair_dist))
+        by_pairs = np.array([how[l] == "pairs" for l in sel.tolist()], bool)
+        pair_tables = _PairTables(band, laps.timings, acgt, budget_bytes, keep=seq_weights and not device_tree)
+        parts = [(sel[~by_pairs], None), (sel[by_pairs], pair_tables)]
     lw = _LeafWeights(be, chunk) if seq_weights and device_tree and len(sel) else None
     if device_tree:
-        merges = _prog_trees(be, chunk, sel, budget_bytes, weights, lw) if len(sel) else {}
+        merges = {}
+        for part, tables in parts:
+            if len(part):
+                merges.update(_prog_trees(be, chunk, part, budget_bytes, weights, lw, tables))
         add_to(laps.timings, "tree_device_loci", len(sel))
         t0 = time.perf_counter()
         plan = _prog_plan(lens, first, counts, None, weights, merges)
     else:
-        shared = _prog_shared(be, chunk, sel, budget_bytes) if len(sel) else {}
+        shared = {}
+        for part, tables in parts:
+            if len(part):
+                shared.update(_prog_shared(be, chunk, part, budget_bytes, tables))
         t0 = time.perf_counter()
         plan = _prog_plan(lens, first, counts, shared, weights)
     add_to(laps.timings, "tree_plan_s", time.perf_counter() - t0)
@@ -1501,11 +1742,15 @@ def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression,
     if seq_weights:
         align = np.ones(len(lens), np.int64)
         if len(sel):
-            lw = lw if device_tree else _prog_weights(be, chunk, sel, plan[4], budget_bytes, weights)
+            for part, tables in () if device_tree else parts:
+                if len(part):
+                    lw = _prog_weights(be, chunk, part, plan[4], budget_bytes, weights, tables, lw)
             rec = _ranges(first[sel], counts[sel])
             align[rec] = np.maximum(lw.q()[rec], 1)            # (an empty record has no row: its entry is never read)
             _seq_weight_counters(laps.timings, len(sel), align[rec][lens[rec] > 0], lw.spent)
         laps.lap("tree_s")
+    if pair_dist is not None:
+        _pair_dist_report(laps.timings, pair_distancing, how, n_leaves, pair_tables.spent, band)
     bufs, live, where = _prog_rounds(be, chunk, plan, budget_bytes, band, laps.timings, weights, align=align)
     laps.lap("progressive_s")
     if retree:

@@ -125,6 +125,14 @@ def register_parser(subparsers):
                         "row order and the objective are unchanged; with --collapse-identical a class's weight replaces its size in "
                         "the merges.  --retree and --refine-tree use the weights of the tree that built the MSA, --refine runs "
                         "after it unweighted, --band and --device-tree give the same bytes.  Off by default")
+    p.add_argument("--pair-distances", dest="pair_distances", action="store_true", default=False,
+                   help="(this implementation) with --unaligned --progressive: the first guide tree of every locus of 3 to "
+                        f"{star_align.PAIR_DIST_MAX_LEAVES} leaves is built from the scores of the pair DP over all pairs of its leaves "
+                        "(ClustalW's pairwise mode, MAFFT's --globalpair; a score-only sweep on the GPU, csrc/k_align_scores.inc) "
+                        "instead of from 6-mer counts, which saturate on diverged sub-families (star_align.py, Pair distances).  A "
+                        "locus with more leaves keeps the 6-mer tree and is reported.  Everything after the tree is unchanged; "
+                        "--band computes the same scores over certified bands, --device-tree keeps the tables on the GPU, --retree, "
+                        "--refine-tree and --refine run after it.  Off by default")
     p.set_defaults(func=run, check=check_options)
     return p
 
@@ -164,6 +172,8 @@ def check_options(args, parser):
             parser.error(f"--retree takes 1 to {star_align.RETREE_MAX} rebuilds, not {args.retree}")
     if getattr(args, "seq_weights", False) and not getattr(args, "progressive", False):
         parser.error("--seq-weights needs --progressive")
+    if getattr(args, "pair_distances", False) and not getattr(args, "progressive", False):
+        parser.error("--pair-distances needs --progressive")
     if getattr(args, "refine", None) is not None:
         if not args.unaligned:
             parser.error("--refine needs --unaligned")
@@ -671,12 +681,13 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
     large_loci = bool(getattr(options, "large_loci", False))
     retree = int(getattr(options, "retree", None) or 0)
     seq_weights = bool(getattr(options, "seq_weights", False))
+    pair_distances = bool(getattr(options, "pair_distances", False))
     for lo in range(0, len(mine), STAR_CHUNK):
         t0 = time.perf_counter()
         recs = [star_align.read_unaligned(f) for f in mine[lo:lo + STAR_CHUNK]]
         t1 = time.perf_counter()
         msas = star_align.star_msas(be, recs, names=loci[lo:lo + STAR_CHUNK], adjust_direction=adjust, orientation=orientation,
-                                    **(dict(band=True) if band else {}), **(dict(timings=counters) if band or collapse or device_tree or refine_tree or retree or seq_weights else {}),
+                                    **(dict(band=True) if band else {}), **(dict(timings=counters) if band or collapse or device_tree or refine_tree or retree or seq_weights or pair_distances else {}),
                                     **(dict(collapse=True) if collapse else {}),
                                     **(dict(refine=refine, refinement=refinement) if refine else {}),
                                     **(dict(progressive=True, progression=progression) if progressive else {}),
@@ -684,7 +695,8 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
                                     **(dict(large_loci=True) if large_loci else {}),
                                     **(dict(refine_tree=refine_tree, tree_refinement=tree_refinement) if refine_tree else {}),
                                     **(dict(retree=retree) if retree else {}),
-                                    **(dict(seq_weights=True) if seq_weights else {}))
+                                    **(dict(seq_weights=True) if seq_weights else {}),
+                                    **(dict(pair_distances=True) if pair_distances else {}))
         t2 = time.perf_counter()
         for locus, m in zip(loci[lo:lo + STAR_CHUNK], msas):
             path = out_dir / f"{locus}.fa"
@@ -705,6 +717,10 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
         logger.info(f"rank {rank}: --progressive --band: {counters.get('prog_band_merges', 0)} merges, "
                     f"{counters.get('prog_band_second_passes', 0)} second passes, {counters.get('prog_band_full_merges', 0)} sent to the "
                     f"full DP, {counters.get('prog_band_cells', 0)} of {counters.get('prog_band_full_cells', 0)} DP cells computed")
+    if pair_distances:
+        logger.info(f"rank {rank}: --pair-distances: {counters.get('pair_dist_loci', 0)} loci, {counters.get('pair_dist_pairs', 0)} pairs, "
+                    f"{counters.get('pair_dist_cells', 0)} DP cells, {counters.get('pair_dist_above_cap', 0)} above the cap, "
+                    f"{counters.get('pair_dist_limit', 0)} beyond the limit")
     if seq_weights:
         logger.info(f"rank {rank}: --seq-weights: {counters.get('seq_weight_loci', 0)} loci weighted, "
                     f"smallest weight {counters.get('seq_weight_min_q', 1)}")

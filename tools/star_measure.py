@@ -41,6 +41,11 @@ sequences once and then seeded picks among them, shuffled: the pan-genome core g
 seq_weight_s (the stage's wall seconds: its launches and downloads; without --device-tree the distances launched again too),
 seq_weight_loci, seq_weight_min_q, and, from an untimed run of the same loci without the flag afterwards, seq_weight_loci_changed
 (the loci whose MSA differs) and s_total_unweighted beside s_total.
+`--pair-distances` (with --progressive): the first guide trees from the pair DP's scores (`from_msa --unaligned --progressive
+--pair-distances`); the line then also gives pair_dist_s (part of tree_s), pair_dist_loci, pair_dist_pairs, pair_dist_cells,
+pair_dist_above_cap, pair_dist_limit (with --band pair_dist_second_passes and pair_dist_full_pairs) and, from an untimed run of the
+same loci without the flag afterwards, pair_dist_loci_changed (the loci whose MSA differs), pair_dist_loci_higher and
+pair_dist_loci_lower (by the locus's objective S) and s_total_kmer beside s_total.
 `--no-prg`: the PRG build over the MSAs written is left out (no prg_build_s): for runs that compare the alignment stages only."""
 import hashlib
 import json
@@ -94,6 +99,9 @@ if "--retree" in sys.argv:
 seq_weights = "--seq-weights" in sys.argv
 if seq_weights and not progressive:
     sys.exit("--seq-weights needs --progressive")
+pair_distances = "--pair-distances" in sys.argv
+if pair_distances and not progressive:
+    sys.exit("--pair-distances needs --progressive")
 records = int(sys.argv[sys.argv.index("--records") + 1]) if "--records" in sys.argv else 0
 if records and not diverged:
     sys.exit("--records needs --diverged")
@@ -102,20 +110,25 @@ if large_loci and not (progressive and collapse):
     sys.exit("--large-loci needs --progressive and --collapse-identical")
 prog_kw = dict(progressive=True, **(dict(device_tree=True) if device_tree else {}), **(dict(large_loci=True) if large_loci else {}),
                **(dict(refine_tree=refine_tree) if refine_tree else {}), **(dict(retree=retree) if retree else {}),
-               **(dict(seq_weights=True) if seq_weights else {})) if progressive else {}
+               **(dict(seq_weights=True) if seq_weights else {}), **(dict(pair_distances=True) if pair_distances else {})) if progressive else {}
 
 
-def objective_total(be, msas):
-    """The objective S of the MSAs, summed over the loci (mprg_refine_counts over their text)."""
+def objectives(be, msas):
+    """The objective S of every MSA (mprg_refine_counts over their text)."""
     import numpy as np
-    s_total = 0
+    out = []
     for lo in range(0, len(msas), 64):
         part = msas[lo:lo + 64]
         R, W = np.array([m.data.shape[0] for m in part], np.int64), np.array([m.data.shape[1] for m in part], np.int64)
         toff = np.concatenate([[0], np.cumsum(R * W)[:-1]]).astype(np.int64)
         text = np.concatenate([np.ascontiguousarray(m.data).reshape(-1) for m in part])
-        s_total += int(sa.refine_counts(be, be.upload(text), len(text), toff, R, W)[4].sum())
-    return s_total
+        out.extend(int(v) for v in sa.refine_counts(be, be.upload(text), len(text), toff, R, W)[4])
+    return out
+
+
+def objective_total(be, msas):
+    """The objective S of the MSAs, summed over the loci."""
+    return sum(objectives(be, msas))
 
 
 def diverged_seqs(seed):
@@ -220,6 +233,13 @@ try:
                              **(dict(collapse=True) if collapse else {}))
         extra.update(seq_weights=True, seq_weight_loci_changed=sum(1 for a, b in zip(msas, plain) if sa.msa_fasta(a) != sa.msa_fasta(b)),
                      s_total_unweighted=objective_total(be, plain))
+    if pair_distances:
+        plain = sa.star_msas(be, recs, adjust_direction=flip is not None, band=band, refine=refine, **dict(prog_kw, pair_distances=False),
+                             **(dict(collapse=True) if collapse else {}))
+        s_on, s_off = objectives(be, msas), objectives(be, plain)
+        extra.update(pair_distances=True, pair_dist_loci_changed=sum(1 for a, b in zip(msas, plain) if sa.msa_fasta(a) != sa.msa_fasta(b)),
+                     pair_dist_loci_higher=sum(1 for a, b in zip(s_on, s_off) if a > b), pair_dist_loci_lower=sum(1 for a, b in zip(s_on, s_off) if a < b),
+                     s_total_kmer=sum(s_off))
     cent = sa.centres(be, codes)
     cells = sum(len(c) * len(cs[int(k)]) for cs, k in zip(codes, cent) for a, c in enumerate(cs) if a != int(k))
     opts = Namespace(input=str(msa_dir), suffix="", output_prefix=str(work / "out" / "prg"), alignment_format="fasta",
