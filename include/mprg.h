@@ -909,6 +909,40 @@ int mprg_prog_leaf_weights(const uint32_t *shared, long long shared_words, const
                            const int32_t *merges, long long merges_words, int32_t *heights, int64_t *raw, int32_t *q, int32_t *status,
                            void *stream);
 
+/* `compare_msa`: a test MSA scored against a reference MSA of the same records (the spec: make_prg_amd/from_msa/msa_compare.py;
+ * DESIGN.md §3b, "Truth recovery").  Texts and bufs are mprg_prog_columns'.  Two launches on one stream, the map first.
+ * loci: n_loci x MPRG_CMP_LOCUS_FIELDS int64 {test buffer, offset of the R x W_T test text in it, W_T >= 1, reference buffer, offset
+ *   of the R x W_R reference text, W_R >= 1, R >= 1, offset of the locus's R W_R words in `tmap` (int32 elements, tmap_words long),
+ *   layout of those words (0: row-major, tmap[row W_R + c]; 1: column-major, tmap[c R + row]), offset of the locus's W_T words in
+ *   `m` (int32 elements, m_words long)}.  Widths are below 2^31 - 1.  The caller zeroes m and counts.
+ * mprg_msa_compare_map: rows: n_rows x MPRG_CMP_ROW_FIELDS int64 {locus, reference row, test row, reversed (0 / 1), offset of the
+ *   row's workspace in `tpos` (int32 elements, tpos_words long), its capacity in words}; every reference row of every locus once,
+ *   no two rows of a locus with the same test row.  A residue is a cell that is not '-' (code 4).  With n the row's residues:
+ *   tpos[offset + p] = the test column of the test row's p-th residue; m[locus's offset + t] += 1 per residue of the test row in
+ *   test column t (integer atomics); for a reference cell (row, c) that holds the row's p-th residue tmap(row, c) = the test
+ *   column of the test row's residue p (reversed: n - 1 - p), for a gap INT32_MAX.
+ *   status: n_rows int32: MPRG_CMP_OK; MPRG_CMP_BAD_ITEM (an index, a text, the row's workspace, the locus's tmap or m words
+ *   outside their table or buffer, a flag or a layout that is neither 0 nor 1: nothing else written); MPRG_CMP_COUNT (the two rows
+ *   do not hold the same number of residues, or more than the capacity: nothing else written); MPRG_CMP_CODE (residue p of the
+ *   reference row is not the code of the test row's residue p, for a reversed row not the complement (A<->T, C<->G, R<->Y, K<->M)
+ *   of its residue n - 1 - p: the row's tpos, tmap and m words are written, the locus's counts mean nothing).  A wavefront per row.
+ * mprg_msa_compare_columns: work: n_work x 2 int32 {locus, column block q}: with P the next power of two >= R and G = 8 192 / P the
+ *   reference columns q G .. min(W_R, (q + 1) G) - 1; every block of every locus once.  R <= MPRG_CMP_MAX_ROWS.  tmap and m as the
+ *   map left them (a tmap word outside [0, W_T) counts as a gap).  With n_c the residues of reference column c, n_{c,t} those of
+ *   them whose tmap word is t, m_t = m[t]: counts[MPRG_CMP_COUNTS locus + .] += {shared: sum of C(n_{c,t}, 2), ref_pairs: sum of
+ *   C(n_c, 2), test_pairs: the block's share of sum of C(m_t, 2), ref_columns: columns with n_c >= 2, kept_columns: those whose
+ *   residues all have one t, identical_columns: those kept ones with m_t = n_c} over the block's columns (64-bit integer atomics,
+ *   so the sums do not depend on the order).
+ *   status: n_work int32: MPRG_CMP_OK, or MPRG_CMP_BAD_ITEM (an index or a block outside its table, R above MPRG_CMP_MAX_ROWS,
+ *   the locus's tmap or m words outside their buffer): nothing else written.  One workgroup per work item, 32 KB of LDS. */
+enum { MPRG_CMP_LOCUS_FIELDS = 10, MPRG_CMP_ROW_FIELDS = 6, MPRG_CMP_COUNTS = 6, MPRG_CMP_MAX_ROWS = 8192,
+       MPRG_CMP_OK = 0, MPRG_CMP_BAD_ITEM = 1, MPRG_CMP_COUNT = 2, MPRG_CMP_CODE = 3 };
+int mprg_msa_compare_map(const int64_t *bufs, int n_bufs, const int64_t *loci, int n_loci, const int64_t *rows, long long n_rows,
+                         int32_t *tpos, long long tpos_words, int32_t *tmap, long long tmap_words, int32_t *m, long long m_words,
+                         int32_t *status, void *stream);
+int mprg_msa_compare_columns(const int64_t *loci, int n_loci, const int32_t *work, int n_work, const int32_t *tmap, long long tmap_words,
+                             const int32_t *m, long long m_words, int64_t *counts, int32_t *status, void *stream);
+
 /* (f)-1 output encoders, HOST functions (host pointers), one pass over a PRG string as PrgBuilder emits it.
  * reference make_prg/utils/prg_encoder.py:44-91 and make_prg/utils/gfa.py:16-109.
  * mprg_prg_encode_host: out[n] receives the uint32 stream (A C G T -> 1 2 3 4, markers as integers, the closing

@@ -5,7 +5,7 @@ import os
 import sys
 
 from . import __version__
-from .subcommands import from_msa, update
+from .subcommands import compare_msa, from_msa, update
 from .subcommands.output_type import OutputType
 
 
@@ -30,13 +30,14 @@ def main(argv=None):
                               "Default: %(default)d")
         par.add_argument("-v", "--verbose", action="count", default=0, help="Increase output verbosity")
         par.add_argument("--log", help="Path to write log to. Default is stderr")
+    compare_msa.register_parser(subparsers)          # (its own -v and --log; it writes no PRG, so no -O, -F or -t)
     args = parser.parse_args(argv)
     if getattr(args, "check", None) is not None:
         args.check(args, msa_parser)
     if hasattr(args, "func"):
         level = [logging.INFO, logging.DEBUG, logging.DEBUG][min(args.verbose, 2)]
         logging.basicConfig(level=level, **({"filename": args.log} if args.log else {"stream": sys.stderr}))
-        if args.threads == 0:
+        if getattr(args, "threads", 1) == 0:
             # "all available": the CPUs this process may use, shared by the ranks of a node.  from_msa: host threads of the
             # native batch stages (one GPU) or host worker processes per GPU (several ranks), where more than ~10 stop paying;
             # update: threads that wait for aligner processes — no such cap

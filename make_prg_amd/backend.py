@@ -137,6 +137,10 @@ SIGNATURES = {
                                      ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
     "mprg_prog_leaf_weights": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, c_void_p,
                                        ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mprg_msa_compare_map": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p,
+                                     ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
+    "mprg_msa_compare_columns": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong,
+                                         c_void_p, c_void_p, c_void_p]),
     "mprg_random_sample_host": (None, [c_uint32, c_int, c_void_p]),
     "mprg_prg_encode_host": (ctypes.c_longlong, [c_void_p, ctypes.c_longlong, c_void_p]),
     "mprg_fasta_scan_host": (ctypes.c_longlong, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),

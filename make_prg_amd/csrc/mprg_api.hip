@@ -29,6 +29,7 @@
 #include "k_tree_refine.inc"
 #include "k_prog_retree.inc"
 #include "k_prog_weights.inc"
+#include "k_msa_compare.inc"
 #include "host_encoders.inc"
 #include "host_batch.inc"
 
@@ -837,6 +838,23 @@ int mprg_prog_leaf_weights(const uint32_t *shared, long long shared_words, const
   LAUNCH(k_prog_leaf_weights, n_loci, PG_THREADS, stream, shared, shared_words, nw, seqs, n_seqs, loci, weights, workspace,
          workspace_words, merges, merges_words, heights, raw, q, status);      // a workgroup per locus
   return check_launch("k_prog_leaf_weights");
+}
+
+int mprg_msa_compare_map(const int64_t *bufs, int n_bufs, const int64_t *loci, int n_loci, const int64_t *rows, long long n_rows,
+                         int32_t *tpos, long long tpos_words, int32_t *tmap, long long tmap_words, int32_t *m, long long m_words,
+                         int32_t *status, void *stream) {
+  if (n_rows <= 0) return 0;
+  LAUNCH(k_msa_compare_map, (n_rows + CM_WAVES - 1) / CM_WAVES, CM_THREADS, stream, bufs, n_bufs, loci, n_loci, rows, n_rows, tpos,
+         tpos_words, tmap, tmap_words, m, m_words, status);      // a wavefront per row
+  return check_launch("k_msa_compare_map");
+}
+
+int mprg_msa_compare_columns(const int64_t *loci, int n_loci, const int32_t *work, int n_work, const int32_t *tmap, long long tmap_words,
+                             const int32_t *m, long long m_words, int64_t *counts, int32_t *status, void *stream) {
+  if (n_work <= 0) return 0;
+  LAUNCH(k_msa_compare_columns, n_work, CC_THREADS, stream, loci, n_loci, work, tmap, tmap_words, m, m_words, counts,
+         status);      // a workgroup per (locus, column block)
+  return check_launch("k_msa_compare_columns");
 }
 
 // ---- the recursion forest on the device (k_forest.inc); F: host array of MPRG_F_FIELDS int64 ------------------------------

@@ -91,5 +91,44 @@ def synth_rows_deep(seed: int, S: int, C: int, fanout=(3, 3, 3, 3, 3), rates=(0.
     return rows
 
 
+def diverged_locus(seed: int, n: int, min_len: int = 800, max_len: int = 1200, p_delete: float = 0.015, p_substitute: float = 0.06,
+                   p_insert: float = 0.015, max_insert: int = 4) -> Tuple[List[str], List[str]]:
+    """(seqs, true_rows): n sequences mutated from one random root of min_len .. max_len nt, and the alignment that is TRUE by
+    construction.  Per root base one draw u on random.Random(seed): u < p_delete deletes it, u < p_delete + p_substitute replaces it
+    by a drawn base (which may be the same one), u > 1 - p_insert puts 1 .. max_insert drawn bases behind it: the draws, and so the
+    sequences, of `tools/star_measure.py --diverged` (the draw order is part of the recorded digests).  A root base and whatever
+    replaces it share a column; a sequence's insertion behind root position j gets columns of its own, behind column j and ordered
+    by sequence index (independent insertions are not homologous); all-gap columns are dropped.  Every row ungaps to its sequence."""
+    import random
+    r = random.Random(seed)
+    root = "".join(r.choice("ACGT") for _ in range(r.randint(min_len, max_len)))
+    base = [[None] * len(root) for _ in range(n)]            # per sequence and root position its base, None: deleted
+    inserts = [dict() for _ in range(n)]                     # per sequence {root position: the insertion behind it}
+    seqs = []
+    for i in range(n):
+        s = []
+        for j, ch in enumerate(root):
+            u = r.random()
+            if u < p_delete:
+                continue
+            base[i][j] = r.choice("ACGT") if u < p_delete + p_substitute else ch
+            s.append(base[i][j])
+            if u > 1.0 - p_insert:
+                inserts[i][j] = "".join(r.choice("ACGT") for _ in range(r.randint(1, max_insert)))
+                s.append(inserts[i][j])
+        seqs.append("".join(s))
+    rows: List[List[str]] = [[] for _ in range(n)]
+    for j in range(len(root)):
+        if any(base[i][j] is not None for i in range(n)):
+            for i in range(n):
+                rows[i].append(base[i][j] or "-")
+        for k in range(n):
+            ins = inserts[k].get(j)
+            if ins:
+                for i in range(n):
+                    rows[i].append(ins if i == k else "-" * len(ins))
+    return seqs, ["".join(x) for x in rows]
+
+
 def synth_deep_fasta(seed: int, S: int, C: int) -> str:
     return "".join(f">s{i}\n{r.decode()}\n" for i, r in enumerate(synth_rows_deep(seed, S, C)))

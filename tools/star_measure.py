@@ -46,6 +46,12 @@ seq_weight_loci, seq_weight_min_q, and, from an untimed run of the same loci wit
 pair_dist_above_cap, pair_dist_limit (with --band pair_dist_second_passes and pair_dist_full_pairs) and, from an untimed run of the
 same loci without the flag afterwards, pair_dist_loci_changed (the loci whose MSA differs), pair_dist_loci_higher and
 pair_dist_loci_lower (by the locus's objective S) and s_total_kmer beside s_total.
+`--truth`: the MSAs written are scored against the alignment that is true by construction (`compare_msa`'s counts,
+make_prg_amd/from_msa/msa_compare.py, after the timed part): synth_rows' own rows for the config-C-shaped loci, diverged_locus'
+true_rows with --diverged; the line then also gives truth_shared, truth_ref_pairs, truth_test_pairs, truth_ref_columns, truth_kept,
+truth_identical (summed over the loci) and compare_s, the wall seconds of the compare stage.  With --flip the truth holds every
+record in the family's orientation, so a row is matched as a reversed row (the `_R_` prefix) exactly where the aligner's choice and
+the file's flip disagree.  Not with --records or --dup.
 `--no-prg`: the PRG build over the MSAs written is left out (no prg_build_s): for runs that compare the alignment stages only."""
 import hashlib
 import json
@@ -63,7 +69,7 @@ from make_prg_amd.device import get_backend  # noqa: E402
 from make_prg_amd.from_msa import star_align as sa  # noqa: E402
 from make_prg_amd.subcommands import from_msa  # noqa: E402
 from make_prg_amd.subcommands.output_type import OutputType  # noqa: E402
-from make_prg_amd.utils.synthetic import config_shape, synth_rows  # noqa: E402
+from make_prg_amd.utils.synthetic import config_shape, diverged_locus, synth_rows  # noqa: E402
 
 n_loci = int(sys.argv[1]) if len(sys.argv) > 1 and not sys.argv[1].startswith("--") else 1000
 COMPLEMENT = str.maketrans("ACGTRYKMSWN", "TGCAYRMKSWN")
@@ -105,6 +111,9 @@ if pair_distances and not progressive:
 records = int(sys.argv[sys.argv.index("--records") + 1]) if "--records" in sys.argv else 0
 if records and not diverged:
     sys.exit("--records needs --diverged")
+truth = "--truth" in sys.argv
+if truth and (records or dup):
+    sys.exit("--truth does not go with --records or --dup")
 large_loci = "--large-loci" in sys.argv
 if large_loci and not (progressive and collapse):
     sys.exit("--large-loci needs --progressive and --collapse-identical")
@@ -131,32 +140,21 @@ def objective_total(be, msas):
     return sum(objectives(be, msas))
 
 
-def diverged_seqs(seed):
-    r = random.Random(seed)
-    root = "".join(r.choice("ACGT") for _ in range(r.randint(800, 1200)))
-    out = []
-    for _ in range(diverged):
-        s = []
-        for ch in root:
-            u = r.random()
-            if u < 0.015:
-                continue
-            s.append(r.choice("ACGT") if u < 0.075 else ch)
-            if u > 0.985:
-                s.append("".join(r.choice("ACGT") for _ in range(r.randint(1, 4))))
-        out.append("".join(s))
-    return out
-
-
 work = Path(tempfile.mkdtemp(prefix="star_measure_"))
 try:
     src, msa_dir = work / "unaligned", work / "msas"
     src.mkdir()
     msa_dir.mkdir()
     t0 = time.perf_counter()
-    rng, flipped = random.Random(1), []
+    rng, flipped, true_rows = random.Random(1), [], []
     for seed in range(n_loci):
-        seqs = diverged_seqs(seed) if diverged else [r.decode().replace("-", "") for r in synth_rows(seed, *config_shape("C", seed))]
+        if diverged:
+            seqs, rows = diverged_locus(seed, diverged)
+        else:
+            rows = [r.decode() for r in synth_rows(seed, *config_shape("C", seed))]
+            seqs = [r.replace("-", "") for r in rows]
+        if truth:
+            true_rows.append(rows)
         if records:
             rrng = random.Random(2000003 + seed)
             seqs = seqs + [rrng.choice(seqs) for _ in range(records - len(seqs))]
@@ -240,6 +238,20 @@ try:
         extra.update(pair_distances=True, pair_dist_loci_changed=sum(1 for a, b in zip(msas, plain) if sa.msa_fasta(a) != sa.msa_fasta(b)),
                      pair_dist_loci_higher=sum(1 for a, b in zip(s_on, s_off) if a > b), pair_dist_loci_lower=sum(1 for a, b in zip(s_on, s_off) if a < b),
                      s_total_kmer=sum(s_off))
+    if truth:
+        from make_prg_amd.from_msa import msa_compare as mc
+        from make_prg_amd.msa import MSA
+        t0 = time.perf_counter()
+        ids = [[f"s{i}" for i in range(len(rows))] for rows in true_rows]
+        tests = msas
+        if flip is not None:          # (a row holds the reverse complement of its truth row where the aligner and the file disagree)
+            tests = [MSA(_data=m.data, _ids=[(sa.REVERSED_PREFIX if a != b else "") + i for i, a, b in zip(ii, rev, fl)], _descs=m.descriptions)
+                     for m, ii, (rev, _), fl in zip(msas, ids, orientation, flipped)]
+        scored = mc.total(mc.compare_msas(be, tests, [MSA.from_strings(rows, ii) for rows, ii in zip(true_rows, ids)],
+                                          names=[f.name for f in files]))
+        extra.update(truth_shared=scored.shared, truth_ref_pairs=scored.ref_pairs, truth_test_pairs=scored.test_pairs,
+                     truth_ref_columns=scored.ref_columns, truth_kept=scored.kept_columns, truth_identical=scored.identical_columns,
+                     compare_s=round(time.perf_counter() - t0, 3))
     cent = sa.centres(be, codes)
     cells = sum(len(c) * len(cs[int(k)]) for cs, k in zip(codes, cent) for a, c in enumerate(cs) if a != int(k))
     opts = Namespace(input=str(msa_dir), suffix="", output_prefix=str(work / "out" / "prg"), alignment_format="fasta",
