@@ -774,6 +774,32 @@ int mprg_prog_band_widths(const int32_t *profile, const int64_t *leaves, int n_l
 int mprg_prog_rows(const int64_t *bufs, int n_bufs, const uint8_t *ops, long long ops_bytes, const int64_t *rows, int n_rows,
                    uint8_t *out, long long out_bytes, int ascii, int32_t *status, void *stream);
 
+/* `--progressive --position-gaps`: the opens of a merge by the occupancy of the column a run starts at (the spec: star_align.py,
+ * "Position gaps").  Opening a run of 'D' ops whose first skipped column of Y is j pays Oc[j] = (64 * -11 * (R_Y -
+ * gaps_j)) / R_Y, a run of 'I' ops whose first column of X is i pays Ox[i] = (64 * -11 * (R_X - gaps_i)) / R_X (C's truncating
+ * division; -704 .. 0), in place of -704; row 0 pays Oc[0], column 0 Ox[0].  Everything else is the entries' above.
+ * mprg_prog_columns_posgap, mprg_prog_columns_weighted_posgap: mprg_prog_columns(_weighted) with a third kind: kind 2 writes 7
+ *   planes of W int32, kind 0's six and Oc.  Kinds 0 and 1 write what they write there (which refuse kind 2: MPRG_PG_BAD_ITEM).
+ * mprg_align_profile_pairs_posgap, mprg_align_profile_pairs_posgap_banded: mprg_align_profile_pairs(_banded) with these opens; the
+ *   leaf's profile at its offset has the 7 planes of kind 2; X's planes are kind 1's (Ox comes from its gap counts and R_X).
+ *   Arguments, workspace need, ops and status codes are unchanged.  With no '-' on either side ops and score are
+ *   mprg_align_profile_pairs'.
+ * mprg_prog_band_widths_posgap: mprg_prog_band_widths over such tables, with U(w) = SB - LY(max(0, D) + w + 1) - LX(w + 1 - min(0, D))
+ *   + max_j Oc[j] + max_i Ox[i] (the last term 0 when n = 0). */
+int mprg_prog_columns_posgap(const int64_t *bufs, int n_bufs, const int64_t *items, int n_items, const int32_t *work, int n_work,
+                             int32_t *cols, long long cols_words, int32_t *status, void *stream);
+int mprg_prog_columns_weighted_posgap(const int64_t *bufs, int n_bufs, const int64_t *items, int n_items, const int32_t *work, int n_work,
+                                      const int32_t *weights, long long weights_words, int32_t *cols, long long cols_words,
+                                      int32_t *status, void *stream);
+int mprg_align_profile_pairs_posgap(const int32_t *profile, const int64_t *leaves, int n_leaves, const int32_t *xcols,
+                                    long long xcols_words, const int64_t *pairs, int n_pairs, int32_t *workspace,
+                                    long long workspace_words, uint8_t *ops, long long ops_bytes, int32_t *out, void *stream);
+int mprg_align_profile_pairs_posgap_banded(const int32_t *profile, const int64_t *leaves, int n_leaves, const int32_t *xcols,
+                                           long long xcols_words, const int64_t *pairs, int n_pairs, int32_t *workspace,
+                                           long long workspace_words, uint8_t *ops, long long ops_bytes, int32_t *out, void *stream);
+int mprg_prog_band_widths_posgap(const int32_t *profile, const int64_t *leaves, int n_leaves, const int32_t *xcols, long long xcols_words,
+                                 const int64_t *pairs, int n_pairs, const int32_t *out, int64_t *bounds, int32_t *status, void *stream);
+
 /* `from_msa --unaligned --collapse-identical`: every distinct sequence of a locus aligned once (the spec: star_align.py, "Collapse";
  * DESIGN.md §3b).  The pair, merge and row calls above are used unchanged, on tables that name a class's representative.
  * mprg_star_identical: codes, seqs, loci as the star calls' (only {first sequence, sequence count} of a locus are read).

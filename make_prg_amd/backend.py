@@ -121,6 +121,15 @@ SIGNATURES = {
                                       c_void_p]),
     "mprg_prog_rows": (c_int, [c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_int, c_void_p,
                                c_void_p]),
+    "mprg_prog_columns_posgap": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
+    "mprg_prog_columns_weighted_posgap": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p,
+                                                  ctypes.c_longlong, c_void_p, c_void_p]),
+    "mprg_align_profile_pairs_posgap": (c_int, [c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p,
+                                                ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
+    "mprg_align_profile_pairs_posgap_banded": (c_int, [c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p,
+                                                       ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
+    "mprg_prog_band_widths_posgap": (c_int, [c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, c_void_p,
+                                             c_void_p, c_void_p]),
     "mprg_star_identical": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                     c_void_p]),
     "mprg_prog_columns_weighted": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p,

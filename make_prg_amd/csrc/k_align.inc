@@ -13,7 +13,8 @@
 //   of that strip wrote), the profile of the columns in flight from a 128-column LDS ring per wavefront (consecutive lanes
 //   on consecutive columns).  A cell's traceback is 4 bits, a lane packs eight steps per dword, so every store is a 256-byte
 //   row.  Lane 0 then walks the traceback back from (n, C) and writes the ops (reversed) and the score.
-//   The cell's recurrence (al_cell.inc) and the walk back (al_walk.inc) are written once for the four sweep kernels (this one,
+//   The cell's recurrence (al_cell.inc; its two open terms are AL_OPEN_D and AL_OPEN_I, here the fixed open and the column) and
+//   the walk back (al_walk.inc) are written once for the sweep kernels (this one,
 //   k_align_pairs_banded below, k_align_profile_pairs in k_prog.inc, k_align_profile_pairs_banded in k_prog_band.inc), a column's
 //   counts (al_counts.inc) and its planes (al_planes.inc) once for the kernels that write profiles (k_align_profiles,
 //   k_prog_columns, k_prog_columns_weighted, and k_refine_profiles for the planes).  All are included as text: an inlined function
@@ -125,7 +126,11 @@ __global__ void __launch_bounds__(AL_THREADS) k_align_pairs(const int32_t *profi
         const int dc = ring[5 * AL_RING + slot];
         const int diag = h_diag + ring[cls * AL_RING + slot];
         const int xcost = AL_INS;
+#define AL_OPEN_D AL_OPEN + dc
+#define AL_OPEN_I AL_OPEN + xcost
 #include "al_cell.inc"
+#undef AL_OPEN_D
+#undef AL_OPEN_I
         if (lane == 63 && s + 1 < n_strips) { row[2 * (c + 1)] = h; row[2 * (c + 1) + 1] = ii; }
       }
       acc |= cell << (4 * (t & 7));
@@ -296,7 +301,11 @@ __global__ void __launch_bounds__(AL_THREADS) k_align_pairs_banded(const int32_t
         const int dc = ring[5 * AL_RING + slot];
         const int diag = h_diag + ring[cls * AL_RING + slot];
         const int xcost = AL_INS;
+#define AL_OPEN_D AL_OPEN + dc
+#define AL_OPEN_I AL_OPEN + xcost
 #include "al_cell.inc"
+#undef AL_OPEN_D
+#undef AL_OPEN_I
         if (lane == 63 && s + 1 < n_strips) { const int k = c + 1 - (i0 + 64 + dlo); row[(unsigned)(2 * k)] = h; row[(unsigned)(2 * k + 1)] = ii; }
       } else {
         h_out = c == -1 && r + 1 + dlo <= 0 ? al_hb(r + 1) : AL_NEG;   // outside the band: minus infinity, never a stale or an accumulated value

@@ -82,7 +82,11 @@ __global__ void __launch_bounds__(AL_THREADS) k_align_scores(const int32_t *prof
         const int dc = ring[5 * AL_RING + slot];
         const int diag = h_diag + ring[cls * AL_RING + slot];
         const int xcost = AL_INS;
+#define AL_OPEN_D AL_OPEN + dc
+#define AL_OPEN_I AL_OPEN + xcost
 #include "al_cell.inc"
+#undef AL_OPEN_D
+#undef AL_OPEN_I
         if (lane == 63 && s + 1 < n_strips) { row[2 * (c + 1)] = h; row[2 * (c + 1) + 1] = ii; }
       }
       (void)cell;                                            // no traceback: the score is all that leaves
@@ -183,7 +187,11 @@ __global__ void __launch_bounds__(AL_THREADS) k_align_scores_banded(const int32_
         const int dc = ring[5 * AL_RING + slot];
         const int diag = h_diag + ring[cls * AL_RING + slot];
         const int xcost = AL_INS;
+#define AL_OPEN_D AL_OPEN + dc
+#define AL_OPEN_I AL_OPEN + xcost
 #include "al_cell.inc"
+#undef AL_OPEN_D
+#undef AL_OPEN_I
         if (lane == 63 && s + 1 < n_strips) { const int k = c + 1 - (i0 + 64 + dlo); row[(unsigned)(2 * k)] = h; row[(unsigned)(2 * k + 1)] = ii; }
       } else {
         h_out = c == -1 && r + 1 + dlo <= 0 ? al_hb(r + 1) : AL_NEG;   // outside the band: minus infinity, never a stale or an accumulated value

@@ -91,7 +91,7 @@ __global__ void __launch_bounds__(ID_THREADS) k_star_identical(const uint8_t *co
 }
 
 __global__ void __launch_bounds__(PG_THREADS) k_prog_columns_weighted(const int64_t *bufs, int n_bufs, const int64_t *items, int n_items,
-                                                                      const int32_t *work, const int32_t *weights, long long weights_words,
+                                                                      const int32_t *work, int max_kind, const int32_t *weights, long long weights_words,
                                                                       int32_t *cols, long long cols_words, int32_t *status) {
   SHARED(long long, red, PG_WAVES);
   SHARED(int, low, 1);

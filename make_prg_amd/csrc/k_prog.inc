@@ -13,8 +13,10 @@
 //   s(a, b) at row a, column b of the locus's m x m table (only b > a is written).  nw_a comes out of the first pass.
 // k_prog_columns: one workgroup per (item, 256-column tile), thread = column, the text's rows walked in order (k_align_profiles'
 //   access pattern).  Kind 0 writes exactly k_align_profiles' 6 planes (Y's profile), kind 1 the 7 planes of an X side: the
-//   counts of A C G T, of R Y K M S W N, of '-', and Ic.
-// k_align_profile_pairs: k_align_pairs' structure with a profile on both sides, a kernel of its own but for the cell and the
+//   counts of A C G T, of R Y K M S W N, of '-', and Ic.  Kind 2 (only where max_kind = 2: mprg_prog_columns_posgap) writes kind 0's
+//   six planes and Oc, the open of a run that starts at the column.
+// k_align_profile_pairs (its text: pg_pairs.inc, included twice: the second time as k_align_profile_pairs_posgap, the merge with
+//   position-specific opens): k_align_pairs' structure with a profile on both sides, a kernel of its own but for the cell and the
 //   walk back (al_cell.inc, al_walk.inc): one wavefront per merge, 64-column strips of X on the anti-diagonal, the row above
 //   by shuffle, Y's six planes in the 128-column LDS ring, 4-bit traceback, lane 0 walking back.  A lane keeps its X column's six
 //   counts and Ic in registers; a cell's score is six multiply-adds and the truncating division by R_X as a multiplication by a
@@ -96,7 +98,7 @@ MPRG_DEV bool pg_text_ok(const int64_t *bufs, int n_bufs, long long buf, long lo
 }
 
 __global__ void __launch_bounds__(PG_THREADS) k_prog_columns(const int64_t *bufs, int n_bufs, const int64_t *items, int n_items,
-                                                             const int32_t *work, int32_t *cols, long long cols_words, int32_t *status) {
+                                                             const int32_t *work, int max_kind, int32_t *cols, long long cols_words, int32_t *status) {
   long long buf = 0, off = 0, R = 0, W = 0, kind = 0, coff = 0;
 #define PG_ITEM_STRIDE MPRG_PG_ITEM_FIELDS
 #define PG_ITEM_READ_MORE
@@ -136,110 +138,16 @@ MPRG_DEV int pg_div(int v, const PgDiv d) {
   return v < 0 ? -q : q;
 }
 
-__global__ void __launch_bounds__(AL_THREADS) k_align_profile_pairs(const int32_t *profile, const int64_t *leaves, int n_leaves,
-                                                                    const int32_t *xcols, long long xcols_words, const int64_t *pairs,
-                                                                    int n_pairs, int32_t *ws, long long ws_words, uint8_t *ops,
-                                                                    long long ops_bytes, int32_t *out) {
-  SHARED(int32_t, ring_all, AL_WAVES * 6 * AL_RING);
-  const int lane = wave_lane();
-  const long long p = (long long)BLOCK_ID * AL_WAVES + wave_id();
-  if (p >= n_pairs) return;                                   // (a whole wavefront: nothing below waits for the others)
-  int32_t *ring = ring_all + wave_id() * 6 * AL_RING;
-  const int64_t *PT = pairs + MPRG_PG_PAIR_FIELDS * p;
-  const long long leaf = PT[0], xoff = PT[1], n = PT[2], wsoff = PT[3], opoff = PT[4], RX = PT[5];
-  int32_t *o = out + 3 * p;
-  int status = MPRG_AL_OK;
-  long long C = 0, poff = 0;
-  if (leaf < 0 || leaf >= n_leaves) status = MPRG_AL_BAD_INPUT;
-  else {
-    C = leaves[MPRG_AL_LEAF_FIELDS * leaf + 2];
-    poff = leaves[MPRG_AL_LEAF_FIELDS * leaf + 3];
-    if (C < 1 || n < 0 || leaves[MPRG_AL_LEAF_FIELDS * leaf + 1] < 1 || RX < 1 || RX > PG_MAX_ROWS) status = MPRG_AL_BAD_INPUT;
-    else if (n + C >= AL_MAX_CELLS_SUM) status = MPRG_AL_TOO_LONG;
-    else if (wsoff < 0 || (wsoff & 63) || wsoff + al_ws_words(n, C) > ws_words || opoff < 0 || opoff + n + C > ops_bytes ||
-             xoff < 0 || xoff > xcols_words || 7 * n > xcols_words - xoff)
-      status = MPRG_AL_NO_SPACE;
-  }
-  if (status != MPRG_AL_OK) {
-    if (lane == 0) { o[0] = status; o[1] = 0; o[2] = 0; }
-    return;
-  }
-  const int32_t *P = profile + al_uniform(poff);
-  const int Ci = (int)al_uniform(C), ni = (int)al_uniform(n);
-  const int32_t *X = xcols + al_uniform(xoff);
-  const PgDiv dv = pg_div_make(al_uniform(RX));
-  const long long wsoff_u = al_uniform(wsoff);
-  int32_t *row = ws + wsoff_u;                               // row[2J] = H, row[2J + 1] = I of the row above the strip, column J
-  uint32_t *tb = (uint32_t *)(ws + wsoff_u + ((2 * ((long long)Ci + 1) + 63) / 64) * 64);
-  const long long nst8 = ((long long)Ci + 63 + 7) / 8;
-  // row 0: H[0][J] = D[0][J] = open + the gap costs of columns < J
-  int carry = 0;
-  for (int c0 = 0; c0 < Ci; c0 += 64) {
-    const int c = c0 + lane;
-    const int incl = wave_scan_incl(c < Ci ? (P + 5LL * Ci)[(unsigned)c] : 0) + carry;
-    if (c < Ci) { row[2 * (c + 1)] = AL_OPEN + incl; row[2 * (c + 1) + 1] = AL_NEG; }
-    carry = __shfl(incl, 63);
-  }
-  if (lane == 0) { row[0] = 0; row[1] = AL_NEG; }
-  WAVE_SYNC_GLOBAL();
-  int score = AL_NEG;
-  int ic_before = 0;                                         // the Ic of all rows above the strip
-  const int n_strips = (ni + 63) / 64;
-  for (int s = 0; s < n_strips; ++s) {
-    const int i0 = s * 64, r = i0 + lane, rows = ni - i0 < 64 ? ni - i0 : 64;
-    const bool valid = r < ni;
-    // this lane's X column: the counts of A C G T, of the ambiguity codes, of '-', and what the column alone costs
-    const int x0 = valid ? X[(unsigned)r] : 0, x1 = valid ? (X + (long long)ni)[(unsigned)r] : 0;
-    const int x2 = valid ? (X + 2LL * ni)[(unsigned)r] : 0, x3 = valid ? (X + 3LL * ni)[(unsigned)r] : 0;
-    const int xa = valid ? (X + 4LL * ni)[(unsigned)r] : 0, xg = valid ? (X + 5LL * ni)[(unsigned)r] : 0;
-    const int ic = valid ? (X + 6LL * ni)[(unsigned)r] : 0;
-    const int ic_incl = wave_scan_incl(ic) + ic_before;     // the Ic of rows 1 .. r + 1
-    int h_left = AL_OPEN + ic_incl, d_left = AL_NEG;       // H, D of this lane's row, the column to the left: H[r + 1][0]
-    int h_out = h_left, i_out = AL_NEG;                     // what the lane below reads next step (before the first column: H[i][0])
-    int h_up_prev = i0 == 0 ? 0 : AL_OPEN + ic_before;      // (lane 0) H of the row above, one column to the left: the diagonal
-    ic_before = __shfl(ic_incl, 63);
-    uint32_t acc = 0;
-    uint32_t *tbs = tb + (long long)s * nst8 * 64;
-    int h_row = AL_NEG, i_row = AL_NEG;                      // H, I of the row above the strip, column t0 + 1 + lane of the 64-step block
-    const int T = Ci + rows - 1;
-    for (int t = 0; t < T; ++t) {
-      if ((t & 63) == 0) {                                   // the ring takes columns [t, t + 64): the block of columns t - 128 is done with
-        WAVE_SYNC();
-#pragma unroll
-        for (int k = 0; k < 6; ++k) ring[k * AL_RING + ((t + lane) & (AL_RING - 1))] = t + lane < Ci ? (P + (long long)k * Ci)[(unsigned)(t + lane)] : 0;
-        // ... and the row above for the block's 64 steps in one coalesced read: a load per step would put the memory latency into
-        // every step of the chain (lane 63 writes the next strip's column c + 1 = t - 62 at step t: after this read of it)
-        h_row = t + lane < Ci ? row[(unsigned)(2 * (t + lane + 1))] : AL_NEG;
-        i_row = t + lane < Ci ? row[(unsigned)(2 * (t + lane + 1) + 1)] : AL_NEG;
-        WAVE_SYNC();
-      }
-      int h_up = __shfl_up(h_out, 1), i_up = __shfl_up(i_out, 1);
-      const int h_top = __shfl(h_row, t & 63), i_top = __shfl(i_row, t & 63);
-      if (lane == 0 && t < Ci) { h_up = h_top; i_up = i_top; }
-      const int h_diag = h_up_prev;
-      h_up_prev = h_up;
-      const int c = t - lane;
-      unsigned cell = 0;
-      if (valid && c >= 0 && c < Ci) {
-        const int slot = c & (AL_RING - 1);
-        const int dc = ring[5 * AL_RING + slot];
-        const int num = x0 * ring[slot] + x1 * ring[AL_RING + slot] + x2 * ring[2 * AL_RING + slot] + x3 * ring[3 * AL_RING + slot] +
-                        xa * ring[4 * AL_RING + slot] + xg * dc;
-        const int diag = h_diag + pg_div(num, dv);
-        const int xcost = ic;
-#include "al_cell.inc"
-        if (lane == 63 && s + 1 < n_strips) { row[2 * (c + 1)] = h; row[2 * (c + 1) + 1] = ii; }
-      }
-      acc |= cell << (4 * (t & 7));
-      if ((t & 7) == 7 || t == T - 1) { tbs[(unsigned)((t >> 3) * 64 + lane)] = acc; acc = 0; }
-    }
-    WAVE_SYNC_GLOBAL();                                      // the row buffer and the traceback, written by every lane, read by lane 0
-  }
-  score = ni > 0 ? __shfl(score, (ni - 1) & 63) : row[2 * Ci];
-  constexpr bool kBand = false;                              // (the full matrix: every strip starts at column 0)
-  constexpr int dlo = 0;
-#include "al_walk.inc"
-}
+#define PG_PAIRS_KERNEL k_align_profile_pairs
+#define PG_POSGAP 0
+#include "pg_pairs.inc"
+#undef PG_PAIRS_KERNEL
+#undef PG_POSGAP
+#define PG_PAIRS_KERNEL k_align_profile_pairs_posgap
+#define PG_POSGAP 1
+#include "pg_pairs.inc"
+#undef PG_PAIRS_KERNEL
+#undef PG_POSGAP
 
 __global__ void __launch_bounds__(PG_THREADS) k_prog_rows(const int64_t *bufs, int n_bufs, const uint8_t *ops, long long ops_bytes,
                                                           const int64_t *rows, int n_rows, uint8_t *out, long long out_bytes, int ascii,

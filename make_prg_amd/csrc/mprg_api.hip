@@ -722,7 +722,14 @@ int mprg_prog_distances(const uint8_t *codes, long long codes_bytes, const int64
 int mprg_prog_columns(const int64_t *bufs, int n_bufs, const int64_t *items, int n_items, const int32_t *work, int n_work,
                       int32_t *cols, long long cols_words, int32_t *status, void *stream) {
   if (n_work <= 0) return 0;
-  LAUNCH(k_prog_columns, n_work, PG_THREADS, stream, bufs, n_bufs, items, n_items, work, cols, cols_words, status);
+  LAUNCH(k_prog_columns, n_work, PG_THREADS, stream, bufs, n_bufs, items, n_items, work, 1, cols, cols_words, status);
+  return check_launch("k_prog_columns");
+}
+
+int mprg_prog_columns_posgap(const int64_t *bufs, int n_bufs, const int64_t *items, int n_items, const int32_t *work, int n_work,
+                             int32_t *cols, long long cols_words, int32_t *status, void *stream) {
+  if (n_work <= 0) return 0;
+  LAUNCH(k_prog_columns, n_work, PG_THREADS, stream, bufs, n_bufs, items, n_items, work, 2, cols, cols_words, status);
   return check_launch("k_prog_columns");
 }
 
@@ -752,6 +759,32 @@ int mprg_prog_band_widths(const int32_t *profile, const int64_t *leaves, int n_l
   return check_launch("k_prog_band_widths");
 }
 
+int mprg_align_profile_pairs_posgap(const int32_t *profile, const int64_t *leaves, int n_leaves, const int32_t *xcols, long long xcols_words,
+                             const int64_t *pairs, int n_pairs, int32_t *workspace, long long workspace_words, uint8_t *ops,
+                             long long ops_bytes, int32_t *out, void *stream) {
+  if (n_pairs <= 0) return 0;
+  LAUNCH(k_align_profile_pairs_posgap, (n_pairs + AL_WAVES - 1) / AL_WAVES, AL_THREADS, stream, profile, leaves, n_leaves, xcols, xcols_words,
+         pairs, n_pairs, workspace, workspace_words, ops, ops_bytes, out);      // a wavefront per pair
+  return check_launch("k_align_profile_pairs_posgap");
+}
+
+int mprg_align_profile_pairs_posgap_banded(const int32_t *profile, const int64_t *leaves, int n_leaves, const int32_t *xcols,
+                                    long long xcols_words, const int64_t *pairs, int n_pairs, int32_t *workspace,
+                                    long long workspace_words, uint8_t *ops, long long ops_bytes, int32_t *out, void *stream) {
+  if (n_pairs <= 0) return 0;
+  LAUNCH(k_align_profile_pairs_posgap_banded, (n_pairs + AL_WAVES - 1) / AL_WAVES, AL_THREADS, stream, profile, leaves, n_leaves, xcols,
+         xcols_words, pairs, n_pairs, workspace, workspace_words, ops, ops_bytes, out);      // a wavefront per pair
+  return check_launch("k_align_profile_pairs_posgap_banded");
+}
+
+int mprg_prog_band_widths_posgap(const int32_t *profile, const int64_t *leaves, int n_leaves, const int32_t *xcols, long long xcols_words,
+                          const int64_t *pairs, int n_pairs, const int32_t *out, int64_t *bounds, int32_t *status, void *stream) {
+  if (n_pairs <= 0) return 0;
+  LAUNCH(k_prog_band_widths_posgap, n_pairs, PG_THREADS, stream, profile, leaves, n_leaves, xcols, xcols_words, pairs, n_pairs, out, bounds,
+         status);      // a workgroup per merge
+  return check_launch("k_prog_band_widths_posgap");
+}
+
 int mprg_prog_rows(const int64_t *bufs, int n_bufs, const uint8_t *ops, long long ops_bytes, const int64_t *rows, int n_rows,
                    uint8_t *out, long long out_bytes, int ascii, int32_t *status, void *stream) {
   if (n_rows <= 0) return 0;
@@ -772,7 +805,16 @@ int mprg_prog_columns_weighted(const int64_t *bufs, int n_bufs, const int64_t *i
                                const int32_t *weights, long long weights_words, int32_t *cols, long long cols_words, int32_t *status,
                                void *stream) {
   if (n_work <= 0) return 0;
-  LAUNCH(k_prog_columns_weighted, n_work, PG_THREADS, stream, bufs, n_bufs, items, n_items, work, weights, weights_words, cols,
+  LAUNCH(k_prog_columns_weighted, n_work, PG_THREADS, stream, bufs, n_bufs, items, n_items, work, 1, weights, weights_words, cols,
+         cols_words, status);
+  return check_launch("k_prog_columns_weighted");
+}
+
+int mprg_prog_columns_weighted_posgap(const int64_t *bufs, int n_bufs, const int64_t *items, int n_items, const int32_t *work, int n_work,
+                                      const int32_t *weights, long long weights_words, int32_t *cols, long long cols_words,
+                                      int32_t *status, void *stream) {
+  if (n_work <= 0) return 0;
+  LAUNCH(k_prog_columns_weighted, n_work, PG_THREADS, stream, bufs, n_bufs, items, n_items, work, 2, weights, weights_words, cols,
          cols_words, status);
   return check_launch("k_prog_columns_weighted");
 }

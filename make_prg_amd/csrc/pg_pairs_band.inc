@@ -1,0 +1,158 @@
+// k_align_profile_pairs_banded (k_prog_band.inc's header) and its form with position-specific opens,
+// k_align_profile_pairs_posgap_banded (star_align.py, "Position gaps"): one text, included twice (DESIGN.md §3a).  The includer
+// provides PG_PAIRS_KERNEL, the kernel's name, and PG_POSGAP: 0 expands to the tokens the kernel had when it stood in
+// k_prog_band.inc; 1 is pg_pairs.inc's: a seventh profile and ring plane, Ox + Ic in a register, Oc[0] on row 0, Ox[0] in column 0.
+#if PG_POSGAP
+#define PG_RING_PLANES 7
+#define PG_OPEN_ROW0 oc0
+#define PG_OPEN_COL0 ox0
+#else
+#define PG_RING_PLANES 6
+#define PG_OPEN_ROW0 AL_OPEN
+#define PG_OPEN_COL0 AL_OPEN
+#endif
+__global__ void __launch_bounds__(AL_THREADS) PG_PAIRS_KERNEL(const int32_t *profile, const int64_t *leaves, int n_leaves,
+                                                                           const int32_t *xcols, long long xcols_words,
+                                                                           const int64_t *pairs, int n_pairs, int32_t *ws,
+                                                                           long long ws_words, uint8_t *ops, long long ops_bytes,
+                                                                           int32_t *out) {
+  SHARED(int32_t, ring_all, AL_WAVES * PG_RING_PLANES * AL_RING);
+  const int lane = wave_lane();
+  const long long p = (long long)BLOCK_ID * AL_WAVES + wave_id();
+  if (p >= n_pairs) return;                                   // (a whole wavefront: nothing below waits for the others)
+  int32_t *ring = ring_all + wave_id() * PG_RING_PLANES * AL_RING;
+  const int64_t *PT = pairs + MPRG_PG_BAND_PAIR_FIELDS * p;
+  const long long leaf = PT[0], xoff = PT[1], n = PT[2], wsoff = PT[3], opoff = PT[4], RX = PT[5];
+  long long blo = PT[6], bhi = PT[7];
+  int32_t *o = out + 3 * p;
+  int status = MPRG_AL_OK;
+  long long C = 0, poff = 0;
+  if (leaf < 0 || leaf >= n_leaves) status = MPRG_AL_BAD_INPUT;
+  else {
+    C = leaves[MPRG_AL_LEAF_FIELDS * leaf + 2];
+    poff = leaves[MPRG_AL_LEAF_FIELDS * leaf + 3];
+    if (C < 1 || n < 0 || leaves[MPRG_AL_LEAF_FIELDS * leaf + 1] < 1 || RX < 1 || RX > PG_MAX_ROWS) status = MPRG_AL_BAD_INPUT;
+    else if (n + C >= AL_MAX_CELLS_SUM) status = MPRG_AL_TOO_LONG;
+    else if (blo > 0 || blo > C - n || bhi < 0 || bhi < C - n) status = MPRG_AL_BAD_INPUT;      // the band must hold both corners
+    else {
+      blo = blo < -n ? -n : blo;
+      bhi = bhi > C ? C : bhi;
+      if (wsoff < 0 || (wsoff & 63) || wsoff + al_band_ws_words(n, C, blo, bhi) > ws_words || opoff < 0 || opoff + n + C > ops_bytes ||
+          xoff < 0 || xoff > xcols_words || 7 * n > xcols_words - xoff)
+        status = MPRG_AL_NO_SPACE;
+    }
+  }
+  if (status != MPRG_AL_OK) {
+    if (lane == 0) { o[0] = status; o[1] = 0; o[2] = 0; }
+    return;
+  }
+  const int32_t *P = profile + al_uniform(poff);
+  const int Ci = (int)al_uniform(C), ni = (int)al_uniform(n), dlo = (int)al_uniform(blo), dhi = (int)al_uniform(bhi);
+  const int W = dhi - dlo + 1;
+  const int32_t *X = xcols + al_uniform(xoff);
+  const PgDiv dv = pg_div_make(al_uniform(RX));
+  const long long wsoff_u = al_uniform(wsoff);
+  int32_t *row = ws + wsoff_u;                               // row[2k] = H, row[2k + 1] = I of the row above the strip (row i0), column i0 + dlo + k
+  uint32_t *tb = (uint32_t *)(ws + wsoff_u + ((2 * (long long)W + 63) / 64) * 64);
+  const long long nst8 = ((W + 63 < Ci ? W + 63 : Ci) + 63 + 7) / 8;
+#if PG_POSGAP
+  const int RXi = (int)al_uniform(RX);
+  const int oc0 = P[(unsigned)(6 * Ci)];                      // what a run that starts at Y's first column pays: row 0
+  const int ox0 = ni > 0 ? pg_div(AL_OPEN * (RXi - X[(unsigned)(5 * ni)]), dv) : 0;   // ... at X's first column: column 0
+#endif
+  // row 0, columns 0 .. dhi: H[0][J] = D[0][J] = open + the gap costs of columns < J
+  int carry = 0;
+  for (int c0 = 0; c0 < dhi; c0 += 64) {
+    const int c = c0 + lane;
+    const int incl = wave_scan_incl(c < dhi ? P[(unsigned)(5 * Ci + c)] : 0) + carry;
+    if (c < dhi) { row[2 * (c + 1 - dlo)] = PG_OPEN_ROW0 + incl; row[2 * (c + 1 - dlo) + 1] = AL_NEG; }
+    carry = __shfl(incl, 63);
+  }
+  if (lane == 0) { row[2 * (-dlo)] = 0; row[2 * (-dlo) + 1] = AL_NEG; }
+  WAVE_SYNC_GLOBAL();
+  int score = AL_NEG;
+  int ic_before = 0;                                         // the Ic of all rows above the strip
+  const int n_strips = (ni + 63) / 64;
+  for (int s = 0; s < n_strips; ++s) {
+    const int i0 = s * 64, r = i0 + lane, rows = ni - i0 < 64 ? ni - i0 : 64;
+    const bool valid = r < ni;
+    // this lane's X column: the counts of A C G T, of the ambiguity codes, of '-', and what the column alone costs
+    // (one base and 32-bit offsets, 7 n < 7 * 10^6: a base per plane would hold seven scalar register pairs through the sweep)
+    const int x0 = valid ? X[(unsigned)r] : 0, x1 = valid ? X[(unsigned)(ni + r)] : 0;
+    const int x2 = valid ? X[(unsigned)(2 * ni + r)] : 0, x3 = valid ? X[(unsigned)(3 * ni + r)] : 0;
+    const int xa = valid ? X[(unsigned)(4 * ni + r)] : 0, xg = valid ? X[(unsigned)(5 * ni + r)] : 0;
+    const int ic = valid ? X[(unsigned)(6 * ni + r)] : 0;
+#if PG_POSGAP
+    const int oxic = pg_div(AL_OPEN * (RXi - xg), dv) + ic;  // opening a run of I ops with this column: Ox + Ic
+#endif
+    const int hb = PG_OPEN_COL0 + wave_scan_incl(ic) + ic_before;  // H[r + 1][0]: open + the Ic of rows 1 .. r + 1
+    const int cs = i0 + dlo > 0 ? i0 + dlo : 0;             // the strip's first column, 0-based
+    const int jtop = i0 + dhi < Ci ? i0 + dhi : Ci;         // the last column of row i0 inside the band
+    const int jend = i0 + rows + dhi < Ci ? i0 + rows + dhi : Ci;   // the strip's last column, 1-based
+    const int d0 = cs - r - dlo;                            // 0-based column c = cs + t - lane of this lane's row (r + 1) lies on diagonal c - r:
+                                                            // inside the band where 0 <= d0 + t - lane <= dhi - dlo (and 0 <= c < C)
+    const bool col0 = r + 1 + dlo <= 0;                     // column 0 of this lane's row lies inside the band
+    int h_left = col0 ? hb : AL_NEG, d_left = AL_NEG;       // H, D of this lane's row, the column to the left of its first one
+    int h_out = col0 && cs == lane ? hb : AL_NEG, i_out = AL_NEG;   // what the lane below reads next step: here of column cs - 1 - lane
+    int h_up_prev = AL_NEG;                                  // H of the row above, one column to the left: the diagonal
+    if (lane == 0) h_up_prev = cs == 0 ? (i0 == 0 ? 0 : PG_OPEN_COL0 + ic_before) : row[0];   // (cs > 0: column cs = i0 + dlo of row i0, its first inside the band)
+    ic_before = __shfl(hb, 63) - PG_OPEN_COL0;
+    uint32_t acc = 0;
+    uint32_t *tbs = tb + (long long)s * nst8 * 64;           // the strip's traceback: wave-uniform bases, 32-bit lane offsets
+    const int T = jend - cs + rows - 1;
+    for (int t = 0; t < T; ++t) {
+      if ((t & 63) == 0) {                                   // the ring takes columns cs + [t, t + 64): the block 128 before is done with
+        WAVE_SYNC();
+#pragma unroll
+        for (int k = 0; k < 6; ++k)
+          ring[k * AL_RING + ((t + lane) & (AL_RING - 1))] = cs + t + lane < Ci ? P[(unsigned)(k * Ci + cs + t + lane)] : 0;
+#if PG_POSGAP
+        ring[6 * AL_RING + ((t + lane) & (AL_RING - 1))] =
+            cs + t + lane < Ci ? P[(unsigned)(6 * Ci + cs + t + lane)] + P[(unsigned)(5 * Ci + cs + t + lane)] : 0;
+#endif
+        WAVE_SYNC();
+      }
+      int h_up = __shfl_up(h_out, 1), i_up = __shfl_up(i_out, 1);
+      if (lane == 0) {
+        const int j = cs + t + 1, k = j - (i0 + dlo);         // (1 <= k; k <= W - 1 where j <= jtop)
+        h_up = j <= jtop ? row[(unsigned)(2 * k)] : AL_NEG;
+        i_up = j <= jtop ? row[(unsigned)(2 * k + 1)] : AL_NEG;
+      }
+      const int h_diag = h_up_prev;
+      h_up_prev = h_up;
+      const int c = cs + t - lane;
+      unsigned cell = 0;
+      if (valid && (unsigned)c < (unsigned)Ci && (unsigned)(d0 + t - lane) < (unsigned)W) {
+        const int slot = (t - lane) & (AL_RING - 1);
+        const int dc = ring[5 * AL_RING + slot];
+        const int num = x0 * ring[slot] + x1 * ring[AL_RING + slot] + x2 * ring[2 * AL_RING + slot] + x3 * ring[3 * AL_RING + slot] +
+                        xa * ring[4 * AL_RING + slot] + xg * dc;
+        const int diag = h_diag + pg_div(num, dv);
+        const int xcost = ic;
+#if PG_POSGAP
+#define AL_OPEN_D ring[6 * AL_RING + slot]
+#define AL_OPEN_I oxic
+#else
+#define AL_OPEN_D AL_OPEN + dc
+#define AL_OPEN_I AL_OPEN + xcost
+#endif
+#include "al_cell.inc"
+#undef AL_OPEN_D
+#undef AL_OPEN_I
+        if (lane == 63 && s + 1 < n_strips) { const int k = c + 1 - (i0 + 64 + dlo); row[(unsigned)(2 * k)] = h; row[(unsigned)(2 * k + 1)] = ii; }
+      } else {
+        h_out = c == -1 && col0 ? hb : AL_NEG;               // outside the band: minus infinity, never a stale or an accumulated value
+        i_out = AL_NEG;
+      }
+      acc |= cell << (4 * (t & 7));
+      if ((t & 7) == 7 || t == T - 1) { tbs[(unsigned)((t >> 3) * 64 + lane)] = acc; acc = 0; }
+    }
+    WAVE_SYNC_GLOBAL();                                      // the row buffer and the traceback, written by every lane, read by lane 0
+  }
+  score = ni > 0 ? __shfl(score, (ni - 1) & 63) : row[2 * (Ci - dlo)];
+  constexpr bool kBand = true;
+#include "al_walk.inc"
+}
+#undef PG_RING_PLANES
+#undef PG_OPEN_ROW0
+#undef PG_OPEN_COL0

@@ -35,6 +35,10 @@ With `--pair-distances` (and `--progressive`) the first guide tree is built from
 leaves instead of from 6-mer counts (Pair distances below; kernels: csrc/k_align_scores.inc, C ABI: mprg_align_pair_scores /
 mprg_align_pair_scores_banded).
 
+With `--position-gaps` (and `--progressive`) a merge charges the opening of a gap run by the occupancy of the column the run starts
+at instead of -704 whatever the column (Position gaps below; kernels: csrc/pg_pairs.inc, csrc/pg_pairs_band.inc,
+csrc/pg_band_widths.inc, C ABI: the _posgap entries).
+
 It is NOT MAFFT.  PRGs built from these alignments differ from PRGs built from a MAFFT alignment of the same sequences.
 
 Spec (the kernels and tests/star_ref.py follow it bit for bit)
@@ -378,6 +382,49 @@ leaves (ClustalW's pairwise mode, MAFFT's --globalpair).
             (8 bytes a record).  A locus's pair scores are computed once per run: on the host's tree with seq_weights the tables
             _prog_shared downloaded are kept and uploaded for the weights launch (_PairTables).
 
+Position gaps (only with progressive and position_gaps; integers only; tests/posgap_ref.py states it in plain Python; kernels:
+csrc/pg_pairs.inc, csrc/pg_pairs_band.inc, csrc/pg_band_widths.inc, C ABI: mprg_prog_columns_posgap /
+mprg_prog_columns_weighted_posgap / mprg_align_profile_pairs_posgap / mprg_align_profile_pairs_posgap_banded /
+mprg_prog_band_widths_posgap).  Progressive's merge scales what a skipped column costs to EXTEND a run by the column's occupancy (Dc,
+Ic) but charges -704 to OPEN one, whatever the column: skipping a Y column in which 1 row of 50 has a residue costs -12 to extend and
+-704 to open, as if all 50 rows had a residue there.  So the DP pushes X's residues into an existing insertion column and closes up
+independent insertions.  Here the open of a run is scaled by the occupancy of the column it starts at, as ClustalW, MUSCLE and
+MAFFT scale a profile position's gap open.
+  Opens.    With Progressive's notation (Y: R_Y rows, g^Y_j gaps in column j; X: R_X rows, g_i gaps in column i; C's truncating
+            division; with weights R is the weight sum and g is weighted):
+                Oc[j] = (64 * -11 * (R_Y - g^Y_j)) / R_Y    opening a run of D ops whose FIRST skipped Y column is j    (-704 .. 0)
+                Ox[i] = (64 * -11 * (R_X - g_i)) / R_X      opening a run of I ops whose FIRST lone X column is i       (-704 .. 0)
+                D[i][j] = max(D[i][j-1] + Dc[j-1],  H[i][j-1] + Oc[j-1] + Dc[j-1])
+                I[i][j] = max(I[i-1][j] + Ic[i-1],  H[i-1][j] + Ox[i-1] + Ic[i-1])
+                H[i][j] = max(H[i-1][j-1] + s(i-1, j-1), D[i][j], I[i][j])
+                H[0][J] = Oc[0] + sum_{j<J} Dc[j],  H[i][0] = Ox[0] + sum_{k<i} Ic[k]
+  Everything else is Progressive's merge, unchanged: s(i, j), Dc, Ic, the int32 arithmetic, the tie order (diagonal, then D, then
+            I; extend before open), the 4-bit traceback cell, the walk back from (n, C), the refusal at n + C >= 10^6, the ops and
+            the status contract.  |64 * -11 * (R_X - g_i)| <= 704 R_X lies inside pg_div's proven range of 1 280 R_X.
+  Which merges.  Every profile-profile merge of a locus: those of Progressive, of a rebuild of Retree and of a step of Tree
+            refinement (all go through _prog_pairs).
+  Nothing else changes: the distances and the tree, which child is Y, the row order, the objective S, refine (which runs afterwards
+            unweighted and with the fixed open), the star pass, adjust_direction, pair_distances (its pair DPs keep the fixed open)
+            and `update --aligner builtin`.  The flag promises these opens, not a higher S.
+  Two facts (tested): when neither side has a '-' cell, Oc = Ox = -704 everywhere, so ops and score are
+            mprg_align_profile_pairs' exactly; in particular every leaf-leaf merge is unchanged.  A profile over weighted rows
+            equals the profile of the rows written that often, for Oc and Ox as well.
+  Band.     With band the same bytes.  "Progressive, band" holds with oy = max_j Oc[j] and ox = max_i Ox[i] (both <= 0; ox = 0 when
+            n = 0) in place of the two -704: a path that leaves the band touches d* > max(0, Delta) or d* < min(0, Delta), so it
+            has at least one D op and at least one I op (on the plus side d* D ops and d* - Delta >= 1 I ops, on the minus side
+            Delta - d* >= 1 D ops and -d* I ops), hence at least one maximal run of each kind.  The run of D ops starts at some
+            column j and pays Oc[j] <= oy, the run of I ops at some column i and pays Ox[i] <= ox; further runs pay <= 0.  The
+            rest of the count is unchanged (a matched or skipped Y column contributes at most B_j or Dc[j], a lone X column
+            Ic[i]; the opens are extra terms, never part of B_j), so
+                U(w) = SB - LY(max(0, Delta) + w + 1) - LX(w + 1 - min(0, Delta)) + oy + ox,
+            which does not rise with w (oy and ox do not depend on w).  With all-ACGT one-row sides oy = ox = -704: the old U.
+            The closed-sides induction of profile_align.py is untouched: it uses only that no path outside the band beats S0.  The
+            bound is weaker by up to 1 408 per merge, so more merges take a second pass; the counts are in DESIGN.md §3b.
+  Host side: _prog_pairs writes Y's items as kind 2 (7 planes: mprg_prog_columns_posgap, with weights
+            mprg_prog_columns_weighted_posgap), sizes the column tables by 7 W_Y + 7 W_X, and calls the _posgap entries in pass 1,
+            for the widths, in pass 2 and for the full form; nothing else in the launches changes.  timings receives
+            position_gap_merges.
+
 Progressive, host side: per chunk the distances in launches whose m x m tables fit budget_bytes (loci of three or more leaves), D
 and the tree per locus in NumPy / Python integers (prog_tree: a float64 quotient only shortlists, the choice is exact).  A node's
 round is 1 + the larger of its children's rounds.  With device_tree the tree is built on the device instead (csrc/k_prog_tree.inc):
@@ -542,7 +589,7 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
               tree_refinement: Optional[list] = None, tree_refine_max_leaves: int = TREE_REFINE_MAX_LEAVES, large_loci: bool = False,
               max_records: Optional[int] = None, retree: Optional[int] = None, retreeing: Optional[list] = None,
               seq_weights: bool = False, pair_distances: bool = False, pair_distancing: Optional[list] = None,
-              pair_dist_max_leaves: int = PAIR_DIST_MAX_LEAVES) -> List[MSA]:
+              pair_dist_max_leaves: int = PAIR_DIST_MAX_LEAVES, position_gaps: bool = False) -> List[MSA]:
     """loci: per locus its records as (title, sequence).  Returns the loci's centre-star MSAs (ids: the titles' first words,
     descriptions: the titles).  names: the loci's names for error messages (default: their indices).  timings: a dict that
     receives the wall seconds of the stages (orient, centre, pairs, merge: each ends at a download, so includes its kernels).
@@ -597,13 +644,19 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
     for fewer than 3 leaves), None for a locus left to the star pass.  timings also receives pair_dist_s (part of tree_s, and with
     seq_weights on the host's tree of its second lap), pair_dist_loci, pair_dist_pairs, pair_dist_cells, pair_dist_above_cap,
     pair_dist_limit, and with band pair_dist_second_passes and pair_dist_full_pairs.  False: nothing launches, uploads or
-    downloads differently."""
+    downloads differently.
+    position_gaps: only with progressive (else a ValueError): the spec's Position gaps: every profile-profile merge of a locus (of
+    Progressive, of a rebuild of retree, of a step of refine_tree) opens its runs by the occupancy of the column they start at.
+    timings also receives position_gap_merges (the merges made with them).  False: nothing launches, uploads or downloads
+    differently."""
     if device_tree and not progressive:
         raise ValueError("device_tree: only with progressive")
     if seq_weights and not progressive:
         raise ValueError("seq_weights: only with progressive")
     if pair_distances and not progressive:
         raise ValueError("pair_distances: only with progressive")
+    if position_gaps and not progressive:
+        raise ValueError("position_gaps: only with progressive")
     if large_loci and not (progressive and collapse):
         raise ValueError("large_loci: only with progressive and collapse")
     if max_records is not None and not (large_loci and 0 <= int(max_records) <= PROG_MAX_RECORDS):
@@ -632,7 +685,8 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
                                  int(refine), refinement, progression, PROG_MAX_LEAVES if max_leaves is None else int(max_leaves), bool(collapse),
                                  bool(device_tree), int(refine_tree or 0), tree_refinement, int(tree_refine_max_leaves),
                                  (PROG_MAX_RECORDS if max_records is None else int(max_records)) if large_loci else None, int(retree or 0),
-                                 retreeing, bool(seq_weights), int(pair_dist_max_leaves) if pair_distances else None, pair_distancing)
+                                 retreeing, bool(seq_weights), int(pair_dist_max_leaves) if pair_distances else None, pair_distancing,
+                                 bool(position_gaps))
     return [m for lo, hi in _chunks(codes, chunk_bytes)
             for m in _star_chunk(backend, loci[lo:hi], codes[lo:hi], names[lo:hi], budget_bytes, timings, adjust_direction, orientation, band,
                                  int(refine), refinement, collapse=bool(collapse))]
@@ -641,7 +695,7 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
 def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings, adjust_direction, orientation, band, refine, refinement,
                       progression, max_leaves, collapse=False, device_tree=False, refine_tree=0, tree_refinement=None,
                       tree_max_leaves=TREE_REFINE_MAX_LEAVES, max_records=None, retree=0, retreeing=None, seq_weights=False,
-                      pair_dist=None, pair_distancing=None) -> List[MSA]:
+                      pair_dist=None, pair_distancing=None, position_gaps=False) -> List[MSA]:
     """star_msas with progressive: the loci within the leaf limit through the progressive chunks, the others through the star
     chunks, the results (and what the caller's lists receive) back in the loci's order.  max_records (the spec's Large loci; None:
     without it): only the loci of more records go to the star chunks here; the progressive chunks count every locus's classes
@@ -661,7 +715,7 @@ def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings
                                     prog, pro, collapse, device_tree and prog, refine_tree if prog else 0,
                                     tre if tree_refinement is not None else None, tree_max_leaves, limits if prog else None,
                                     retree if prog else 0, ret if retreeing is not None else None, seq_weights and prog,
-                                    pair_dist if prog else None, pdi if pair_distancing is not None else None))
+                                    pair_dist if prog else None, pdi if pair_distancing is not None else None, position_gaps and prog))
         if not prog:
             pro = [(n_leaves[l], 0, True) for l in sel]
         for k, l in enumerate(sel):
@@ -685,7 +739,7 @@ def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings
 def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direction=False, orientation=None, band=None, refine=0,
                 refinement=None, progressive=False, progression=None, collapse=False, device_tree=False, refine_tree=0,
                 tree_refinement=None, tree_max_leaves=TREE_REFINE_MAX_LEAVES, limits=None, retree=0, retreeing=None, seq_weights=False,
-                pair_dist=None, pair_distancing=None) -> List[MSA]:
+                pair_dist=None, pair_distancing=None, position_gaps=False) -> List[MSA]:
     """One chunk: pack, optionally orient, optionally collapse, the star pass or the progressive one (with its tree refinement),
     optionally refine, collect.  limits (the spec's Large loci; only with progressive and collapse): (max_leaves, max_records): the
     loci with more classes of non-empty records, or more records, go through the star pass."""
@@ -702,14 +756,16 @@ def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direc
         build = (n_classes <= limits[0]) & (chunk.counts <= limits[1])
         if not build.all():
             return _star_chunk_parts(be, chunk, classes, build, budget_bytes, laps, band, refine, refinement, progression, device_tree,
-                                     refine_tree, tree_refinement, tree_max_leaves, retree, retreeing, seq_weights, pair_dist, pair_distancing)
+                                     refine_tree, tree_refinement, tree_max_leaves, retree, retreeing, seq_weights, pair_dist, pair_distancing,
+                                     position_gaps)
     return _star_chunk_rest(be, chunk, classes, budget_bytes, laps, band, refine, refinement, progressive, progression, device_tree,
-                            refine_tree, tree_refinement, tree_max_leaves, retree, retreeing, seq_weights, pair_dist, pair_distancing)
+                            refine_tree, tree_refinement, tree_max_leaves, retree, retreeing, seq_weights, pair_dist, pair_distancing,
+                            position_gaps)
 
 
 def _star_chunk_parts(be, chunk: Chunk, classes, build, budget_bytes, laps, band, refine, refinement, progression, device_tree,
                       refine_tree, tree_refinement, tree_max_leaves, retree=0, retreeing=None, seq_weights=False, pair_dist=None,
-                      pair_distancing=None) -> List[MSA]:
+                      pair_distancing=None, position_gaps=False) -> List[MSA]:
     """_star_chunk behind Collapse for a chunk of which only the loci `build` (a bool per locus) are built progressively (the spec's
     Large loci): those as one chunk through the progressive pass, the others as one through the star pass, both over the same code
     buffer and the classes already made; the MSAs, and what the caller's lists receive, back in the chunk's order."""
@@ -727,7 +783,7 @@ def _star_chunk_parts(be, chunk: Chunk, classes, build, budget_bytes, laps, band
         got = [[], [], [], [], []]
         out = _star_chunk_rest(be, part, Classes(at[classes.rep[rec]], classes.weight[rec]), budget_bytes, laps, band, refine, got[0], prog,
                                got[1], device_tree and prog, refine_tree if prog else 0, got[2], tree_max_leaves, retree if prog else 0, got[3],
-                               seq_weights and prog, pair_dist if prog else None, got[4])
+                               seq_weights and prog, pair_dist if prog else None, got[4], position_gaps and prog)
         if not prog:
             got[1] = [(int(n_filled[l]), 0, True) for l in sel]
         for k, l in enumerate(sel.tolist()):
@@ -744,11 +800,11 @@ def _star_chunk_parts(be, chunk: Chunk, classes, build, budget_bytes, laps, band
 
 def _star_chunk_rest(be, chunk: Chunk, classes, budget_bytes, laps, band, refine, refinement, progressive, progression, device_tree,
                      refine_tree, tree_refinement, tree_max_leaves, retree=0, retreeing=None, seq_weights=False, pair_dist=None,
-                     pair_distancing=None) -> List[MSA]:
+                     pair_distancing=None, position_gaps=False) -> List[MSA]:
     """_star_chunk behind Collapse: the star pass or the progressive one (with its tree refinement), optionally refine, collect."""
     timings = laps.timings
     text = (_progressive(be, chunk, budget_bytes, band, laps, progression, classes, device_tree, refine_tree, tree_refinement,
-                         tree_max_leaves, retree, retreeing, seq_weights, pair_dist, pair_distancing) if progressive else
+                         tree_max_leaves, retree, retreeing, seq_weights, pair_dist, pair_distancing, position_gaps) if progressive else
             _star_pass(be, chunk, budget_bytes, band, laps, classes))
     moved = {}
     if refine:
@@ -1521,50 +1577,52 @@ def _prog_w0(band):
     return w0
 
 
-def _prog_groups(WX, WY, budget_bytes, band=None):
+def _prog_groups(WX, WY, budget_bytes, band=None, position_gaps=False):
     """The merges (X's and Y's columns) longest first in groups whose workspace and column tables each fit the budget; with band
-    the workspace is pass 1's (the full DP's for a merge its band does not help)."""
+    the workspace is pass 1's (the full DP's for a merge its band does not help).  position_gaps: Y's profile has 7 planes."""
     order = np.argsort(-((WX + 1) * WY), kind="stable")
     need, w0 = pa.workspace_words_v(WX, WY), _prog_w0(band)
     if w0 is not None:
         dlo, dhi, helps = pa.band_first(WX, WY, w0)
         need = np.where(helps, pa.band_workspace_words(WX, WY, dlo, dhi), need)
-    for grp, _, _ in pa.budget_launches(order, need, budget_bytes, StarAlignError, "merge", WX, WY, also=7 * WX + 6 * WY):
+    for grp, _, _ in pa.budget_launches(order, need, budget_bytes, StarAlignError, "merge", WX, WY, also=7 * WX + (7 if position_gaps else 6) * WY):
         yield grp
 
 
-def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUDGET_BYTES, counters=None, weights=None):
+def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUDGET_BYTES, counters=None, weights=None, position_gaps=False):
     """One group of merges on the device: X, Y (n, 4) int64 {buffer, offset, R, W} of the two sides' texts.  mprg_prog_columns (Y's
     profiles, X's column tables) and mprg_align_profile_pairs in one launch each; {status, score, op count} downloaded.  With band
     the spec's two passes instead (the module docstring, host side), counters receiving the prog_band_* counts.
     weights: (per merge the weights of X's rows, of Y's rows), the spec's Collapse: the column tables through
     mprg_prog_columns_weighted and R_X the weight sum; everything else is the same.
+    position_gaps (the spec's Position gaps): Y's profile gets its seventh plane (kind 2) and every call its _posgap form.
     Returns (the ops buffer, its bytes, each merge's ops offset, op count, score)."""
     n = len(X)
     WX, WY = X[:, 3], Y[:, 3]
     k = np.nonzero(WX + WY >= pa.MAX_LEN)[0]
     if len(k):
         raise StarAlignError(f"a merge of {WX[k[0]]} columns against {WY[k[0]]}: their sum must stay below {pa.MAX_LEN}")
-    ycol = exclusive_sum(6 * WY + 7 * WX)
-    xcol = ycol + 6 * WY
-    words = int((6 * WY + 7 * WX).sum())
+    posgap, PY = ("_posgap", 7) if position_gaps else ("", 6)    # the calls' suffix, the planes of Y's profile
+    ycol = exclusive_sum(PY * WY + 7 * WX)
+    xcol = ycol + PY * WY
+    words = int((PY * WY + 7 * WX).sum())
     items = np.zeros((2 * n, PG_ITEM_FIELDS if weights is None else PG_WITEM_FIELDS), np.int64)
-    items[:n, :4], items[:n, 4], items[:n, 5] = Y, 0, ycol
+    items[:n, :4], items[:n, 4], items[:n, 5] = Y, 2 if position_gaps else 0, ycol
     items[n:, :4], items[n:, 4], items[n:, 5] = X, 1, xcol
     work = _tile_work(items[:, 3])
-    RX, columns = X[:, 2], "mprg_prog_columns"
+    RX, columns = X[:, 2], "mprg_prog_columns" + posgap
     if weights is not None:
         per_item = list(weights[1]) + list(weights[0])          # Y's items, then X's
         flat = np.concatenate(per_item).astype(np.int32)
         items[:, 6], items[:, 7] = exclusive_sum(items[:, 2]), [int(w.sum()) for w in per_item]
-        RX, columns = items[n:, 7], "mprg_prog_columns_weighted"
+        RX, columns = items[n:, 7], "mprg_prog_columns_weighted" + posgap
     d_items, d_work, d_cols, d_status = be.upload(items), be.upload(work), be.empty(4 * words), be.empty(4 * len(work))
     if weights is None:
-        be.call("mprg_prog_columns", be.ptr(d_bufs), n_bufs, be.ptr(d_items), len(items), be.ptr(d_work), len(work), be.ptr(d_cols), words,
+        be.call("mprg_prog_columns" + posgap, be.ptr(d_bufs), n_bufs, be.ptr(d_items), len(items), be.ptr(d_work), len(work), be.ptr(d_cols), words,
                 be.ptr(d_status), be.stream, work=float((items[:, 2] * items[:, 3]).sum()))
     else:
         d_weights = be.upload(flat)
-        be.call("mprg_prog_columns_weighted", be.ptr(d_bufs), n_bufs, be.ptr(d_items), len(items), be.ptr(d_work), len(work), be.ptr(d_weights),
+        be.call("mprg_prog_columns_weighted" + posgap, be.ptr(d_bufs), n_bufs, be.ptr(d_items), len(items), be.ptr(d_work), len(work), be.ptr(d_weights),
                 len(flat), be.ptr(d_cols), words, be.ptr(d_status), be.stream, work=float((items[:, 2] * items[:, 3]).sum()))
     need = pa.workspace_words_v(WX, WY)
     ops_off = exclusive_sum(WX + WY)
@@ -1573,6 +1631,7 @@ def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUD
     d_leaves = be.upload(leaf_tab)
     d_ops = be.empty(ops_bytes)
     w0 = _prog_w0(band)
+    full, banded = "mprg_align_profile_pairs" + posgap, "mprg_align_profile_pairs" + posgap + "_banded"
     pending = []                                                # (merges, call, the launch's triples, its table): downloaded at the end
 
     def launches(call, idx, wordsv, dlo=None, dhi=None):
@@ -1588,10 +1647,10 @@ def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUD
     def pass1(first, dlo, dhi):
         # one launch where the group was sized by its need; the widths over the same table and its triples
         wstar = np.zeros(n, np.int64)
-        launches("mprg_align_profile_pairs_banded", first, pa.band_workspace_words(WX, WY, dlo, dhi), dlo, dhi)
+        launches(banded, first, pa.band_workspace_words(WX, WY, dlo, dhi), dlo, dhi)
         for sel, _, d_out, d_pairs in list(pending):
             d_got = be.empty(20 * len(sel))                     # {SB, w*} per merge, then the status words
-            be.call("mprg_prog_band_widths", be.ptr(d_cols), be.ptr(d_leaves), n, be.ptr(d_cols), words, be.ptr(d_pairs), len(sel),
+            be.call("mprg_prog_band_widths" + posgap, be.ptr(d_cols), be.ptr(d_leaves), n, be.ptr(d_cols), words, be.ptr(d_pairs), len(sel),
                     be.ptr(d_out), be.ptr(d_got), be.ptr(d_got) + 16 * len(sel), be.stream, work=float((WX[sel] + WY[sel]).sum()))
             got = be.download(d_got, np.uint8, 20 * len(sel))
             status = got[16 * len(sel):].view(np.int32)
@@ -1599,15 +1658,15 @@ def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUD
                 _check(be.download(d_status, np.int32, len(work)), columns, PG_STATUS)
                 res = be.download(d_out, np.int32, 3 * len(sel)).reshape(-1, 3)
                 code = int(res[res[:, 0] != 0][0, 0]) if res[:, 0].any() else int(status[status != 0][0])
-                raise StarAlignError(f"mprg_align_profile_pairs_banded / mprg_prog_band_widths: {pa.STATUS.get(code, code)}")
+                raise StarAlignError(f"{banded} / mprg_prog_band_widths{posgap}: {pa.STATUS.get(code, code)}")
             wstar[sel] = got[:16 * len(sel)].view(np.int64).reshape(-1, 2)[:, 1]
         return wstar, wstar
     if w0 is None:                                              # (one launch: _prog_groups sized the group by this need)
-        launches("mprg_align_profile_pairs", np.arange(n), need)
+        launches(full, np.arange(n), need)
     else:
         second, rest, dlo, dhi, counts = pa.band_plan(WX, WY, w0, pass1)
-        launches("mprg_align_profile_pairs_banded", second, pa.band_workspace_words(WX, WY, dlo, dhi), dlo, dhi)
-        launches("mprg_align_profile_pairs", rest, need)
+        launches(banded, second, pa.band_workspace_words(WX, WY, dlo, dhi), dlo, dhi)
+        launches(full, rest, need)
     _check(be.download(d_status, np.int32, len(work)), columns, PG_STATUS)
     count, score = np.zeros(n, np.int64), np.zeros(n, np.int64)
     for sel, call, d_out, _ in pending:                          # in launch order: a later pass's result replaces pass 1's
@@ -1616,6 +1675,8 @@ def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUD
         if len(bad):
             raise StarAlignError(f"{call}: {pa.STATUS.get(int(res[bad[0], 0]), int(res[bad[0], 0]))}")
         score[sel], count[sel] = res[:, 1], res[:, 2]
+    if position_gaps:
+        add_to(counters, "position_gap_merges", n)
     for key, v in zip(("prog_band_merges", "prog_band_second_passes", "prog_band_full_merges", "prog_band_cells", "prog_band_full_cells"),
                       () if w0 is None else counts):
         add_to(counters, key, int(v))
@@ -1628,10 +1689,11 @@ def _bufs_table(be, bufs):
 
 
 def merge_profiles(backend, pairs: Sequence[Tuple[np.ndarray, np.ndarray]], budget_bytes: int = pa.DEFAULT_BUDGET_BYTES, band=None,
-                   counters: Optional[dict] = None):
+                   counters: Optional[dict] = None, position_gaps: bool = False):
     """mprg_align_profile_pairs on (X, Y) pairs of cell-code matrices (R_X x W_X, R_Y x W_Y), through the launches a round of
     merges makes: per pair (ops as bytes over b"MID" in forward order, score).  band (True: PROG_BAND_W0, or pass 1's half-width):
-    the spec's banded two passes, the same results; counters then receives the prog_band_* counts (added up)."""
+    the spec's banded two passes, the same results; counters then receives the prog_band_* counts (added up).  position_gaps:
+    the spec's Position gaps (mprg_align_profile_pairs_posgap and the other _posgap entries)."""
     be = backend
     mats = [m for xy in pairs for m in xy]
     off = np.concatenate([[0], np.cumsum([m.size for m in mats])]).astype(np.int64)
@@ -1641,8 +1703,9 @@ def merge_profiles(backend, pairs: Sequence[Tuple[np.ndarray, np.ndarray]], budg
     X = np.array([[0, off[2 * k], *pairs[k][0].shape] for k in range(len(pairs))], np.int64).reshape(-1, 4)
     Y = np.array([[0, off[2 * k + 1], *pairs[k][1].shape] for k in range(len(pairs))], np.int64).reshape(-1, 4)
     out = [None] * len(pairs)
-    for grp in _prog_groups(X[:, 3], Y[:, 3], budget_bytes, band):
-        d_ops, ops_bytes, ops_off, count, score = _prog_pairs(be, d_bufs, 1, X[grp], Y[grp], band, budget_bytes, counters)
+    for grp in _prog_groups(X[:, 3], Y[:, 3], budget_bytes, band, position_gaps):
+        d_ops, ops_bytes, ops_off, count, score = _prog_pairs(be, d_bufs, 1, X[grp], Y[grp], band, budget_bytes, counters,
+                                                              position_gaps=position_gaps)
         ops = be.download(d_ops, np.uint8, ops_bytes)
         for i, k in enumerate(grp.tolist()):
             out[k] = (ops[ops_off[i]:ops_off[i] + count[i]][::-1].tobytes(), int(score[i]))
@@ -1681,7 +1744,7 @@ def _seq_weight_counters(counters, n_loci, q, spent):
 
 def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression, classes: Optional[Classes] = None, device_tree=False,
                  refine_tree=0, tree_refinement=None, max_leaves=None, retree=0, retreeing=None, seq_weights=False, pair_dist=None,
-                 pair_distancing=None):
+                 pair_distancing=None, position_gaps=False):
     """The spec's Progressive over one chunk, on the (oriented) sequences in chunk.d_codes.  Returns what the star pass leaves: the
     device buffer of the MSAs' ASCII text, its bytes, each locus's offset in it and its width.  classes: the spec's Collapse: the
     tree and the merges over the representatives with their weights, the root's rows written for every member.  device_tree: the
@@ -1690,7 +1753,8 @@ def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression,
     rebuilds of the spec's Retree, in front of that (0: none); retreeing receives its tuples, progression then the tuples of the
     trees that built the texts that are written.  seq_weights: the spec's Sequence weights: q per leaf from the trees, after the
     plan, as the rows' weights in every merge.  pair_dist: the spec's Pair distances: its leaf cap (None: without it);
-    pair_distancing receives its tuples."""
+    pair_distancing receives its tuples.  position_gaps: the spec's Position gaps, in every merge of the three stages below (the
+    pair DPs of pair_dist keep the fixed open)."""
     laps.lap()
     lens, first, counts = chunk.lens, chunk.first, chunk.counts
     acgt = _acgt(chunk) if pair_dist is not None else None
@@ -1751,10 +1815,11 @@ def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression,
         laps.lap("tree_s")
     if pair_dist is not None:
         _pair_dist_report(laps.timings, pair_distancing, how, n_leaves, pair_tables.spent, band)
-    bufs, live, where = _prog_rounds(be, chunk, plan, budget_bytes, band, laps.timings, weights, align=align)
+    bufs, live, where = _prog_rounds(be, chunk, plan, budget_bytes, band, laps.timings, weights, align=align, position_gaps=position_gaps)
     laps.lap("progressive_s")
     if retree:
-        plan, result = _retree(be, chunk, plan, bufs, live, where, weights, retree, budget_bytes, band, device_tree, laps.timings, align)
+        plan, result = _retree(be, chunk, plan, bufs, live, where, weights, retree, budget_bytes, band, device_tree, laps.timings, align,
+                               position_gaps)
         if retreeing is not None:
             retreeing.extend(result)
         laps.lap("retree_s")
@@ -1763,7 +1828,7 @@ def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression,
     order = plan[3]
     if refine_tree:
         order, result = _tree_refine(be, chunk, plan, bufs, live, where, weights, refine_tree, max_leaves, budget_bytes, band, laps.timings,
-                                     align)
+                                     align, position_gaps)
         if tree_refinement is not None:
             tree_refinement.extend(result)
         laps.lap("tree_refine_s")
@@ -1796,7 +1861,7 @@ def _prog_parents(be, d_bufs, n_bufs, Xg, Yg, d_ops, ops_bytes, ops_off, count):
     return d_new, new_bytes, poff, R
 
 
-def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters, weights=None, beyond=None, align=None):
+def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters, weights=None, beyond=None, align=None, position_gaps=False):
     """_progressive's device part: the plan's rounds (every node of a round, over all loci of the chunk, in one set of launches
     per budget group).  Returns (bufs, live, where) as the last round left them: of every locus only its root is in where.
     The texts' lifetime: bufs[b] is (buffer, bytes) of text buffer b, 0 the chunk's code buffer (the leaves); where[locus, node]
@@ -1807,7 +1872,8 @@ def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters, weights=N
     beyond (the spec's Retree): a set that receives the loci with a merge beyond Tree refinement's Limit (_tree_step_fits) instead
     of an error: such a locus takes no further merge and none of its nodes stays in where.
     align (the spec's Sequence weights): per record of the chunk's tables the weight q its row has in a merge, in place of the
-    multiplicities, which keep their role in the plan."""
+    multiplicities, which keep their role in the plan.
+    position_gaps (the spec's Position gaps): every merge through _prog_pairs' _posgap calls."""
     lens, seq_off, first, n_loci = chunk.lens, chunk.seq_off, chunk.first, chunk.n_loci
     leaves, by_round = plan[:2]
     bufs, live = [(chunk.d_codes, chunk.codes_bytes)], [0]
@@ -1835,7 +1901,7 @@ def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters, weights=N
                 continue
         Y = np.array([where[l, y] for l, y, _, _ in todo], np.int64)
         X = np.array([where[l, x] for l, _, x, _ in todo], np.int64)
-        for grp in _prog_groups(X[:, 3], Y[:, 3], budget_bytes, band):
+        for grp in _prog_groups(X[:, 3], Y[:, 3], budget_bytes, band, position_gaps):
             d_bufs = _bufs_table(be, bufs)
             Xg, Yg = X[grp], Y[grp]
             wg = None
@@ -1843,7 +1909,7 @@ def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters, weights=N
                 wg = ([rw[todo[k][0], todo[k][2]] for k in grp.tolist()], [rw[todo[k][0], todo[k][1]] for k in grp.tolist()])
             if weights is not None:
                 add_to(counters, "collapse_merges", len(grp))
-            d_ops, ops_bytes, ops_off, count, _ = _prog_pairs(be, d_bufs, len(bufs), Xg, Yg, band, budget_bytes, counters, wg)
+            d_ops, ops_bytes, ops_off, count, _ = _prog_pairs(be, d_bufs, len(bufs), Xg, Yg, band, budget_bytes, counters, wg, position_gaps)
             d_new, new_bytes, poff, R = _prog_parents(be, d_bufs, len(bufs), Xg, Yg, d_ops, ops_bytes, ops_off, count)
             bufs.append((d_new, new_bytes))
             live.append(len(grp))
@@ -1982,14 +2048,15 @@ def _retree_trees(be, chunk: Chunk, sel, texts, order, bufs, weights, budget_byt
     return out
 
 
-def _retree(be, chunk: Chunk, plan, bufs, live, where, weights, rebuilds, budget_bytes, band, device_tree, counters, align=None):
+def _retree(be, chunk: Chunk, plan, bufs, live, where, weights, rebuilds, budget_bytes, band, device_tree, counters, align=None,
+            position_gaps=False):
     """The spec's Retree over one chunk, on the roots' texts as _prog_rounds left them (bufs, live, where: its state, kept up here
     as _tree_refine keeps it up).  Per iteration all loci that are still iterating go together: the identities and the trees
     (_retree_trees), _prog_plan and _prog_rounds for the loci whose tree changed, from the leaves, into buffers of their own, one
     objective launch, S downloaded; the text that loses goes with its buffer.  Returns (the plan with the accepted trees, their
     row orders and progression tuples in place of the first ones, per locus (iterations, accepted, why it stopped, S before, S
     after)).  align (the spec's Sequence weights): per record its q; a rebuild runs with the q of the rebuilt tree on D', and an
-    accepted locus's entries of align are replaced by them, in place."""
+    accepted locus's entries of align are replaced by them, in place.  position_gaps: _prog_rounds'."""
     lens, first, counts, n_loci = chunk.lens, chunk.first, chunk.counts, chunk.n_loci
     leaves, root = plan[0], plan[2]
     order, trees, progression = [np.array(x, np.int64) for x in plan[3]], list(plan[4]), list(plan[5])
@@ -2031,7 +2098,7 @@ def _retree(be, chunk: Chunk, plan, bufs, live, where, weights, rebuilds, budget
         part = chunk._replace(first=first[todo], counts=counts[todo])
         plan2 = _prog_plan(lens, part.first, part.counts, None, weights, [merges[l] for l in todo])
         beyond = set()
-        bufs2, live2, where2 = _prog_rounds(be, part, plan2, budget_bytes, band, counters, weights, beyond, align2)
+        bufs2, live2, where2 = _prog_rounds(be, part, plan2, budget_bytes, band, counters, weights, beyond, align2, position_gaps)
         made, new = {}, {}
         for k, l in enumerate(todo):
             if k in beyond:
@@ -2122,14 +2189,15 @@ def _tree_step_fits(WX, WY, budget_words):
     return (WX + WY < pa.MAX_LEN) & (pa.workspace_words_v(WX, WY) <= budget_words)
 
 
-def _tree_refine(be, chunk: Chunk, plan, bufs, live, where, weights, passes, max_leaves, budget_bytes, band, counters, align=None):
+def _tree_refine(be, chunk: Chunk, plan, bufs, live, where, weights, passes, max_leaves, budget_bytes, band, counters, align=None,
+                 position_gaps=False):
     """The spec's Tree refinement over one chunk, on the roots' texts as _prog_rounds left them (bufs, live, where: its state, kept
     up here: where[locus, root] names the locus's current text, a buffer is dropped when nothing points to it; weights: per
     record of the chunk's tables, the spec's Collapse).  Step s of every locus that still has one goes together: one split launch,
     the widths downloaded, the merges in _prog_groups' groups through _prog_pairs and _prog_parents, one objective launch, S
     downloaded.  Returns (per locus the records of its text's rows in row order, per locus (steps tried, accepted, skipped, S
     before, S after)).  align (the spec's Sequence weights): per record the q its row has in a realignment, in place of the
-    multiplicities, which keep the choice of Y and the objective."""
+    multiplicities, which keep the choice of Y and the objective.  position_gaps: _prog_pairs'."""
     first, counts, n_loci = chunk.first, chunk.counts, chunk.n_loci
     leaves, root, trees = plan[0], plan[2], plan[4]
     order = [np.array(x, np.int64) for x in plan[3]]
@@ -2188,13 +2256,14 @@ def _tree_refine(be, chunk: Chunk, plan, bufs, live, where, weights, passes, max
             fits = _tree_step_fits(WX, WY, budget_words)           # (a step beyond the limit is skipped: it counts as refused)
             sel = np.nonzero(fits)[0]
             new, made = {}, [b]
-            for grp in _prog_groups(X[sel, 3], Y[sel, 3], budget_bytes, band):
+            for grp in _prog_groups(X[sel, 3], Y[sel, 3], budget_bytes, band, position_gaps):
                 g = sel[grp]
                 d_bufs = _bufs_table(be, bufs)
                 wg = None
                 if weights is not None or align is not None:
                     wg = ([al[its[k]][order[its[k]][sides[k] == 1]] for k in g.tolist()], [al[its[k]][order[its[k]][sides[k] == 0]] for k in g.tolist()])
-                d_ops, ops_bytes, ops_off, count, _ = _prog_pairs(be, d_bufs, len(bufs), X[g], Y[g], band, budget_bytes, counters, wg)
+                d_ops, ops_bytes, ops_off, count, _ = _prog_pairs(be, d_bufs, len(bufs), X[g], Y[g], band, budget_bytes, counters, wg,
+                                                                  position_gaps)
                 d_new, new_bytes, poff, R = _prog_parents(be, d_bufs, len(bufs), X[g], Y[g], d_ops, ops_bytes, ops_off, count)
                 made.append(add_buf(d_new, new_bytes))
                 for i, k in enumerate(g.tolist()):

@@ -133,6 +133,15 @@ def register_parser(subparsers):
                         "locus with more leaves keeps the 6-mer tree and is reported.  Everything after the tree is unchanged; "
                         "--band computes the same scores over certified bands, --device-tree keeps the tables on the GPU, --retree, "
                         "--refine-tree and --refine run after it.  Off by default")
+    p.add_argument("--position-gaps", dest="position_gaps", action="store_true", default=False,
+                   help="(this implementation) with --unaligned --progressive: a profile merge charges the opening of a gap run by "
+                        "the occupancy of the column the run starts at, -704 times the share of rows with a residue there (ClustalW, "
+                        "MUSCLE and MAFFT scale a profile position's gap open the same way), instead of -704 whatever the column; "
+                        "so skipping a column in which one row of fifty has a residue costs about as little to open as to extend, and "
+                        "independent insertions are no longer pushed into one column (star_align.py, Position gaps; "
+                        "csrc/pg_pairs.inc).  The tree, the row order and the objective are unchanged; the merges of --retree and "
+                        "--refine-tree use the same opens, --refine runs afterwards with the fixed open, --band and --device-tree "
+                        "give the same bytes.  Off by default")
     p.set_defaults(func=run, check=check_options)
     return p
 
@@ -174,6 +183,8 @@ def check_options(args, parser):
         parser.error("--seq-weights needs --progressive")
     if getattr(args, "pair_distances", False) and not getattr(args, "progressive", False):
         parser.error("--pair-distances needs --progressive")
+    if getattr(args, "position_gaps", False) and not getattr(args, "progressive", False):
+        parser.error("--position-gaps needs --progressive")
     if getattr(args, "refine", None) is not None:
         if not args.unaligned:
             parser.error("--refine needs --unaligned")
@@ -682,12 +693,13 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
     retree = int(getattr(options, "retree", None) or 0)
     seq_weights = bool(getattr(options, "seq_weights", False))
     pair_distances = bool(getattr(options, "pair_distances", False))
+    position_gaps = bool(getattr(options, "position_gaps", False))
     for lo in range(0, len(mine), STAR_CHUNK):
         t0 = time.perf_counter()
         recs = [star_align.read_unaligned(f) for f in mine[lo:lo + STAR_CHUNK]]
         t1 = time.perf_counter()
         msas = star_align.star_msas(be, recs, names=loci[lo:lo + STAR_CHUNK], adjust_direction=adjust, orientation=orientation,
-                                    **(dict(band=True) if band else {}), **(dict(timings=counters) if band or collapse or device_tree or refine_tree or retree or seq_weights or pair_distances else {}),
+                                    **(dict(band=True) if band else {}), **(dict(timings=counters) if band or collapse or device_tree or refine_tree or retree or seq_weights or pair_distances or position_gaps else {}),
                                     **(dict(collapse=True) if collapse else {}),
                                     **(dict(refine=refine, refinement=refinement) if refine else {}),
                                     **(dict(progressive=True, progression=progression) if progressive else {}),
@@ -696,7 +708,8 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
                                     **(dict(refine_tree=refine_tree, tree_refinement=tree_refinement) if refine_tree else {}),
                                     **(dict(retree=retree) if retree else {}),
                                     **(dict(seq_weights=True) if seq_weights else {}),
-                                    **(dict(pair_distances=True) if pair_distances else {}))
+                                    **(dict(pair_distances=True) if pair_distances else {}),
+                                    **(dict(position_gaps=True) if position_gaps else {}))
         t2 = time.perf_counter()
         for locus, m in zip(loci[lo:lo + STAR_CHUNK], msas):
             path = out_dir / f"{locus}.fa"
@@ -717,6 +730,8 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
         logger.info(f"rank {rank}: --progressive --band: {counters.get('prog_band_merges', 0)} merges, "
                     f"{counters.get('prog_band_second_passes', 0)} second passes, {counters.get('prog_band_full_merges', 0)} sent to the "
                     f"full DP, {counters.get('prog_band_cells', 0)} of {counters.get('prog_band_full_cells', 0)} DP cells computed")
+    if position_gaps:
+        logger.info(f"rank {rank}: --position-gaps: {counters.get('position_gap_merges', 0)} merges with opens by occupancy")
     if pair_distances:
         logger.info(f"rank {rank}: --pair-distances: {counters.get('pair_dist_loci', 0)} loci, {counters.get('pair_dist_pairs', 0)} pairs, "
                     f"{counters.get('pair_dist_cells', 0)} DP cells, {counters.get('pair_dist_above_cap', 0)} above the cap, "

@@ -46,6 +46,8 @@ seq_weight_loci, seq_weight_min_q, and, from an untimed run of the same loci wit
 pair_dist_above_cap, pair_dist_limit (with --band pair_dist_second_passes and pair_dist_full_pairs) and, from an untimed run of the
 same loci without the flag afterwards, pair_dist_loci_changed (the loci whose MSA differs), pair_dist_loci_higher and
 pair_dist_loci_lower (by the locus's objective S) and s_total_kmer beside s_total.
+`--position-gaps` (with --progressive): the merges' opens by occupancy (`from_msa --unaligned --progressive --position-gaps`); the
+line then also gives position_gap_merges.
 `--truth`: the MSAs written are scored against the alignment that is true by construction (`compare_msa`'s counts,
 make_prg_amd/from_msa/msa_compare.py, after the timed part): synth_rows' own rows for the config-C-shaped loci, diverged_locus'
 true_rows with --diverged; the line then also gives truth_shared, truth_ref_pairs, truth_test_pairs, truth_ref_columns, truth_kept,
@@ -108,6 +110,9 @@ if seq_weights and not progressive:
 pair_distances = "--pair-distances" in sys.argv
 if pair_distances and not progressive:
     sys.exit("--pair-distances needs --progressive")
+position_gaps = "--position-gaps" in sys.argv
+if position_gaps and not progressive:
+    sys.exit("--position-gaps needs --progressive")
 records = int(sys.argv[sys.argv.index("--records") + 1]) if "--records" in sys.argv else 0
 if records and not diverged:
     sys.exit("--records needs --diverged")
@@ -119,7 +124,8 @@ if large_loci and not (progressive and collapse):
     sys.exit("--large-loci needs --progressive and --collapse-identical")
 prog_kw = dict(progressive=True, **(dict(device_tree=True) if device_tree else {}), **(dict(large_loci=True) if large_loci else {}),
                **(dict(refine_tree=refine_tree) if refine_tree else {}), **(dict(retree=retree) if retree else {}),
-               **(dict(seq_weights=True) if seq_weights else {}), **(dict(pair_distances=True) if pair_distances else {})) if progressive else {}
+               **(dict(seq_weights=True) if seq_weights else {}), **(dict(pair_distances=True) if pair_distances else {}),
+               **(dict(position_gaps=True) if position_gaps else {})) if progressive else {}
 
 
 def objectives(be, msas):
@@ -238,6 +244,8 @@ try:
         extra.update(pair_distances=True, pair_dist_loci_changed=sum(1 for a, b in zip(msas, plain) if sa.msa_fasta(a) != sa.msa_fasta(b)),
                      pair_dist_loci_higher=sum(1 for a, b in zip(s_on, s_off) if a > b), pair_dist_loci_lower=sum(1 for a, b in zip(s_on, s_off) if a < b),
                      s_total_kmer=sum(s_off))
+    if position_gaps:
+        extra.update(position_gaps=True)
     if truth:
         from make_prg_amd.from_msa import msa_compare as mc
         from make_prg_amd.msa import MSA
