@@ -800,6 +800,34 @@ int mprg_align_profile_pairs_posgap_banded(const int32_t *profile, const int64_t
 int mprg_prog_band_widths_posgap(const int32_t *profile, const int64_t *leaves, int n_leaves, const int32_t *xcols, long long xcols_words,
                                  const int64_t *pairs, int n_pairs, const int32_t *out, int64_t *bounds, int32_t *status, void *stream);
 
+/* `--progressive --free-end-gaps`: a merge as an overlap (semi-global) alignment (the spec: star_align.py, "Free end gaps";
+ * DESIGN.md §3b).  Row 0 and column 0 of the DP are 0; in the last row a 'D' op costs 0 to extend and 0 to open, in the last column
+ * an 'I' op; every other cell, the cell scores, the ties, the walk back from (n, C) and the score taken there are the twins'.  So
+ * the run of ops at either end of a merge that holds one side's columns alone is free, and the score is the overlap optimum.
+ * mprg_align_profile_pairs_endgap, mprg_align_profile_pairs_endgap_banded: mprg_align_profile_pairs(_banded) with these boundaries.
+ * mprg_align_profile_pairs_posgap_endgap, mprg_align_profile_pairs_posgap_endgap_banded: the _posgap entries with them (the leaf's
+ *   profile has the 7 planes of kind 2).  Arguments, workspace need, ops and status codes are the twins'.  With n = 0: C 'D' ops,
+ *   score 0.
+ * mprg_prog_band_widths_endgap: mprg_prog_band_widths' arguments and status codes, for both forms of the open (only the first six
+ *   planes of a leaf's profile are read: kind 0 or kind 2), with B'_j = max(B_j, 0), bounds[2p] = SB' = sum_j B'_j and
+ *   U(w) = SB' - LY'(max(0, D) + w + 1), LY'(k) the sum of the k smallest B'_j (k clamped to C); bounds[2p + 1] = the smallest w in
+ *   [0, min(n, C)] with U(w) < S0, min(n, C) when there is none. */
+int mprg_align_profile_pairs_endgap(const int32_t *profile, const int64_t *leaves, int n_leaves, const int32_t *xcols,
+                                    long long xcols_words, const int64_t *pairs, int n_pairs, int32_t *workspace,
+                                    long long workspace_words, uint8_t *ops, long long ops_bytes, int32_t *out, void *stream);
+int mprg_align_profile_pairs_endgap_banded(const int32_t *profile, const int64_t *leaves, int n_leaves, const int32_t *xcols,
+                                           long long xcols_words, const int64_t *pairs, int n_pairs, int32_t *workspace,
+                                           long long workspace_words, uint8_t *ops, long long ops_bytes, int32_t *out, void *stream);
+int mprg_align_profile_pairs_posgap_endgap(const int32_t *profile, const int64_t *leaves, int n_leaves, const int32_t *xcols,
+                                           long long xcols_words, const int64_t *pairs, int n_pairs, int32_t *workspace,
+                                           long long workspace_words, uint8_t *ops, long long ops_bytes, int32_t *out, void *stream);
+int mprg_align_profile_pairs_posgap_endgap_banded(const int32_t *profile, const int64_t *leaves, int n_leaves, const int32_t *xcols,
+                                                  long long xcols_words, const int64_t *pairs, int n_pairs, int32_t *workspace,
+                                                  long long workspace_words, uint8_t *ops, long long ops_bytes, int32_t *out,
+                                                  void *stream);
+int mprg_prog_band_widths_endgap(const int32_t *profile, const int64_t *leaves, int n_leaves, const int32_t *xcols, long long xcols_words,
+                                 const int64_t *pairs, int n_pairs, const int32_t *out, int64_t *bounds, int32_t *status, void *stream);
+
 /* `from_msa --unaligned --collapse-identical`: every distinct sequence of a locus aligned once (the spec: star_align.py, "Collapse";
  * DESIGN.md §3b).  The pair, merge and row calls above are used unchanged, on tables that name a class's representative.
  * mprg_star_identical: codes, seqs, loci as the star calls' (only {first sequence, sequence count} of a locus are read).

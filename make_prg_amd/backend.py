@@ -130,6 +130,17 @@ SIGNATURES = {
                                                        ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
     "mprg_prog_band_widths_posgap": (c_int, [c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, c_void_p,
                                              c_void_p, c_void_p]),
+    "mprg_align_profile_pairs_endgap": (c_int, [c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p,
+                                                ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
+    "mprg_align_profile_pairs_endgap_banded": (c_int, [c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p,
+                                                       ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
+    "mprg_align_profile_pairs_posgap_endgap": (c_int, [c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p,
+                                                       ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
+    "mprg_align_profile_pairs_posgap_endgap_banded": (c_int, [c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_int,
+                                                              c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p,
+                                                              c_void_p]),
+    "mprg_prog_band_widths_endgap": (c_int, [c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, c_void_p,
+                                             c_void_p, c_void_p]),
     "mprg_star_identical": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                     c_void_p]),
     "mprg_prog_columns_weighted": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p,

@@ -15,8 +15,8 @@
 //   access pattern).  Kind 0 writes exactly k_align_profiles' 6 planes (Y's profile), kind 1 the 7 planes of an X side: the
 //   counts of A C G T, of R Y K M S W N, of '-', and Ic.  Kind 2 (only where max_kind = 2: mprg_prog_columns_posgap) writes kind 0's
 //   six planes and Oc, the open of a run that starts at the column.
-// k_align_profile_pairs (its text: pg_pairs.inc, included twice: the second time as k_align_profile_pairs_posgap, the merge with
-//   position-specific opens): k_align_pairs' structure with a profile on both sides, a kernel of its own but for the cell and the
+// k_align_profile_pairs (its text: pg_pairs.inc, included four times: as k_align_profile_pairs_posgap, the merge with
+//   position-specific opens, and as the _endgap forms of both, the merges with free end gaps): k_align_pairs' structure with a profile on both sides, a kernel of its own but for the cell and the
 //   walk back (al_cell.inc, al_walk.inc): one wavefront per merge, 64-column strips of X on the anti-diagonal, the row above
 //   by shuffle, Y's six planes in the 128-column LDS ring, 4-bit traceback, lane 0 walking back.  A lane keeps its X column's six
 //   counts and Ic in registers; a cell's score is six multiply-adds and the truncating division by R_X as a multiplication by a
@@ -138,6 +138,7 @@ MPRG_DEV int pg_div(int v, const PgDiv d) {
   return v < 0 ? -q : q;
 }
 
+#define PG_ENDGAP 0
 #define PG_PAIRS_KERNEL k_align_profile_pairs
 #define PG_POSGAP 0
 #include "pg_pairs.inc"
@@ -148,6 +149,20 @@ MPRG_DEV int pg_div(int v, const PgDiv d) {
 #include "pg_pairs.inc"
 #undef PG_PAIRS_KERNEL
 #undef PG_POSGAP
+#undef PG_ENDGAP
+// ... and with free end gaps (star_align.py, "Free end gaps"), for both forms of the open
+#define PG_ENDGAP 1
+#define PG_PAIRS_KERNEL k_align_profile_pairs_endgap
+#define PG_POSGAP 0
+#include "pg_pairs.inc"
+#undef PG_PAIRS_KERNEL
+#undef PG_POSGAP
+#define PG_PAIRS_KERNEL k_align_profile_pairs_posgap_endgap
+#define PG_POSGAP 1
+#include "pg_pairs.inc"
+#undef PG_PAIRS_KERNEL
+#undef PG_POSGAP
+#undef PG_ENDGAP
 
 __global__ void __launch_bounds__(PG_THREADS) k_prog_rows(const int64_t *bufs, int n_bufs, const uint8_t *ops, long long ops_bytes,
                                                           const int64_t *rows, int n_rows, uint8_t *out, long long out_bytes, int ascii,

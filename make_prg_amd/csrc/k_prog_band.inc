@@ -4,7 +4,8 @@
 //      of the diagonals dlo <= j - i <= dhi only, and the certified half-width of every merge of a launch, found on the device.
 //
 // (The three kernels' texts are pg_pairs_band.inc and pg_band_widths.inc, each included twice: as the kernels below and as their
-//   _posgap forms, the merges with position-specific opens.)
+//   _posgap forms, the merges with position-specific opens; the pair kernel twice more as the _endgap forms of both and the widths
+//   kernel once more as k_prog_band_widths_endgap, the merges with free end gaps.)
 // k_align_profile_pairs_banded: k_align_profile_pairs' cell (X's six counts and Ic in registers, six multiply-adds, pg_div) with
 //   k_align_pairs_banded's geometry, a kernel of its own but for the cell and the walk back (al_cell.inc, al_walk.inc).  Strip s (rows
 //   i0 + 1 .. i0 + rows) sweeps columns cs + 1 .. min(C, i0 + rows + dhi), cs = max(0, i0 + dlo); a lane computes only where its
@@ -24,6 +25,7 @@
 #define PB_LOSS_BINS 2048                      // loss_j <= 1 280 + 640 = 1 920; eight bins per thread
 #define PB_INS_BINS 768                        // ins_i <= 640; three bins per thread
 
+#define PG_ENDGAP 0
 #define PG_PAIRS_KERNEL k_align_profile_pairs_banded
 #define PG_POSGAP 0
 #include "pg_pairs_band.inc"
@@ -34,6 +36,20 @@
 #include "pg_pairs_band.inc"
 #undef PG_PAIRS_KERNEL
 #undef PG_POSGAP
+#undef PG_ENDGAP
+// ... and with free end gaps (star_align.py, "Free end gaps"), for both forms of the open
+#define PG_ENDGAP 1
+#define PG_PAIRS_KERNEL k_align_profile_pairs_endgap_banded
+#define PG_POSGAP 0
+#include "pg_pairs_band.inc"
+#undef PG_PAIRS_KERNEL
+#undef PG_POSGAP
+#define PG_PAIRS_KERNEL k_align_profile_pairs_posgap_endgap_banded
+#define PG_POSGAP 1
+#include "pg_pairs_band.inc"
+#undef PG_PAIRS_KERNEL
+#undef PG_POSGAP
+#undef PG_ENDGAP
 
 // cnt[0 .. PER * PG_THREADS) (a histogram over values = bin indices) into cumulative counts, in place, and cumulative sums of
 // count * value; every thread of the workgroup calls it; part: 2 * PG_WAVES long long of LDS
@@ -69,6 +85,7 @@ MPRG_DEV long long pb_smallest(const uint32_t *cc, const long long *cs, int bins
   return lo == 0 ? 0 : cs[lo - 1] + (k - (long long)cc[lo - 1]) * lo;
 }
 
+#define PG_ENDGAP 0
 #define PG_WIDTHS_KERNEL k_prog_band_widths
 #define PG_POSGAP 0
 #include "pg_band_widths.inc"
@@ -79,3 +96,12 @@ MPRG_DEV long long pb_smallest(const uint32_t *cc, const long long *cs, int bins
 #include "pg_band_widths.inc"
 #undef PG_WIDTHS_KERNEL
 #undef PG_POSGAP
+#undef PG_ENDGAP
+// ... and for free end gaps: no open enters its bound, so one kernel serves both forms of the open
+#define PG_ENDGAP 1
+#define PG_WIDTHS_KERNEL k_prog_band_widths_endgap
+#define PG_POSGAP 0
+#include "pg_band_widths.inc"
+#undef PG_WIDTHS_KERNEL
+#undef PG_POSGAP
+#undef PG_ENDGAP

@@ -785,6 +785,30 @@ int mprg_prog_band_widths_posgap(const int32_t *profile, const int64_t *leaves, 
   return check_launch("k_prog_band_widths_posgap");
 }
 
+// the merges with free end gaps: one launcher per kernel, the twins' arguments
+#define PG_ENDGAP_PAIRS(entry, kernel)                                                                                              \
+  int entry(const int32_t *profile, const int64_t *leaves, int n_leaves, const int32_t *xcols, long long xcols_words,               \
+            const int64_t *pairs, int n_pairs, int32_t *workspace, long long workspace_words, uint8_t *ops, long long ops_bytes,    \
+            int32_t *out, void *stream) {                                                                                           \
+    if (n_pairs <= 0) return 0;                                                                                                     \
+    LAUNCH(kernel, (n_pairs + AL_WAVES - 1) / AL_WAVES, AL_THREADS, stream, profile, leaves, n_leaves, xcols, xcols_words, pairs,   \
+           n_pairs, workspace, workspace_words, ops, ops_bytes, out); /* a wavefront per pair */                                    \
+    return check_launch(#kernel);                                                                                                   \
+  }
+PG_ENDGAP_PAIRS(mprg_align_profile_pairs_endgap, k_align_profile_pairs_endgap)
+PG_ENDGAP_PAIRS(mprg_align_profile_pairs_endgap_banded, k_align_profile_pairs_endgap_banded)
+PG_ENDGAP_PAIRS(mprg_align_profile_pairs_posgap_endgap, k_align_profile_pairs_posgap_endgap)
+PG_ENDGAP_PAIRS(mprg_align_profile_pairs_posgap_endgap_banded, k_align_profile_pairs_posgap_endgap_banded)
+#undef PG_ENDGAP_PAIRS
+
+int mprg_prog_band_widths_endgap(const int32_t *profile, const int64_t *leaves, int n_leaves, const int32_t *xcols, long long xcols_words,
+                                 const int64_t *pairs, int n_pairs, const int32_t *out, int64_t *bounds, int32_t *status, void *stream) {
+  if (n_pairs <= 0) return 0;
+  LAUNCH(k_prog_band_widths_endgap, n_pairs, PG_THREADS, stream, profile, leaves, n_leaves, xcols, xcols_words, pairs, n_pairs, out, bounds,
+         status);      // a workgroup per merge
+  return check_launch("k_prog_band_widths_endgap");
+}
+
 int mprg_prog_rows(const int64_t *bufs, int n_bufs, const uint8_t *ops, long long ops_bytes, const int64_t *rows, int n_rows,
                    uint8_t *out, long long out_bytes, int ascii, int32_t *status, void *stream) {
   if (n_rows <= 0) return 0;

@@ -3,13 +3,18 @@
 // PG_POSGAP: 0 expands to the tokens the kernel had when it stood in k_prog_band.inc.  1: a path that leaves the band pays at most
 // oy = max_j Oc[j] (Y's seventh plane) and ox = max_i Ox[i] (pg_div over X's gap plane; 0 when n = 0) for its two runs, both
 // reduced like SB, in place of 2 * AL_OPEN.
+// PG_ENDGAP (with PG_POSGAP 0 only: k_prog_band_widths_endgap; star_align.py, "Free end gaps", band): 0 expands to those tokens.
+// 1: B'_j = max(B_j, 0) is both the column's share of SB' and its loss (0 .. 1 280), X's side and the opens do not count:
+// U(w) = SB' - LY'(max(0, D) + w + 1).  Only the first six planes of Y's profile are read, so profiles of kind 0 and 2 both serve.
 __global__ void __launch_bounds__(PG_THREADS) PG_WIDTHS_KERNEL(const int32_t *profile, const int64_t *leaves, int n_leaves,
                                                                  const int32_t *xcols, long long xcols_words, const int64_t *pairs,
                                                                  int n_pairs, const int32_t *out, int64_t *bounds, int32_t *status) {
   SHARED(uint32_t, hy, PB_LOSS_BINS);
   SHARED(long long, sy, PB_LOSS_BINS);
+#if !PG_ENDGAP
   SHARED(uint32_t, hx, PB_INS_BINS);
   SHARED(long long, sx, PB_INS_BINS);
+#endif
   SHARED(long long, part, 2 * PG_WAVES);
 #if PG_POSGAP
   SHARED(int, opens, 2 * PG_WAVES);
@@ -31,7 +36,9 @@ __global__ void __launch_bounds__(PG_THREADS) PG_WIDTHS_KERNEL(const int32_t *pr
   ONE_THREAD status[p] = st;
   if (st != MPRG_AL_OK) return;                              // (the whole workgroup)
   PAR_FOR(k, PB_LOSS_BINS) hy[k] = 0;
+#if !PG_ENDGAP
   PAR_FOR(k, PB_INS_BINS) hx[k] = 0;
+#endif
   BARRIER();
   const int32_t *P = profile + poff;
   long long sb = 0;
@@ -44,14 +51,21 @@ __global__ void __launch_bounds__(PG_THREADS) PG_WIDTHS_KERNEL(const int32_t *pr
     int b = dc;
 #pragma unroll
     for (int x = 0; x < 5; ++x) { const int v = P[x * C + j]; b = v > b ? v : b; }
+#if PG_ENDGAP
+    b = b > 0 ? b : 0;
+    sb += b;
+    const int loss = b;                                      // 0 .. 1 280: a skipped column, charged or free, contributes at most 0
+#else
     sb += b;
     const int loss = b - dc;                                 // 0 .. 1 920 for the planes k_prog_columns writes
+#endif
     ATOMIC_ADD(&hy[loss < 0 ? 0 : loss > 1920 ? 1920 : loss], 1u);
 #if PG_POSGAP
     const int oc = P[6 * C + j];
     oy = oc > oy ? oc : oy;
 #endif
   }
+#if !PG_ENDGAP
   PAR_FOR(i, n) {
     const int ins = -xcols[xoff + 6 * n + i];                // 0 .. 640
     ATOMIC_ADD(&hx[ins < 0 ? 0 : ins > 640 ? 640 : ins], 1u);
@@ -60,6 +74,7 @@ __global__ void __launch_bounds__(PG_THREADS) PG_WIDTHS_KERNEL(const int32_t *pr
     ox = oi > ox ? oi : ox;
 #endif
   }
+#endif
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) sb += __shfl_xor(sb, d);
 #if PG_POSGAP
@@ -73,7 +88,9 @@ __global__ void __launch_bounds__(PG_THREADS) PG_WIDTHS_KERNEL(const int32_t *pr
 #endif
   BARRIER();                                                 // the histograms are complete
   pb_cumulate<PB_LOSS_BINS / PG_THREADS>(hy, sy, part);
+#if !PG_ENDGAP
   pb_cumulate<PB_INS_BINS / PG_THREADS>(hx, sx, part);
+#endif
   if (wave_lane() == 0) part[wave_id()] = sb;                // (part was last read before pb_cumulate's closing barrier)
   BARRIER();
   ONE_THREAD {
@@ -94,7 +111,11 @@ __global__ void __launch_bounds__(PG_THREADS) PG_WIDTHS_KERNEL(const int32_t *pr
     long long lo = 0, hi = n < C ? n : C;                    // the smallest w with U(w) < S0; none: min(n, C), both sides at the edge
     while (lo < hi) {
       const long long w = (lo + hi) >> 1;
+#if PG_ENDGAP
+      const long long U = SB - pb_smallest(hy, sy, PB_LOSS_BINS, dpos + w + 1);
+#else
       const long long U = SB - pb_smallest(hy, sy, PB_LOSS_BINS, dpos + w + 1) - pb_smallest(hx, sx, PB_INS_BINS, w + 1 - dneg) + PG_TWO_OPENS;
+#endif
       if (U < S0) hi = w; else lo = w + 1;
     }
 #undef PG_TWO_OPENS

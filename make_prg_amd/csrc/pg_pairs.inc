@@ -4,6 +4,10 @@
 // Oc (k_prog_columns' kind 2), the ring a seventh plane Oc[j] + Dc[j], so that opening a run of D ops at column j is one LDS
 // read and one addition; a lane keeps Ox + Ic of its X column, Ox = (-704 (R_X - g)) / R_X by pg_div (|v| <= 704 R_X, inside its
 // proven range); row 0 opens with Oc[0], column 0 with Ox[0].
+// PG_ENDGAP (star_align.py, "Free end gaps"; both values of PG_POSGAP): 0 expands to the tokens above.  1: row 0 and column 0 are
+// 0, so neither the prefix sums nor Oc[0] / Ox[0] are taken; the lane of the last row (r == ni - 1, fixed over a strip) extends and
+// opens a run of D ops for 0, every lane a run of I ops for 0 in the last column (c == Ci - 1): plain selects in front of
+// al_cell.inc, which stays as it is.  The cell's score keeps Y's real Dc.
 #if PG_POSGAP
 #define PG_RING_PLANES 7
 #define PG_OPEN_ROW0 oc0
@@ -51,6 +55,18 @@ __global__ void __launch_bounds__(AL_THREADS) PG_PAIRS_KERNEL(const int32_t *pro
   const long long nst8 = ((long long)Ci + 63 + 7) / 8;
 #if PG_POSGAP
   const int RXi = (int)al_uniform(RX);
+#endif
+#if PG_ENDGAP
+  // row 0: H[0][J] = D[0][J] = 0, Y's leading columns alone are free
+  for (int c0 = 0; c0 < Ci; c0 += 64) {
+    const int c = c0 + lane;
+    if (c < Ci) { row[2 * (c + 1)] = 0; row[2 * (c + 1) + 1] = AL_NEG; }
+  }
+  if (lane == 0) { row[0] = 0; row[1] = AL_NEG; }
+  WAVE_SYNC_GLOBAL();
+  int score = AL_NEG;
+#else
+#if PG_POSGAP
   const int oc0 = (P + 6LL * Ci)[0];                          // what a run that starts at Y's first column pays: row 0
   const int ox0 = ni > 0 ? pg_div(AL_OPEN * (RXi - (X + 5LL * ni)[0]), dv) : 0;   // ... at X's first column: column 0
 #endif
@@ -66,6 +82,7 @@ __global__ void __launch_bounds__(AL_THREADS) PG_PAIRS_KERNEL(const int32_t *pro
   WAVE_SYNC_GLOBAL();
   int score = AL_NEG;
   int ic_before = 0;                                         // the Ic of all rows above the strip
+#endif
   const int n_strips = (ni + 63) / 64;
   for (int s = 0; s < n_strips; ++s) {
     const int i0 = s * 64, r = i0 + lane, rows = ni - i0 < 64 ? ni - i0 : 64;
@@ -78,11 +95,18 @@ __global__ void __launch_bounds__(AL_THREADS) PG_PAIRS_KERNEL(const int32_t *pro
 #if PG_POSGAP
     const int oxic = pg_div(AL_OPEN * (RXi - xg), dv) + ic;  // opening a run of I ops with this column: Ox + Ic
 #endif
+#if PG_ENDGAP
+    const bool last_row = r == ni - 1;                      // its D ops are the trailing ones: free
+    int h_left = 0, d_left = AL_NEG;                        // H, D of this lane's row, the column to the left: H[r + 1][0] = 0
+    int h_out = 0, i_out = AL_NEG;                          // what the lane below reads next step (before the first column: H[i][0])
+    int h_up_prev = 0;                                      // (lane 0) H of the row above, one column to the left: the diagonal
+#else
     const int ic_incl = wave_scan_incl(ic) + ic_before;     // the Ic of rows 1 .. r + 1
     int h_left = PG_OPEN_COL0 + ic_incl, d_left = AL_NEG;  // H, D of this lane's row, the column to the left: H[r + 1][0]
     int h_out = h_left, i_out = AL_NEG;                     // what the lane below reads next step (before the first column: H[i][0])
     int h_up_prev = i0 == 0 ? 0 : PG_OPEN_COL0 + ic_before; // (lane 0) H of the row above, one column to the left: the diagonal
     ic_before = __shfl(ic_incl, 63);
+#endif
     uint32_t acc = 0;
     uint32_t *tbs = tb + (long long)s * nst8 * 64;
     int h_row = AL_NEG, i_row = AL_NEG;                      // H, I of the row above the strip, column t0 + 1 + lane of the 64-step block
@@ -111,10 +135,29 @@ __global__ void __launch_bounds__(AL_THREADS) PG_PAIRS_KERNEL(const int32_t *pro
       unsigned cell = 0;
       if (valid && c >= 0 && c < Ci) {
         const int slot = c & (AL_RING - 1);
+#if PG_ENDGAP
+        const int dc_y = ring[5 * AL_RING + slot];           // Y's column alone, for the cell's score; dc: what extending a run of D ops costs here
+        const int dc = last_row ? 0 : dc_y;
+#define PG_DC_Y dc_y
+#else
         const int dc = ring[5 * AL_RING + slot];
+#define PG_DC_Y dc
+#endif
         const int num = x0 * ring[slot] + x1 * ring[AL_RING + slot] + x2 * ring[2 * AL_RING + slot] + x3 * ring[3 * AL_RING + slot] +
-                        xa * ring[4 * AL_RING + slot] + xg * dc;
+                        xa * ring[4 * AL_RING + slot] + xg * PG_DC_Y;
+#undef PG_DC_Y
         const int diag = h_diag + pg_div(num, dv);
+#if PG_ENDGAP
+        const bool last_col = c == Ci - 1;                   // its I ops are the trailing ones: free
+        const int xcost = last_col ? 0 : ic;
+#if PG_POSGAP
+#define AL_OPEN_D (last_row ? 0 : ring[6 * AL_RING + slot])
+#define AL_OPEN_I (last_col ? 0 : oxic)
+#else
+#define AL_OPEN_D (last_row ? 0 : AL_OPEN) + dc
+#define AL_OPEN_I (last_col ? 0 : AL_OPEN) + xcost
+#endif
+#else
         const int xcost = ic;
 #if PG_POSGAP
 #define AL_OPEN_D ring[6 * AL_RING + slot]
@@ -122,6 +165,7 @@ __global__ void __launch_bounds__(AL_THREADS) PG_PAIRS_KERNEL(const int32_t *pro
 #else
 #define AL_OPEN_D AL_OPEN + dc
 #define AL_OPEN_I AL_OPEN + xcost
+#endif
 #endif
 #include "al_cell.inc"
 #undef AL_OPEN_D

@@ -2,6 +2,8 @@
 // k_align_profile_pairs_posgap_banded (star_align.py, "Position gaps"): one text, included twice (DESIGN.md §3a).  The includer
 // provides PG_PAIRS_KERNEL, the kernel's name, and PG_POSGAP: 0 expands to the tokens the kernel had when it stood in
 // k_prog_band.inc; 1 is pg_pairs.inc's: a seventh profile and ring plane, Ox + Ic in a register, Oc[0] on row 0, Ox[0] in column 0.
+// PG_ENDGAP (star_align.py, "Free end gaps"): 0 expands to those tokens; 1 is pg_pairs.inc's: row 0 and column 0 are 0 where the
+// band holds them (hb = 0, and no ic_before is derived from it), the last row's D ops and the last column's I ops are free.
 #if PG_POSGAP
 #define PG_RING_PLANES 7
 #define PG_OPEN_ROW0 oc0
@@ -57,6 +59,18 @@ __global__ void __launch_bounds__(AL_THREADS) PG_PAIRS_KERNEL(const int32_t *pro
   const long long nst8 = ((W + 63 < Ci ? W + 63 : Ci) + 63 + 7) / 8;
 #if PG_POSGAP
   const int RXi = (int)al_uniform(RX);
+#endif
+#if PG_ENDGAP
+  // row 0, columns 0 .. dhi: H[0][J] = D[0][J] = 0, Y's leading columns alone are free
+  for (int c0 = 0; c0 < dhi; c0 += 64) {
+    const int c = c0 + lane;
+    if (c < dhi) { row[2 * (c + 1 - dlo)] = 0; row[2 * (c + 1 - dlo) + 1] = AL_NEG; }
+  }
+  if (lane == 0) { row[2 * (-dlo)] = 0; row[2 * (-dlo) + 1] = AL_NEG; }
+  WAVE_SYNC_GLOBAL();
+  int score = AL_NEG;
+#else
+#if PG_POSGAP
   const int oc0 = P[(unsigned)(6 * Ci)];                      // what a run that starts at Y's first column pays: row 0
   const int ox0 = ni > 0 ? pg_div(AL_OPEN * (RXi - X[(unsigned)(5 * ni)]), dv) : 0;   // ... at X's first column: column 0
 #endif
@@ -72,6 +86,7 @@ __global__ void __launch_bounds__(AL_THREADS) PG_PAIRS_KERNEL(const int32_t *pro
   WAVE_SYNC_GLOBAL();
   int score = AL_NEG;
   int ic_before = 0;                                         // the Ic of all rows above the strip
+#endif
   const int n_strips = (ni + 63) / 64;
   for (int s = 0; s < n_strips; ++s) {
     const int i0 = s * 64, r = i0 + lane, rows = ni - i0 < 64 ? ni - i0 : 64;
@@ -85,7 +100,12 @@ __global__ void __launch_bounds__(AL_THREADS) PG_PAIRS_KERNEL(const int32_t *pro
 #if PG_POSGAP
     const int oxic = pg_div(AL_OPEN * (RXi - xg), dv) + ic;  // opening a run of I ops with this column: Ox + Ic
 #endif
+#if PG_ENDGAP
+    const bool last_row = r == ni - 1;                      // its D ops are the trailing ones: free
+    const int hb = 0;                                       // H[r + 1][0]: X's leading columns alone are free
+#else
     const int hb = PG_OPEN_COL0 + wave_scan_incl(ic) + ic_before;  // H[r + 1][0]: open + the Ic of rows 1 .. r + 1
+#endif
     const int cs = i0 + dlo > 0 ? i0 + dlo : 0;             // the strip's first column, 0-based
     const int jtop = i0 + dhi < Ci ? i0 + dhi : Ci;         // the last column of row i0 inside the band
     const int jend = i0 + rows + dhi < Ci ? i0 + rows + dhi : Ci;   // the strip's last column, 1-based
@@ -95,8 +115,12 @@ __global__ void __launch_bounds__(AL_THREADS) PG_PAIRS_KERNEL(const int32_t *pro
     int h_left = col0 ? hb : AL_NEG, d_left = AL_NEG;       // H, D of this lane's row, the column to the left of its first one
     int h_out = col0 && cs == lane ? hb : AL_NEG, i_out = AL_NEG;   // what the lane below reads next step: here of column cs - 1 - lane
     int h_up_prev = AL_NEG;                                  // H of the row above, one column to the left: the diagonal
+#if PG_ENDGAP
+    if (lane == 0) h_up_prev = cs == 0 ? 0 : row[0];        // (cs > 0: column cs = i0 + dlo of row i0, its first inside the band)
+#else
     if (lane == 0) h_up_prev = cs == 0 ? (i0 == 0 ? 0 : PG_OPEN_COL0 + ic_before) : row[0];   // (cs > 0: column cs = i0 + dlo of row i0, its first inside the band)
     ic_before = __shfl(hb, 63) - PG_OPEN_COL0;
+#endif
     uint32_t acc = 0;
     uint32_t *tbs = tb + (long long)s * nst8 * 64;           // the strip's traceback: wave-uniform bases, 32-bit lane offsets
     const int T = jend - cs + rows - 1;
@@ -124,10 +148,29 @@ __global__ void __launch_bounds__(AL_THREADS) PG_PAIRS_KERNEL(const int32_t *pro
       unsigned cell = 0;
       if (valid && (unsigned)c < (unsigned)Ci && (unsigned)(d0 + t - lane) < (unsigned)W) {
         const int slot = (t - lane) & (AL_RING - 1);
+#if PG_ENDGAP
+        const int dc_y = ring[5 * AL_RING + slot];           // Y's column alone, for the cell's score; dc: what extending a run of D ops costs here
+        const int dc = last_row ? 0 : dc_y;
+#define PG_DC_Y dc_y
+#else
         const int dc = ring[5 * AL_RING + slot];
+#define PG_DC_Y dc
+#endif
         const int num = x0 * ring[slot] + x1 * ring[AL_RING + slot] + x2 * ring[2 * AL_RING + slot] + x3 * ring[3 * AL_RING + slot] +
-                        xa * ring[4 * AL_RING + slot] + xg * dc;
+                        xa * ring[4 * AL_RING + slot] + xg * PG_DC_Y;
+#undef PG_DC_Y
         const int diag = h_diag + pg_div(num, dv);
+#if PG_ENDGAP
+        const bool last_col = c == Ci - 1;                   // its I ops are the trailing ones: free
+        const int xcost = last_col ? 0 : ic;
+#if PG_POSGAP
+#define AL_OPEN_D (last_row ? 0 : ring[6 * AL_RING + slot])
+#define AL_OPEN_I (last_col ? 0 : oxic)
+#else
+#define AL_OPEN_D (last_row ? 0 : AL_OPEN) + dc
+#define AL_OPEN_I (last_col ? 0 : AL_OPEN) + xcost
+#endif
+#else
         const int xcost = ic;
 #if PG_POSGAP
 #define AL_OPEN_D ring[6 * AL_RING + slot]
@@ -135,6 +178,7 @@ __global__ void __launch_bounds__(AL_THREADS) PG_PAIRS_KERNEL(const int32_t *pro
 #else
 #define AL_OPEN_D AL_OPEN + dc
 #define AL_OPEN_I AL_OPEN + xcost
+#endif
 #endif
 #include "al_cell.inc"
 #undef AL_OPEN_D

@@ -39,6 +39,9 @@ With `--position-gaps` (and `--progressive`) a merge charges the opening of a ga
 at instead of -704 whatever the column (Position gaps below; kernels: csrc/pg_pairs.inc, csrc/pg_pairs_band.inc,
 csrc/pg_band_widths.inc, C ABI: the _posgap entries).
 
+With `--free-end-gaps` (and `--progressive`) a merge is an overlap alignment: the run of one side's columns alone at either end of
+it is free (Free end gaps below; the same three kernel texts, C ABI: the _endgap entries).
+
 It is NOT MAFFT.  PRGs built from these alignments differ from PRGs built from a MAFFT alignment of the same sequences.
 
 Spec (the kernels and tests/star_ref.py follow it bit for bit)
@@ -425,6 +428,57 @@ MAFFT scale a profile position's gap open.
             for the widths, in pass 2 and for the full form; nothing else in the launches changes.  timings receives
             position_gap_merges.
 
+Free end gaps (only with progressive and free_end_gaps; integers only; tests/endgap_ref.py states it in plain Python; kernels:
+csrc/pg_pairs.inc, csrc/pg_pairs_band.inc, csrc/pg_band_widths.inc, C ABI: mprg_align_profile_pairs_endgap /
+mprg_align_profile_pairs_endgap_banded / mprg_align_profile_pairs_posgap_endgap / mprg_align_profile_pairs_posgap_endgap_banded /
+mprg_prog_band_widths_endgap).  Progressive's merge is a global alignment with end gaps charged: a run of gaps at either end of a
+merge pays the open and every column, like an internal deletion.  For a partial record (a gene cut at a contig edge, a truncated
+hit) that is wrong twice: the missing end is billed as a deletion of hundreds of columns, and since that deletion costs no more than
+an internal gap the DP can push the fragment's last residues to the far end of the profile whenever they match there slightly
+better.  Here the merge is an overlap (semi-global) alignment.
+  The merge of a node's two children is Progressive's merge, or Position gaps' merge when position_gaps is given too, with four
+            changes to the boundary and nothing else (X has n columns, Y has C columns):
+                Row 0.      H[0][J] = D[0][J] = 0 for all J: the leading D ops, where Y's columns come before X starts, pay
+                            neither an open nor Dc.
+                Column 0.   H[i][0] = I[i][0] = 0 for all i.
+                Row n.      In the cells of the last row a D op costs 0 to extend and 0 to open:
+                                D[n][j] = max(D[n][j-1], H[n][j-1])
+                            (a D op in row n can only be followed by D ops, so these are exactly the trailing ones).
+                Column C.   In the cells of the last column an I op costs 0 to extend and 0 to open:
+                                I[i][C] = max(I[i-1][C], H[i-1][C])
+  Unchanged: s(i, j), Dc, Ic and the opens of every other cell; the int32 arithmetic; the tie order (diagonal, then D, then I;
+            extend before open: d_ext >= d_open extends, also where both are free); the 4-bit traceback cell; the walk back from
+            (n, C) in state H; the refusal at n + C >= 10^6; the ops and the status contract.
+  Score.    The score at (n, C) is the overlap optimum: it equals the maximum over the last row and the last column of the DP with
+            zero borders and every other cell charged (tested against that by-definition form).  With n = 0 the result is C D ops
+            and a score of 0.  Only one leading and one trailing run can be free: an I run that follows a free leading D run is an
+            ordinary run and is charged.
+  Which merges.  Every merge that goes through _prog_pairs: those of Progressive, of a rebuild of Retree and of a step of Tree
+            refinement, the leaf-leaf merges included.
+  Nothing else changes: the distances and the tree; which child is Y, and the row order; the objective S, which still counts end
+            runs, so Retree and Tree refinement accept by the same S; refine, which runs afterwards with charged ends (as it runs
+            with the fixed open after position_gaps); the star pass; adjust_direction; the pair DPs of pair_distances; `update
+            --aligner builtin`.  Not part of it: treating the terminal '-' cells inside a profile's rows as missing data in the
+            planes; free ends in the pair scores of pair_distances; any change of defaults.  The flag promises these boundaries,
+            not a higher S.
+  Band.     With band the same bytes.  The bound of "Progressive, band" does not carry over: a path that leaves the band can now
+            take both of its forced runs for free, a leading D run in row 0 and a trailing I run in column C.  With B_j as there,
+                B'_j = max(B_j, 0),   SB' = sum_j B'_j,   LY'(k) = the sum of the k smallest B'_j (k clamped to C).
+            Proof.  (1) Of a path's score a matched Y column contributes at most B_j <= B'_j; a skipped Y column, charged or free,
+            at most 0 = B'_j - B'_j; lone X columns and opens at most 0.  (2) A path that touches a diagonal beyond half-width w
+            has at least k = max(0, Delta) + w + 1 D ops: on the plus side it touches d* >= max(0, Delta) + w + 1 and has d* D ops,
+            on the minus side d* <= min(0, Delta) - w - 1 and has Delta - d* >= max(0, Delta) + w + 1 of them: the same count on
+            both sides, as before.  (3) So it scores at most SB' minus the B'_j of the columns it skips, which is at most
+                U(w) = SB' - LY'(max(0, Delta) + w + 1).
+            U does not rise with w (LY' does not fall with k).  No open enters it, so it holds for both forms of the open and one
+            widths kernel serves both.  The two-pass rule, the clamping at the matrix's edge, band_helps, w0 = PROG_BAND_W0 and
+            the closed-sides induction (it uses only that no path outside the band beats S0) are unchanged.  The bound is weaker
+            than Progressive's: a dense column loses about 1 280 instead of about 1 920, X's side and the two opens no longer
+            count; so more merges take a second pass or go to the full DP (the counts are in DESIGN.md §3b).
+  Host side: _prog_pairs chooses the entry by (position_gaps, free_end_gaps) in pass 1, for the widths
+            (mprg_prog_band_widths_endgap with either open), in pass 2 and for the full form; the column tables, the sizing and
+            the groups do not change.  timings receives free_end_gap_merges.
+
 Progressive, host side: per chunk the distances in launches whose m x m tables fit budget_bytes (loci of three or more leaves), D
 and the tree per locus in NumPy / Python integers (prog_tree: a float64 quotient only shortlists, the choice is exact).  A node's
 round is 1 + the larger of its children's rounds.  With device_tree the tree is built on the device instead (csrc/k_prog_tree.inc):
@@ -589,7 +643,8 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
               tree_refinement: Optional[list] = None, tree_refine_max_leaves: int = TREE_REFINE_MAX_LEAVES, large_loci: bool = False,
               max_records: Optional[int] = None, retree: Optional[int] = None, retreeing: Optional[list] = None,
               seq_weights: bool = False, pair_distances: bool = False, pair_distancing: Optional[list] = None,
-              pair_dist_max_leaves: int = PAIR_DIST_MAX_LEAVES, position_gaps: bool = False) -> List[MSA]:
+              pair_dist_max_leaves: int = PAIR_DIST_MAX_LEAVES, position_gaps: bool = False,
+              free_end_gaps: bool = False) -> List[MSA]:
     """loci: per locus its records as (title, sequence).  Returns the loci's centre-star MSAs (ids: the titles' first words,
     descriptions: the titles).  names: the loci's names for error messages (default: their indices).  timings: a dict that
     receives the wall seconds of the stages (orient, centre, pairs, merge: each ends at a download, so includes its kernels).
@@ -648,7 +703,10 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
     position_gaps: only with progressive (else a ValueError): the spec's Position gaps: every profile-profile merge of a locus (of
     Progressive, of a rebuild of retree, of a step of refine_tree) opens its runs by the occupancy of the column they start at.
     timings also receives position_gap_merges (the merges made with them).  False: nothing launches, uploads or downloads
-    differently."""
+    differently.
+    free_end_gaps: only with progressive (else a ValueError): the spec's Free end gaps: every such merge as an overlap alignment,
+    the run of one side's columns alone at either end of it free; with position_gaps too, its opens elsewhere.  timings also
+    receives free_end_gap_merges.  False: nothing launches, uploads or downloads differently."""
     if device_tree and not progressive:
         raise ValueError("device_tree: only with progressive")
     if seq_weights and not progressive:
@@ -657,6 +715,8 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
         raise ValueError("pair_distances: only with progressive")
     if position_gaps and not progressive:
         raise ValueError("position_gaps: only with progressive")
+    if free_end_gaps and not progressive:
+        raise ValueError("free_end_gaps: only with progressive")
     if large_loci and not (progressive and collapse):
         raise ValueError("large_loci: only with progressive and collapse")
     if max_records is not None and not (large_loci and 0 <= int(max_records) <= PROG_MAX_RECORDS):
@@ -686,7 +746,7 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
                                  bool(device_tree), int(refine_tree or 0), tree_refinement, int(tree_refine_max_leaves),
                                  (PROG_MAX_RECORDS if max_records is None else int(max_records)) if large_loci else None, int(retree or 0),
                                  retreeing, bool(seq_weights), int(pair_dist_max_leaves) if pair_distances else None, pair_distancing,
-                                 bool(position_gaps))
+                                 bool(position_gaps), bool(free_end_gaps))
     return [m for lo, hi in _chunks(codes, chunk_bytes)
             for m in _star_chunk(backend, loci[lo:hi], codes[lo:hi], names[lo:hi], budget_bytes, timings, adjust_direction, orientation, band,
                                  int(refine), refinement, collapse=bool(collapse))]
@@ -695,7 +755,7 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
 def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings, adjust_direction, orientation, band, refine, refinement,
                       progression, max_leaves, collapse=False, device_tree=False, refine_tree=0, tree_refinement=None,
                       tree_max_leaves=TREE_REFINE_MAX_LEAVES, max_records=None, retree=0, retreeing=None, seq_weights=False,
-                      pair_dist=None, pair_distancing=None, position_gaps=False) -> List[MSA]:
+                      pair_dist=None, pair_distancing=None, position_gaps=False, free_end_gaps=False) -> List[MSA]:
     """star_msas with progressive: the loci within the leaf limit through the progressive chunks, the others through the star
     chunks, the results (and what the caller's lists receive) back in the loci's order.  max_records (the spec's Large loci; None:
     without it): only the loci of more records go to the star chunks here; the progressive chunks count every locus's classes
@@ -715,7 +775,8 @@ def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings
                                     prog, pro, collapse, device_tree and prog, refine_tree if prog else 0,
                                     tre if tree_refinement is not None else None, tree_max_leaves, limits if prog else None,
                                     retree if prog else 0, ret if retreeing is not None else None, seq_weights and prog,
-                                    pair_dist if prog else None, pdi if pair_distancing is not None else None, position_gaps and prog))
+                                    pair_dist if prog else None, pdi if pair_distancing is not None else None, position_gaps and prog,
+                                    free_end_gaps and prog))
         if not prog:
             pro = [(n_leaves[l], 0, True) for l in sel]
         for k, l in enumerate(sel):
@@ -739,7 +800,7 @@ def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings
 def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direction=False, orientation=None, band=None, refine=0,
                 refinement=None, progressive=False, progression=None, collapse=False, device_tree=False, refine_tree=0,
                 tree_refinement=None, tree_max_leaves=TREE_REFINE_MAX_LEAVES, limits=None, retree=0, retreeing=None, seq_weights=False,
-                pair_dist=None, pair_distancing=None, position_gaps=False) -> List[MSA]:
+                pair_dist=None, pair_distancing=None, position_gaps=False, free_end_gaps=False) -> List[MSA]:
     """One chunk: pack, optionally orient, optionally collapse, the star pass or the progressive one (with its tree refinement),
     optionally refine, collect.  limits (the spec's Large loci; only with progressive and collapse): (max_leaves, max_records): the
     loci with more classes of non-empty records, or more records, go through the star pass."""
@@ -757,15 +818,15 @@ def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direc
         if not build.all():
             return _star_chunk_parts(be, chunk, classes, build, budget_bytes, laps, band, refine, refinement, progression, device_tree,
                                      refine_tree, tree_refinement, tree_max_leaves, retree, retreeing, seq_weights, pair_dist, pair_distancing,
-                                     position_gaps)
+                                     position_gaps, free_end_gaps)
     return _star_chunk_rest(be, chunk, classes, budget_bytes, laps, band, refine, refinement, progressive, progression, device_tree,
                             refine_tree, tree_refinement, tree_max_leaves, retree, retreeing, seq_weights, pair_dist, pair_distancing,
-                            position_gaps)
+                            position_gaps, free_end_gaps)
 
 
 def _star_chunk_parts(be, chunk: Chunk, classes, build, budget_bytes, laps, band, refine, refinement, progression, device_tree,
                       refine_tree, tree_refinement, tree_max_leaves, retree=0, retreeing=None, seq_weights=False, pair_dist=None,
-                      pair_distancing=None, position_gaps=False) -> List[MSA]:
+                      pair_distancing=None, position_gaps=False, free_end_gaps=False) -> List[MSA]:
     """_star_chunk behind Collapse for a chunk of which only the loci `build` (a bool per locus) are built progressively (the spec's
     Large loci): those as one chunk through the progressive pass, the others as one through the star pass, both over the same code
     buffer and the classes already made; the MSAs, and what the caller's lists receive, back in the chunk's order."""
@@ -783,7 +844,8 @@ def _star_chunk_parts(be, chunk: Chunk, classes, build, budget_bytes, laps, band
         got = [[], [], [], [], []]
         out = _star_chunk_rest(be, part, Classes(at[classes.rep[rec]], classes.weight[rec]), budget_bytes, laps, band, refine, got[0], prog,
                                got[1], device_tree and prog, refine_tree if prog else 0, got[2], tree_max_leaves, retree if prog else 0, got[3],
-                               seq_weights and prog, pair_dist if prog else None, got[4], position_gaps and prog)
+                               seq_weights and prog, pair_dist if prog else None, got[4], position_gaps and prog,
+                               free_end_gaps and prog)
         if not prog:
             got[1] = [(int(n_filled[l]), 0, True) for l in sel]
         for k, l in enumerate(sel.tolist()):
@@ -800,11 +862,12 @@ def _star_chunk_parts(be, chunk: Chunk, classes, build, budget_bytes, laps, band
 
 def _star_chunk_rest(be, chunk: Chunk, classes, budget_bytes, laps, band, refine, refinement, progressive, progression, device_tree,
                      refine_tree, tree_refinement, tree_max_leaves, retree=0, retreeing=None, seq_weights=False, pair_dist=None,
-                     pair_distancing=None, position_gaps=False) -> List[MSA]:
+                     pair_distancing=None, position_gaps=False, free_end_gaps=False) -> List[MSA]:
     """_star_chunk behind Collapse: the star pass or the progressive one (with its tree refinement), optionally refine, collect."""
     timings = laps.timings
     text = (_progressive(be, chunk, budget_bytes, band, laps, progression, classes, device_tree, refine_tree, tree_refinement,
-                         tree_max_leaves, retree, retreeing, seq_weights, pair_dist, pair_distancing, position_gaps) if progressive else
+                         tree_max_leaves, retree, retreeing, seq_weights, pair_dist, pair_distancing, position_gaps,
+                         free_end_gaps) if progressive else
             _star_pass(be, chunk, budget_bytes, band, laps, classes))
     moved = {}
     if refine:
@@ -1589,13 +1652,16 @@ def _prog_groups(WX, WY, budget_bytes, band=None, position_gaps=False):
         yield grp
 
 
-def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUDGET_BYTES, counters=None, weights=None, position_gaps=False):
+def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUDGET_BYTES, counters=None, weights=None, position_gaps=False,
+                free_end_gaps=False):
     """One group of merges on the device: X, Y (n, 4) int64 {buffer, offset, R, W} of the two sides' texts.  mprg_prog_columns (Y's
     profiles, X's column tables) and mprg_align_profile_pairs in one launch each; {status, score, op count} downloaded.  With band
     the spec's two passes instead (the module docstring, host side), counters receiving the prog_band_* counts.
     weights: (per merge the weights of X's rows, of Y's rows), the spec's Collapse: the column tables through
     mprg_prog_columns_weighted and R_X the weight sum; everything else is the same.
     position_gaps (the spec's Position gaps): Y's profile gets its seventh plane (kind 2) and every call its _posgap form.
+    free_end_gaps (the spec's Free end gaps): the DP calls get their _endgap form (of either open) and the widths come from
+    mprg_prog_band_widths_endgap (one entry for both opens); the column tables, the sizing and the groups are unchanged.
     Returns (the ops buffer, its bytes, each merge's ops offset, op count, score)."""
     n = len(X)
     WX, WY = X[:, 3], Y[:, 3]
@@ -1631,7 +1697,9 @@ def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUD
     d_leaves = be.upload(leaf_tab)
     d_ops = be.empty(ops_bytes)
     w0 = _prog_w0(band)
-    full, banded = "mprg_align_profile_pairs" + posgap, "mprg_align_profile_pairs" + posgap + "_banded"
+    endgap = "_endgap" if free_end_gaps else ""
+    full, banded = "mprg_align_profile_pairs" + posgap + endgap, "mprg_align_profile_pairs" + posgap + endgap + "_banded"
+    widths = "mprg_prog_band_widths" + (endgap or posgap)
     pending = []                                                # (merges, call, the launch's triples, its table): downloaded at the end
 
     def launches(call, idx, wordsv, dlo=None, dhi=None):
@@ -1650,7 +1718,7 @@ def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUD
         launches(banded, first, pa.band_workspace_words(WX, WY, dlo, dhi), dlo, dhi)
         for sel, _, d_out, d_pairs in list(pending):
             d_got = be.empty(20 * len(sel))                     # {SB, w*} per merge, then the status words
-            be.call("mprg_prog_band_widths" + posgap, be.ptr(d_cols), be.ptr(d_leaves), n, be.ptr(d_cols), words, be.ptr(d_pairs), len(sel),
+            be.call(widths, be.ptr(d_cols), be.ptr(d_leaves), n, be.ptr(d_cols), words, be.ptr(d_pairs), len(sel),
                     be.ptr(d_out), be.ptr(d_got), be.ptr(d_got) + 16 * len(sel), be.stream, work=float((WX[sel] + WY[sel]).sum()))
             got = be.download(d_got, np.uint8, 20 * len(sel))
             status = got[16 * len(sel):].view(np.int32)
@@ -1658,7 +1726,7 @@ def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUD
                 _check(be.download(d_status, np.int32, len(work)), columns, PG_STATUS)
                 res = be.download(d_out, np.int32, 3 * len(sel)).reshape(-1, 3)
                 code = int(res[res[:, 0] != 0][0, 0]) if res[:, 0].any() else int(status[status != 0][0])
-                raise StarAlignError(f"{banded} / mprg_prog_band_widths{posgap}: {pa.STATUS.get(code, code)}")
+                raise StarAlignError(f"{banded} / {widths}: {pa.STATUS.get(code, code)}")
             wstar[sel] = got[:16 * len(sel)].view(np.int64).reshape(-1, 2)[:, 1]
         return wstar, wstar
     if w0 is None:                                              # (one launch: _prog_groups sized the group by this need)
@@ -1677,6 +1745,8 @@ def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUD
         score[sel], count[sel] = res[:, 1], res[:, 2]
     if position_gaps:
         add_to(counters, "position_gap_merges", n)
+    if free_end_gaps:
+        add_to(counters, "free_end_gap_merges", n)
     for key, v in zip(("prog_band_merges", "prog_band_second_passes", "prog_band_full_merges", "prog_band_cells", "prog_band_full_cells"),
                       () if w0 is None else counts):
         add_to(counters, key, int(v))
@@ -1689,11 +1759,12 @@ def _bufs_table(be, bufs):
 
 
 def merge_profiles(backend, pairs: Sequence[Tuple[np.ndarray, np.ndarray]], budget_bytes: int = pa.DEFAULT_BUDGET_BYTES, band=None,
-                   counters: Optional[dict] = None, position_gaps: bool = False):
+                   counters: Optional[dict] = None, position_gaps: bool = False, free_end_gaps: bool = False):
     """mprg_align_profile_pairs on (X, Y) pairs of cell-code matrices (R_X x W_X, R_Y x W_Y), through the launches a round of
     merges makes: per pair (ops as bytes over b"MID" in forward order, score).  band (True: PROG_BAND_W0, or pass 1's half-width):
     the spec's banded two passes, the same results; counters then receives the prog_band_* counts (added up).  position_gaps:
-    the spec's Position gaps (mprg_align_profile_pairs_posgap and the other _posgap entries)."""
+    the spec's Position gaps (mprg_align_profile_pairs_posgap and the other _posgap entries); free_end_gaps: the spec's Free end
+    gaps (the _endgap entries)."""
     be = backend
     mats = [m for xy in pairs for m in xy]
     off = np.concatenate([[0], np.cumsum([m.size for m in mats])]).astype(np.int64)
@@ -1705,7 +1776,7 @@ def merge_profiles(backend, pairs: Sequence[Tuple[np.ndarray, np.ndarray]], budg
     out = [None] * len(pairs)
     for grp in _prog_groups(X[:, 3], Y[:, 3], budget_bytes, band, position_gaps):
         d_ops, ops_bytes, ops_off, count, score = _prog_pairs(be, d_bufs, 1, X[grp], Y[grp], band, budget_bytes, counters,
-                                                              position_gaps=position_gaps)
+                                                              position_gaps=position_gaps, free_end_gaps=free_end_gaps)
         ops = be.download(d_ops, np.uint8, ops_bytes)
         for i, k in enumerate(grp.tolist()):
             out[k] = (ops[ops_off[i]:ops_off[i] + count[i]][::-1].tobytes(), int(score[i]))
@@ -1744,7 +1815,7 @@ def _seq_weight_counters(counters, n_loci, q, spent):
 
 def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression, classes: Optional[Classes] = None, device_tree=False,
                  refine_tree=0, tree_refinement=None, max_leaves=None, retree=0, retreeing=None, seq_weights=False, pair_dist=None,
-                 pair_distancing=None, position_gaps=False):
+                 pair_distancing=None, position_gaps=False, free_end_gaps=False):
     """The spec's Progressive over one chunk, on the (oriented) sequences in chunk.d_codes.  Returns what the star pass leaves: the
     device buffer of the MSAs' ASCII text, its bytes, each locus's offset in it and its width.  classes: the spec's Collapse: the
     tree and the merges over the representatives with their weights, the root's rows written for every member.  device_tree: the
@@ -1754,7 +1825,8 @@ def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression,
     trees that built the texts that are written.  seq_weights: the spec's Sequence weights: q per leaf from the trees, after the
     plan, as the rows' weights in every merge.  pair_dist: the spec's Pair distances: its leaf cap (None: without it);
     pair_distancing receives its tuples.  position_gaps: the spec's Position gaps, in every merge of the three stages below (the
-    pair DPs of pair_dist keep the fixed open)."""
+    pair DPs of pair_dist keep the fixed open); free_end_gaps: the spec's Free end gaps, in the same merges (those pair DPs keep
+    their charged ends)."""
     laps.lap()
     lens, first, counts = chunk.lens, chunk.first, chunk.counts
     acgt = _acgt(chunk) if pair_dist is not None else None
@@ -1815,11 +1887,12 @@ def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression,
         laps.lap("tree_s")
     if pair_dist is not None:
         _pair_dist_report(laps.timings, pair_distancing, how, n_leaves, pair_tables.spent, band)
-    bufs, live, where = _prog_rounds(be, chunk, plan, budget_bytes, band, laps.timings, weights, align=align, position_gaps=position_gaps)
+    bufs, live, where = _prog_rounds(be, chunk, plan, budget_bytes, band, laps.timings, weights, align=align, position_gaps=position_gaps,
+                                     free_end_gaps=free_end_gaps)
     laps.lap("progressive_s")
     if retree:
         plan, result = _retree(be, chunk, plan, bufs, live, where, weights, retree, budget_bytes, band, device_tree, laps.timings, align,
-                               position_gaps)
+                               position_gaps, free_end_gaps)
         if retreeing is not None:
             retreeing.extend(result)
         laps.lap("retree_s")
@@ -1828,7 +1901,7 @@ def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression,
     order = plan[3]
     if refine_tree:
         order, result = _tree_refine(be, chunk, plan, bufs, live, where, weights, refine_tree, max_leaves, budget_bytes, band, laps.timings,
-                                     align, position_gaps)
+                                     align, position_gaps, free_end_gaps)
         if tree_refinement is not None:
             tree_refinement.extend(result)
         laps.lap("tree_refine_s")
@@ -1861,7 +1934,8 @@ def _prog_parents(be, d_bufs, n_bufs, Xg, Yg, d_ops, ops_bytes, ops_off, count):
     return d_new, new_bytes, poff, R
 
 
-def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters, weights=None, beyond=None, align=None, position_gaps=False):
+def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters, weights=None, beyond=None, align=None, position_gaps=False,
+                 free_end_gaps=False):
     """_progressive's device part: the plan's rounds (every node of a round, over all loci of the chunk, in one set of launches
     per budget group).  Returns (bufs, live, where) as the last round left them: of every locus only its root is in where.
     The texts' lifetime: bufs[b] is (buffer, bytes) of text buffer b, 0 the chunk's code buffer (the leaves); where[locus, node]
@@ -1873,7 +1947,8 @@ def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters, weights=N
     of an error: such a locus takes no further merge and none of its nodes stays in where.
     align (the spec's Sequence weights): per record of the chunk's tables the weight q its row has in a merge, in place of the
     multiplicities, which keep their role in the plan.
-    position_gaps (the spec's Position gaps): every merge through _prog_pairs' _posgap calls."""
+    position_gaps (the spec's Position gaps): every merge through _prog_pairs' _posgap calls; free_end_gaps (the spec's Free end
+    gaps): through its _endgap calls."""
     lens, seq_off, first, n_loci = chunk.lens, chunk.seq_off, chunk.first, chunk.n_loci
     leaves, by_round = plan[:2]
     bufs, live = [(chunk.d_codes, chunk.codes_bytes)], [0]
@@ -1909,7 +1984,8 @@ def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters, weights=N
                 wg = ([rw[todo[k][0], todo[k][2]] for k in grp.tolist()], [rw[todo[k][0], todo[k][1]] for k in grp.tolist()])
             if weights is not None:
                 add_to(counters, "collapse_merges", len(grp))
-            d_ops, ops_bytes, ops_off, count, _ = _prog_pairs(be, d_bufs, len(bufs), Xg, Yg, band, budget_bytes, counters, wg, position_gaps)
+            d_ops, ops_bytes, ops_off, count, _ = _prog_pairs(be, d_bufs, len(bufs), Xg, Yg, band, budget_bytes, counters, wg, position_gaps,
+                                                              free_end_gaps)
             d_new, new_bytes, poff, R = _prog_parents(be, d_bufs, len(bufs), Xg, Yg, d_ops, ops_bytes, ops_off, count)
             bufs.append((d_new, new_bytes))
             live.append(len(grp))
@@ -2049,14 +2125,14 @@ def _retree_trees(be, chunk: Chunk, sel, texts, order, bufs, weights, budget_byt
 
 
 def _retree(be, chunk: Chunk, plan, bufs, live, where, weights, rebuilds, budget_bytes, band, device_tree, counters, align=None,
-            position_gaps=False):
+            position_gaps=False, free_end_gaps=False):
     """The spec's Retree over one chunk, on the roots' texts as _prog_rounds left them (bufs, live, where: its state, kept up here
     as _tree_refine keeps it up).  Per iteration all loci that are still iterating go together: the identities and the trees
     (_retree_trees), _prog_plan and _prog_rounds for the loci whose tree changed, from the leaves, into buffers of their own, one
     objective launch, S downloaded; the text that loses goes with its buffer.  Returns (the plan with the accepted trees, their
     row orders and progression tuples in place of the first ones, per locus (iterations, accepted, why it stopped, S before, S
     after)).  align (the spec's Sequence weights): per record its q; a rebuild runs with the q of the rebuilt tree on D', and an
-    accepted locus's entries of align are replaced by them, in place.  position_gaps: _prog_rounds'."""
+    accepted locus's entries of align are replaced by them, in place.  position_gaps, free_end_gaps: _prog_rounds'."""
     lens, first, counts, n_loci = chunk.lens, chunk.first, chunk.counts, chunk.n_loci
     leaves, root = plan[0], plan[2]
     order, trees, progression = [np.array(x, np.int64) for x in plan[3]], list(plan[4]), list(plan[5])
@@ -2098,7 +2174,8 @@ def _retree(be, chunk: Chunk, plan, bufs, live, where, weights, rebuilds, budget
         part = chunk._replace(first=first[todo], counts=counts[todo])
         plan2 = _prog_plan(lens, part.first, part.counts, None, weights, [merges[l] for l in todo])
         beyond = set()
-        bufs2, live2, where2 = _prog_rounds(be, part, plan2, budget_bytes, band, counters, weights, beyond, align2, position_gaps)
+        bufs2, live2, where2 = _prog_rounds(be, part, plan2, budget_bytes, band, counters, weights, beyond, align2, position_gaps,
+                                            free_end_gaps)
         made, new = {}, {}
         for k, l in enumerate(todo):
             if k in beyond:
@@ -2190,14 +2267,14 @@ def _tree_step_fits(WX, WY, budget_words):
 
 
 def _tree_refine(be, chunk: Chunk, plan, bufs, live, where, weights, passes, max_leaves, budget_bytes, band, counters, align=None,
-                 position_gaps=False):
+                 position_gaps=False, free_end_gaps=False):
     """The spec's Tree refinement over one chunk, on the roots' texts as _prog_rounds left them (bufs, live, where: its state, kept
     up here: where[locus, root] names the locus's current text, a buffer is dropped when nothing points to it; weights: per
     record of the chunk's tables, the spec's Collapse).  Step s of every locus that still has one goes together: one split launch,
     the widths downloaded, the merges in _prog_groups' groups through _prog_pairs and _prog_parents, one objective launch, S
     downloaded.  Returns (per locus the records of its text's rows in row order, per locus (steps tried, accepted, skipped, S
     before, S after)).  align (the spec's Sequence weights): per record the q its row has in a realignment, in place of the
-    multiplicities, which keep the choice of Y and the objective.  position_gaps: _prog_pairs'."""
+    multiplicities, which keep the choice of Y and the objective.  position_gaps, free_end_gaps: _prog_pairs'."""
     first, counts, n_loci = chunk.first, chunk.counts, chunk.n_loci
     leaves, root, trees = plan[0], plan[2], plan[4]
     order = [np.array(x, np.int64) for x in plan[3]]
@@ -2263,7 +2340,7 @@ def _tree_refine(be, chunk: Chunk, plan, bufs, live, where, weights, passes, max
                 if weights is not None or align is not None:
                     wg = ([al[its[k]][order[its[k]][sides[k] == 1]] for k in g.tolist()], [al[its[k]][order[its[k]][sides[k] == 0]] for k in g.tolist()])
                 d_ops, ops_bytes, ops_off, count, _ = _prog_pairs(be, d_bufs, len(bufs), X[g], Y[g], band, budget_bytes, counters, wg,
-                                                                  position_gaps)
+                                                                  position_gaps, free_end_gaps)
                 d_new, new_bytes, poff, R = _prog_parents(be, d_bufs, len(bufs), X[g], Y[g], d_ops, ops_bytes, ops_off, count)
                 made.append(add_buf(d_new, new_bytes))
                 for i, k in enumerate(g.tolist()):

@@ -142,6 +142,14 @@ def register_parser(subparsers):
                         "csrc/pg_pairs.inc).  The tree, the row order and the objective are unchanged; the merges of --retree and "
                         "--refine-tree use the same opens, --refine runs afterwards with the fixed open, --band and --device-tree "
                         "give the same bytes.  Off by default")
+    p.add_argument("--free-end-gaps", dest="free_end_gaps", action="store_true", default=False,
+                   help="(this implementation) with --unaligned --progressive: a profile merge is an overlap (semi-global) "
+                        "alignment: the run of one side's columns alone at either end of it costs neither an open nor its "
+                        "columns, instead of being charged like an internal deletion (star_align.py, Free end gaps; "
+                        "csrc/pg_pairs.inc).  For loci with partial records: genes cut at a contig edge, truncated hits.  The tree, "
+                        "the row order and the objective (which keeps charging end runs) are unchanged; the merges of --retree and "
+                        "--refine-tree use the same boundaries, --position-gaps keeps its opens inside, --refine runs afterwards "
+                        "with charged ends, --band and --device-tree give the same bytes.  Off by default")
     p.set_defaults(func=run, check=check_options)
     return p
 
@@ -185,6 +193,8 @@ def check_options(args, parser):
         parser.error("--pair-distances needs --progressive")
     if getattr(args, "position_gaps", False) and not getattr(args, "progressive", False):
         parser.error("--position-gaps needs --progressive")
+    if getattr(args, "free_end_gaps", False) and not getattr(args, "progressive", False):
+        parser.error("--free-end-gaps needs --progressive")
     if getattr(args, "refine", None) is not None:
         if not args.unaligned:
             parser.error("--refine needs --unaligned")
@@ -694,12 +704,13 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
     seq_weights = bool(getattr(options, "seq_weights", False))
     pair_distances = bool(getattr(options, "pair_distances", False))
     position_gaps = bool(getattr(options, "position_gaps", False))
+    free_end_gaps = bool(getattr(options, "free_end_gaps", False))
     for lo in range(0, len(mine), STAR_CHUNK):
         t0 = time.perf_counter()
         recs = [star_align.read_unaligned(f) for f in mine[lo:lo + STAR_CHUNK]]
         t1 = time.perf_counter()
         msas = star_align.star_msas(be, recs, names=loci[lo:lo + STAR_CHUNK], adjust_direction=adjust, orientation=orientation,
-                                    **(dict(band=True) if band else {}), **(dict(timings=counters) if band or collapse or device_tree or refine_tree or retree or seq_weights or pair_distances or position_gaps else {}),
+                                    **(dict(band=True) if band else {}), **(dict(timings=counters) if band or collapse or device_tree or refine_tree or retree or seq_weights or pair_distances or position_gaps or free_end_gaps else {}),
                                     **(dict(collapse=True) if collapse else {}),
                                     **(dict(refine=refine, refinement=refinement) if refine else {}),
                                     **(dict(progressive=True, progression=progression) if progressive else {}),
@@ -709,7 +720,8 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
                                     **(dict(retree=retree) if retree else {}),
                                     **(dict(seq_weights=True) if seq_weights else {}),
                                     **(dict(pair_distances=True) if pair_distances else {}),
-                                    **(dict(position_gaps=True) if position_gaps else {}))
+                                    **(dict(position_gaps=True) if position_gaps else {}),
+                                    **(dict(free_end_gaps=True) if free_end_gaps else {}))
         t2 = time.perf_counter()
         for locus, m in zip(loci[lo:lo + STAR_CHUNK], msas):
             path = out_dir / f"{locus}.fa"
@@ -732,6 +744,8 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
                     f"full DP, {counters.get('prog_band_cells', 0)} of {counters.get('prog_band_full_cells', 0)} DP cells computed")
     if position_gaps:
         logger.info(f"rank {rank}: --position-gaps: {counters.get('position_gap_merges', 0)} merges with opens by occupancy")
+    if free_end_gaps:
+        logger.info(f"rank {rank}: --free-end-gaps: {counters.get('free_end_gap_merges', 0)} merges with free end gaps")
     if pair_distances:
         logger.info(f"rank {rank}: --pair-distances: {counters.get('pair_dist_loci', 0)} loci, {counters.get('pair_dist_pairs', 0)} pairs, "
                     f"{counters.get('pair_dist_cells', 0)} DP cells, {counters.get('pair_dist_above_cap', 0)} above the cap, "

@@ -130,5 +130,37 @@ def diverged_locus(seed: int, n: int, min_len: int = 800, max_len: int = 1200, p
     return seqs, ["".join(x) for x in rows]
 
 
+def fragment_locus(seed: int, n: int, min_len: int = 800, max_len: int = 1200, share: float = 0.3,
+                   keep: Tuple[float, float] = (0.3, 0.8)) -> Tuple[List[str], List[str]]:
+    """(seqs, true_rows): diverged_locus(seed, n, min_len, max_len) with partial records: every record but the first is, with
+    probability `share`, cut to a piece of keep[0] .. keep[1] of its length (at least 20 nt) that keeps its left end, its right end
+    or lies inside, the choice drawn too; the residues cut away become '-' in its true row and all-gap columns are dropped, so the
+    alignment stays TRUE by construction.  The cuts are drawn on a generator of their own (seed ^ 0x5EED), behind diverged_locus'
+    draws, which are untouched: the sequences of `tools/star_measure.py --diverged --fragments`."""
+    import random
+    seqs, rows = diverged_locus(seed, n, min_len, max_len)
+    r = random.Random(seed ^ 0x5EED)
+    out = []
+    for k, row in enumerate(rows):
+        if k > 0 and r.random() < share:                     # record 0 stays whole
+            L = len(seqs[k])
+            m = max(20, int(L * r.uniform(*keep)))
+            side = r.choice("LRB")                           # keep the left end, the right end, or a piece inside
+            a = 0 if side == "L" else (L - m if side == "R" else r.randint(0, L - m))
+            q = -1
+            new = []
+            for ch in row:
+                if ch != "-":
+                    q += 1
+                    new.append(ch if a <= q < a + m else "-")
+                else:
+                    new.append("-")
+            row = "".join(new)
+        out.append(row)
+    cols = [c for c in range(len(out[0])) if any(x[c] != "-" for x in out)]
+    out = ["".join(x[c] for c in cols) for x in out]
+    return [x.replace("-", "") for x in out], out
+
+
 def synth_deep_fasta(seed: int, S: int, C: int) -> str:
     return "".join(f">s{i}\n{r.decode()}\n" for i, r in enumerate(synth_rows_deep(seed, S, C)))

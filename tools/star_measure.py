@@ -48,6 +48,10 @@ same loci without the flag afterwards, pair_dist_loci_changed (the loci whose MS
 pair_dist_loci_lower (by the locus's objective S) and s_total_kmer beside s_total.
 `--position-gaps` (with --progressive): the merges' opens by occupancy (`from_msa --unaligned --progressive --position-gaps`); the
 line then also gives position_gap_merges.
+`--free-end-gaps` (with --progressive): the merges as overlap alignments (`from_msa --unaligned --progressive --free-end-gaps`); the
+line then also gives free_end_gap_merges.
+`--fragments SHARE` (with --diverged): that share of each locus's records but the first is cut to a piece of 30-80 % of its length
+at either end or inside (utils/synthetic.py's fragment_locus, seeded); the truth keeps the cut residues out.
 `--truth`: the MSAs written are scored against the alignment that is true by construction (`compare_msa`'s counts,
 make_prg_amd/from_msa/msa_compare.py, after the timed part): synth_rows' own rows for the config-C-shaped loci, diverged_locus'
 true_rows with --diverged; the line then also gives truth_shared, truth_ref_pairs, truth_test_pairs, truth_ref_columns, truth_kept,
@@ -71,7 +75,7 @@ from make_prg_amd.device import get_backend  # noqa: E402
 from make_prg_amd.from_msa import star_align as sa  # noqa: E402
 from make_prg_amd.subcommands import from_msa  # noqa: E402
 from make_prg_amd.subcommands.output_type import OutputType  # noqa: E402
-from make_prg_amd.utils.synthetic import config_shape, diverged_locus, synth_rows  # noqa: E402
+from make_prg_amd.utils.synthetic import config_shape, diverged_locus, fragment_locus, synth_rows  # noqa: E402
 
 n_loci = int(sys.argv[1]) if len(sys.argv) > 1 and not sys.argv[1].startswith("--") else 1000
 COMPLEMENT = str.maketrans("ACGTRYKMSWN", "TGCAYRMKSWN")
@@ -113,6 +117,12 @@ if pair_distances and not progressive:
 position_gaps = "--position-gaps" in sys.argv
 if position_gaps and not progressive:
     sys.exit("--position-gaps needs --progressive")
+free_end_gaps = "--free-end-gaps" in sys.argv
+if free_end_gaps and not progressive:
+    sys.exit("--free-end-gaps needs --progressive")
+fragments = float(sys.argv[sys.argv.index("--fragments") + 1]) if "--fragments" in sys.argv else None
+if fragments is not None and not diverged:
+    sys.exit("--fragments needs --diverged")
 records = int(sys.argv[sys.argv.index("--records") + 1]) if "--records" in sys.argv else 0
 if records and not diverged:
     sys.exit("--records needs --diverged")
@@ -125,7 +135,8 @@ if large_loci and not (progressive and collapse):
 prog_kw = dict(progressive=True, **(dict(device_tree=True) if device_tree else {}), **(dict(large_loci=True) if large_loci else {}),
                **(dict(refine_tree=refine_tree) if refine_tree else {}), **(dict(retree=retree) if retree else {}),
                **(dict(seq_weights=True) if seq_weights else {}), **(dict(pair_distances=True) if pair_distances else {}),
-               **(dict(position_gaps=True) if position_gaps else {})) if progressive else {}
+               **(dict(position_gaps=True) if position_gaps else {}),
+               **(dict(free_end_gaps=True) if free_end_gaps else {})) if progressive else {}
 
 
 def objectives(be, msas):
@@ -155,7 +166,7 @@ try:
     rng, flipped, true_rows = random.Random(1), [], []
     for seed in range(n_loci):
         if diverged:
-            seqs, rows = diverged_locus(seed, diverged)
+            seqs, rows = diverged_locus(seed, diverged) if fragments is None else fragment_locus(seed, diverged, share=fragments)
         else:
             rows = [r.decode() for r in synth_rows(seed, *config_shape("C", seed))]
             seqs = [r.replace("-", "") for r in rows]
@@ -246,6 +257,10 @@ try:
                      s_total_kmer=sum(s_off))
     if position_gaps:
         extra.update(position_gaps=True)
+    if free_end_gaps:
+        extra.update(free_end_gaps=True)
+    if fragments is not None:
+        extra.update(fragments=fragments)
     if truth:
         from make_prg_amd.from_msa import msa_compare as mc
         from make_prg_amd.msa import MSA
