@@ -635,19 +635,9 @@ def _chunks(codes: List[List[np.ndarray]], limit: int):
         yield lo, len(codes)
 
 
-def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optional[Sequence[str]] = None,
-              budget_bytes: int = pa.DEFAULT_BUDGET_BYTES, chunk_bytes: int = CHUNK_BYTES, timings: Optional[dict] = None,
-              adjust_direction: bool = False, orientation: Optional[list] = None, band=False, refine: int = 0,
-              refinement: Optional[list] = None, progressive: bool = False, progression: Optional[list] = None,
-              max_leaves: Optional[int] = None, collapse: bool = False, device_tree: bool = False, refine_tree: Optional[int] = None,
-              tree_refinement: Optional[list] = None, tree_refine_max_leaves: int = TREE_REFINE_MAX_LEAVES, large_loci: bool = False,
-              max_records: Optional[int] = None, retree: Optional[int] = None, retreeing: Optional[list] = None,
-              seq_weights: bool = False, pair_distances: bool = False, pair_distancing: Optional[list] = None,
-              pair_dist_max_leaves: int = PAIR_DIST_MAX_LEAVES, position_gaps: bool = False,
-              free_end_gaps: bool = False) -> List[MSA]:
-    """loci: per locus its records as (title, sequence).  Returns the loci's centre-star MSAs (ids: the titles' first words,
-    descriptions: the titles).  names: the loci's names for error messages (default: their indices).  timings: a dict that
-    receives the wall seconds of the stages (orient, centre, pairs, merge: each ends at a download, so includes its kernels).
+class Options(NamedTuple):
+    """The settings of star_msas, made once from its keywords and handed down to every stage.  Per keyword, with the list of
+    Reports and the counters of timings that go with it:
     adjust_direction: the spec's Orientation step first; the title of a reversed record gets the prefix _R_.  orientation: a list
     that then receives per locus (reversed: a bool per record, how: a string of one of "-kdt" per record).
     band: the pairs over a certified band (True: profile_align.BAND_W0, or pass 1's half-width); the same MSAs.  timings then also
@@ -706,31 +696,84 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
     differently.
     free_end_gaps: only with progressive (else a ValueError): the spec's Free end gaps: every such merge as an overlap alignment,
     the run of one side's columns alone at either end of it free; with position_gaps too, its opens elsewhere.  timings also
-    receives free_end_gap_merges.  False: nothing launches, uploads or downloads differently."""
-    if device_tree and not progressive:
-        raise ValueError("device_tree: only with progressive")
-    if seq_weights and not progressive:
-        raise ValueError("seq_weights: only with progressive")
-    if pair_distances and not progressive:
-        raise ValueError("pair_distances: only with progressive")
-    if position_gaps and not progressive:
-        raise ValueError("position_gaps: only with progressive")
-    if free_end_gaps and not progressive:
-        raise ValueError("free_end_gaps: only with progressive")
+    receives free_end_gap_merges.  False: nothing launches, uploads or downloads differently.
+    The fields hold them as the stages read them: band is None, True or pass 1's half-width; refine_tree and retree are 0 when off;
+    limits (large_loci, max_records) is None or (max_leaves, max_records); pair_dist (pair_distances, its cap) None or the cap."""
+    budget_bytes: int = pa.DEFAULT_BUDGET_BYTES
+    band: object = None
+    adjust_direction: bool = False
+    refine: int = 0
+    progressive: bool = False
+    max_leaves: int = PROG_MAX_LEAVES
+    collapse: bool = False
+    device_tree: bool = False
+    refine_tree: int = 0
+    tree_refine_max_leaves: int = TREE_REFINE_MAX_LEAVES
+    limits: Optional[Tuple[int, int]] = None
+    retree: int = 0
+    seq_weights: bool = False
+    pair_dist: Optional[int] = None
+    position_gaps: bool = False
+    free_end_gaps: bool = False
+
+    def star(self) -> "Options":
+        """The settings of loci that go to the star pass: none of the options of progressive."""
+        return self._replace(progressive=False, device_tree=False, refine_tree=0, limits=None, retree=0, seq_weights=False, pair_dist=None,
+                             position_gaps=False, free_end_gaps=False)
+
+    def merge(self, counters: Optional[dict]) -> "_Merge":
+        """How the merges of a stage run under these settings, their counters into `counters`."""
+        return _Merge(self.band, self.budget_bytes, counters, self.position_gaps, self.free_end_gaps)
+
+
+class Reports(dict):
+    """The per-locus lists star_msas fills for its caller, by keyword (KEYS); None: the caller did not ask for that one."""
+    KEYS = ("orientation", "refinement", "progression", "tree_refinement", "retreeing", "pair_distancing")
+
+    @classmethod
+    def of(cls, make) -> "Reports":
+        """Lists of the host's own for loci that are aligned in parts: make() for every keyword."""
+        return cls((key, make()) for key in cls.KEYS)
+
+    def add(self, key: str, values):
+        if self[key] is not None:
+            self[key].extend(values)
+
+    def scatter(self, sel, part: "Reports"):
+        """What the stages reported on a part's loci, `sel` of these lists' slots, into those slots (a stage that did not run: nothing)."""
+        for key, vals in part.items():
+            if vals:
+                for k, l in enumerate(sel):
+                    self[key][l] = vals[k]
+
+
+def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optional[Sequence[str]] = None,
+              budget_bytes: int = pa.DEFAULT_BUDGET_BYTES, chunk_bytes: int = CHUNK_BYTES, timings: Optional[dict] = None,
+              adjust_direction: bool = False, orientation: Optional[list] = None, band=False, refine: int = 0,
+              refinement: Optional[list] = None, progressive: bool = False, progression: Optional[list] = None,
+              max_leaves: Optional[int] = None, collapse: bool = False, device_tree: bool = False, refine_tree: Optional[int] = None,
+              tree_refinement: Optional[list] = None, tree_refine_max_leaves: int = TREE_REFINE_MAX_LEAVES, large_loci: bool = False,
+              max_records: Optional[int] = None, retree: Optional[int] = None, retreeing: Optional[list] = None,
+              seq_weights: bool = False, pair_distances: bool = False, pair_distancing: Optional[list] = None,
+              pair_dist_max_leaves: int = PAIR_DIST_MAX_LEAVES, position_gaps: bool = False,
+              free_end_gaps: bool = False) -> List[MSA]:
+    """loci: per locus its records as (title, sequence).  Returns the loci's centre-star MSAs (ids: the titles' first words,
+    descriptions: the titles).  names: the loci's names for error messages (default: their indices).  timings: a dict that
+    receives the wall seconds of the stages (orient, centre, pairs, merge: each ends at a download, so includes its kernels).
+    Every other keyword is a setting, described at Options, or one of the lists of Reports, described there with its setting."""
+    for key, on in (("device_tree", device_tree), ("seq_weights", seq_weights), ("pair_distances", pair_distances),
+                    ("position_gaps", position_gaps), ("free_end_gaps", free_end_gaps)):
+        if on and not progressive:
+            raise ValueError(f"{key}: only with progressive")
     if large_loci and not (progressive and collapse):
         raise ValueError("large_loci: only with progressive and collapse")
     if max_records is not None and not (large_loci and 0 <= int(max_records) <= PROG_MAX_RECORDS):
         raise ValueError(f"max_records: only with large_loci, and at most {PROG_MAX_RECORDS}, not {max_records!r}")
-    if refine_tree is not None:
-        if not progressive:
-            raise ValueError("refine_tree: only with progressive")
-        if not (isinstance(refine_tree, (int, np.integer)) and not isinstance(refine_tree, bool) and 1 <= refine_tree <= TREE_REFINE_MAX):
-            raise ValueError(f"refine_tree: a number of passes from 1 to {TREE_REFINE_MAX}, not {refine_tree!r}")
-    if retree is not None:
-        if not progressive:
-            raise ValueError("retree: only with progressive")
-        if not (isinstance(retree, (int, np.integer)) and not isinstance(retree, bool) and 1 <= retree <= RETREE_MAX):
-            raise ValueError(f"retree: a number of rebuilds from 1 to {RETREE_MAX}, not {retree!r}")
+    for key, n, what, most in (("refine_tree", refine_tree, "passes", TREE_REFINE_MAX), ("retree", retree, "rebuilds", RETREE_MAX)):
+        if n is not None and not progressive:
+            raise ValueError(f"{key}: only with progressive")
+        if n is not None and not (isinstance(n, (int, np.integer)) and not isinstance(n, bool) and 1 <= n <= most):
+            raise ValueError(f"{key}: a number of {what} from 1 to {most}, not {n!r}")
     if not (isinstance(refine, (int, np.integer)) and not isinstance(refine, bool) and 0 <= refine <= REFINE_MAX):
         raise ValueError(f"refine: a number of rounds from 0 to {REFINE_MAX}, not {refine!r}")
     band = None if band is False or band is None else band      # from here on: None, True or pass 1's half-width
@@ -740,98 +783,74 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
             from ..subcommands.from_msa import EmptyMSAError
             raise EmptyMSAError(f"No records found in MSA of locus {name}")
     codes = [locus_codes(n, recs) for n, recs in zip(names, loci)]
+    max_leaves = PROG_MAX_LEAVES if max_leaves is None else int(max_leaves)
+    opts = Options(budget_bytes, band, adjust_direction, int(refine), bool(progressive), max_leaves, bool(collapse), bool(device_tree),
+                   int(refine_tree or 0), int(tree_refine_max_leaves),
+                   (max_leaves, PROG_MAX_RECORDS if max_records is None else int(max_records)) if large_loci else None, int(retree or 0),
+                   bool(seq_weights), int(pair_dist_max_leaves) if pair_distances else None, bool(position_gaps), bool(free_end_gaps))
+    reports = Reports(orientation=orientation, refinement=refinement, progression=progression, tree_refinement=tree_refinement,
+                      retreeing=retreeing, pair_distancing=pair_distancing)
     if progressive:
-        return _progressive_msas(backend, loci, codes, names, budget_bytes, chunk_bytes, timings, adjust_direction, orientation, band,
-                                 int(refine), refinement, progression, PROG_MAX_LEAVES if max_leaves is None else int(max_leaves), bool(collapse),
-                                 bool(device_tree), int(refine_tree or 0), tree_refinement, int(tree_refine_max_leaves),
-                                 (PROG_MAX_RECORDS if max_records is None else int(max_records)) if large_loci else None, int(retree or 0),
-                                 retreeing, bool(seq_weights), int(pair_dist_max_leaves) if pair_distances else None, pair_distancing,
-                                 bool(position_gaps), bool(free_end_gaps))
+        return _progressive_msas(backend, loci, codes, names, opts, chunk_bytes, timings, reports)
     return [m for lo, hi in _chunks(codes, chunk_bytes)
-            for m in _star_chunk(backend, loci[lo:hi], codes[lo:hi], names[lo:hi], budget_bytes, timings, adjust_direction, orientation, band,
-                                 int(refine), refinement, collapse=bool(collapse))]
+            for m in _star_chunk(backend, loci[lo:hi], codes[lo:hi], names[lo:hi], opts, timings, reports)]
 
 
-def _progressive_msas(be, loci, codes, names, budget_bytes, chunk_bytes, timings, adjust_direction, orientation, band, refine, refinement,
-                      progression, max_leaves, collapse=False, device_tree=False, refine_tree=0, tree_refinement=None,
-                      tree_max_leaves=TREE_REFINE_MAX_LEAVES, max_records=None, retree=0, retreeing=None, seq_weights=False,
-                      pair_dist=None, pair_distancing=None, position_gaps=False, free_end_gaps=False) -> List[MSA]:
+def _progressive_msas(be, loci, codes, names, opts: Options, chunk_bytes, timings, reports: Reports) -> List[MSA]:
     """star_msas with progressive: the loci within the leaf limit through the progressive chunks, the others through the star
-    chunks, the results (and what the caller's lists receive) back in the loci's order.  max_records (the spec's Large loci; None:
+    chunks, the results (and what the caller's lists receive) back in the loci's order.  opts.limits (the spec's Large loci; None:
     without it): only the loci of more records go to the star chunks here; the progressive chunks count every locus's classes
     once Collapse has made them and send those above max_leaves through the star pass themselves."""
     n_leaves = [sum(1 for c in cs if len(c)) for cs in codes]
-    out = [None] * len(loci)
-    got = {k: [None] * len(loci) for k in ("orientation", "refinement", "progression", "tree_refinement", "retreeing", "pair_distancing")}
-    limits = None if max_records is None else (max_leaves, max_records)
+    out, got = [None] * len(loci), Reports.of(lambda: [None] * len(loci))
     for prog in (True, False):
-        sel = [l for l in range(len(loci)) if (n_leaves[l] <= max_leaves if limits is None else len(codes[l]) <= max_records) == prog]
+        sel = [l for l in range(len(loci)) if (n_leaves[l] <= opts.max_leaves if opts.limits is None else len(codes[l]) <= opts.limits[1]) == prog]
         sub = [codes[l] for l in sel]
-        ori, ref, pro, tre, ret, pdi, msas = [], [], [], [], [], [], []
+        part, msas = Reports.of(list), []
         for lo, hi in _chunks(sub, chunk_bytes):
             idx = sel[lo:hi]
-            msas.extend(_star_chunk(be, [loci[l] for l in idx], sub[lo:hi], [names[l] for l in idx], budget_bytes, timings, adjust_direction,
-                                    ori if orientation is not None else None, band, refine, ref if refinement is not None else None,
-                                    prog, pro, collapse, device_tree and prog, refine_tree if prog else 0,
-                                    tre if tree_refinement is not None else None, tree_max_leaves, limits if prog else None,
-                                    retree if prog else 0, ret if retreeing is not None else None, seq_weights and prog,
-                                    pair_dist if prog else None, pdi if pair_distancing is not None else None, position_gaps and prog,
-                                    free_end_gaps and prog))
+            msas.extend(_star_chunk(be, [loci[l] for l in idx], sub[lo:hi], [names[l] for l in idx], opts if prog else opts.star(), timings, part))
         if not prog:
-            pro = [(n_leaves[l], 0, True) for l in sel]
+            part["progression"] = [(n_leaves[l], 0, True) for l in sel]
         for k, l in enumerate(sel):
             out[l] = msas[k]
-            for key, vals in (("orientation", ori), ("refinement", ref), ("progression", pro), ("tree_refinement", tre), ("retreeing", ret),
-                              ("pair_distancing", pdi)):
-                if vals:
-                    got[key][l] = vals[k]
-    if limits is not None:
-        built = [l for l in range(len(loci)) if n_leaves[l] > max_leaves and not got["progression"][l][2]]
+        got.scatter(sel, part)
+    progression = got["progression"]
+    if opts.limits is not None:
+        built = [l for l in range(len(loci)) if n_leaves[l] > opts.max_leaves and not progression[l][2]]
         add_to(timings, "large_loci", len(built))
         add_to(timings, "large_records", sum(len(codes[l]) for l in built))
-        add_to(timings, "large_fallbacks", sum(1 for p in got["progression"] if p[2]))
-    for key, dest in (("orientation", orientation), ("refinement", refinement), ("progression", progression),
-                      ("tree_refinement", tree_refinement), ("retreeing", retreeing), ("pair_distancing", pair_distancing)):
-        if dest is not None:
-            dest.extend(got[key])
+        add_to(timings, "large_fallbacks", sum(1 for p in progression if p[2]))
+    for key in Reports.KEYS:
+        reports.add(key, got[key])
     return out
 
 
-def _star_chunk(be, loci, codes, names, budget_bytes, timings=None, adjust_direction=False, orientation=None, band=None, refine=0,
-                refinement=None, progressive=False, progression=None, collapse=False, device_tree=False, refine_tree=0,
-                tree_refinement=None, tree_max_leaves=TREE_REFINE_MAX_LEAVES, limits=None, retree=0, retreeing=None, seq_weights=False,
-                pair_dist=None, pair_distancing=None, position_gaps=False, free_end_gaps=False) -> List[MSA]:
+def _star_chunk(be, loci, codes, names, opts: Options, timings, reports: Reports) -> List[MSA]:
     """One chunk: pack, optionally orient, optionally collapse, the star pass or the progressive one (with its tree refinement),
-    optionally refine, collect.  limits (the spec's Large loci; only with progressive and collapse): (max_leaves, max_records): the
-    loci with more classes of non-empty records, or more records, go through the star pass."""
+    optionally refine, collect.  opts.limits (the spec's Large loci; only with progressive and collapse): (max_leaves, max_records):
+    the loci with more classes of non-empty records, or more records, go through the star pass."""
     laps = _Laps(timings)
     chunk = _pack(be, codes, names, [[t for t, _ in recs] for recs in loci])
-    if adjust_direction:
-        chunk, result = _orient(be, chunk, budget_bytes)
-        if orientation is not None:
-            orientation.extend(result)
+    if opts.adjust_direction:
+        chunk, result = _orient(be, chunk, opts.budget_bytes)
+        reports.add("orientation", result)
         laps.lap("orient_s")
-    classes = _collapse(be, chunk, laps) if collapse else None
-    if limits is not None:
+    classes = _collapse(be, chunk, laps) if opts.collapse else None
+    if opts.limits is not None:
         n_classes = np.add.reduceat(((classes.weight > 0) & (chunk.lens > 0)).astype(np.int64), chunk.first)
-        build = (n_classes <= limits[0]) & (chunk.counts <= limits[1])
+        build = (n_classes <= opts.limits[0]) & (chunk.counts <= opts.limits[1])
         if not build.all():
-            return _star_chunk_parts(be, chunk, classes, build, budget_bytes, laps, band, refine, refinement, progression, device_tree,
-                                     refine_tree, tree_refinement, tree_max_leaves, retree, retreeing, seq_weights, pair_dist, pair_distancing,
-                                     position_gaps, free_end_gaps)
-    return _star_chunk_rest(be, chunk, classes, budget_bytes, laps, band, refine, refinement, progressive, progression, device_tree,
-                            refine_tree, tree_refinement, tree_max_leaves, retree, retreeing, seq_weights, pair_dist, pair_distancing,
-                            position_gaps, free_end_gaps)
+            return _star_chunk_parts(be, chunk, classes, build, opts, laps, reports)
+    return _star_chunk_rest(be, chunk, classes, opts, laps, reports)
 
 
-def _star_chunk_parts(be, chunk: Chunk, classes, build, budget_bytes, laps, band, refine, refinement, progression, device_tree,
-                      refine_tree, tree_refinement, tree_max_leaves, retree=0, retreeing=None, seq_weights=False, pair_dist=None,
-                      pair_distancing=None, position_gaps=False, free_end_gaps=False) -> List[MSA]:
+def _star_chunk_parts(be, chunk: Chunk, classes, build, opts: Options, laps, reports: Reports) -> List[MSA]:
     """_star_chunk behind Collapse for a chunk of which only the loci `build` (a bool per locus) are built progressively (the spec's
     Large loci): those as one chunk through the progressive pass, the others as one through the star pass, both over the same code
     buffer and the classes already made; the MSAs, and what the caller's lists receive, back in the chunk's order."""
     n_filled = np.add.reduceat((chunk.lens > 0).astype(np.int64), chunk.first)
-    msas, ref, pro, tre, ret, pdi = ([None] * chunk.n_loci for _ in range(6))
+    msas, got = [None] * chunk.n_loci, Reports.of(lambda: [None] * chunk.n_loci)
     for prog in (True, False):
         sel = np.nonzero(build == prog)[0]
         if not len(sel):
@@ -841,43 +860,32 @@ def _star_chunk_parts(be, chunk: Chunk, classes, build, budget_bytes, laps, band
         at[rec] = np.arange(len(rec))
         part = chunk._replace(names=[chunk.names[l] for l in sel], titles=[chunk.titles[l] for l in sel], codes=[chunk.codes[l] for l in sel],
                               lens=chunk.lens[rec], seq_off=chunk.seq_off[rec], first=exclusive_sum(chunk.counts[sel]), counts=chunk.counts[sel])
-        got = [[], [], [], [], []]
-        out = _star_chunk_rest(be, part, Classes(at[classes.rep[rec]], classes.weight[rec]), budget_bytes, laps, band, refine, got[0], prog,
-                               got[1], device_tree and prog, refine_tree if prog else 0, got[2], tree_max_leaves, retree if prog else 0, got[3],
-                               seq_weights and prog, pair_dist if prog else None, got[4], position_gaps and prog,
-                               free_end_gaps and prog)
+        mine = Reports.of(list)
+        out = _star_chunk_rest(be, part, Classes(at[classes.rep[rec]], classes.weight[rec]), opts if prog else opts.star(), laps, mine)
         if not prog:
-            got[1] = [(int(n_filled[l]), 0, True) for l in sel]
+            mine["progression"] = [(int(n_filled[l]), 0, True) for l in sel]
         for k, l in enumerate(sel.tolist()):
             msas[l] = out[k]
-            for dest, vals in zip((ref, pro, tre, ret, pdi), got):
-                if vals:
-                    dest[l] = vals[k]
-    for dest, vals, wanted in ((refinement, ref, refine), (progression, pro, True), (tree_refinement, tre, refine_tree), (retreeing, ret, retree),
-                               (pair_distancing, pdi, pair_dist is not None)):
-        if dest is not None and wanted:
-            dest.extend(vals)
+        got.scatter(sel.tolist(), mine)
+    # (orientation has been reported for the whole chunk; every other list only when its stage was asked for)
+    for key, asked in (("refinement", opts.refine), ("progression", True), ("tree_refinement", opts.refine_tree), ("retreeing", opts.retree),
+                       ("pair_distancing", opts.pair_dist is not None)):
+        if asked:
+            reports.add(key, got[key])
     return msas
 
 
-def _star_chunk_rest(be, chunk: Chunk, classes, budget_bytes, laps, band, refine, refinement, progressive, progression, device_tree,
-                     refine_tree, tree_refinement, tree_max_leaves, retree=0, retreeing=None, seq_weights=False, pair_dist=None,
-                     pair_distancing=None, position_gaps=False, free_end_gaps=False) -> List[MSA]:
+def _star_chunk_rest(be, chunk: Chunk, classes, opts: Options, laps, reports: Reports) -> List[MSA]:
     """_star_chunk behind Collapse: the star pass or the progressive one (with its tree refinement), optionally refine, collect."""
-    timings = laps.timings
-    text = (_progressive(be, chunk, budget_bytes, band, laps, progression, classes, device_tree, refine_tree, tree_refinement,
-                         tree_max_leaves, retree, retreeing, seq_weights, pair_dist, pair_distancing, position_gaps,
-                         free_end_gaps) if progressive else
-            _star_pass(be, chunk, budget_bytes, band, laps, classes))
+    text = _progressive(be, chunk, opts, laps, reports, classes) if opts.progressive else _star_pass(be, chunk, opts.budget_bytes, opts.band, laps, classes)
     moved = {}
-    if refine:
-        res = _refine(be, chunk, text, refine, budget_bytes, band, timings)
+    if opts.refine:
+        res = _refine(be, chunk, text, opts.refine, opts.budget_bytes, opts.band, laps.timings)
         moved = {l: r[3] for l, r in enumerate(res) if r[3] is not None}
-        if refinement is not None:
-            refinement.extend(r[:3] for r in res)
+        reports.add("refinement", (r[:3] for r in res))
         laps.lap("refine_s")
     msas = _collect(be, chunk, text, moved)
-    laps.lap(None if progressive else "merge_s")                # (merge_s ends at the star MSAs' download)
+    laps.lap(None if opts.progressive else "merge_s")           # (merge_s ends at the star MSAs' download)
     return msas
 
 
@@ -1357,12 +1365,12 @@ def prog_weights_words(m):
     return 6 * m
 
 
-def _prog_trees(be, chunk: Chunk, sel, budget_bytes, weights=None, seq_weights: Optional["_LeafWeights"] = None, tables=None):
+def _prog_trees(be, chunk: Chunk, sel, budget_bytes, weights=None, lw: Optional["_LeafWeights"] = None, tables=None):
     """The spec's Tree of the loci `sel` of a chunk on the device, in groups whose m x m tables and tree workspaces fit budget_bytes:
     per group one mprg_prog_distances launch and one mprg_prog_tree launch over the tables it left on the device; the status words
     and the merges are all that is downloaded.  Per locus its merges as prog_tree gives them.  weights: per record of the chunk's
     tables how many times it counts (the spec's Collapse).  The loci whose weight sum exceeds PROG_MAX_LEAVES (the spec's Large
-    loci) form groups of their own, whose trees mprg_prog_tree_wide builds.  seq_weights (the spec's Sequence weights): every group
+    loci) form groups of their own, whose trees mprg_prog_tree_wide builds.  lw (the spec's Sequence weights): every group
     is followed by an mprg_prog_leaf_weights launch over the same tables and the merges where the tree launch left them.  tables:
     another source of the tables, called like _distances_launch (the spec's Pair distances)."""
     lens, first = chunk.lens, chunk.first
@@ -1375,8 +1383,8 @@ def _prog_trees(be, chunk: Chunk, sel, budget_bytes, weights=None, seq_weights: 
     for grp, entry, table in _tree_groups(chunk, sel, budget_bytes, weights):
         m, toff, words, d_shared, d_nw, d_status, n_work = (tables or _distances_launch)(be, chunk, d_seqs, grp)
         launched = _tree_launch(be, chunk, grp, entry, d_seqs, d_weights, n_leaves, toff, words, d_shared, d_nw)
-        if seq_weights is not None:
-            seq_weights.launch(grp, d_seqs, d_weights, toff, words, d_shared, d_nw, *launched[1:])
+        if lw is not None:
+            lw.launch(grp, d_seqs, d_weights, toff, words, d_shared, d_nw, *launched[1:])
         _check(be.download(d_status, np.int32, n_work), "mprg_prog_distances", PG_STATUS)
         out.update(_tree_merges(be, grp, entry, table, *launched))
     return out
@@ -1595,12 +1603,22 @@ def prog_tree(D: np.ndarray, leaves: Sequence[int], weights=None) -> List[Tuple[
     return merges
 
 
-def _prog_plan(lens, first, counts, shared, weights=None, merges=None):
-    """What the spec's Tree decides for a chunk, from its tables and _prog_shared's of the loci of three or more leaves (two leaves
-    have one tree); no device, no clock.  A leaf's node id is its record index, an inner node's counts on from the locus's records.
-    Returns (per locus its leaves: the non-empty records; per round its merges (locus, y, x, parent), Y the child with more rows;
-    per locus its root node; per locus the records of the root's rows in row order: Y's rows, then X's, at every node; per locus
-    its tree: the merges (key(U), key(V)) in the order UPGMA made them; per locus the progression tuple (leaves, rounds, False)).
+class Plan(NamedTuple):
+    """What the spec's Tree decides for a chunk (_prog_plan): leaves: per locus the non-empty records; by_round: per round its merges
+    (locus, y, x, parent), Y the child with more rows; root: per locus its root node; order: per locus the records of the root's
+    rows in row order: Y's rows, then X's, at every node; trees: per locus the merges (key(U), key(V)) in the order UPGMA made
+    them; progression: per locus the tuple (leaves, rounds, False)."""
+    leaves: list
+    by_round: dict
+    root: list
+    order: list
+    trees: list
+    progression: list
+
+
+def _prog_plan(lens, first, counts, shared, weights=None, merges=None) -> Plan:
+    """The Plan of a chunk, from its tables and _prog_shared's of the loci of three or more leaves (two leaves have one tree); no
+    device, no clock.  A leaf's node id is its record index, an inner node's counts on from the locus's records.
     weights: per record of the tables how many rows it stands for (the spec's Collapse): the tree is the weighted one and Y the
     child with the larger weight sum.  merges: per locus of three or more leaves its tree as _prog_trees gave it; `shared` is then
     not read."""
@@ -1627,7 +1645,7 @@ def _prog_plan(lens, first, counts, shared, weights=None, merges=None):
         root_members.append(members[roots[-1]])
         trees.append(tree)
         progression.append((len(lv), rnd[roots[-1]], False))
-    return leaves, by_round, roots, root_members, trees, progression
+    return Plan(leaves, by_round, roots, root_members, trees, progression)
 
 
 def _prog_w0(band):
@@ -1640,29 +1658,50 @@ def _prog_w0(band):
     return w0
 
 
-def _prog_groups(WX, WY, budget_bytes, band=None, position_gaps=False):
+class _Merge(NamedTuple):
+    """How the merges of a stage run (Options.merge); counters: the dict that receives their counters, or None."""
+    band: object = None
+    budget_bytes: int = pa.DEFAULT_BUDGET_BYTES
+    counters: Optional[dict] = None
+    position_gaps: bool = False
+    free_end_gaps: bool = False
+
+    def group(self, be, texts: "_Texts", X, Y, weights=None, reuse=True) -> list:
+        """One budget group of merges end to end: X, Y (n, 4) int64 {buffer, offset, R, W} of the two sides' texts in `texts`.  The
+        table of the buffers uploaded, _prog_pairs, _prog_parents into a buffer of the group's own, which joins `texts` (reuse: in a
+        dropped buffer's place if there is one).  Returns per merge the parent's (buffer, offset, rows, width); the caller places
+        them.  weights: _prog_pairs'."""
+        d_bufs, n_bufs = texts.table(be), len(texts.bufs)
+        d_ops, ops_bytes, ops_off, count, _ = _prog_pairs(be, d_bufs, n_bufs, X, Y, self, weights)
+        d_new, new_bytes, poff, R = _prog_parents(be, d_bufs, n_bufs, X, Y, d_ops, ops_bytes, ops_off, count)
+        b = texts.add(d_new, new_bytes, reuse)
+        return [(b, int(poff[i]), int(R[i]), int(count[i])) for i in range(len(X))]
+
+
+def _prog_groups(WX, WY, merge: _Merge):
     """The merges (X's and Y's columns) longest first in groups whose workspace and column tables each fit the budget; with band
-    the workspace is pass 1's (the full DP's for a merge its band does not help).  position_gaps: Y's profile has 7 planes."""
+    the workspace is pass 1's (the full DP's for a merge its band does not help).  merge.position_gaps: Y's profile has 7 planes."""
     order = np.argsort(-((WX + 1) * WY), kind="stable")
-    need, w0 = pa.workspace_words_v(WX, WY), _prog_w0(band)
+    need, w0 = pa.workspace_words_v(WX, WY), _prog_w0(merge.band)
     if w0 is not None:
         dlo, dhi, helps = pa.band_first(WX, WY, w0)
         need = np.where(helps, pa.band_workspace_words(WX, WY, dlo, dhi), need)
-    for grp, _, _ in pa.budget_launches(order, need, budget_bytes, StarAlignError, "merge", WX, WY, also=7 * WX + (7 if position_gaps else 6) * WY):
+    for grp, _, _ in pa.budget_launches(order, need, merge.budget_bytes, StarAlignError, "merge", WX, WY,
+                                        also=7 * WX + (7 if merge.position_gaps else 6) * WY):
         yield grp
 
 
-def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUDGET_BYTES, counters=None, weights=None, position_gaps=False,
-                free_end_gaps=False):
+def _prog_pairs(be, d_bufs, n_bufs, X, Y, merge: _Merge = _Merge(), weights=None):
     """One group of merges on the device: X, Y (n, 4) int64 {buffer, offset, R, W} of the two sides' texts.  mprg_prog_columns (Y's
-    profiles, X's column tables) and mprg_align_profile_pairs in one launch each; {status, score, op count} downloaded.  With band
-    the spec's two passes instead (the module docstring, host side), counters receiving the prog_band_* counts.
+    profiles, X's column tables) and mprg_align_profile_pairs in one launch each; {status, score, op count} downloaded.  With
+    merge.band the spec's two passes instead (the module docstring, host side), merge.counters receiving the prog_band_* counts.
     weights: (per merge the weights of X's rows, of Y's rows), the spec's Collapse: the column tables through
     mprg_prog_columns_weighted and R_X the weight sum; everything else is the same.
-    position_gaps (the spec's Position gaps): Y's profile gets its seventh plane (kind 2) and every call its _posgap form.
-    free_end_gaps (the spec's Free end gaps): the DP calls get their _endgap form (of either open) and the widths come from
+    merge.position_gaps (the spec's Position gaps): Y's profile gets its seventh plane (kind 2) and every call its _posgap form.
+    merge.free_end_gaps (the spec's Free end gaps): the DP calls get their _endgap form (of either open) and the widths come from
     mprg_prog_band_widths_endgap (one entry for both opens); the column tables, the sizing and the groups are unchanged.
     Returns (the ops buffer, its bytes, each merge's ops offset, op count, score)."""
+    band, budget_bytes, counters, position_gaps, free_end_gaps = merge
     n = len(X)
     WX, WY = X[:, 3], Y[:, 3]
     k = np.nonzero(WX + WY >= pa.MAX_LEN)[0]
@@ -1683,13 +1722,10 @@ def _prog_pairs(be, d_bufs, n_bufs, X, Y, band=None, budget_bytes=pa.DEFAULT_BUD
         items[:, 6], items[:, 7] = exclusive_sum(items[:, 2]), [int(w.sum()) for w in per_item]
         RX, columns = items[n:, 7], "mprg_prog_columns_weighted" + posgap
     d_items, d_work, d_cols, d_status = be.upload(items), be.upload(work), be.empty(4 * words), be.empty(4 * len(work))
-    if weights is None:
-        be.call("mprg_prog_columns" + posgap, be.ptr(d_bufs), n_bufs, be.ptr(d_items), len(items), be.ptr(d_work), len(work), be.ptr(d_cols), words,
-                be.ptr(d_status), be.stream, work=float((items[:, 2] * items[:, 3]).sum()))
-    else:
-        d_weights = be.upload(flat)
-        be.call("mprg_prog_columns_weighted" + posgap, be.ptr(d_bufs), n_bufs, be.ptr(d_items), len(items), be.ptr(d_work), len(work), be.ptr(d_weights),
-                len(flat), be.ptr(d_cols), words, be.ptr(d_status), be.stream, work=float((items[:, 2] * items[:, 3]).sum()))
+    d_weights = None if weights is None else be.upload(flat)    # (the weighted entry takes the rows' weights in front of the tables)
+    be.call(columns, be.ptr(d_bufs), n_bufs, be.ptr(d_items), len(items), be.ptr(d_work), len(work),
+            *(() if weights is None else (be.ptr(d_weights), len(flat))), be.ptr(d_cols), words, be.ptr(d_status), be.stream,
+            work=float((items[:, 2] * items[:, 3]).sum()))
     need = pa.workspace_words_v(WX, WY)
     ops_off = exclusive_sum(WX + WY)
     ops_bytes = int((WX + WY).sum())
@@ -1758,6 +1794,48 @@ def _bufs_table(be, bufs):
     return be.upload(np.array([[be.ptr(b), n] if b is not None else [0, 0] for b, n in bufs], np.int64))
 
 
+class _Texts:
+    """The texts of a chunk's nodes on the device and their lifetime: bufs[b] is (buffer, bytes) of text buffer b, 0 the chunk's
+    code buffer (the leaves), (None, 0) a dropped one; where[locus, node] is (b, offset, rows, width) of a node not yet merged
+    (behind the last round: of every locus its root, whose entry then names the locus's current text); live[b] counts the nodes
+    of where in b.  A buffer (but 0) is dropped when nothing of where is in it."""
+
+    def __init__(self, chunk: Chunk, leaves):
+        lens, seq_off, first = chunk.lens, chunk.seq_off, chunk.first
+        self.where = {(l, a): (0, int(seq_off[first[l] + a]), 1, int(lens[first[l] + a])) for l in range(chunk.n_loci) for a in leaves[l]}
+        self.bufs, self.live = [(chunk.d_codes, chunk.codes_bytes)], [len(self.where)]
+
+    def table(self, be):
+        return _bufs_table(be, self.bufs)
+
+    def add(self, buf, nbytes, reuse=True) -> int:
+        """The buffer's index in bufs: with reuse a dropped buffer's place if there is one (the rounds number theirs as they come)."""
+        b = next((i for i in range(1, len(self.bufs)) if self.bufs[i][0] is None), len(self.bufs)) if reuse else len(self.bufs)
+        if b == len(self.bufs):
+            self.bufs.append(None)
+            self.live.append(0)
+        self.bufs[b], self.live[b] = (buf, nbytes), 0
+        return b
+
+    def place(self, locus, node, text):
+        """The node's text is `text` (b, offset, rows, width) from now on, in place of the one it had."""
+        if (locus, node) in self.where:
+            self.live[self.where[locus, node][0]] -= 1
+        self.where[locus, node] = text
+        self.live[text[0]] += 1
+
+    def merged(self, locus, node):
+        """The node has gone into its parent: its buffer goes with its last node."""
+        b = self.where.pop((locus, node))[0]
+        self.live[b] -= 1
+        self.drop_unused([b])
+
+    def drop_unused(self, bs):
+        for b in bs:
+            if b and not self.live[b]:
+                self.bufs[b] = (None, 0)
+
+
 def merge_profiles(backend, pairs: Sequence[Tuple[np.ndarray, np.ndarray]], budget_bytes: int = pa.DEFAULT_BUDGET_BYTES, band=None,
                    counters: Optional[dict] = None, position_gaps: bool = False, free_end_gaps: bool = False):
     """mprg_align_profile_pairs on (X, Y) pairs of cell-code matrices (R_X x W_X, R_Y x W_Y), through the launches a round of
@@ -1774,9 +1852,9 @@ def merge_profiles(backend, pairs: Sequence[Tuple[np.ndarray, np.ndarray]], budg
     X = np.array([[0, off[2 * k], *pairs[k][0].shape] for k in range(len(pairs))], np.int64).reshape(-1, 4)
     Y = np.array([[0, off[2 * k + 1], *pairs[k][1].shape] for k in range(len(pairs))], np.int64).reshape(-1, 4)
     out = [None] * len(pairs)
-    for grp in _prog_groups(X[:, 3], Y[:, 3], budget_bytes, band, position_gaps):
-        d_ops, ops_bytes, ops_off, count, score = _prog_pairs(be, d_bufs, 1, X[grp], Y[grp], band, budget_bytes, counters,
-                                                              position_gaps=position_gaps, free_end_gaps=free_end_gaps)
+    merge = _Merge(band, budget_bytes, counters, position_gaps, free_end_gaps)
+    for grp in _prog_groups(X[:, 3], Y[:, 3], merge):
+        d_ops, ops_bytes, ops_off, count, score = _prog_pairs(be, d_bufs, 1, X[grp], Y[grp], merge)
         ops = be.download(d_ops, np.uint8, ops_bytes)
         for i, k in enumerate(grp.tolist()):
             out[k] = (ops[ops_off[i]:ops_off[i] + count[i]][::-1].tobytes(), int(score[i]))
@@ -1794,15 +1872,14 @@ def _pair_dist_how(chunk: Chunk, n_leaves, cap: int) -> list:
     return how
 
 
-def _pair_dist_report(counters, pair_distancing, how, n_leaves, spent, band=None):
+def _pair_dist_report(counters, reports: Reports, how, n_leaves, spent, band=None):
     """The spec's Pair distances in the counters and in the caller's list: per locus (leaves, pairs run, how)."""
     add_to(counters, "pair_dist_s", float(spent))
     for key in ("pair_dist_pairs", "pair_dist_cells") + (("pair_dist_second_passes", "pair_dist_full_pairs") if band is not None else ()):
         add_to(counters, key, 0)
     for key, word in (("pair_dist_loci", "pairs"), ("pair_dist_above_cap", "cap"), ("pair_dist_limit", "limit")):
         add_to(counters, key, sum(1 for h in how if h == word))
-    if pair_distancing is not None:
-        pair_distancing.extend((int(n), int(n) * (int(n) - 1) // 2 if h == "pairs" else 0, h) for n, h in zip(n_leaves, how))
+    reports.add("pair_distancing", ((int(n), int(n) * (int(n) - 1) // 2 if h == "pairs" else 0, h) for n, h in zip(n_leaves, how)))
 
 
 def _seq_weight_counters(counters, n_loci, q, spent):
@@ -1813,21 +1890,17 @@ def _seq_weight_counters(counters, n_loci, q, spent):
         counters["seq_weight_min_q"] = min(int(counters.get("seq_weight_min_q", SEQ_WEIGHT_UNIT)), int(q.min()))
 
 
-def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression, classes: Optional[Classes] = None, device_tree=False,
-                 refine_tree=0, tree_refinement=None, max_leaves=None, retree=0, retreeing=None, seq_weights=False, pair_dist=None,
-                 pair_distancing=None, position_gaps=False, free_end_gaps=False):
+def _progressive(be, chunk: Chunk, opts: Options, laps: _Laps, reports: Reports, classes: Optional[Classes] = None):
     """The spec's Progressive over one chunk, on the (oriented) sequences in chunk.d_codes.  Returns what the star pass leaves: the
     device buffer of the MSAs' ASCII text, its bytes, each locus's offset in it and its width.  classes: the spec's Collapse: the
-    tree and the merges over the representatives with their weights, the root's rows written for every member.  device_tree: the
-    trees by mprg_prog_tree (_prog_trees) instead of prog_tree.  refine_tree: the passes of the spec's Tree refinement on the
-    roots' texts before they are written out (0: none); tree_refinement receives its tuples, max_leaves is its cap.  retree: the
-    rebuilds of the spec's Retree, in front of that (0: none); retreeing receives its tuples, progression then the tuples of the
-    trees that built the texts that are written.  seq_weights: the spec's Sequence weights: q per leaf from the trees, after the
-    plan, as the rows' weights in every merge.  pair_dist: the spec's Pair distances: its leaf cap (None: without it);
-    pair_distancing receives its tuples.  position_gaps: the spec's Position gaps, in every merge of the three stages below (the
-    pair DPs of pair_dist keep the fixed open); free_end_gaps: the spec's Free end gaps, in the same merges (those pair DPs keep
-    their charged ends)."""
+    tree and the merges over the representatives with their weights, the root's rows written for every member.  Of opts:
+    device_tree: the trees by mprg_prog_tree (_prog_trees) instead of prog_tree; pair_dist: their tables from the pair scores;
+    seq_weights: q per leaf from the trees, after the plan, as the rows' weights in every merge; retree, then refine_tree, on the
+    roots' texts before they are written out (progression then reports the trees that built the texts that are written);
+    position_gaps and free_end_gaps in every merge of these three stages (the pair DPs of pair_dist keep the fixed open and their
+    charged ends)."""
     laps.lap()
+    budget_bytes, band, device_tree, seq_weights, pair_dist = opts.budget_bytes, opts.band, opts.device_tree, opts.seq_weights, opts.pair_dist
     lens, first, counts = chunk.lens, chunk.first, chunk.counts
     acgt = _acgt(chunk) if pair_dist is not None else None
     n_leaves = np.add.reduceat((lens > 0).astype(np.int64), first)          # (every locus has a record)
@@ -1880,32 +1953,26 @@ def _progressive(be, chunk: Chunk, budget_bytes, band, laps: _Laps, progression,
         if len(sel):
             for part, tables in () if device_tree else parts:
                 if len(part):
-                    lw = _prog_weights(be, chunk, part, plan[4], budget_bytes, weights, tables, lw)
+                    lw = _prog_weights(be, chunk, part, plan.trees, budget_bytes, weights, tables, lw)
             rec = _ranges(first[sel], counts[sel])
             align[rec] = np.maximum(lw.q()[rec], 1)            # (an empty record has no row: its entry is never read)
             _seq_weight_counters(laps.timings, len(sel), align[rec][lens[rec] > 0], lw.spent)
         laps.lap("tree_s")
     if pair_dist is not None:
-        _pair_dist_report(laps.timings, pair_distancing, how, n_leaves, pair_tables.spent, band)
-    bufs, live, where = _prog_rounds(be, chunk, plan, budget_bytes, band, laps.timings, weights, align=align, position_gaps=position_gaps,
-                                     free_end_gaps=free_end_gaps)
+        _pair_dist_report(laps.timings, reports, how, n_leaves, pair_tables.spent, band)
+    texts = _prog_rounds(be, chunk, plan, opts.merge(laps.timings), weights, align=align)
     laps.lap("progressive_s")
-    if retree:
-        plan, result = _retree(be, chunk, plan, bufs, live, where, weights, retree, budget_bytes, band, device_tree, laps.timings, align,
-                               position_gaps, free_end_gaps)
-        if retreeing is not None:
-            retreeing.extend(result)
+    if opts.retree:
+        plan, result = _retree(be, chunk, plan, texts, weights, opts, laps.timings, align)
+        reports.add("retreeing", result)
         laps.lap("retree_s")
-    if progression is not None:
-        progression.extend(plan[-1])
-    order = plan[3]
-    if refine_tree:
-        order, result = _tree_refine(be, chunk, plan, bufs, live, where, weights, refine_tree, max_leaves, budget_bytes, band, laps.timings,
-                                     align, position_gaps, free_end_gaps)
-        if tree_refinement is not None:
-            tree_refinement.extend(result)
+    reports.add("progression", plan.progression)
+    order = plan.order
+    if opts.refine_tree:
+        order, result = _tree_refine(be, chunk, plan, texts, weights, opts, laps.timings, align)
+        reports.add("tree_refinement", result)
         laps.lap("tree_refine_s")
-    text = _prog_output(be, chunk, plan[2], order, bufs, where, expand)
+    text = _prog_output(be, chunk, plan.root, order, texts, expand)
     laps.lap("progressive_s")
     return text
 
@@ -1934,77 +2001,56 @@ def _prog_parents(be, d_bufs, n_bufs, Xg, Yg, d_ops, ops_bytes, ops_off, count):
     return d_new, new_bytes, poff, R
 
 
-def _prog_rounds(be, chunk: Chunk, plan, budget_bytes, band, counters, weights=None, beyond=None, align=None, position_gaps=False,
-                 free_end_gaps=False):
+def _prog_rounds(be, chunk: Chunk, plan: Plan, merge: _Merge, weights=None, beyond=None, align=None) -> _Texts:
     """_progressive's device part: the plan's rounds (every node of a round, over all loci of the chunk, in one set of launches
-    per budget group).  Returns (bufs, live, where) as the last round left them: of every locus only its root is in where.
-    The texts' lifetime: bufs[b] is (buffer, bytes) of text buffer b, 0 the chunk's code buffer (the leaves); where[locus, node]
-    is (b, offset, rows, width) of a node not yet merged; live[b] counts the nodes of where in b.  A group's parents go into a
-    buffer of their own; a buffer (but 0) is dropped when its last node has been merged into a parent.
+    per budget group, _Merge.group).  Returns the texts as the last round left them: of every locus only its root is in where.
+    A group's parents go into a buffer of their own; a buffer (but 0) is dropped when its last node has been merged into a parent.
     weights (the spec's Collapse): the chunk's tables hold the representatives only, weights per record of them; rw[locus, node]
     then is the weights of the node's rows.
     beyond (the spec's Retree): a set that receives the loci with a merge beyond Tree refinement's Limit (_tree_step_fits) instead
     of an error: such a locus takes no further merge and none of its nodes stays in where.
     align (the spec's Sequence weights): per record of the chunk's tables the weight q its row has in a merge, in place of the
-    multiplicities, which keep their role in the plan.
-    position_gaps (the spec's Position gaps): every merge through _prog_pairs' _posgap calls; free_end_gaps (the spec's Free end
-    gaps): through its _endgap calls."""
-    lens, seq_off, first, n_loci = chunk.lens, chunk.seq_off, chunk.first, chunk.n_loci
-    leaves, by_round = plan[:2]
-    bufs, live = [(chunk.d_codes, chunk.codes_bytes)], [0]
-    where = {(l, a): (0, int(seq_off[first[l] + a]), 1, int(lens[first[l] + a])) for l in range(n_loci) for a in leaves[l]}
+    multiplicities, which keep their role in the plan."""
+    first, n_loci = chunk.first, chunk.n_loci
+    texts = _Texts(chunk, plan.leaves)
+    where = texts.where
     row_w = weights if align is None else align
-    rw = {} if row_w is None else {(l, a): row_w[first[l] + a:first[l] + a + 1] for l in range(n_loci) for a in leaves[l]}
-
-    def merged(l, node):
-        """The node has gone into its parent: its buffer goes with its last node."""
-        b = where.pop((l, node))[0]
-        live[b] -= 1
-        if b and not live[b]:
-            bufs[b] = (None, 0)
-
-    for _, todo in sorted(by_round.items()):
+    rw = {} if row_w is None else {(l, a): row_w[first[l] + a:first[l] + a + 1] for l in range(n_loci) for a in plan.leaves[l]}
+    for _, todo in sorted(plan.by_round.items()):
         if beyond is not None:
             todo = [t for t in todo if t[0] not in beyond]
             fits = _tree_step_fits(np.array([where[l, x][3] for l, _, x, _ in todo], np.int64),
-                                   np.array([where[l, y][3] for l, y, _, _ in todo], np.int64), max(64, int(budget_bytes) // 4))
+                                   np.array([where[l, y][3] for l, y, _, _ in todo], np.int64), max(64, int(merge.budget_bytes) // 4))
             beyond.update(t[0] for t, ok in zip(todo, fits.tolist()) if not ok)
             for key in [key for key in where if key[0] in beyond]:
-                merged(*key)
+                texts.merged(*key)
             todo = [t for t in todo if t[0] not in beyond]
             if not todo:
                 continue
         Y = np.array([where[l, y] for l, y, _, _ in todo], np.int64)
         X = np.array([where[l, x] for l, _, x, _ in todo], np.int64)
-        for grp in _prog_groups(X[:, 3], Y[:, 3], budget_bytes, band, position_gaps):
-            d_bufs = _bufs_table(be, bufs)
-            Xg, Yg = X[grp], Y[grp]
+        for grp in _prog_groups(X[:, 3], Y[:, 3], merge):
             wg = None
             if row_w is not None:
                 wg = ([rw[todo[k][0], todo[k][2]] for k in grp.tolist()], [rw[todo[k][0], todo[k][1]] for k in grp.tolist()])
             if weights is not None:
-                add_to(counters, "collapse_merges", len(grp))
-            d_ops, ops_bytes, ops_off, count, _ = _prog_pairs(be, d_bufs, len(bufs), Xg, Yg, band, budget_bytes, counters, wg, position_gaps,
-                                                              free_end_gaps)
-            d_new, new_bytes, poff, R = _prog_parents(be, d_bufs, len(bufs), Xg, Yg, d_ops, ops_bytes, ops_off, count)
-            bufs.append((d_new, new_bytes))
-            live.append(len(grp))
-            for i, k in enumerate(grp.tolist()):
+                add_to(merge.counters, "collapse_merges", len(grp))
+            for k, parent_text in zip(grp.tolist(), merge.group(be, texts, X[grp], Y[grp], wg, reuse=False)):
                 l, y, x, parent = todo[k]
-                where[l, parent] = (len(bufs) - 1, int(poff[i]), int(R[i]), int(count[i]))
+                texts.place(l, parent, parent_text)
                 if row_w is not None:
                     rw[l, parent] = np.concatenate([rw.pop((l, y)), rw.pop((l, x))])
-                merged(l, y)
-                merged(l, x)
-    return bufs, live, where
+                texts.merged(l, y)
+                texts.merged(l, x)
+    return texts
 
 
-def _prog_output(be, chunk: Chunk, root, root_members, bufs, where, expand=None):
+def _prog_output(be, chunk: Chunk, root, root_members, texts: _Texts, expand=None):
     """The roots' rows into input order, as ASCII; an empty record is a row of '-': one more mprg_prog_rows launch.  root_members:
     per locus the records of the root's rows, in row order.  expand (the spec's Collapse): (records per locus, each locus's first
     record, per record its representative's index in the chunk's tables) of the output: every record gets its representative's
     row.  Returns what the star pass leaves: (the buffer, its bytes, each locus's offset in it, its width)."""
-    first, counts, n_loci = chunk.first, chunk.counts, chunk.n_loci
+    first, counts, n_loci, where = chunk.first, chunk.counts, chunk.n_loci, texts.where
     W = np.array([where[l, root[l]][3] for l in range(n_loci)], np.int64)
     o_counts, o_first, slot = (counts, first, None) if expand is None else expand
     base = exclusive_sum(o_counts * W)
@@ -2024,28 +2070,12 @@ def _prog_output(be, chunk: Chunk, root, root_members, bufs, where, expand=None)
             at = at_of[slot[rec] - first[l]]
             rec, at = rec[at >= 0], at[at >= 0]
         rows[rec, 0], rows[rec, 1], rows[rec, 2] = b, off + at * w, w
-    d_bufs = _bufs_table(be, bufs)
+    d_bufs = texts.table(be)
     d_rows, d_out, d_status = be.upload(rows), be.empty(max(out_bytes, 1)), be.empty(4 * len(rows))
-    be.call("mprg_prog_rows", be.ptr(d_bufs), len(bufs), be.ptr(d_out), 0, be.ptr(d_rows), len(rows), be.ptr(d_out), max(out_bytes, 1), 1,
+    be.call("mprg_prog_rows", be.ptr(d_bufs), len(texts.bufs), be.ptr(d_out), 0, be.ptr(d_rows), len(rows), be.ptr(d_out), max(out_bytes, 1), 1,
             be.ptr(d_status), be.stream, work=float(2 * out_bytes))
     _check(be.download(d_status, np.int32, len(rows)), "mprg_prog_rows", PG_STATUS)
     return d_out, out_bytes, base, W
-
-
-def _add_buf(bufs, live, buf, nbytes):
-    """The buffer's index in _prog_rounds' bufs: a dropped buffer's place if there is one."""
-    b = next((i for i in range(1, len(bufs)) if bufs[i][0] is None), len(bufs))
-    if b == len(bufs):
-        bufs.append(None)
-        live.append(0)
-    bufs[b], live[b] = (buf, nbytes), 0
-    return b
-
-
-def _drop_unused(bufs, live, bs):
-    for b in bs:
-        if b and not live[b]:
-            bufs[b] = (None, 0)
 
 
 # ---- retree
@@ -2086,28 +2116,28 @@ def prog_identities(backend, texts: Sequence[np.ndarray], leaf: Optional[Sequenc
     return [(shared[toff[k]:toff[k] + m[k] * m[k]].reshape(int(m[k]), int(m[k])), nw[first[k]:first[k] + m[k]]) for k in range(len(mats))]
 
 
-def _retree_trees(be, chunk: Chunk, sel, texts, order, bufs, weights, budget_bytes, device_tree, seq_weights=None):
+def _retree_trees(be, chunk: Chunk, sel, texts, order, bufs, weights, budget_bytes, on_device, lw=None):
     """The spec's Retree, Distance and Tree, for the loci `sel` of a chunk: texts[l] {buffer, offset, R, W} is the locus's current
-    MSA, order[l] the records of its rows.  In _prog_trees' groups: one mprg_prog_identities launch, then with device_tree the tree
+    MSA, order[l] the records of its rows.  In _prog_trees' groups: one mprg_prog_identities launch, then with on_device the tree
     launch over the tables where they are (the merges and the status words come back), without it the tables downloaded and
-    prog_tree on the host.  Per locus its merges as prog_tree gives them.  seq_weights (a _LeafWeights; the spec's Sequence
+    prog_tree on the host.  Per locus its merges as prog_tree gives them.  lw (a _LeafWeights; the spec's Sequence
     weights): every group's trees (uploaded, where the host built them) go through mprg_prog_leaf_weights over the group's
     identity tables, which are still on the device."""
     lens, first, counts = chunk.lens, chunk.first, chunk.counts
     out = {}
     n_leaves = np.add.reduceat((lens > 0).astype(np.int64), first)
-    on_device = device_tree or seq_weights is not None
-    d_seqs = be.upload(np.stack([chunk.seq_off, lens], 1).reshape(-1)) if on_device else None
-    d_weights = None if weights is None or not on_device else be.upload(np.asarray(weights, np.int32))
-    for grp, entry, table in _tree_groups(chunk, sel, budget_bytes, weights if device_tree else None):
+    tables_stay = on_device or lw is not None
+    d_seqs = be.upload(np.stack([chunk.seq_off, lens], 1).reshape(-1)) if tables_stay else None
+    d_weights = None if weights is None or not tables_stay else be.upload(np.asarray(weights, np.int32))
+    for grp, entry, table in _tree_groups(chunk, sel, budget_bytes, weights if on_device else None):
         loci = grp.tolist()
         toff, words, d_shared, d_nw, d_status, n_work = _identities_launch(
             be, _bufs_table(be, bufs), len(bufs), np.array([texts[l] for l in loci], np.int64), [order[l] for l in loci], first[grp], counts[grp],
             len(lens))
-        if device_tree:
+        if on_device:
             launched = _tree_launch(be, chunk, grp, entry, d_seqs, d_weights, n_leaves, toff, words, d_shared, d_nw)
-            if seq_weights is not None:
-                seq_weights.launch(grp, d_seqs, d_weights, toff, words, d_shared, d_nw, *launched[1:])
+            if lw is not None:
+                lw.launch(grp, d_seqs, d_weights, toff, words, d_shared, d_nw, *launched[1:])
             _check(be.download(d_status, np.int32, n_work), "mprg_prog_identities", PG_STATUS)
             out.update(_tree_merges(be, grp, entry, table, *launched))
             continue
@@ -2119,42 +2149,33 @@ def _retree_trees(be, chunk: Chunk, sel, texts, order, bufs, weights, budget_byt
             lv = np.nonzero(lens[rec] > 0)[0]
             out[l] = prog_tree(prog_distance_matrix(shared[toff[k]:toff[k] + mk * mk].reshape(mk, mk), nw[rec]), lv,
                                None if weights is None else weights[rec][lv])
-        if seq_weights is not None:
-            seq_weights.upload_and_launch(grp, out, d_seqs, d_weights, toff, words, d_shared, d_nw)
+        if lw is not None:
+            lw.upload_and_launch(grp, out, d_seqs, d_weights, toff, words, d_shared, d_nw)
     return out
 
 
-def _retree(be, chunk: Chunk, plan, bufs, live, where, weights, rebuilds, budget_bytes, band, device_tree, counters, align=None,
-            position_gaps=False, free_end_gaps=False):
-    """The spec's Retree over one chunk, on the roots' texts as _prog_rounds left them (bufs, live, where: its state, kept up here
-    as _tree_refine keeps it up).  Per iteration all loci that are still iterating go together: the identities and the trees
+def _retree(be, chunk: Chunk, plan: Plan, texts: _Texts, weights, opts: Options, counters, align=None):
+    """The spec's Retree over one chunk, on the roots' texts as _prog_rounds left them (texts, kept up here as _tree_refine keeps
+    them up), opts.retree times.  Per iteration all loci that are still iterating go together: the identities and the trees
     (_retree_trees), _prog_plan and _prog_rounds for the loci whose tree changed, from the leaves, into buffers of their own, one
     objective launch, S downloaded; the text that loses goes with its buffer.  Returns (the plan with the accepted trees, their
     row orders and progression tuples in place of the first ones, per locus (iterations, accepted, why it stopped, S before, S
     after)).  align (the spec's Sequence weights): per record its q; a rebuild runs with the q of the rebuilt tree on D', and an
-    accepted locus's entries of align are replaced by them, in place.  position_gaps, free_end_gaps: _prog_rounds'."""
+    accepted locus's entries of align are replaced by them, in place."""
     lens, first, counts, n_loci = chunk.lens, chunk.first, chunk.counts, chunk.n_loci
-    leaves, root = plan[0], plan[2]
-    order, trees, progression = [np.array(x, np.int64) for x in plan[3]], list(plan[4]), list(plan[5])
-    wl = [np.ones(int(counts[l]), np.int64) if weights is None else weights[first[l]:first[l] + counts[l]] for l in range(n_loci)]
-    empty = np.array([counts[l] - len(leaves[l]) for l in range(n_loci)], np.int64)
-    # mprg_tree_objective's bound, as in _tree_refine: a locus that misses it is left out and reported
-    in_bound = np.array([(int(wl[l][order[l]].sum()) + int(empty[l])) ** 2 * where[l, root[l]][3] <= 1 << 58 for l in range(n_loci)], bool)
+    leaves, root, where = plan.leaves, plan.root, texts.where
+    order, trees, progression = [np.array(x, np.int64) for x in plan.order], list(plan.trees), list(plan.progression)
+    wl, empty, in_bound, S = _root_objectives(be, chunk, plan, order, texts, weights)
     add_to(counters, "retree_over_bound", int((~in_bound).sum()))
-    known = np.nonzero(in_bound)[0].tolist()
-    S = np.zeros(n_loci, np.int64)
-    if known:
-        S[known] = tree_objective(be, _bufs_table(be, bufs), len(bufs), np.array([where[l, root[l]] for l in known], np.int64),
-                                  [wl[l][order[l]] for l in known], empty[known])
     out = [[0, 0, None if in_bound[l] else "bound", int(S[l]), int(S[l])] for l in range(n_loci)]
-    active = [l for l in known if len(leaves[l]) >= 3]
+    active = [l for l in np.nonzero(in_bound)[0].tolist() if len(leaves[l]) >= 3]
     add_to(counters, "retree_loci", len(active))
-    for _ in range(rebuilds):
+    for _ in range(opts.retree):
         if not active:
             break
         lw = None if align is None else _LeafWeights(be, chunk)
-        merges = _retree_trees(be, chunk, np.array(active, np.int64), {l: where[l, root[l]] for l in active}, order, bufs, weights, budget_bytes,
-                               device_tree, lw)
+        merges = _retree_trees(be, chunk, np.array(active, np.int64), {l: where[l, root[l]] for l in active}, order, texts.bufs, weights,
+                               opts.budget_bytes, opts.device_tree, lw)
         align2 = None
         if lw is not None:                                      # every active locus's q on the tree just built
             align2, rec = align.copy(), _ranges(first[active], counts[active])
@@ -2174,39 +2195,36 @@ def _retree(be, chunk: Chunk, plan, bufs, live, where, weights, rebuilds, budget
         part = chunk._replace(first=first[todo], counts=counts[todo])
         plan2 = _prog_plan(lens, part.first, part.counts, None, weights, [merges[l] for l in todo])
         beyond = set()
-        bufs2, live2, where2 = _prog_rounds(be, part, plan2, budget_bytes, band, counters, weights, beyond, align2, position_gaps,
-                                            free_end_gaps)
+        texts2 = _prog_rounds(be, part, plan2, opts.merge(counters), weights, beyond, align2)
         made, new = {}, {}
         for k, l in enumerate(todo):
             if k in beyond:
                 out[l][2] = "limit"
                 continue
-            b, off, R, W = where2[k, plan2[2][k]]
+            b, off, R, W = texts2.where[k, plan2.root[k]]
             if b not in made:
-                made[b] = _add_buf(bufs, live, *bufs2[b])
+                made[b] = texts.add(*texts2.bufs[b])
             new[l] = (made[b], off, R, W, k)
         ks = sorted(new)
-        S2 = (tree_objective(be, _bufs_table(be, bufs), len(bufs), np.array([new[l][:4] for l in ks], np.int64),
-                             [wl[l][np.array(plan2[3][new[l][4]], np.int64)] for l in ks], empty[ks]) if ks else [])
+        S2 = (tree_objective(be, texts.table(be), len(texts.bufs), np.array([new[l][:4] for l in ks], np.int64),
+                             [wl[l][np.array(plan2.order[new[l][4]], np.int64)] for l in ks], empty[ks]) if ks else [])
         used = list(made.values())
         for l, s2 in zip(ks, S2):
             k = new[l][4]
             if int(s2) > out[l][4]:                             # accepted: the locus's text is the new one, its tree the new tree
-                old = where[l, root[l]][0]
-                live[old] -= 1
-                live[new[l][0]] += 1
-                where[l, root[l]], order[l], trees[l], progression[l] = new[l][:4], np.array(plan2[3][k], np.int64), merges[l], plan2[5][k]
+                used.append(where[l, root[l]][0])
+                texts.place(l, root[l], new[l][:4])
+                order[l], trees[l], progression[l] = np.array(plan2.order[k], np.int64), merges[l], plan2.progression[k]
                 out[l][1], out[l][4] = out[l][1] + 1, int(s2)
                 if align is not None:
                     align[first[l]:first[l] + counts[l]] = align2[first[l]:first[l] + counts[l]]
-                used.append(old)
                 active.append(l)
             else:
                 out[l][2] = "refused"
-        _drop_unused(bufs, live, used)
+        texts.drop_unused(used)
     add_to(counters, "retree_accepted", sum(o[1] for o in out))
     add_to(counters, "retree_refused", sum(o[2] == "refused" for o in out))
-    return (leaves, plan[1], root, [o.tolist() for o in order], trees, progression), [tuple(o) for o in out]
+    return plan._replace(order=[o.tolist() for o in order], trees=trees, progression=progression), [tuple(o) for o in out]
 
 
 # ---- tree refinement
@@ -2266,51 +2284,52 @@ def _tree_step_fits(WX, WY, budget_words):
     return (WX + WY < pa.MAX_LEN) & (pa.workspace_words_v(WX, WY) <= budget_words)
 
 
-def _tree_refine(be, chunk: Chunk, plan, bufs, live, where, weights, passes, max_leaves, budget_bytes, band, counters, align=None,
-                 position_gaps=False, free_end_gaps=False):
-    """The spec's Tree refinement over one chunk, on the roots' texts as _prog_rounds left them (bufs, live, where: its state, kept
-    up here: where[locus, root] names the locus's current text, a buffer is dropped when nothing points to it; weights: per
-    record of the chunk's tables, the spec's Collapse).  Step s of every locus that still has one goes together: one split launch,
-    the widths downloaded, the merges in _prog_groups' groups through _prog_pairs and _prog_parents, one objective launch, S
-    downloaded.  Returns (per locus the records of its text's rows in row order, per locus (steps tried, accepted, skipped, S
-    before, S after)).  align (the spec's Sequence weights): per record the q its row has in a realignment, in place of the
-    multiplicities, which keep the choice of Y and the objective.  position_gaps, free_end_gaps: _prog_pairs'."""
+def _root_objectives(be, chunk: Chunk, plan: Plan, order, texts: _Texts, weights):
+    """What _retree and _tree_refine start from, per locus: its records' multiplicities (all 1 without weights, the spec's Collapse),
+    its empty records, whether mprg_tree_objective's bound, rows^2 W <= 2^58, holds for its root's text (only a locus of the spec's
+    Large loci can miss it: 4 096 rows do not, below the DP's 10^6 columns; the caller leaves it out and reports it) and S of that
+    text, 0 out of bound: one mprg_tree_objective launch.  order: per locus the records of its text's rows."""
     first, counts, n_loci = chunk.first, chunk.counts, chunk.n_loci
-    leaves, root, trees = plan[0], plan[2], plan[4]
-    order = [np.array(x, np.int64) for x in plan[3]]
+    roots = [texts.where[l, plan.root[l]] for l in range(n_loci)]
     wl = [np.ones(int(counts[l]), np.int64) if weights is None else weights[first[l]:first[l] + counts[l]] for l in range(n_loci)]
-    al = wl if align is None else [align[first[l]:first[l] + counts[l]] for l in range(n_loci)]
-    empty = np.array([counts[l] - len(leaves[l]) for l in range(n_loci)], np.int64)
-    budget_words = max(64, int(budget_bytes) // 4)
-
-    def add_buf(buf, nbytes):
-        return _add_buf(bufs, live, buf, nbytes)
-
-    def drop_unused(bs):
-        _drop_unused(bufs, live, bs)
-
-    # mprg_tree_objective's bound, rows^2 W <= 2^58: only a locus of the spec's Large loci can miss it (4 096 rows do not, below the
-    # DP's 10^6 columns); it is left out of the stage and reported with no step and S = 0
-    in_bound = np.array([(int(wl[l][order[l]].sum()) + int(empty[l])) ** 2 * where[l, root[l]][3] <= 1 << 58 for l in range(n_loci)], bool)
-    if not in_bound.all():
-        add_to(counters, "tree_refine_over_bound", int((~in_bound).sum()))
+    empty = np.array([counts[l] - len(plan.leaves[l]) for l in range(n_loci)], np.int64)
+    in_bound = np.array([(int(wl[l][order[l]].sum()) + int(empty[l])) ** 2 * roots[l][3] <= 1 << 58 for l in range(n_loci)], bool)
     known = np.nonzero(in_bound)[0].tolist()
     S = np.zeros(n_loci, np.int64)
     if known:
-        S[known] = tree_objective(be, _bufs_table(be, bufs), len(bufs), np.array([where[l, root[l]] for l in known], np.int64),
+        S[known] = tree_objective(be, texts.table(be), len(texts.bufs), np.array([roots[l] for l in known], np.int64),
                                   [wl[l][order[l]] for l in known], empty[known])
+    return wl, empty, in_bound, S
+
+
+def _tree_refine(be, chunk: Chunk, plan: Plan, texts: _Texts, weights, opts: Options, counters, align=None):
+    """The spec's Tree refinement over one chunk, on the roots' texts as _prog_rounds left them (texts, kept up here: where[locus,
+    root] names the locus's current text; weights: per record of the chunk's tables, the spec's Collapse), opts.refine_tree passes
+    over the loci of at most opts.tree_refine_max_leaves leaves.  Step s of every locus that still has one goes together: one
+    split launch, the widths downloaded, the merges in _prog_groups' groups through _Merge.group, one objective launch, S
+    downloaded.  Returns (per locus the records of its text's rows in row order, per locus (steps tried, accepted, skipped, S
+    before, S after)).  align (the spec's Sequence weights): per record the q its row has in a realignment, in place of the
+    multiplicities, which keep the choice of Y and the objective."""
+    first, counts, n_loci = chunk.first, chunk.counts, chunk.n_loci
+    leaves, root, where, merge = plan.leaves, plan.root, texts.where, opts.merge(counters)
+    order = [np.array(x, np.int64) for x in plan.order]
+    wl, empty, in_bound, S = _root_objectives(be, chunk, plan, order, texts, weights)
+    al = wl if align is None else [align[first[l]:first[l] + counts[l]] for l in range(n_loci)]
+    budget_words = max(64, int(opts.budget_bytes) // 4)
+    if not in_bound.all():                                      # (such a locus is left out of the stage: no step and S = 0)
+        add_to(counters, "tree_refine_over_bound", int((~in_bound).sum()))
     out = [[0, 0, 0, int(S[l]), int(S[l])] for l in range(n_loci)]
     n_lv = np.array([len(x) for x in leaves], np.int64)
-    add_to(counters, "tree_refine_above_cap", int((n_lv > max_leaves).sum()))
+    add_to(counters, "tree_refine_above_cap", int((n_lv > opts.tree_refine_max_leaves).sum()))
     steps = {}                                                  # per refinable locus, per step: is the record a leaf of G?
-    for l in np.nonzero((n_lv >= TREE_REFINE_MIN_LEAVES) & (n_lv <= max_leaves) & in_bound)[0].tolist():
-        groups = tree_steps(trees[l])
+    for l in np.nonzero((n_lv >= TREE_REFINE_MIN_LEAVES) & (n_lv <= opts.tree_refine_max_leaves) & in_bound)[0].tolist():
+        groups = tree_steps(plan.trees[l])
         steps[l] = np.zeros((len(groups), int(counts[l])), bool)
         for s, g in enumerate(groups):
             steps[l][s, g] = True
     active = [l for l in steps if len(steps[l])]
     add_to(counters, "tree_refine_loci", len(active))
-    for _ in range(passes):
+    for _ in range(opts.refine_tree):
         moved = set()
         for s in range(max((len(steps[l]) for l in active), default=0)):
             its = [l for l in active if s < len(steps[l])]
@@ -2323,31 +2342,26 @@ def _tree_refine(be, chunk: Chunk, plan, bufs, live, where, weights, passes, max
                 wg, wo = int(w[in_g].sum()), int(w[~in_g].sum())
                 g_is_y = wg > wo or (wg == wo and bool(in_g[np.argmin(o)]))
                 sides.append((in_g != g_is_y).astype(np.uint8))
-            texts = np.array([where[l, root[l]] for l in its], np.int64)
-            d_split, split_bytes, soff, widths = tree_split(be, _bufs_table(be, bufs), len(bufs), texts, sides)
+            split = np.array([where[l, root[l]] for l in its], np.int64)
+            d_split, split_bytes, soff, widths = tree_split(be, texts.table(be), len(texts.bufs), split, sides)
             RY = np.array([int((sd == 0).sum()) for sd in sides], np.int64)
             WY, WX = widths[:, 0], widths[:, 1]
-            b = add_buf(d_split, split_bytes)
+            b = texts.add(d_split, split_bytes)
             Y = np.stack([np.full(n, b), soff, RY, WY], 1).astype(np.int64)
-            X = np.stack([np.full(n, b), soff + RY * WY, texts[:, 2] - RY, WX], 1).astype(np.int64)
+            X = np.stack([np.full(n, b), soff + RY * WY, split[:, 2] - RY, WX], 1).astype(np.int64)
             fits = _tree_step_fits(WX, WY, budget_words)           # (a step beyond the limit is skipped: it counts as refused)
             sel = np.nonzero(fits)[0]
             new, made = {}, [b]
-            for grp in _prog_groups(X[sel, 3], Y[sel, 3], budget_bytes, band, position_gaps):
+            for grp in _prog_groups(X[sel, 3], Y[sel, 3], merge):
                 g = sel[grp]
-                d_bufs = _bufs_table(be, bufs)
                 wg = None
                 if weights is not None or align is not None:
                     wg = ([al[its[k]][order[its[k]][sides[k] == 1]] for k in g.tolist()], [al[its[k]][order[its[k]][sides[k] == 0]] for k in g.tolist()])
-                d_ops, ops_bytes, ops_off, count, _ = _prog_pairs(be, d_bufs, len(bufs), X[g], Y[g], band, budget_bytes, counters, wg,
-                                                                  position_gaps, free_end_gaps)
-                d_new, new_bytes, poff, R = _prog_parents(be, d_bufs, len(bufs), X[g], Y[g], d_ops, ops_bytes, ops_off, count)
-                made.append(add_buf(d_new, new_bytes))
-                for i, k in enumerate(g.tolist()):
-                    new[k] = (made[-1], int(poff[i]), int(R[i]), int(count[i]))
+                new.update(zip(g.tolist(), merge.group(be, texts, X[g], Y[g], wg)))
+                made.append(new[int(g[0])][0])
             ks = sorted(new)
             rows2 = {k: np.concatenate([order[its[k]][sides[k] == 0], order[its[k]][sides[k] == 1]]) for k in ks}     # Y's rows, then X's
-            S2 = (tree_objective(be, _bufs_table(be, bufs), len(bufs), np.array([new[k] for k in ks], np.int64),
+            S2 = (tree_objective(be, texts.table(be), len(texts.bufs), np.array([new[k] for k in ks], np.int64),
                                  [wl[its[k]][rows2[k]] for k in ks], empty[[its[k] for k in ks]]) if ks else [])
             for k in range(n):
                 out[its[k]][0] += 1
@@ -2355,14 +2369,12 @@ def _tree_refine(be, chunk: Chunk, plan, bufs, live, where, weights, passes, max
             for k, s2 in zip(ks, S2):
                 l = its[k]
                 if int(s2) > out[l][4]:                             # accepted: the locus's text is the new one
-                    old = where[l, root[l]][0]
-                    live[old] -= 1
-                    live[new[k][0]] += 1
-                    where[l, root[l]], order[l] = new[k], rows2[k]
+                    made.append(where[l, root[l]][0])
+                    texts.place(l, root[l], new[k])
+                    order[l] = rows2[k]
                     out[l][1], out[l][4] = out[l][1] + 1, int(s2)
                     moved.add(l)
-                    made.append(old)
-            drop_unused(made)
+            texts.drop_unused(made)
         active = [l for l in active if l in moved]
         if not active:
             break

@@ -687,41 +687,27 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
     be = backend or get_backend("runtime")
     t_read = t_align = t_write = 0.0
     written = []
-    adjust = bool(getattr(options, "adjust_direction", False))
-    orientation = []
-    band = bool(getattr(options, "band", False))
     counters: Dict[str, float] = {}
-    refine = int(getattr(options, "refine", None) or 0)
-    refinement = []
-    progressive = bool(getattr(options, "progressive", False))
-    progression = []
-    collapse = bool(getattr(options, "collapse_identical", False))
-    device_tree = bool(getattr(options, "device_tree", False))
-    refine_tree = int(getattr(options, "refine_tree", None) or 0)
-    tree_refinement = []
-    large_loci = bool(getattr(options, "large_loci", False))
-    retree = int(getattr(options, "retree", None) or 0)
-    seq_weights = bool(getattr(options, "seq_weights", False))
-    pair_distances = bool(getattr(options, "pair_distances", False))
-    position_gaps = bool(getattr(options, "position_gaps", False))
-    free_end_gaps = bool(getattr(options, "free_end_gaps", False))
+    # (argparse attribute, star_msas keyword, kind: a flag is passed as True, a count as its number); each only when set, a keyword of
+    # `lists` with the list that receives its per-locus reports, and timings when an option with counters of its own is set
+    table = (("adjust_direction", "adjust_direction", "flag"), ("band", "band", "flag"), ("collapse_identical", "collapse", "flag"),
+             ("refine", "refine", "count"), ("progressive", "progressive", "flag"), ("device_tree", "device_tree", "flag"),
+             ("large_loci", "large_loci", "flag"), ("refine_tree", "refine_tree", "count"), ("retree", "retree", "count"),
+             ("seq_weights", "seq_weights", "flag"), ("pair_distances", "pair_distances", "flag"), ("position_gaps", "position_gaps", "flag"),
+             ("free_end_gaps", "free_end_gaps", "flag"))
+    lists = dict(adjust_direction="orientation", refine="refinement", progressive="progression", refine_tree="tree_refinement")
+    on = {key: bool(getattr(options, attr, False)) if kind == "flag" else int(getattr(options, attr, None) or 0) for attr, key, kind in table}
+    kw = {key: value for key, value in on.items() if value}
+    if any(key not in ("adjust_direction", "refine", "progressive", "large_loci") for key in kw):
+        kw["timings"] = counters
+    kw.update({lists[key]: [] for key in lists if key in kw})
+    adjust, band, progressive, refine, refine_tree, retree = (on[key] for key in ("adjust_direction", "band", "progressive", "refine", "refine_tree", "retree"))
+    orientation, refinement, progression, tree_refinement = (kw.get(name, []) for name in lists.values())
     for lo in range(0, len(mine), STAR_CHUNK):
         t0 = time.perf_counter()
         recs = [star_align.read_unaligned(f) for f in mine[lo:lo + STAR_CHUNK]]
         t1 = time.perf_counter()
-        msas = star_align.star_msas(be, recs, names=loci[lo:lo + STAR_CHUNK], adjust_direction=adjust, orientation=orientation,
-                                    **(dict(band=True) if band else {}), **(dict(timings=counters) if band or collapse or device_tree or refine_tree or retree or seq_weights or pair_distances or position_gaps or free_end_gaps else {}),
-                                    **(dict(collapse=True) if collapse else {}),
-                                    **(dict(refine=refine, refinement=refinement) if refine else {}),
-                                    **(dict(progressive=True, progression=progression) if progressive else {}),
-                                    **(dict(device_tree=True) if device_tree else {}),
-                                    **(dict(large_loci=True) if large_loci else {}),
-                                    **(dict(refine_tree=refine_tree, tree_refinement=tree_refinement) if refine_tree else {}),
-                                    **(dict(retree=retree) if retree else {}),
-                                    **(dict(seq_weights=True) if seq_weights else {}),
-                                    **(dict(pair_distances=True) if pair_distances else {}),
-                                    **(dict(position_gaps=True) if position_gaps else {}),
-                                    **(dict(free_end_gaps=True) if free_end_gaps else {}))
+        msas = star_align.star_msas(be, recs, names=loci[lo:lo + STAR_CHUNK], **kw)
         t2 = time.perf_counter()
         for locus, m in zip(loci[lo:lo + STAR_CHUNK], msas):
             path = out_dir / f"{locus}.fa"
@@ -742,15 +728,15 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
         logger.info(f"rank {rank}: --progressive --band: {counters.get('prog_band_merges', 0)} merges, "
                     f"{counters.get('prog_band_second_passes', 0)} second passes, {counters.get('prog_band_full_merges', 0)} sent to the "
                     f"full DP, {counters.get('prog_band_cells', 0)} of {counters.get('prog_band_full_cells', 0)} DP cells computed")
-    if position_gaps:
+    if on["position_gaps"]:
         logger.info(f"rank {rank}: --position-gaps: {counters.get('position_gap_merges', 0)} merges with opens by occupancy")
-    if free_end_gaps:
+    if on["free_end_gaps"]:
         logger.info(f"rank {rank}: --free-end-gaps: {counters.get('free_end_gap_merges', 0)} merges with free end gaps")
-    if pair_distances:
+    if on["pair_distances"]:
         logger.info(f"rank {rank}: --pair-distances: {counters.get('pair_dist_loci', 0)} loci, {counters.get('pair_dist_pairs', 0)} pairs, "
                     f"{counters.get('pair_dist_cells', 0)} DP cells, {counters.get('pair_dist_above_cap', 0)} above the cap, "
                     f"{counters.get('pair_dist_limit', 0)} beyond the limit")
-    if seq_weights:
+    if on["seq_weights"]:
         logger.info(f"rank {rank}: --seq-weights: {counters.get('seq_weight_loci', 0)} loci weighted, "
                     f"smallest weight {counters.get('seq_weight_min_q', 1)}")
     if retree:
@@ -765,16 +751,16 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
     if refine:
         logger.info(f"rank {rank}: --refine {refine}: {sum(1 for a, _, _ in refinement if a)} loci refined, "
                     f"{sum(a for a, _, _ in refinement)} rounds accepted, {sum(1 for a, _, _ in refinement if not a)} loci left as the star MSA")
-    if collapse:
+    if on["collapse"]:
         logger.info(f"rank {rank}: --collapse-identical: {counters.get('collapse_records', 0)} records, "
                     f"{counters.get('collapse_classes', 0)} classes")
     if progressive:
         built = [(n, r) for n, r, star in progression if not star]
         logger.info(f"rank {rank}: --progressive: {len(built)} loci built, {sum(n - 1 for n, _ in built)} merges, "
                     f"{max((r for _, r in built), default=0)} rounds at most, {len(progression) - len(built)} loci left to the star pass")
-    if device_tree:
+    if on["device_tree"]:
         logger.info(f"rank {rank}: --device-tree: {counters.get('tree_device_loci', 0)} loci's trees built on the device")
-    if large_loci:
+    if on["large_loci"]:
         logger.info(f"rank {rank}: --large-loci: {counters.get('large_loci', 0)} loci of more than {star_align.PROG_MAX_LEAVES} records built "
                     f"progressively ({counters.get('large_records', 0)} records), {counters.get('large_fallbacks', 0)} over a limit")
     align_unaligned_inputs.timings = dict(read_s=t_read, align_s=t_align, write_s=t_write)

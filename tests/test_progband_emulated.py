@@ -103,7 +103,7 @@ def test_the_four_entries_of_the_sweep_agree_on_a_one_row_x(emu):
 def test_constants_and_a_negative_half_width():
     assert sa.PROG_BAND_W0 == pbr.W0 == 64 and sa.PG_BAND_PAIR_FIELDS == 8
     with pytest.raises(sa.StarAlignError, match="negative half-width"):
-        list(sa._prog_groups(*[__import__("numpy").array([5])] * 2, 1 << 20, band=-1))
+        list(sa._prog_groups(*[__import__("numpy").array([5])] * 2, sa._Merge(-1, 1 << 20)))
 
 
 def test_from_msa_unaligned_progressive_band_writes_the_same_files_and_logs_the_counters(emu, tmp_path, caplog):
