@@ -320,7 +320,14 @@ int mprg_cluster_further_bounded(const uint8_t *arena, const int64_t *views, con
  * its representative (rep_g == own position), and counts with its size; the smallest tie-break key of a class is its representative's.
  * out_further, assign and the majority strings are what the other two entry points give (integer counts: bit for bit).  Problems of more
  * than MPRG_CF_ROWS rows take the same wide launch as there (every row), only their distance check leaves the copies out.  The
- * one-workgroup form keeps 4 more bytes of LDS per row, so a few views just inside its bound go to the tiled launches instead.
+ * one-workgroup form keeps 4 more bytes of LDS per row and stages only the representatives' cells, so it takes a view when
+ *     (S rounded up to 4) + (2 S rounded up to 4) + 4 S + k cp + G cp <= 8 192,   cp = columns rounded up to 4,
+ * S the view's rows and G its representatives (mprg_ungap_dedupe's summary[8 v + 1]; the call counts them from rep_g itself, the list it
+ * stages, and only for a view that fits with G = 1 and not with G = S).  Such a view's G is left in the two bytes behind its 10
+ * majority strings in `scratch`, where the tiled launches of the same call read it: one side takes a view, never both or neither.  A
+ * view taken for its G leaves its majority strings in `scratch` as the tiled launches would.
+ * MPRG_CF_REP_RULE=0 (read once at load): the rule with G = S, as before.  rep_g without gcodes is an error (-1): the forest's work
+ * lists (S3, S5 below) count on the one-workgroup form, which reads the dense copies.
  * MPRG_CF_CLASSES=0 in the environment (read once at load): rep_g is ignored here and in mprg_forest_level. */
 int mprg_cluster_further_classes(const uint8_t *arena, const int64_t *views, const int32_t *rowidx, const int64_t *prob,
                                  int n_probs, int k, const int32_t *d_of_row, const int32_t *labels, int32_t *assign,
@@ -516,7 +523,10 @@ int mprg_forest_classify(const int64_t *F, void *stream);
 int mprg_forest_children(const int64_t *F, void *stream);
 /* S3  after mprg_ungap_dedupe (summary): leaf alleles of the selected views; candidates that go on (recursion_tree.py:538-556).
  *     hdr: 0 problems of the k = 1 check, 1 their column tiles, 2 their row chunks, 3 cells of all candidates, 4 cells of the
- *     problems. */
+ *     problems.  Tiles and chunks (MPRG_F_WORK_COLS / _ROWS, filled by _fill) leave out the problems that mprg_cluster_further's
+ *     one-workgroup form takes at k = 1 whichever entry point is called (the bound of mprg_cluster_further_classes with G = S): the
+ *     call must then be given gcodes.  A list may be empty (the call skips that launch).  MPRG_CF_ONE=0 or MPRG_CF_LISTS=0 in the
+ *     environment (read once at load): every problem is listed. */
 int mprg_forest_cluster_count(const int64_t *F, void *stream);
 int mprg_forest_cluster_fill(const int64_t *F, void *stream);
 /* S4  after mprg_cluster_further(k = 1): hdr: 0 clustering problems, 1 bytes of k-mer tables, 2 bytes of first-appearance flags,
@@ -525,7 +535,9 @@ int mprg_forest_problems_count(const int64_t *F, void *stream);
 int mprg_forest_problems_fill(const int64_t *F, void *stream);
 /* S5  after mprg_kmer_dictionary (MPRG_F_DV): hdr: 0 doubles of count matrices, 1 doubles of KMeans workspaces, 2-6 problems
  *     per mprg_kmeans_prepare class (LDS need <= 12, 24, 64, 156 KB, global form), 7 / 8 work items of mprg_cluster_further
- *     (column tiles, row chunks of ALL problems: MPRG_F_WORK_COLS / _ROWS are filled by _fill), 15 error: too many features, 16-20 largest
+ *     (column tiles, row chunks of the problems that the one-workgroup form does not take at k = 10 — as in S3; what it takes at 10 it
+ *     takes in every round: MPRG_F_WORK_COLS / _ROWS are filled by _fill; not inside mprg_forest_level, whatever MPRG_CF_LISTS says: its loops
+ *     are the fused ones and read no lists), 15 error: too many features, 16-20 largest
  *     LDS need per class.  _fill: MPRG_F_PTAB in launch order (biggest fits first), class lists, loop state. */
 int mprg_forest_sizes_count(const int64_t *F, void *stream);
 int mprg_forest_sizes_fill(const int64_t *F, void *stream);

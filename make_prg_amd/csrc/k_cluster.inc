@@ -37,10 +37,32 @@ MPRG_DEV long long cf_lds_bytes(long long S, long long n, long long k) {
   const long long cp = (n + 3) & ~3LL;
   return ((S + 3) & ~3LL) + ((2 * S + 3) & ~3LL) + k * cp + S * cp;
 }
-// (cls: the launch was given rep_g — the one-workgroup form then keeps a class size and a list entry per row, 4 S bytes more)
-MPRG_DEV long long cf_lds_bytes_cls(long long S, long long n, long long k) { return cf_lds_bytes(S, n, k) + 4 * S; }
-MPRG_DEV bool cf_one_fits(long long S, long long n, long long k, bool cls = false) {
-  return S >= 1 && S < 65536 && n >= 1 && (cls ? cf_lds_bytes_cls(S, n, k) : cf_lds_bytes(S, n, k)) <= CFO_POOL;
+// (cls: the launch was given rep_g — the one-workgroup form then keeps a class size and a list entry per row, 4 S bytes more, and stages
+//  ONLY the representatives' cells, representative j at slot j: G rows of cells, G = the view's distinct gapped rows, where the tables
+//  stay sized by the S rows)
+MPRG_DEV long long cf_lds_bytes_cls(long long S, long long n, long long k, long long G) {
+  const long long cp = (n + 3) & ~3LL;
+  return ((S + 3) & ~3LL) + ((2 * S + 3) & ~3LL) + 4 * S + k * cp + G * cp;
+}
+MPRG_DEV bool cf_one_fits(long long S, long long n, long long k) { return S >= 1 && S < 65536 && n >= 1 && cf_lds_bytes(S, n, k) <= CFO_POOL; }
+MPRG_DEV bool cf_one_fits_cls(long long S, long long n, long long k, long long G) {
+  return S >= 1 && S < 65536 && n >= 1 && G >= 1 && G <= S && cf_lds_bytes_cls(S, n, k, G) <= CFO_POOL;
+}
+// The tiled launches' work lists (k_forest.inc) leave a view out when the one-workgroup form takes it whatever the call: with every row
+// staged and the wider tables of a call with rep_g (what fits so fits without rep_g too), for every k up to the one given.
+MPRG_DEV bool cf_lists_skip(long long S, long long n, long long k, int one_form) { return one_form && cf_one_fits_cls(S, n, k, S); }
+// The rule with rep_g (by_reps; MPRG_CF_REP_RULE=0: by the S rows, as without it).  A view that fits with every row staged is the
+// one-workgroup form's whatever G is, one that does not fit with a single representative is the tiled kernels'; for the views in
+// between (cf_one_asks_g) k_cluster_further_one — the first launch of the call — counts the representatives of rep_g, the very list
+// it would stage, and leaves G in the two bytes behind the view's KM_KMAX majority strings in `scratch` (cf_g_slot), where the tiled
+// launches behind it read it: one count, one function (cf_one_takes), so a view is claimed by exactly one side.
+MPRG_DEV bool cf_one_asks_g(long long S, long long n, long long k) { return !cf_one_fits_cls(S, n, k, S) && cf_one_fits_cls(S, n, k, 1); }
+static_assert(KM_KMAX * 1 + 2 <= 12 && (KM_KMAX & 1) == 0, "scratch is 12 bytes per column: two bytes behind the KM_KMAX strings of a one-column view");
+MPRG_DEV uint16_t *cf_g_slot(int32_t *scratch_all, const ViewD &d) { return (uint16_t *)((uint8_t *)(scratch_all + d.col_off * 3) + (long long)KM_KMAX * d.n_cols); }
+MPRG_DEV bool cf_one_takes(const ViewD &d, long long k, bool cls, bool by_reps, const int32_t *scratch_all) {
+  if (!cls) return cf_one_fits(d.n_rows, d.n_cols, k);
+  if (!by_reps || !cf_one_asks_g(d.n_rows, d.n_cols, k)) return cf_one_fits_cls(d.n_rows, d.n_cols, k, d.n_rows);
+  return cf_one_fits_cls(d.n_rows, d.n_cols, k, *cf_g_slot((int32_t *)scratch_all, d));
 }
 // rep_g (optional, all three kernels; mprg_ungap_dedupe's table: the smallest row of the view with identical gapped content): rows of one
 // gapped class share their cluster, their symbol in every column and their distance to any string, so a class is counted ONCE, by its
@@ -66,7 +88,7 @@ KERNEL(k_cluster_majority, const uint8_t *arena, const int64_t *views, const int
   if (kinfo && kinfo[5 * (long long)wk[0] + 1] == 0) return;      // this problem sat the round out (k_kl_advance)
   const int64_t *P = prob_all + (long long)wk[0] * PF;
   const ViewD d = load_view(views, (int)P[0]);
-  if (one_form && cf_one_fits(d.n_rows, d.n_cols, k, rep_g_all != nullptr)) return;     // k_cluster_further_one's
+  if (one_form && cf_one_takes(d, k, rep_g_all != nullptr, (one_form & 2) != 0, scratch_all)) return;     // k_cluster_further_one's (one_form: 1 on, 2 by representatives)
   const int n = d.n_cols, S = d.n_rows, D = (int)P[1], tile = S > CF_ROWS ? CF_TILE_BIG : CF_TILE, c0 = wk[1] * tile;
   const int32_t *dor = d_of_row_all + d.row_off;
   const int32_t *labels = labels_all ? labels_all + P[10] : nullptr;      // null: one cluster holding every member
@@ -172,7 +194,7 @@ KERNEL(k_cluster_majority, const uint8_t *arena, const int64_t *views, const int
 #define CFB_THREADS 1024
 KERNEL(k_cluster_majority_big, const uint8_t *arena, const int64_t *views, const int32_t *rowidx, const int64_t *prob_all,
        const int32_t *work, int k, const int32_t *d_of_row_all, const int32_t *labels_all, int32_t *scratch_all,
-       const uint8_t *gcodes_all, const int32_t *kinfo, DsCount dc) {
+       const uint8_t *gcodes_all, const int32_t *kinfo, int one_form, const int32_t *rep_g_all, DsCount dc) {
   DS_GUARD(dc, 1);
   const int32_t *wk = work + 2 * (long long)BLOCK_ID;
   if (kinfo && kinfo[5 * (long long)wk[0] + 1] == 0) return;
@@ -180,6 +202,7 @@ KERNEL(k_cluster_majority_big, const uint8_t *arena, const int64_t *views, const
   const ViewD d = load_view(views, (int)P[0]);
   const int n = d.n_cols, S = d.n_rows, c0 = wk[1] * CF_TILE_BIG;
   if (S <= CF_ROWS) return;
+  if ((one_form & 2) && rep_g_all && cf_one_takes(d, k, true, true, scratch_all)) return;     // (a tall view of a few columns and classes: k_cluster_further_one's by its representatives)
   const int32_t *dor = d_of_row_all + d.row_off;
   const int32_t *labels = labels_all ? labels_all + P[10] : nullptr;
   uint8_t *maj = (uint8_t *)(scratch_all + d.col_off * 3);
@@ -251,7 +274,7 @@ KERNEL(k_cluster_hamming, const uint8_t *arena, const int64_t *views, const int3
   if (kinfo && kinfo[5 * (long long)wk[0] + 1] == 0) return;
   const int64_t *P = prob_all + (long long)wk[0] * PF;
   const ViewD d = load_view(views, (int)P[0]);
-  if (one_form_k && cf_one_fits(d.n_rows, d.n_cols, one_form_k, rep_g_all != nullptr)) return;     // (one_form_k: the round's k when the one-workgroup form is on)
+  if (one_form_k && cf_one_takes(d, one_form_k & 255, rep_g_all != nullptr, (one_form_k & 256) != 0, scratch_all)) return;     // (one_form_k: the round's k when the one-workgroup form is on, + 256: by representatives)
   const int32_t *rg = rep_g_all ? rep_g_all + d.row_off : nullptr;      // a row that is not its class's representative has nothing to decide
   const int n = d.n_cols, S = d.n_rows, chunk = cf_chunk_rows(n, S), r0 = wk[1] * chunk;
   const int32_t *dor = d_of_row_all + d.row_off;

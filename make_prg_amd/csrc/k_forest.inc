@@ -369,8 +369,10 @@ KERNEL(k_lv_sub, const int64_t *nodes, long long f0, long long n, const int64_t 
 //      cluster_sequences.py:235-246) ------------------------------------------------------------------------------------
 // columns: 0 problem of the k = 1 check, 1 its column tiles, 2 its row chunks, 3 cells of clustering candidates, 4 cells of
 // the problems of the check
+// (cf_one: mprg_cluster_further's one-workgroup form is on — a problem it takes at k = 1, cf_lists_skip, has no tiles and no chunks: its
+//  workgroups of the tiled launches would only find that out and leave)
 KERNEL(k_cl_classify, int64_t *nodes, long long nsel, const int64_t *selnode, const int64_t *sub, const int64_t *summary,
-       int max_nesting, int64_t *vals, DsCount dc) {
+       int max_nesting, int cf_one, int64_t *vals, DsCount dc) {
   const long long q = KF_GID;
   if (q >= ds_n(dc, nsel)) return;
   int64_t *nd = NODE(nodes, selnode[q]);
@@ -382,11 +384,12 @@ KERNEL(k_cl_classify, int64_t *nodes, long long nsel, const int64_t *selnode, co
   const bool leaf_now = nd[MPRG_N_LEVEL] + 1 >= max_nesting || sm[0] <= 2 || sm[0] < sm[1] || sm[2] <= 2;
   const bool pq = cand && !leaf_now;
   if (pq) nd[MPRG_N_FLAGS] |= NF_PQ;
-  v[0] = pq; v[1] = pq ? cf_col_tiles(sv[7], sv[5]) : 0; v[2] = pq ? cf_row_chunks(sv[7], sv[5]) : 0;
+  const bool tiled = pq && !cf_lists_skip(sv[5], sv[7], 1, cf_one);
+  v[0] = pq; v[1] = tiled ? cf_col_tiles(sv[7], sv[5]) : 0; v[2] = tiled ? cf_row_chunks(sv[7], sv[5]) : 0;
   v[3] = cand ? sv[5] * sv[7] : 0; v[4] = pq ? sv[5] * sv[7] : 0;
 }
 KERNEL(k_cl_fill_pq, const int64_t *nodes, long long nsel, const int64_t *selnode, const int64_t *sub, const int64_t *summary,
-       const int64_t *vals, int64_t *t1, int32_t *work_cols, int32_t *work_rows, DsCount dc) {
+       const int64_t *vals, int cf_one, int64_t *t1, int32_t *work_cols, int32_t *work_rows, DsCount dc) {
   const long long q = KF_GID;
   if (q >= ds_n(dc, nsel) || !(NODE(nodes, selnode[q])[MPRG_N_FLAGS] & NF_PQ)) return;
   const KfRow v = KF_ROW(vals, nsel, q);
@@ -395,6 +398,7 @@ KERNEL(k_cl_fill_pq, const int64_t *nodes, long long nsel, const int64_t *selnod
   int64_t *o = t1 + i * PF;
   for (int f = 0; f < PF; ++f) o[f] = 0;
   o[0] = q; o[1] = summary[8 * q + 2];
+  if (cf_lists_skip(sv[5], sv[7], 1, cf_one)) return;
   int32_t *w = work_cols + 2 * v[1];
   for (long long c = 0; c < cf_col_tiles(sv[7], sv[5]); ++c) { w[0] = (int32_t)i; w[1] = (int32_t)c; w += 2; }
   w = work_rows + 2 * v[2];
@@ -439,7 +443,8 @@ MPRG_DEV int kf_size_bucket(long long dv) {     // 0 = biggest
   while (lg < 2 * (KF_BUCKETS - 1) && (dv >> (lg + 1)) > 0) ++lg;
   return KF_BUCKETS - 1 - lg / 2;
 }
-KERNEL(k_sz_count, long long P, const int64_t *ptab, const int32_t *dV, const int64_t *sub, int n_init, int64_t *vals, int64_t *hdr, DsCount dc) {
+// (cf_one: as in k_cl_classify, for the rounds k = 2 .. KM_KMAX: a problem the one-workgroup form takes at KM_KMAX it takes in every round)
+KERNEL(k_sz_count, long long P, const int64_t *ptab, const int32_t *dV, const int64_t *sub, int n_init, int cf_one, int64_t *vals, int64_t *hdr, DsCount dc) {
   const long long p = KF_GID;
   if (p >= ds_n(dc, P)) return;
   const long long D = ptab[p * PF + 1], V = dV[p] & 0xffffff;
@@ -450,14 +455,15 @@ KERNEL(k_sz_count, long long P, const int64_t *ptab, const int32_t *dV, const in
   v[0] = D * V; v[1] = km_common_doubles(D, V) + (long long)n_init * km_restart_doubles(D, V);
   for (int c = 0; c < 5; ++c) v[2 + c] = c == cls;
   const int64_t *sv = sub + ptab[p * PF] * VF;
-  v[7] = cf_col_tiles(sv[7], sv[5]); v[8] = cf_row_chunks(sv[7], sv[5]);
+  const bool tiled = !cf_lists_skip(sv[5], sv[7], KM_KMAX, cf_one);
+  v[7] = tiled ? cf_col_tiles(sv[7], sv[5]) : 0; v[8] = tiled ? cf_row_chunks(sv[7], sv[5]) : 0;
   atomicMax((unsigned long long *)hdr + 16 + cls, (unsigned long long)need);
   atomicAdd((unsigned long long *)hdr + 24 + kf_size_bucket(D * V), 1ull);
   if (V > (128LL << (KM_PW_DEPTH - 1))) hdr[15] = 1;
 }
 // the final problem table in launch order (row b = fit b of every round), the prepare lists, the k-loop's state
 KERNEL(k_sz_fill, long long P, const int64_t *ptab0, const int32_t *dV, const int64_t *sub, const int64_t *vals, int64_t *hdr, int64_t *ptab,
-       int32_t *cls_lists, int32_t *num_clusters, int32_t *active, int32_t *work_cols, int32_t *work_rows, DsCount dc) {
+       int32_t *cls_lists, int32_t *num_clusters, int32_t *active, int cf_one, int32_t *work_cols, int32_t *work_rows, DsCount dc) {
   const long long p = KF_GID;
   if (p >= ds_n(dc, P)) return;
   const KfRow v = KF_ROW(vals, P, p);
@@ -476,6 +482,7 @@ KERNEL(k_sz_fill, long long P, const int64_t *ptab0, const int32_t *dV, const in
   num_clusters[row] = 1; active[row] = 1;
   if (!work_cols) return;                  // (the fused clustering loop needs no per-round work items)
   const int64_t *sv = sub + src[0] * VF;
+  if (cf_lists_skip(sv[5], sv[7], KM_KMAX, cf_one)) return;
   int32_t *w = work_cols + 2 * v[7];
   for (long long c = 0; c < cf_col_tiles(sv[7], sv[5]); ++c) { w[0] = (int32_t)row; w[1] = (int32_t)c; w += 2; }
   w = work_rows + 2 * v[8];

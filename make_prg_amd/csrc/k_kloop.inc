@@ -187,7 +187,7 @@ KL_CF_FN bool cf_problem_fb(const int S, const int n, const int D, const int k, 
 // rows follows it: 4 S bytes more (cf_lds_bytes_cls); flag_s[1] counts the list.
 template <bool OPT = false, bool CLS = false>
 MPRG_DEV bool cf_problem_lds(const int S, const int n, const int D, const int k, const int32_t *dor, const int32_t *labels, int32_t *assign,
-                             const uint8_t *G, uint8_t *pool, int *flag_s, const int32_t *rep_g = nullptr) {
+                             const uint8_t *G, uint8_t *pool, int *flag_s, const int32_t *rep_g = nullptr, uint8_t *maj_out = nullptr) {
   typedef CfWords<16> Words;
   const int cpitch = u_pitch(n), cp = (n + 3) & ~3, cw4 = cp >> 2;
   uint8_t *mlab = pool;
@@ -248,6 +248,7 @@ MPRG_DEV bool cf_problem_lds(const int S, const int n, const int D, const int k,
         }
       }
       majs[cl * cp + c] = (uint8_t)best;
+      if (maj_out) maj_out[cl * n + c] = (uint8_t)best;
     }
     BARRIER();
     const int thresh = n < 5 ? 1 : (int)(0.2 * (double)n);
@@ -536,20 +537,38 @@ __attribute__((amdgpu_flat_work_group_size(64, 1024), amdgpu_waves_per_eu(KM_WAV
 //      The two-launch kernels leave these problems alone (cf_one_fits, same rule on both sides).
 KERNEL(k_cluster_further_one, const int64_t *views, const int64_t *prob_all, int n_probs, int k, const int32_t *d_of_row_all,
        const int32_t *labels_all, int32_t *assign_all, const double *km_info, int32_t *out_further, const uint8_t *gcodes_all,
-       const int32_t *kinfo, const int32_t *rep_g_all, DsCount dc) {
+       const int32_t *kinfo, const int32_t *rep_g_all, int by_reps, int32_t *scratch_all, DsCount dc) {
   DS_GUARD(dc, 1);
   const int b = BLOCK_ID;
   if (kinfo && kinfo[5 * (long long)b + 1] == 0) return;          // this problem sat the round out (k_kl_advance)
   const int64_t *P = prob_all + (long long)b * PF;
   const ViewD d = load_view(views, (int)P[0]);
-  if (!cf_one_fits(d.n_rows, d.n_cols, k, rep_g_all != nullptr)) return;
   __shared__ __attribute__((aligned(16))) uint8_t pool[CFO_POOL];
   SHARED(int, flag, 2);                                           // 0 some row is too far, 1 representatives listed (rep_g)
+  // a view that only fits if few of its rows are representatives (cf_one_asks_g): count them — cf_rep, the test cf_problem_lds lists them
+  // by, so the list it stages cannot be longer than the G the rule admitted, whatever rep_g holds — and leave G for the launches behind
+  const bool asks = rep_g_all && by_reps && cf_one_asks_g(d.n_rows, d.n_cols, k);
+  int reps = 0;
+  if (asks) {
+    ONE_THREAD { flag[1] = 0; }
+    BARRIER();
+    const int32_t *rg = rep_g_all + d.row_off;
+    int mine = 0;
+    PAR_FOR(i, d.n_rows) { mine += cf_rep(rg, i) == (int)i ? 1 : 0; }
+    if (mine) ATOMIC_ADD(flag + 1, mine);
+    BARRIER();
+    reps = flag[1];
+    ONE_THREAD { *cf_g_slot(scratch_all, d) = (uint16_t)reps; }
+    BARRIER();                                                    // (everyone has read the count: cf_problem_lds starts the list over)
+  }
+  if (!(asks ? cf_one_fits_cls(d.n_rows, d.n_cols, k, reps) : cf_one_takes(d, k, rep_g_all != nullptr, false, scratch_all))) return;
   const int32_t *labels = labels_all ? labels_all + P[10] : nullptr;
   // accepted fit: its labels become the problem's assignment (a fit with fewer than k distinct labels is not: cluster_sequences.py:267-273)
   int32_t *assign = (labels && assign_all && (!km_info || km_info[8 * (long long)b + 3] >= (double)k)) ? assign_all + P[10] : nullptr;
+  // (a view admitted by its representatives leaves its majority strings in `scratch`, where the tiled kernels left them before the rule)
+  uint8_t *maj_out = asks ? (uint8_t *)(scratch_all + d.col_off * 3) : nullptr;
   const bool further = rep_g_all ? cf_problem_lds<true, true>(d.n_rows, d.n_cols, (int)P[1], k, d_of_row_all + d.row_off, labels, assign, gcodes_all + d.aux0,
-                                                              pool, flag, rep_g_all + d.row_off)
+                                                              pool, flag, rep_g_all + d.row_off, maj_out)
                                  : cf_problem_lds<true>(d.n_rows, d.n_cols, (int)P[1], k, d_of_row_all + d.row_off, labels, assign, gcodes_all + d.aux0, pool, flag);
   ONE_THREAD { out_further[b] = further ? 1 : 0; }
 }

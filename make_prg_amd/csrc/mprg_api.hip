@@ -81,6 +81,11 @@ static const int g_pw_wave = [] { const char *e = getenv("MPRG_WAVE_VIEWS"); ret
 // the row groups of narrow views by one workgroup with a lane per row, all stages in one launch (k_rows_narrow, k_rows_narrow_s), and the
 // mprg_cluster_further_classes / mprg_forest_level: each class of identical gapped rows counted once, by its size (rep_g); MPRG_CF_CLASSES=0: every row
 static const int g_cf_classes = [] { const char *e = getenv("MPRG_CF_CLASSES"); return (e && atoi(e) == 0) ? 0 : 1; }();
+// ... and the one-workgroup form, which stages the representatives' cells only, admits a view by its representatives (cf_one_takes, k_cluster.inc);
+// MPRG_CF_REP_RULE=0: by its rows, as without rep_g
+// the forest's work lists for the tiled launches leave out what the one-workgroup form takes (cf_lists_skip); MPRG_CF_LISTS=0: every problem listed
+static const int g_cf_lists = [] { const char *e = getenv("MPRG_CF_LISTS"); return (g_cf_one && !(e && atoi(e) == 0)) ? 1 : 0; }();
+static const int g_cf_rep_rule = [] { const char *e = getenv("MPRG_CF_REP_RULE"); return (e && atoi(e) == 0) ? 0 : 1; }();
 // same row phase for the small views' wavefronts (k_rows_wave); MPRG_ROW_VIEWS=0: the launches of the wider views / k_dedupe_wave for them
 static const int g_row_views = [] { const char *e = getenv("MPRG_ROW_VIEWS"); return (e && atoi(e) == 0) ? 0 : 1; }();
 // mprg_forest_children: a non-match interval that its parent's partition kernel found to partition into itself (MPRG_IV_SELF) becomes a
@@ -504,18 +509,24 @@ static int d_cluster_further(const uint8_t *arena, const int64_t *views, const i
   if (!g_cf_classes) rep_g = nullptr;
   if (hipMemsetAsync(out_further, 0, sizeof(int32_t) * n_probs, (hipStream_t)stream) != hipSuccess) return fail("memset");
   // problems whose cells fit a workgroup's LDS: the whole check in ONE workgroup and launch (needs the dense gapped copy)
-  const int one = (g_cf_one && gcodes) ? 1 : 0;
+  // (the forest's work lists leave out the problems of the one-workgroup form, which needs gcodes: lists that are shorter than the
+  //  problems' tiles and chunks would leave those problems to nobody — refused rather than answered with zeros)
+  if (g_cf_lists && !gcodes && rep_g) return fail("mprg_cluster_further_classes: rep_g without gcodes (the forest's work lists need the one-workgroup form)");
+  const int one = (g_cf_one && gcodes) ? 1 : 0, by_reps = (one && rep_g && g_cf_rep_rule) ? 1 : 0;
   if (one) LAUNCH(k_cluster_further_one, n_probs, CFO_THREADS, stream, views, prob, n_probs, k, d_of_row, labels, assign, km_info, out_further, gcodes,
-                  kinfo, rep_g, dc_probs);
+                  kinfo, rep_g, by_reps, scratch, dc_probs);
   // problems of more than CF_ROWS rows: their majority strings by wide workgroups in a launch of their own over the same work items
   // (left out when the caller's bound on the rows of a view says there is none: max_rows, 0 = none known)
   const int big = (max_rows <= 0 || max_rows > CF_ROWS) ? 1 : 0;
+  // (the forest's lists leave out the problems of the one-workgroup form: often nothing is left for the tiled launches)
+  if (n_work_cols > 0)
   LAUNCH(k_cluster_majority, n_work_cols, CF_THREADS, stream, arena, views, rowidx, prob, work_cols, k, d_of_row, labels,
-         assign, km_info, scratch, gcodes, kinfo, one, rep_g, dc_cols);
-  if (big) LAUNCH(k_cluster_majority_big, n_work_cols, CFB_THREADS, stream, arena, views, rowidx, prob, work_cols, k, d_of_row, labels,
-                  scratch, gcodes, kinfo, dc_cols);
+         assign, km_info, scratch, gcodes, kinfo, one | (by_reps << 1), rep_g, dc_cols);
+  if (big && n_work_cols > 0) LAUNCH(k_cluster_majority_big, n_work_cols, CFB_THREADS, stream, arena, views, rowidx, prob, work_cols, k, d_of_row, labels,
+                  scratch, gcodes, kinfo, one | (by_reps << 1), rep_g, dc_cols);
+  if (n_work_rows > 0)
   LAUNCH(k_cluster_hamming, n_work_rows, CF_TILE, stream, arena, views, rowidx, prob, work_rows, d_of_row, labels,
-         (const int32_t *)scratch, out_further, gcodes, kinfo, one ? k : 0, rep_g, dc_rows);
+         (const int32_t *)scratch, out_further, gcodes, kinfo, one ? (k | (by_reps << 8)) : 0, rep_g, dc_rows);
   return check_launch("k_cluster_further");
 }
 
@@ -984,14 +995,14 @@ static int kf_cluster_count(const int64_t *F, const KfStep &st, const int64_t *n
   const long long n = F[MPRG_F_NSEL];
   const DsCount dn = kf_dc(st, kf_slot(st, n_sel));
   if (n > 0) LAUNCH(k_cl_classify, KF_GRID(n), 256, stream, FP(int64_t, MPRG_F_NODES), n, FP(const int64_t, MPRG_F_SELNODE),
-                    FP(const int64_t, MPRG_F_SUB), FP(const int64_t, MPRG_F_SUMMARY), (int)F[MPRG_F_MAX_NESTING], FP(int64_t, MPRG_F_VALS), dn);
+                    FP(const int64_t, MPRG_F_SUB), FP(const int64_t, MPRG_F_SUMMARY), (int)F[MPRG_F_MAX_NESTING], g_cf_lists, FP(int64_t, MPRG_F_VALS), dn);
   return kf_count_done(F, st, n, 5, dn, stream, "k_cl_classify");
 }
 static int kf_cluster_fill(const int64_t *F, const KfStep &st, const int64_t *n_sel, void *stream) {
   const long long n = F[MPRG_F_NSEL];
   if (n <= 0 || F[MPRG_F_NPQ] <= 0) return 0;
   LAUNCH(k_cl_fill_pq, KF_GRID(n), 256, stream, FP(const int64_t, MPRG_F_NODES), n, FP(const int64_t, MPRG_F_SELNODE),
-         FP(const int64_t, MPRG_F_SUB), FP(const int64_t, MPRG_F_SUMMARY), FP(const int64_t, MPRG_F_VALS), FP(int64_t, MPRG_F_T1),
+         FP(const int64_t, MPRG_F_SUB), FP(const int64_t, MPRG_F_SUMMARY), FP(const int64_t, MPRG_F_VALS), g_cf_lists, FP(int64_t, MPRG_F_T1),
          FP(int32_t, MPRG_F_WORK_COLS), FP(int32_t, MPRG_F_WORK_ROWS), kf_dc(st, kf_slot(st, n_sel)));
   return check_launch("k_cl_fill_pq");
 }
@@ -1017,7 +1028,7 @@ static int kf_sizes_count(const int64_t *F, const KfStep &st, const int64_t *n_p
   // (the header collects atomics; a block of the device state is zero already: mprg_forest_state_init / _rewind)
   if (!st.ds && hipMemsetAsync(st.hdr, 0, sizeof(int64_t) * MPRG_FOREST_HDR, (hipStream_t)stream) != hipSuccess) return fail("memset");
   if (P > 0) LAUNCH(k_sz_count, KF_GRID(P), 256, stream, P, FP(const int64_t, MPRG_F_PTAB0), FP(const int32_t, MPRG_F_DV),
-                    FP(const int64_t, MPRG_F_SUB), (int)F[MPRG_F_N_INIT], FP(int64_t, MPRG_F_VALS), st.hdr, dn);
+                    FP(const int64_t, MPRG_F_SUB), (int)F[MPRG_F_N_INIT], g_cf_lists, FP(int64_t, MPRG_F_VALS), st.hdr, dn);
   return kf_count_done(F, st, P, 9, dn, stream, "k_sz_count");
 }
 static int kf_sizes_fill(const int64_t *F, const KfStep &st, const int64_t *n_p, void *stream) {
@@ -1025,7 +1036,8 @@ static int kf_sizes_fill(const int64_t *F, const KfStep &st, const int64_t *n_p,
   if (P <= 0) return 0;
   LAUNCH(k_sz_fill, KF_GRID(P), 256, stream, P, FP(const int64_t, MPRG_F_PTAB0), FP(const int32_t, MPRG_F_DV), FP(const int64_t, MPRG_F_SUB),
          FP(const int64_t, MPRG_F_VALS), st.hdr, FP(int64_t, MPRG_F_PTAB), FP(int32_t, MPRG_F_CLS_LISTS), FP(int32_t, MPRG_F_NUM_CLUSTERS),
-         FP(int32_t, MPRG_F_ACTIVE), FP(int32_t, MPRG_F_WORK_COLS), FP(int32_t, MPRG_F_WORK_ROWS), kf_dc(st, kf_slot(st, n_p)));
+         FP(int32_t, MPRG_F_ACTIVE), g_cf_lists, st.ds ? nullptr : FP(int32_t, MPRG_F_WORK_COLS), st.ds ? nullptr : FP(int32_t, MPRG_F_WORK_ROWS),
+         kf_dc(st, kf_slot(st, n_p)));          // (mprg_forest_level runs the fused loops: no per-round work items, and the level's lists are sized for the k = 1 check)
   return check_launch("k_sz_fill");
 }
 static int kf_splits_count(const int64_t *F, const KfStep &st, const int64_t *n_p, void *stream) {
