@@ -145,7 +145,9 @@ int mprg_ungap_dedupe(const uint8_t *arena, const int64_t *views, const int32_t 
 /* A9b — from_msa/cluster_sequences.py:26-38 (count_distinct_kmers): k-mer dictionary in first-appearance order.
  * One workgroup per clustering problem.  prob: n_probs x MPRG_PROB_FIELDS int64 (see enum).  seqrow int32[]:
  * row positions (within the view) of the D distinct long sequences in first-appearance order.
- * table: uint64 keys[cap] then uint32 minocc[cap], uint32 id[cap] per problem (cap = power of two >= 2*T).
+ * table: uint64 keys[cap] then uint32 minocc[cap], uint32 id[cap] per problem (cap = power of two >= 2*T, at least 16; 16 * cap bytes;
+ * a slot without a k-mer keeps the key 0xffffffffffffffff).  first_flag[prob[FLAG_OFF] + o] = 1 where occurrence o is its k-mer's first, else 0
+ * (T bytes per problem; the caller lays the regions out, the hosts round them up to 16).
  * Keys: the k-mer packed at 4 bits per character for kmer_size <= 16; beyond, a seeded 64-bit hash whose every use is verified
  * character by character (a collision rebuilds the dictionary with the next seed), so ids are exact for any k-mer size.
  * out_V[n_probs] = number of distinct k-mers (bits 0-23, saturating at 0xffffff) | the hash seed that held << 24 (0x7f: none of 64 did).  The seed must
