@@ -125,6 +125,10 @@ int mprg_partition(const uint8_t *arena, const int64_t *views, const int32_t *ro
  * workgroup per view with a lane per row (k_rows_narrow; k_rows_narrow_s for at most 128 rows), or a wavefront per view of at most 64
  * rows (k_rows_wave); their work items in work_rows are skipped.  Same outputs, bit for bit.  MPRG_ROW_VIEWS=0 (environment, read
  * once when the library is loaded) leaves every view to the launches above (and MPRG_WAVE_VIEWS=0 the small ones to a workgroup each).
+ * MID-WIDTH views (65 .. 1 024 columns, at most 128 rows) likewise: one launch, a workgroup per view with a group of lanes per row and
+ * 16 cells per lane (k_rows_mid); MPRG_ROW_MID=0 (implied by MPRG_ROW_VIEWS=0) leaves them to the launches above.  Its 16-byte loads
+ * begin inside a view's columns and may end up to 15 bytes behind them: 16 bytes behind every row-major copy of the arena must be
+ * readable (the hosts put the alignment's transposed copy there, and 256 spare bytes behind the last).
  * views[AUX0] = byte offset (a multiple of 16) of this view's region in `ucodes`: n_rows * upitch bytes, upitch =
  * round_up(n_cols, 16); ungapped codes are stored ROW-MAJOR: character j of row position i at i*upitch + j.
  * per row (at row_off): ulen, rep_u (smallest row position with identical ungapped content), rep_g (same for gapped

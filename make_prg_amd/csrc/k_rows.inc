@@ -19,6 +19,9 @@
 // LANE per row for the row phase: a lane that walks its row alone keeps the kept-byte count, both hashes and the compaction state in
 // registers (no prefix sum over a group of lanes, no second pass over the compacted rows), and the hashes are in LDS when the dedupe
 // table is built.  Same hashes, lengths, rows and lists as K3a + K3a' + K3b write.  MPRG_ROW_VIEWS=0 leaves every view to those.
+// K3m (k_rows_mid): MID-WIDTH views (RV_COLS < columns <= RM_COLS, at most RV_ROWS_S rows: most of the root's non-match intervals that are
+// not narrow) in one launch too — a group of lanes per row as in K3a, but 16 cells per lane, two rows' loads in flight per lane, the
+// compaction through a staging row in LDS, from which the ungapped hash is taken.  MPRG_ROW_MID=0 leaves them to K3a + K3a' + K3b.
 // ---------------------------------------------------------------------------------------------------------------
 MPRG_DEV uint64_t hash_mix(uint64_t x) {          // splitmix64 finaliser
   x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ULL; x ^= x >> 27; x *= 0x94d049bb133111ebULL; x ^= x >> 31;
@@ -73,12 +76,21 @@ MPRG_DEV bool dw_is_small(long long S, long long n) { return S >= 1 && S <= DW_R
 #define RV_ROWS_S 128                  // ... of at most so many rows by k_rows_narrow_s: a quarter of the LDS, four times the workgroups per CU
 #define RV_SLOTS_S 256
 // `form` of the row kernels' launches: bit 0 = the small views are k_dedupe_wave's / k_rows_wave's, bit 1 = the narrow ones
-// k_rows_narrow's / k_rows_narrow_s's (small views stay with the wavefront kernels where both are on)
+// k_rows_narrow's / k_rows_narrow_s's (small views stay with the wavefront kernels where both are on), bit 2 = the mid-width ones k_rows_mid's
 #define RF_WAVE 1
 #define RF_ROWS 2
 MPRG_DEV bool rv_is_narrow(long long S, long long n) { return n >= 1 && n <= RV_COLS && S >= 1 && S <= DD_ROWS; }
 MPRG_DEV bool rv_takes(int form, long long S, long long n) { return (form & RF_ROWS) && rv_is_narrow(S, n) && !((form & RF_WAVE) && dw_is_small(S, n)); }
-MPRG_DEV bool rows_elsewhere(int form, long long S, long long n) { return ((form & RF_WAVE) && dw_is_small(S, n)) || rv_takes(form, S, n); }
+// mid-width views (the children of the root's non-match intervals that are wider than RV_COLS: ~100 rows x 65 .. a few hundred columns):
+// all three stages by ONE workgroup, a group of lanes per row and 16 cells per lane, so that a row is one step (k_rows_mid below);
+// bit 2 of `form`.  Wider than RM_COLS or more than RV_ROWS_S rows: the general launches.
+#define RM_COLS 1024                   // 64 lanes x 16 cells: the widest row that is one step of a wavefront
+#define RF_MID 4
+MPRG_DEV bool rm_is_mid(long long S, long long n) { return n > RV_COLS && n <= RM_COLS && S >= 1 && S <= RV_ROWS_S; }
+MPRG_DEV bool rm_takes(int form, long long S, long long n) { return (form & RF_MID) && rm_is_mid(S, n); }
+MPRG_DEV bool rows_elsewhere(int form, long long S, long long n) {
+  return ((form & RF_WAVE) && dw_is_small(S, n)) || rv_takes(form, S, n) || rm_takes(form, S, n);
+}
 // rows [r0, r0 + chunk) of the view, wavefront `wv` of `n_waves`
 MPRG_DEV void ug_hash_rows(const uint8_t *arena, const ViewD &d, const int32_t *rowidx, int r0, int chunk, int wv, int n_waves,
                            uint8_t *ucodes_all, uint64_t *hashes, int32_t *ulen_all, uint8_t *gcodes_all) {
@@ -492,7 +504,7 @@ KERNEL(k_ungap_dedupe, const uint8_t *arena, const int64_t *views, const int32_t
        int32_t *seqrow_all, int64_t *occ_off_all, int64_t *summary, int form, DsCount dc) {
   DS_GUARD(dc, 1);
   const ViewD d = load_view(views, BLOCK_ID);
-  if (rows_elsewhere(form, d.n_rows, d.n_cols)) return;          // k_dedupe_wave's, k_rows_narrow's
+  if (rows_elsewhere(form, d.n_rows, d.n_cols)) return;          // k_dedupe_wave's, k_rows_narrow's, k_rows_mid's
   __shared__ DdLds<DD_ROWS, DD_SLOTS> L;
   dd_view<false, DD_ROWS, DD_SLOTS>(BLOCK_ID, d, arena, rowidx, kmer_size, ucodes_all, gcodes_all, hashes, ulen_all, rep_u_all, rep_g_all, d_of_row_all,
                                     s_of_row_all, reps_pos_all, reps_len_all, seqrow_all, occ_off_all, summary, L);
@@ -592,6 +604,146 @@ MPRG_DEV void rv_rows(const uint8_t *arena, const ViewD &d, const int32_t *rowid
 KERNEL(k_rows_narrow, RV_PARAMS) { RV_BODY(DD_ROWS, DD_SLOTS, d.n_rows > RV_ROWS_S); }
 KERNEL(k_rows_narrow_s, RV_PARAMS) { RV_BODY(RV_ROWS_S, RV_SLOTS_S, d.n_rows <= RV_ROWS_S); }
 #undef RV_BODY
+// K3m  a MID-WIDTH selected view (rm_is_mid: RV_COLS < n <= RM_COLS columns, at most RV_ROWS_S rows) — the same outputs as K3n — by ONE
+//      workgroup of RM_WAVES wavefronts.  Row phase: a group of G = 8 .. 64 lanes per row, a lane takes SIXTEEN consecutive cells (one
+//      unaligned 16-byte load), so a row is ONE step of its group and a wavefront holds 64 / G rows (a "batch": 1 KB) at once; the
+//      loads of RM_BATCH batches are issued before the first is consumed (32 bytes per lane in flight: k_ungap_hash's wavefront waits
+//      for 256 bytes per trip, and its stores keep the compiler from starting the next row's load).
+//      Per lane and batch: the four words k_ungap_hash forms (columns c, c + 4, c + 8, c + 12; cells past n count as gaps) give the
+//      gapped hash (sum of hash_word(w, c)) and the dense gapped copy (one aligned 16-byte store: the cells past n up to the pitch are
+//      gaps); ONE prefix sum over the group, on the lane's kept count, places the lane's kept bytes in the row's staging row in LDS
+//      (a word without a gap as one store, else byte by byte).  After a wavefront-scope sync a lane takes 16 bytes of the staging row:
+//      bytes past the row's length zeroed, its two 8-byte words give the ungapped hash as k_ungap_hash_u forms it (sum of
+//      hash_word(w8, p), p = 0, 8, ... below the length), and they go to the ungapped row as one aligned 16-byte store (only blocks
+//      that begin below the length are written; nothing reads a row past its length).  Hashes and lengths go to `hashes` / `ulen` and
+//      into the LDS arrays of the dedupe; dd_view runs from the nominee table on, over the quarter-size block as in k_rows_narrow_s.
+//      The 16-byte loads are NOT guarded: a load begins at a column below n, so it ends at most 15 bytes behind the view's last column,
+//      which is at most 15 bytes behind the alignment's row-major copy (row pitch = columns rounded up to 16) for the last row; behind
+//      every row-major copy the arena holds that alignment's transposed copy (at least 16 bytes: the hosts round both to 256), and
+//      include/mprg.h asks for 16 readable bytes behind a row-major copy that stands last.
+#define RM_WAVES 4
+#define RM_BATCH 2
+#define RM_STAGE (16 * WAVE)           // bytes of a wavefront's batch: 64 / G rows of 16 G bytes
+MPRG_DEV void rm_rows(const uint8_t *arena, const ViewD &d, const int32_t *rowidx, uint8_t *ucodes_all, uint64_t *hashes, int32_t *ulen_all,
+                      uint8_t *gcodes_all, uint64_t *s_hu, uint64_t *s_hg, int32_t *s_len, uint8_t *stage /* this wavefront's RM_BATCH x RM_STAGE */) {
+  const int n = d.n_cols, S = d.n_rows, upitch = u_pitch(n);
+  uint64_t *hu = hashes + 2 * d.row_off, *hg = hu + S;
+  int32_t *ulen = ulen_all + d.row_off;
+  int G = WAVE;                                        // lanes per row: 16 cells per lane (n > RV_COLS: at least 8)
+  while (G > 8 && 16 * (G >> 1) >= n) G >>= 1;
+  const int rows_per_wave = WAVE / G, gl = wave_lane() & (G - 1), sub = wave_lane() / G, c = 16 * gl;
+  const int n_waves = N_THREADS / WAVE;
+  for (int ib = wave_id() * RM_BATCH * rows_per_wave; ib < S; ib += n_waves * RM_BATCH * rows_per_wave) {   // uniform per wavefront
+    uint32_t w[RM_BATCH][4];
+    int row[RM_BATCH];
+    // every batch's row numbers (loads where the view has a row list), then every batch's cells, before the first is looked at.  The
+    // loads are not predicated (a lane past the row's end reads the row's first cells, a row past the view's end the last row): behind a
+    // branch the compiler waits for ALL loads in flight before it issues the next one
+#pragma unroll
+    for (int h = 0; h < RM_BATCH; ++h) {
+      const int i = ib + h * rows_per_wave + sub;
+      row[h] = i < S ? i : S - 1;
+    }
+    if (d.rows_off >= 0) {
+#pragma unroll
+      for (int h = 0; h < RM_BATCH; ++h) row[h] = rowidx[d.rows_off + row[h]];
+    }
+#pragma unroll
+    for (int h = 0; h < RM_BATCH; ++h) __builtin_memcpy(w[h], arena + d.rm + (long long)row[h] * d.pitchC + d.col0 + (c < n ? c : 0), 16);
+#pragma unroll
+    for (int h = 0; h < RM_BATCH; ++h) {               // gaps: a lane past the row's end, a row past the view's
+      const bool dead = ib + h * rows_per_wave + sub >= S || c >= n;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) w[h][q] = dead ? 0x04040404u : w[h][q];
+    }
+    int len[RM_BATCH];
+    uint64_t g[RM_BATCH];
+#pragma unroll
+    for (int h = 0; h < RM_BATCH; ++h) {
+      const int i = ib + h * rows_per_wave + sub;
+      const bool live = i < S;
+      uint8_t *srow = stage + h * RM_STAGE + sub * 16 * G;
+      uint32_t gap[4];
+      int kept = 0;
+      g[h] = 0;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int cq = c + 4 * q;
+        if (cq + 4 > n) {                              // the row's last word: cells past n count as gaps
+          const uint32_t keep = cq >= n ? 0u : 0xffffffffu >> (8 * (cq + 4 - n));
+          w[h][q] = (w[h][q] & keep) | (0x04040404u & ~keep);
+        }
+        if (cq < n) g[h] += hash_word(w[h][q], (unsigned)cq);
+        const uint32_t v = w[h][q] ^ 0x04040404u;      // zero bytes = gaps
+        gap[q] = ~(((v & 0x7f7f7f7fu) + 0x7f7f7f7fu) | v) & 0x80808080u;   // 0x80 in every gap byte, exactly
+        kept += 4 - __popc(gap[q]);
+      }
+      if (live && gcodes_all && c < n) {               // (upitch >= c + 16: rows are 16-byte aligned)
+        uint4 x;
+        x.x = w[h][0]; x.y = w[h][1]; x.z = w[h][2]; x.w = w[h][3];
+        *(uint4 *)(gcodes_all + d.aux0 + (long long)i * upitch + c) = x;
+      }
+      int incl = kept;                                 // inclusive prefix sum over the row's G lanes
+      for (int dd = 1; dd < G; dd <<= 1) { const int y = __shfl_up(incl, dd, G); if (gl >= dd) incl += y; }
+      len[h] = __shfl(incl, G - 1, G);
+      int o = incl - kept;                             // (a lane of a row past the view's keeps nothing)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int k = 4 - __popc(gap[q]);
+        if (k == 4) __builtin_memcpy(srow + o, &w[h][q], 4);
+        else if (k) {
+          int oo = o;
+#pragma unroll
+          for (int u = 0; u < 4; ++u) if (!((gap[q] >> (8 * u + 7)) & 1u)) srow[oo++] = (uint8_t)(w[h][q] >> (8 * u));
+        }
+        o += k;
+      }
+    }
+    WAVE_SYNC();                                       // the staging rows are complete
+#pragma unroll
+    for (int h = 0; h < RM_BATCH; ++h) {
+      const int i = ib + h * rows_per_wave + sub;
+      const bool live = i < S;
+      const uint4 x = *(const uint4 *)(stage + h * RM_STAGE + sub * 16 * G + c);
+      uint64_t lo = 0, hi = 0, a = 0;
+      if (c < len[h]) {
+        lo = (uint64_t)x.x | (uint64_t)x.y << 32;
+        if (c + 8 > len[h]) lo &= 0xffffffffffffffffULL >> (8 * (c + 8 - len[h]));
+        a = hash_word(lo, (unsigned)c);
+      }
+      if (c + 8 < len[h]) {
+        hi = (uint64_t)x.z | (uint64_t)x.w << 32;
+        if (c + 16 > len[h]) hi &= 0xffffffffffffffffULL >> (8 * (c + 16 - len[h]));
+        a += hash_word(hi, (unsigned)(c + 8));
+      }
+      if (live && c < len[h]) {                        // (c + 16 <= upitch)
+        uint4 y;
+        y.x = (uint32_t)lo; y.y = (uint32_t)(lo >> 32); y.z = (uint32_t)hi; y.w = (uint32_t)(hi >> 32);
+        *(uint4 *)(ucodes_all + d.aux0 + (long long)i * upitch + c) = y;
+      }
+      uint64_t gg = g[h];
+      for (int dd = G >> 1; dd >= 1; dd >>= 1) {
+        a += (uint64_t)__shfl_xor((unsigned long long)a, dd, G);
+        gg += (uint64_t)__shfl_xor((unsigned long long)gg, dd, G);
+      }
+      if (live && gl == 0) { hu[i] = a; hg[i] = gg; ulen[i] = len[h]; s_hu[i] = a; s_hg[i] = gg; s_len[i] = len[h]; }
+    }
+    WAVE_SYNC();                                       // ... and read, before the next batches overwrite them
+  }
+}
+KERNEL(k_rows_mid, RV_PARAMS) {
+  DS_GUARD(dc, 1);
+  const ViewD d = load_view(views, BLOCK_ID);
+  if (!rm_takes(form, d.n_rows, d.n_cols)) return;
+  __shared__ DdLds<RV_ROWS_S, RV_SLOTS_S> L;
+  __shared__ __attribute__((aligned(16))) uint8_t stage[RM_WAVES * RM_BATCH * RM_STAGE];
+  rm_rows(arena, d, rowidx, ucodes_all, hashes, ulen_all, gcodes_all, L.s_hu, L.s_hg, L.s_len, stage + wave_id() * RM_BATCH * RM_STAGE);
+  __threadfence_block();               // the rows' stores before the other threads' loads of them (the comparisons of dd_view)
+  BARRIER();
+  dd_view<false, RV_ROWS_S, RV_SLOTS_S, true>(BLOCK_ID, d, arena, rowidx, kmer_size, ucodes_all, gcodes_all, hashes, ulen_all, rep_u_all,
+                                              rep_g_all, d_of_row_all, s_of_row_all, reps_pos_all, reps_len_all, seqrow_all, occ_off_all,
+                                              summary, L);
+}
 #undef RV_PARAMS
 // K3w  a SMALL selected view — ungap + hashes + row groups + first-appearance lists — by ONE wavefront, DW_WAVES views per workgroup:
 //      the three stages above in a row (their results pass through global memory as they do between the launches: a

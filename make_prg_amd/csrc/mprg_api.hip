@@ -88,6 +88,9 @@ static const int g_cf_lists = [] { const char *e = getenv("MPRG_CF_LISTS"); retu
 static const int g_cf_rep_rule = [] { const char *e = getenv("MPRG_CF_REP_RULE"); return (e && atoi(e) == 0) ? 0 : 1; }();
 // same row phase for the small views' wavefronts (k_rows_wave); MPRG_ROW_VIEWS=0: the launches of the wider views / k_dedupe_wave for them
 static const int g_row_views = [] { const char *e = getenv("MPRG_ROW_VIEWS"); return (e && atoi(e) == 0) ? 0 : 1; }();
+// ... and the mid-width views (65 .. RM_COLS columns, at most 128 rows) by one workgroup with a group of lanes per row, 16 cells per lane
+// (k_rows_mid); MPRG_ROW_MID=0, or MPRG_ROW_VIEWS=0: the launches of the wider views for them, as before
+static const int g_row_mid = [] { const char *e = getenv("MPRG_ROW_MID"); return (g_row_views && !(e && atoi(e) == 0)) ? 1 : 0; }();
 // mprg_forest_children: a non-match interval that its parent's partition kernel found to partition into itself (MPRG_IV_SELF) becomes a
 // node no partition kernel visits (MPRG_NF_SELF); MPRG_IV_SELF=0: the hint is ignored (the partition kernels still write it)
 static const int g_iv_self = [] { const char *e = getenv("MPRG_IV_SELF"); return (e && atoi(e) == 0) ? 0 : 1; }();
@@ -200,7 +203,7 @@ static int d_ungap_dedupe(const uint8_t *arena, const int64_t *views, const int3
                           int32_t *reps_len, int32_t *seqrow, int64_t *occ_off, int64_t *summary, uint8_t *gcodes, void *stream,
                           DsCount dc_views, DsCount dc_rows, long long max_rows = 0) {
   if (n_views <= 0) return 0;
-  const int form = (g_pw_wave ? RF_WAVE : 0) | (g_row_views ? RF_ROWS : 0);
+  const int form = (g_pw_wave ? RF_WAVE : 0) | (g_row_views ? RF_ROWS : 0) | (g_row_mid ? RF_MID : 0);
   // the SMALL views by a wavefront each, all stages in one launch (k_rows_wave: a lane per row; k_dedupe_wave: a group of lanes per
   // row); the launches below leave them alone
   if (g_pw_wave && g_row_views)
@@ -216,6 +219,10 @@ static int d_ungap_dedupe(const uint8_t *arena, const int64_t *views, const int3
     LAUNCH(k_rows_narrow_s, n_views, RV_THREADS_S, stream, arena, views, rowidx, kmer_size, ucodes, gcodes, hashes, ulen, rep_u, rep_g, d_of_row, s_of_row,
            reps_pos, reps_len, seqrow, occ_off, summary, form, dc_views);
   }
+  // the MID-WIDTH views by a workgroup each with a group of lanes per row, likewise
+  if (g_row_mid)
+    LAUNCH(k_rows_mid, n_views, RM_WAVES * WAVE, stream, arena, views, rowidx, kmer_size, ucodes, gcodes, hashes, ulen, rep_u, rep_g, d_of_row, s_of_row,
+           reps_pos, reps_len, seqrow, occ_off, summary, form, dc_views);
   if (n_work_rows > 0) {
     LAUNCH(k_ungap_hash, n_work_rows, UG_ROWS, stream, arena, views, rowidx, work_rows, ucodes, hashes, ulen, gcodes, form, dc_rows);
     LAUNCH(k_ungap_hash_u, n_work_rows, UG_ROWS, stream, views, work_rows, (const uint8_t *)ucodes, hashes, (const int32_t *)ulen, form, dc_rows);
