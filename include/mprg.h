@@ -623,6 +623,21 @@ int mprg_align_pairs_banded(const int32_t *profile, const int64_t *leaves, int n
                             int n_pairs, int32_t *workspace, long long workspace_words, uint8_t *ops, long long ops_bytes, int32_t *out,
                             void *stream);
 
+/* `from_msa --unaligned --free-end-pairs`: the pairs as overlap (semi-global) alignments (the spec and the band's proof:
+ * make_prg_amd/from_msa/star_align.py, "Free end pairs"): row 0 and column 0 of the DP are 0, a run of D ops in the
+ * last row and a run of I ops in the last column cost nothing; everything else is mprg_align_pairs'.
+ * mprg_align_pairs_endgap: signature, pair table, workspace need, ops, `out` and status codes of mprg_align_pairs.
+ * mprg_align_pairs_endgap_banded: those of mprg_align_pairs_banded (the band must hold (0, 0) and (n, C) as there).
+ * mprg_align_bounds_endgap: mprg_align_bounds' arguments; bounds: n_leaves x 3 int64 {SB' = sum_j B'_j with B'_j = max(B_j, 0), m' =
+ *   the smallest B'_j >= 640 (0 if there is none), z = the number of columns with B'_j < 640}: what that band's certificate needs. */
+int mprg_align_pairs_endgap(const int32_t *profile, const int64_t *leaves, int n_leaves, const uint8_t *seqs, const int64_t *pairs,
+                            int n_pairs, int32_t *workspace, long long workspace_words, uint8_t *ops, long long ops_bytes, int32_t *out,
+                            void *stream);
+int mprg_align_bounds_endgap(const int32_t *profile, const int64_t *leaves, int n_leaves, int64_t *bounds, void *stream);
+int mprg_align_pairs_endgap_banded(const int32_t *profile, const int64_t *leaves, int n_leaves, const uint8_t *seqs, const int64_t *pairs,
+                                   int n_pairs, int32_t *workspace, long long workspace_words, uint8_t *ops, long long ops_bytes,
+                                   int32_t *out, void *stream);
+
 /* `from_msa --unaligned --progressive --pair-distances`: the scores of mprg_align_pairs / mprg_align_pairs_banded alone, no traceback
  * and no ops, for guide trees from all pairs of a locus (the spec: make_prg_amd/from_msa/star_align.py, "Pair distances"; DESIGN.md
  * §3b).  profile, leaves, seqs are mprg_align_pairs'; leaves of any R.

@@ -91,6 +91,11 @@ SIGNATURES = {
     "mprg_align_bounds": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "mprg_align_pairs_banded": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p,
                                         ctypes.c_longlong, c_void_p, c_void_p]),
+    "mprg_align_pairs_endgap": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p,
+                                        ctypes.c_longlong, c_void_p, c_void_p]),
+    "mprg_align_bounds_endgap": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "mprg_align_pairs_endgap_banded": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong,
+                                               c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
     "mprg_align_pair_scores": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p,
                                        ctypes.c_longlong, c_void_p, c_void_p]),
     "mprg_align_pair_scores_banded": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong,

@@ -19,6 +19,8 @@
 //   counts (al_counts.inc) and its planes (al_planes.inc) once for the kernels that write profiles (k_align_profiles,
 //   k_prog_columns, k_prog_columns_weighted, and k_refine_profiles for the planes).  All are included as text: an inlined function
 //   body shared between kernels compiles them to other instructions, text that expands to the same tokens cannot (DESIGN.md §3a).
+//   The kernel's own text is al_pairs.inc, included below once as k_align_pairs and once, with AL_ENDGAP 1, as k_align_pairs_endgap
+//   (star_align.py, "Free end pairs"); k_align_pairs_banded's is al_pairs_band.inc, likewise.
 // ---------------------------------------------------------------------------------------------------------------
 #define AL_THREADS 256
 #define AL_WAVES (AL_THREADS / 64)
@@ -55,94 +57,17 @@ MPRG_DEV long long al_ws_words(long long n, long long C) {
 }
 MPRG_DEV int al_hb(long long i) { return i == 0 ? 0 : (int)(AL_OPEN + AL_INS * i); }     // H[i][0]
 
-__global__ void __launch_bounds__(AL_THREADS) k_align_pairs(const int32_t *profile, const int64_t *leaves, int n_leaves,
-                                                            const uint8_t *seqs, const int64_t *pairs, int n_pairs, int32_t *ws,
-                                                            long long ws_words, uint8_t *ops, long long ops_bytes, int32_t *out) {
-  SHARED(int32_t, ring_all, AL_WAVES * 6 * AL_RING);
-  const int lane = wave_lane();
-  const long long p = (long long)BLOCK_ID * AL_WAVES + wave_id();
-  if (p >= n_pairs) return;                                   // (a whole wavefront: nothing below waits for the others)
-  int32_t *ring = ring_all + wave_id() * 6 * AL_RING;
-  const int64_t *PT = pairs + MPRG_AL_PAIR_FIELDS * p;
-  const long long leaf = PT[0], soff = PT[1], n = PT[2], wsoff = PT[3], opoff = PT[4];
-  int32_t *o = out + 3 * p;
-  int status = MPRG_AL_OK;
-  long long C = 0, poff = 0;
-  if (leaf < 0 || leaf >= n_leaves) status = MPRG_AL_BAD_INPUT;
-  else {
-    C = leaves[MPRG_AL_LEAF_FIELDS * leaf + 2];
-    poff = leaves[MPRG_AL_LEAF_FIELDS * leaf + 3];
-    if (C < 1 || n < 0 || leaves[MPRG_AL_LEAF_FIELDS * leaf + 1] < 1) status = MPRG_AL_BAD_INPUT;
-    else if (n + C >= AL_MAX_CELLS_SUM) status = MPRG_AL_TOO_LONG;
-    else if (wsoff < 0 || (wsoff & 63) || wsoff + al_ws_words(n, C) > ws_words || opoff < 0 || opoff + n + C > ops_bytes)
-      status = MPRG_AL_NO_SPACE;
-  }
-  if (status != MPRG_AL_OK) {
-    if (lane == 0) { o[0] = status; o[1] = 0; o[2] = 0; }
-    return;
-  }
-  const int32_t *P = profile + poff;
-  const int Ci = (int)C, ni = (int)n;
-  int32_t *row = ws + wsoff;                                 // row[2J] = H, row[2J + 1] = I of the row above the strip, column J
-  uint32_t *tb = (uint32_t *)(ws + wsoff + ((2 * (C + 1) + 63) / 64) * 64);
-  const long long nst8 = (C + 63 + 7) / 8;
-  // row 0: H[0][J] = D[0][J] = open + the gap costs of columns < J
-  int carry = 0;
-  for (int c0 = 0; c0 < Ci; c0 += 64) {
-    const int c = c0 + lane;
-    const int incl = wave_scan_incl(c < Ci ? P[5LL * C + c] : 0) + carry;
-    if (c < Ci) { row[2 * (c + 1)] = AL_OPEN + incl; row[2 * (c + 1) + 1] = AL_NEG; }
-    carry = __shfl(incl, 63);
-  }
-  if (lane == 0) { row[0] = 0; row[1] = AL_NEG; }
-  WAVE_SYNC_GLOBAL();
-  int score = AL_NEG;
-  const int n_strips = (ni + 63) / 64;
-  for (int s = 0; s < n_strips; ++s) {
-    const int i0 = s * 64, r = i0 + lane, rows = ni - i0 < 64 ? ni - i0 : 64;
-    const bool valid = r < ni;
-    const unsigned code = valid ? seqs[soff + r] : 0u;
-    const int cls = code < 4 ? (int)code : 4;
-    int h_left = al_hb(r + 1), d_left = AL_NEG;            // H, D of this lane's row, the column to the left
-    int h_out = h_left, i_out = AL_NEG;                     // what the lane below reads next step (before the first column: H[i][0])
-    int h_up_prev = al_hb(i0);                               // (lane 0) H of the row above, one column to the left: the diagonal
-    uint32_t acc = 0;
-    const int T = Ci + rows - 1;
-    for (int t = 0; t < T; ++t) {
-      if ((t & 63) == 0) {                                   // the ring takes columns [t, t + 64): the block of columns t - 128 is done with
-        WAVE_SYNC();
-#pragma unroll
-        for (int k = 0; k < 6; ++k) ring[k * AL_RING + ((t + lane) & (AL_RING - 1))] = t + lane < Ci ? P[(long long)k * C + t + lane] : 0;
-        WAVE_SYNC();
-      }
-      int h_up = __shfl_up(h_out, 1), i_up = __shfl_up(i_out, 1);
-      if (lane == 0 && t < Ci) { h_up = row[2 * (t + 1)]; i_up = row[2 * (t + 1) + 1]; }
-      const int h_diag = h_up_prev;
-      h_up_prev = h_up;
-      const int c = t - lane;
-      unsigned cell = 0;
-      if (valid && c >= 0 && c < Ci) {
-        const int slot = c & (AL_RING - 1);
-        const int dc = ring[5 * AL_RING + slot];
-        const int diag = h_diag + ring[cls * AL_RING + slot];
-        const int xcost = AL_INS;
-#define AL_OPEN_D AL_OPEN + dc
-#define AL_OPEN_I AL_OPEN + xcost
-#include "al_cell.inc"
-#undef AL_OPEN_D
-#undef AL_OPEN_I
-        if (lane == 63 && s + 1 < n_strips) { row[2 * (c + 1)] = h; row[2 * (c + 1) + 1] = ii; }
-      }
-      acc |= cell << (4 * (t & 7));
-      if ((t & 7) == 7 || t == T - 1) { tb[((long long)s * nst8 + (t >> 3)) * 64 + lane] = acc; acc = 0; }
-    }
-    WAVE_SYNC_GLOBAL();                                      // the row buffer and the traceback, written by every lane, read by lane 0
-  }
-  score = ni > 0 ? __shfl(score, (ni - 1) & 63) : row[2 * C];
-  constexpr bool kBand = false;                              // (the full matrix: every strip starts at column 0)
-  constexpr int dlo = 0;
-#include "al_walk.inc"
-}
+// k_align_pairs and k_align_pairs_endgap: one text (al_pairs.inc), the second with the free ends of "Free end pairs"
+#define AL_PAIRS_KERNEL k_align_pairs
+#define AL_ENDGAP 0
+#include "al_pairs.inc"
+#undef AL_PAIRS_KERNEL
+#undef AL_ENDGAP
+#define AL_PAIRS_KERNEL k_align_pairs_endgap
+#define AL_ENDGAP 1
+#include "al_pairs.inc"
+#undef AL_PAIRS_KERNEL
+#undef AL_ENDGAP
 
 // ---------------------------------------------------------------------------------------------------------------
 // K-A banded (`from_msa --unaligned --band`; the spec, the certificate and its proof: make_prg_amd/update/profile_align.py,
@@ -209,114 +134,45 @@ __global__ void __launch_bounds__(AL_THREADS) k_align_bounds(const int32_t *prof
   if (lane == 0) { bounds[2 * leaf] = sb; bounds[2 * leaf + 1] = lmin; }
 }
 
-__global__ void __launch_bounds__(AL_THREADS) k_align_pairs_banded(const int32_t *profile, const int64_t *leaves, int n_leaves,
-                                                                   const uint8_t *seqs, const int64_t *pairs, int n_pairs, int32_t *ws,
-                                                                   long long ws_words, uint8_t *ops, long long ops_bytes, int32_t *out) {
-  SHARED(int32_t, ring_all, AL_WAVES * 6 * AL_RING);
+// k_align_bounds_endgap (star_align.py, "Free end pairs", band): k_align_bounds' wavefront per leaf for the counted bound of the
+//   pairs with free ends: with B'_j = max(B_j, 0) and the threshold T = AL_BOUND_T, three int64 per leaf: SB' = sum_j B'_j, m' = the
+//   smallest B'_j >= T (0 if there is none) and z = the number of columns with B'_j < T.
+#define AL_BOUND_T 640
+__global__ void __launch_bounds__(AL_THREADS) k_align_bounds_endgap(const int32_t *profile, const int64_t *leaves, int n_leaves, int64_t *bounds) {
   const int lane = wave_lane();
-  const long long p = (long long)BLOCK_ID * AL_WAVES + wave_id();
-  if (p >= n_pairs) return;                                   // (a whole wavefront: nothing below waits for the others)
-  int32_t *ring = ring_all + wave_id() * 6 * AL_RING;
-  const int64_t *PT = pairs + MPRG_AL_BAND_PAIR_FIELDS * p;
-  const long long leaf = PT[0], soff = PT[1], n = PT[2], wsoff = PT[3], opoff = PT[4];
-  long long blo = PT[5], bhi = PT[6];
-  int32_t *o = out + 3 * p;
-  int status = MPRG_AL_OK;
-  long long C = 0, poff = 0;
-  if (leaf < 0 || leaf >= n_leaves) status = MPRG_AL_BAD_INPUT;
-  else {
-    C = leaves[MPRG_AL_LEAF_FIELDS * leaf + 2];
-    poff = leaves[MPRG_AL_LEAF_FIELDS * leaf + 3];
-    if (C < 1 || n < 0 || leaves[MPRG_AL_LEAF_FIELDS * leaf + 1] < 1) status = MPRG_AL_BAD_INPUT;
-    else if (n + C >= AL_MAX_CELLS_SUM) status = MPRG_AL_TOO_LONG;
-    else if (blo > 0 || blo > C - n || bhi < 0 || bhi < C - n) status = MPRG_AL_BAD_INPUT;      // the band must hold both corners
-    else {
-      blo = blo < -n ? -n : blo;
-      bhi = bhi > C ? C : bhi;
-      if (wsoff < 0 || (wsoff & 63) || wsoff + al_band_ws_words(n, C, blo, bhi) > ws_words || opoff < 0 || opoff + n + C > ops_bytes)
-        status = MPRG_AL_NO_SPACE;
-    }
-  }
-  if (status != MPRG_AL_OK) {
-    if (lane == 0) { o[0] = status; o[1] = 0; o[2] = 0; }
-    return;
-  }
-  const int32_t *P = profile + al_uniform(poff);
-  const int Ci = (int)al_uniform(C), ni = (int)al_uniform(n), dlo = (int)al_uniform(blo), dhi = (int)al_uniform(bhi);
-  const int W = dhi - dlo + 1;
-  const long long wsoff_u = al_uniform(wsoff), soff_u = al_uniform(soff);
-  int32_t *row = ws + wsoff_u;                               // row[2k] = H, row[2k + 1] = I of the row above the strip (row i0), column i0 + dlo + k
-  uint32_t *tb = (uint32_t *)(ws + wsoff_u + ((2 * (long long)W + 63) / 64) * 64);
-  const long long nst8 = ((W + 63 < Ci ? W + 63 : Ci) + 63 + 7) / 8;
-  // row 0, columns 0 .. dhi: H[0][J] = D[0][J] = open + the gap costs of columns < J
-  int carry = 0;
-  for (int c0 = 0; c0 < dhi; c0 += 64) {
-    const int c = c0 + lane;
-    const int incl = wave_scan_incl(c < dhi ? (P + 5LL * Ci)[(unsigned)c] : 0) + carry;
-    if (c < dhi) { row[2 * (c + 1 - dlo)] = AL_OPEN + incl; row[2 * (c + 1 - dlo) + 1] = AL_NEG; }
-    carry = __shfl(incl, 63);
-  }
-  if (lane == 0) { row[2 * (-dlo)] = 0; row[2 * (-dlo) + 1] = AL_NEG; }
-  WAVE_SYNC_GLOBAL();
-  int score = AL_NEG;
-  const int n_strips = (ni + 63) / 64;
-  for (int s = 0; s < n_strips; ++s) {
-    const int i0 = s * 64, r = i0 + lane, rows = ni - i0 < 64 ? ni - i0 : 64;
-    const bool valid = r < ni;
-    const unsigned code = valid ? (seqs + soff_u)[(unsigned)r] : 0u;
-    const int cls = code < 4 ? (int)code : 4;
-    const int cs = i0 + dlo > 0 ? i0 + dlo : 0;             // the strip's first column, 0-based
-    const int jtop = i0 + dhi < Ci ? i0 + dhi : Ci;         // the last column of row i0 inside the band
-    const int jend = i0 + rows + dhi < Ci ? i0 + rows + dhi : Ci;   // the strip's last column, 1-based
-    const int d0 = cs - r - dlo;                            // 0-based column c = cs + t - lane of this lane's row (r + 1) lies on diagonal c - r:
-                                                            // inside the band where 0 <= d0 + t - lane <= dhi - dlo (and 0 <= c < C)
-    const bool col0 = r + 1 + dlo <= 0;                     // column 0 of this lane's row lies inside the band
-    int h_left = col0 ? al_hb(r + 1) : AL_NEG, d_left = AL_NEG;     // H, D of this lane's row, the column to the left of its first one
-    int h_out = col0 && cs == lane ? al_hb(r + 1) : AL_NEG, i_out = AL_NEG;   // what the lane below reads next step: here of column cs - 1 - lane
-    int h_up_prev = AL_NEG;                                  // H of the row above, one column to the left: the diagonal
-    if (lane == 0) h_up_prev = cs == 0 ? al_hb(i0) : row[0];   // (cs > 0: column cs = i0 + dlo of row i0, its first inside the band)
-    uint32_t acc = 0;
-    uint32_t *tbs = tb + (long long)s * nst8 * 64;           // the strip's traceback: wave-uniform bases, 32-bit lane offsets
-    const int T = jend - cs + rows - 1;
-    for (int t = 0; t < T; ++t) {
-      if ((t & 63) == 0) {                                   // the ring takes columns cs + [t, t + 64): the block 128 before is done with
-        WAVE_SYNC();
+  const long long leaf = (long long)BLOCK_ID * AL_WAVES + wave_id();
+  if (leaf >= n_leaves) return;
+  const long long C = leaves[MPRG_AL_LEAF_FIELDS * leaf + 2];
+  const int32_t *P = profile + leaves[MPRG_AL_LEAF_FIELDS * leaf + 3];
+  long long sb = 0, z = 0;
+  int mmin = 2147483647;
+  for (long long c = lane; c < C; c += 64) {
+    int b = P[5 * C + c];
 #pragma unroll
-        for (int k = 0; k < 6; ++k)
-          ring[k * AL_RING + ((t + lane) & (AL_RING - 1))] = cs + t + lane < Ci ? (P + (long long)k * Ci)[(unsigned)(cs + t + lane)] : 0;
-        WAVE_SYNC();
-      }
-      int h_up = __shfl_up(h_out, 1), i_up = __shfl_up(i_out, 1);
-      if (lane == 0) {
-        const int j = cs + t + 1, k = j - (i0 + dlo);         // (1 <= k; k <= W - 1 where j <= jtop)
-        h_up = j <= jtop ? row[(unsigned)(2 * k)] : AL_NEG;
-        i_up = j <= jtop ? row[(unsigned)(2 * k + 1)] : AL_NEG;
-      }
-      const int h_diag = h_up_prev;
-      h_up_prev = h_up;
-      const int c = cs + t - lane;
-      unsigned cell = 0;
-      if (valid && (unsigned)c < (unsigned)Ci && (unsigned)(d0 + t - lane) < (unsigned)W) {
-        const int slot = (t - lane) & (AL_RING - 1);
-        const int dc = ring[5 * AL_RING + slot];
-        const int diag = h_diag + ring[cls * AL_RING + slot];
-        const int xcost = AL_INS;
-#define AL_OPEN_D AL_OPEN + dc
-#define AL_OPEN_I AL_OPEN + xcost
-#include "al_cell.inc"
-#undef AL_OPEN_D
-#undef AL_OPEN_I
-        if (lane == 63 && s + 1 < n_strips) { const int k = c + 1 - (i0 + 64 + dlo); row[(unsigned)(2 * k)] = h; row[(unsigned)(2 * k + 1)] = ii; }
-      } else {
-        h_out = c == -1 && r + 1 + dlo <= 0 ? al_hb(r + 1) : AL_NEG;   // outside the band: minus infinity, never a stale or an accumulated value
-        i_out = AL_NEG;
-      }
-      acc |= cell << (4 * (t & 7));
-      if ((t & 7) == 7 || t == T - 1) { tbs[(unsigned)((t >> 3) * 64 + lane)] = acc; acc = 0; }
-    }
-    WAVE_SYNC_GLOBAL();                                      // the row buffer and the traceback, written by every lane, read by lane 0
+    for (int x = 0; x < 5; ++x) { const int v = P[x * C + c]; b = v > b ? v : b; }
+    b = b > 0 ? b : 0;
+    sb += b;
+    if (b < AL_BOUND_T) ++z;
+    else mmin = b < mmin ? b : mmin;
   }
-  score = ni > 0 ? __shfl(score, (ni - 1) & 63) : row[2 * (Ci - dlo)];
-  constexpr bool kBand = true;
-#include "al_walk.inc"
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    sb += __shfl_xor(sb, d);
+    z += __shfl_xor(z, d);
+    const int y = __shfl_xor(mmin, d);
+    mmin = y < mmin ? y : mmin;
+  }
+  if (lane == 0) { bounds[3 * leaf] = sb; bounds[3 * leaf + 1] = mmin == 2147483647 ? 0 : mmin; bounds[3 * leaf + 2] = z; }
 }
+
+// k_align_pairs_banded and k_align_pairs_endgap_banded: one text (al_pairs_band.inc)
+#define AL_PAIRS_KERNEL k_align_pairs_banded
+#define AL_ENDGAP 0
+#include "al_pairs_band.inc"
+#undef AL_PAIRS_KERNEL
+#undef AL_ENDGAP
+#define AL_PAIRS_KERNEL k_align_pairs_endgap_banded
+#define AL_ENDGAP 1
+#include "al_pairs_band.inc"
+#undef AL_PAIRS_KERNEL
+#undef AL_ENDGAP

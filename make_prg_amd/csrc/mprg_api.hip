@@ -632,6 +632,31 @@ int mprg_align_pairs_banded(const int32_t *profile, const int64_t *leaves, int n
   return check_launch("k_align_pairs_banded");
 }
 
+// `from_msa --unaligned --free-end-pairs`: the three entries above with free ends (star_align.py, "Free end pairs")
+int mprg_align_pairs_endgap(const int32_t *profile, const int64_t *leaves, int n_leaves, const uint8_t *seqs, const int64_t *pairs,
+                            int n_pairs, int32_t *workspace, long long workspace_words, uint8_t *ops, long long ops_bytes, int32_t *out,
+                            void *stream) {
+  if (n_pairs <= 0) return 0;
+  LAUNCH(k_align_pairs_endgap, (n_pairs + AL_WAVES - 1) / AL_WAVES, AL_THREADS, stream, profile, leaves, n_leaves, seqs, pairs, n_pairs,
+         workspace, workspace_words, ops, ops_bytes, out);      // a wavefront per pair
+  return check_launch("k_align_pairs_endgap");
+}
+
+int mprg_align_bounds_endgap(const int32_t *profile, const int64_t *leaves, int n_leaves, int64_t *bounds, void *stream) {
+  if (n_leaves <= 0) return 0;
+  LAUNCH(k_align_bounds_endgap, (n_leaves + AL_WAVES - 1) / AL_WAVES, AL_THREADS, stream, profile, leaves, n_leaves, bounds);      // a wavefront per leaf
+  return check_launch("k_align_bounds_endgap");
+}
+
+int mprg_align_pairs_endgap_banded(const int32_t *profile, const int64_t *leaves, int n_leaves, const uint8_t *seqs, const int64_t *pairs,
+                                   int n_pairs, int32_t *workspace, long long workspace_words, uint8_t *ops, long long ops_bytes,
+                                   int32_t *out, void *stream) {
+  if (n_pairs <= 0) return 0;
+  LAUNCH(k_align_pairs_endgap_banded, (n_pairs + AL_WAVES - 1) / AL_WAVES, AL_THREADS, stream, profile, leaves, n_leaves, seqs, pairs,
+         n_pairs, workspace, workspace_words, ops, ops_bytes, out);      // a wavefront per pair
+  return check_launch("k_align_pairs_endgap_banded");
+}
+
 int mprg_align_pair_scores(const int32_t *profile, const int64_t *leaves, int n_leaves, const uint8_t *seqs, const int64_t *pairs,
                            int n_pairs, int32_t *workspace, long long workspace_words, uint32_t *table, long long table_words, int32_t *out,
                            void *stream) {

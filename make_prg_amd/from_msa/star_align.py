@@ -479,6 +479,56 @@ better.  Here the merge is an overlap (semi-global) alignment.
             (mprg_prog_band_widths_endgap with either open), in pass 2 and for the full form; the column tables, the sizing and
             the groups do not change.  timings receives free_end_gap_merges.
 
+Free end pairs (opt-in: free_end_pairs, with or without progressive; integers only; tests/freepairs_ref.py states it in plain
+Python; kernels: csrc/al_pairs.inc, csrc/al_pairs_band.inc, k_align_bounds_endgap in csrc/k_align.inc; C ABI:
+mprg_align_pairs_endgap / mprg_align_pairs_endgap_banded / mprg_align_bounds_endgap).  Free end gaps left the sequence-against-profile
+DP alone: the Pairs of the star pass and the realignments of Refinement still charge end gaps, so a fragment's missing end is billed
+as a deletion of hundreds of columns there, and refine after free_end_gaps realigns every row by the DP that flag replaced.  Here
+that DP is an overlap alignment too.
+  The DP of a sequence s (n >= 1 residues) against a profile of C columns is profile_align.py's DP with the four boundary changes of
+            Free end gaps, taken at R_X = 1 with the fixed open:
+                Row 0.      H[0][J] = D[0][J] = 0.
+                Column 0.   H[i][0] = I[i][0] = 0.
+                Row n.      D[n][j] = max(D[n][j-1], H[n][j-1]).
+                Column C.   I[i][C] = max(I[i-1][C], H[i-1][C]).
+  Unchanged: P and Dc, -640, and -704 for every other run; the int32 arithmetic; the tie order (diagonal, then D, then I; extend
+            before open, also where both are free); the 4-bit traceback cell; the walk back from (n, C) in state H; the refusal at
+            n + C >= 10^6; the ops and the {status, score, count} contract.
+  Score.    The score at (n, C) is the overlap optimum.  Identity (tested): the ops and the score equal those of
+            mprg_align_profile_pairs_endgap with X the sequence as a one-row side: then s(i, j) = P[j][x] and Ic = -640.
+  Which alignments.  The Pairs of the star pass, also of the loci a progressive run leaves to it (with collapse: the
+            representatives' pairs), and every realignment of Refinement, on a star or a progressive MSA.
+  Not changed: the score-only DPs of adjust_direction; pair_distances; `update --aligner builtin`; the merges (free_end_gaps'
+            business); Centre; the Merge rule (insertions at boundaries 0 and C are left-justified as always); the objective S and
+            the acceptance rule, limits and reports of Refinement; the planes of a profile (terminal '-' cells stay gaps there);
+            any default.
+  Promised (tested): every row with its gaps removed is its input sequence; no all-gap column; identical sequences get identical
+            rows in the star pass; collapse gives the bytes of the run without it; band gives the same bytes; a sequence that is an
+            exact substring of the centre, occurring once, gets its residues in place with no internal gap (no path scores more
+            than 1 280 n, a path with an op other than M between its first and last M, or a mismatch, scores less, and only an
+            occurrence reaches 1 280 n); with the flag off every byte and every call, upload and download is what it was.
+  Band.     With band the same bytes.  "Free end gaps, Band" applies with a one-row X: with B'_j = max(B_j, 0) and SB' = sum_j B'_j
+            a path that leaves the band at half-width w skips at least k = max(0, Delta) + w + 1 of the profile's columns and so
+            scores at most SB' - LY'(k), LY'(k) the sum of the k smallest B'_j.  The pair stage has no sort, so LY' is bounded from
+            below by counting: T = 640 (a design constant, not part of any result), z = the number of columns with B'_j < T, m' =
+            the smallest B'_j >= T (0 if there is none).
+            Proof.  Among any k columns at most z have B'_j < T, and those contribute >= 0; each of the other max(0, k - z) or more
+            has B'_j >= m'.  So LY'(k) >= m' max(0, k - z), and a path that leaves the band scores at most
+                U(w) = SB' - m' max(0, max(0, Delta) + w + 1 - z),
+            which does not rise with w.  (k <= C for every w < min(n, C), so no column is counted that the profile does not have;
+            at w >= min(n, C) the band is the matrix.)  S0, pass 1's score, is the score of a real path, so S0 <= SB'.  The
+            smallest w >= 0 with U(w) < S0 is
+                w* = max(0, floor((SB' - S0) / m') + z - max(0, Delta)),
+            the same on both sides, clamped per side as certified_widths clamps; with m' = 0 no U(w) falls below SB' and w* =
+            min(n, C), which sends the pair to the full DP.  The two-pass rule, band_plan, band_helps, BAND_W0 and the closed-sides
+            induction (it uses only that no path outside the band beats S0) are unchanged.  For a one-row centre of ACGT m' = 1 280
+            and z = 0; an N in the centre costs one column of width, not the band; the sparse columns of a leave-one-out profile
+            land in z.
+  Host side: _star_pass and _refine hand free_end_pairs to profile_align.pairs_on_device(free_ends=True), which calls the _endgap
+            form of the three entries and certified_widths_endgap; nothing else in the launches, the sizing or the counters
+            changes.  timings receives free_end_pair_alignments: the pairs run with free ends, over the star pass and all
+            refine rounds.
+
 Progressive, host side: per chunk the distances in launches whose m x m tables fit budget_bytes (loci of three or more leaves), D
 and the tree per locus in NumPy / Python integers (prog_tree: a float64 quotient only shortlists, the choice is exact).  A node's
 round is 1 + the larger of its children's rounds.  With device_tree the tree is built on the device instead (csrc/k_prog_tree.inc):
@@ -697,6 +747,10 @@ class Options(NamedTuple):
     free_end_gaps: only with progressive (else a ValueError): the spec's Free end gaps: every such merge as an overlap alignment,
     the run of one side's columns alone at either end of it free; with position_gaps too, its opens elsewhere.  timings also
     receives free_end_gap_merges.  False: nothing launches, uploads or downloads differently.
+    free_end_pairs: with or without progressive: the spec's Free end pairs: the pairs of the star pass (also of the loci a
+    progressive run leaves to it) and every realignment of refine as overlap alignments.  timings also receives
+    free_end_pair_alignments (the pairs run with free ends, over the star pass and all refine rounds).  False: nothing launches,
+    uploads or downloads differently.
     The fields hold them as the stages read them: band is None, True or pass 1's half-width; refine_tree and retree are 0 when off;
     limits (large_loci, max_records) is None or (max_leaves, max_records); pair_dist (pair_distances, its cap) None or the cap."""
     budget_bytes: int = pa.DEFAULT_BUDGET_BYTES
@@ -715,9 +769,10 @@ class Options(NamedTuple):
     pair_dist: Optional[int] = None
     position_gaps: bool = False
     free_end_gaps: bool = False
+    free_end_pairs: bool = False
 
     def star(self) -> "Options":
-        """The settings of loci that go to the star pass: none of the options of progressive."""
+        """The settings of loci that go to the star pass: none of the options of progressive (free_end_pairs is not one: kept)."""
         return self._replace(progressive=False, device_tree=False, refine_tree=0, limits=None, retree=0, seq_weights=False, pair_dist=None,
                              position_gaps=False, free_end_gaps=False)
 
@@ -756,7 +811,7 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
               max_records: Optional[int] = None, retree: Optional[int] = None, retreeing: Optional[list] = None,
               seq_weights: bool = False, pair_distances: bool = False, pair_distancing: Optional[list] = None,
               pair_dist_max_leaves: int = PAIR_DIST_MAX_LEAVES, position_gaps: bool = False,
-              free_end_gaps: bool = False) -> List[MSA]:
+              free_end_gaps: bool = False, free_end_pairs: bool = False) -> List[MSA]:
     """loci: per locus its records as (title, sequence).  Returns the loci's centre-star MSAs (ids: the titles' first words,
     descriptions: the titles).  names: the loci's names for error messages (default: their indices).  timings: a dict that
     receives the wall seconds of the stages (orient, centre, pairs, merge: each ends at a download, so includes its kernels).
@@ -787,7 +842,8 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
     opts = Options(budget_bytes, band, adjust_direction, int(refine), bool(progressive), max_leaves, bool(collapse), bool(device_tree),
                    int(refine_tree or 0), int(tree_refine_max_leaves),
                    (max_leaves, PROG_MAX_RECORDS if max_records is None else int(max_records)) if large_loci else None, int(retree or 0),
-                   bool(seq_weights), int(pair_dist_max_leaves) if pair_distances else None, bool(position_gaps), bool(free_end_gaps))
+                   bool(seq_weights), int(pair_dist_max_leaves) if pair_distances else None, bool(position_gaps), bool(free_end_gaps),
+                   bool(free_end_pairs))
     reports = Reports(orientation=orientation, refinement=refinement, progression=progression, tree_refinement=tree_refinement,
                       retreeing=retreeing, pair_distancing=pair_distancing)
     if progressive:
@@ -877,10 +933,10 @@ def _star_chunk_parts(be, chunk: Chunk, classes, build, opts: Options, laps, rep
 
 def _star_chunk_rest(be, chunk: Chunk, classes, opts: Options, laps, reports: Reports) -> List[MSA]:
     """_star_chunk behind Collapse: the star pass or the progressive one (with its tree refinement), optionally refine, collect."""
-    text = _progressive(be, chunk, opts, laps, reports, classes) if opts.progressive else _star_pass(be, chunk, opts.budget_bytes, opts.band, laps, classes)
+    text = _progressive(be, chunk, opts, laps, reports, classes) if opts.progressive else _star_pass(be, chunk, opts.budget_bytes, opts.band, laps, classes, opts.free_end_pairs)
     moved = {}
     if opts.refine:
-        res = _refine(be, chunk, text, opts.refine, opts.budget_bytes, opts.band, laps.timings)
+        res = _refine(be, chunk, text, opts.refine, opts.budget_bytes, opts.band, laps.timings, opts.free_end_pairs)
         moved = {l: r[3] for l, r in enumerate(res) if r[3] is not None}
         reports.add("refinement", (r[:3] for r in res))
         laps.lap("refine_s")
@@ -992,10 +1048,11 @@ def _centre_launch(be, call, chunk: Chunk):
     return centre, (d_seqs, d_loci, d_centre)
 
 
-def _star_pass(be, chunk: Chunk, budget_bytes, band, laps: _Laps, classes: Optional[Classes] = None):
+def _star_pass(be, chunk: Chunk, budget_bytes, band, laps: _Laps, classes: Optional[Classes] = None, free_ends: bool = False):
     """The spec's Centre, Pairs and Merge over one chunk, on the (oriented) sequences in chunk.d_codes.  Returns the MSAs' ASCII
     text on the device: (the buffer, its bytes, each locus's offset in it, its width).  classes: the spec's Collapse: pairs for
-    the representatives only, the columns from their rows, every member's row through its representative's ops."""
+    the representatives only, the columns from their rows, every member's row through its representative's ops.
+    free_ends: the spec's Free end pairs: the pairs as overlap alignments."""
     codes, first, counts, n_loci = chunk.codes, chunk.first, chunk.counts, chunk.n_loci
     centre = _centre_launch(be, "mprg_star_centres", chunk)[0]
     laps.lap("centre_s")
@@ -1009,7 +1066,10 @@ def _star_pass(be, chunk: Chunk, budget_bytes, band, laps: _Laps, classes: Optio
         is_rep = classes.weight > 0
         others = [[a for a in oth if is_rep[first[l] + a]] for l, oth in enumerate(others)]
         add_to(laps.timings, "collapse_pairs", sum(map(len, others)))
-    dp = pa.pairs_on_device(be, leaves, [[codes[l][a] for a in others[l]] for l in range(n_loci)], budget_bytes, band, laps.timings)
+    dp = pa.pairs_on_device(be, leaves, [[codes[l][a] for a in others[l]] for l in range(n_loci)], budget_bytes, band, laps.timings,
+                            free_ends=free_ends)
+    if free_ends:
+        add_to(laps.timings, "free_end_pair_alignments", sum(map(len, others)))
     laps.lap("pairs_s")
     # rows in input order: {locus, sequence offset, n, ops offset, ops count (-1: residue i in column i), output offset}
     rows = np.zeros((len(chunk.lens), ROW_FIELDS), np.int64)
@@ -2431,10 +2491,10 @@ def refine_compact(be, d_text, text_bytes: int, rtab: np.ndarray, d_keep, n_cols
     return d_out
 
 
-def _refine(be, chunk: Chunk, text, rounds, budget_bytes, band, counters):
+def _refine(be, chunk: Chunk, text, rounds, budget_bytes, band, counters, free_ends: bool = False):
     """The spec's Refinement over one chunk, on the MSA text the star or progressive pass left on the device (text: what they
     return).  Per locus: (rounds accepted, S of the star MSA, S of the result, None or where its new text is: (device buffer, its
-    bytes, offset, width))."""
+    bytes, offset, width)).  free_ends: the spec's Free end pairs: every realignment as an overlap alignment."""
     lens, seq_off, first = chunk.lens, chunk.seq_off, chunk.first
     d_text, text_bytes, base, W = text
     text_bytes = max(text_bytes, 1)
@@ -2463,7 +2523,9 @@ def _refine(be, chunk: Chunk, text, rounds, budget_bytes, band, counters):
             row_locus, grow = of_locus[q], all_rows[q]
             d_prof, poff, _ = refine_profiles(be, buf, buf_bytes, tab, cnt, cols, row_locus, grow - first[act][row_locus])
             prepared = pa.PreparedProfiles(d_prof, np.stack([R[row_locus] - 1, Wc[row_locus]], 1), poff, chunk.d_codes, seq_off[grow], lens[grow])
-            dp = pa.pairs_on_device(be, None, None, budget_bytes, band, counters, prepared)
+            dp = pa.pairs_on_device(be, None, None, budget_bytes, band, counters, prepared, free_ends=free_ends)
+            if free_ends:
+                add_to(counters, "free_end_pair_alignments", len(q))
             # the merge over the W columns: every non-empty row has ops, an empty one stays all gaps (count -1, n = 0)
             rows = np.zeros((len(all_rows), ROW_FIELDS), np.int64)
             rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 4] = of_locus, seq_off[all_rows], lens[all_rows], -1

@@ -150,6 +150,14 @@ def register_parser(subparsers):
                         "the row order and the objective (which keeps charging end runs) are unchanged; the merges of --retree and "
                         "--refine-tree use the same boundaries, --position-gaps keeps its opens inside, --refine runs afterwards "
                         "with charged ends, --band and --device-tree give the same bytes.  Off by default")
+    p.add_argument("--free-end-pairs", dest="free_end_pairs", action="store_true", default=False,
+                   help="(this implementation) with --unaligned, with or without --progressive: every sequence-against-profile "
+                        "alignment is an overlap (semi-global) alignment: the pairs of the star pass (also of the loci a "
+                        "progressive run leaves to it) and every realignment of --refine (star_align.py, Free end pairs; "
+                        "csrc/al_pairs.inc).  For loci with partial records: a fragment's missing end is no longer billed as a "
+                        "deletion of hundreds of columns.  --progressive --free-end-gaps --refine wants it: without it --refine "
+                        "realigns every row with charged ends.  The centre, the merges, the objective and --adjust-direction are "
+                        "unchanged; --band and --collapse-identical give the same bytes.  Off by default")
     p.set_defaults(func=run, check=check_options)
     return p
 
@@ -195,6 +203,8 @@ def check_options(args, parser):
         parser.error("--position-gaps needs --progressive")
     if getattr(args, "free_end_gaps", False) and not getattr(args, "progressive", False):
         parser.error("--free-end-gaps needs --progressive")
+    if getattr(args, "free_end_pairs", False) and not args.unaligned:
+        parser.error("--free-end-pairs needs --unaligned")
     if getattr(args, "refine", None) is not None:
         if not args.unaligned:
             parser.error("--refine needs --unaligned")
@@ -694,7 +704,7 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
              ("refine", "refine", "count"), ("progressive", "progressive", "flag"), ("device_tree", "device_tree", "flag"),
              ("large_loci", "large_loci", "flag"), ("refine_tree", "refine_tree", "count"), ("retree", "retree", "count"),
              ("seq_weights", "seq_weights", "flag"), ("pair_distances", "pair_distances", "flag"), ("position_gaps", "position_gaps", "flag"),
-             ("free_end_gaps", "free_end_gaps", "flag"))
+             ("free_end_gaps", "free_end_gaps", "flag"), ("free_end_pairs", "free_end_pairs", "flag"))
     lists = dict(adjust_direction="orientation", refine="refinement", progressive="progression", refine_tree="tree_refinement")
     on = {key: bool(getattr(options, attr, False)) if kind == "flag" else int(getattr(options, attr, None) or 0) for attr, key, kind in table}
     kw = {key: value for key, value in on.items() if value}
@@ -732,6 +742,8 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
         logger.info(f"rank {rank}: --position-gaps: {counters.get('position_gap_merges', 0)} merges with opens by occupancy")
     if on["free_end_gaps"]:
         logger.info(f"rank {rank}: --free-end-gaps: {counters.get('free_end_gap_merges', 0)} merges with free end gaps")
+    if on["free_end_pairs"]:
+        logger.info(f"rank {rank}: --free-end-pairs: {counters.get('free_end_pair_alignments', 0)} pair alignments with free ends")
     if on["pair_distances"]:
         logger.info(f"rank {rank}: --pair-distances: {counters.get('pair_dist_loci', 0)} loci, {counters.get('pair_dist_pairs', 0)} pairs, "
                     f"{counters.get('pair_dist_cells', 0)} DP cells, {counters.get('pair_dist_above_cap', 0)} above the cap, "

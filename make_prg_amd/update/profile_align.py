@@ -59,6 +59,11 @@ kernel: k_align_pairs_banded, C ABI: mprg_align_bounds / mprg_align_pairs_banded
             multi-row profiles whose m is small).  `update --aligner builtin` and the score-only DP of --adjust-direction keep
             the full form.
 
+Free ends (opt-in: pairs_on_device(free_ends=True), `from_msa --unaligned --free-end-pairs`): the DP above as an overlap alignment,
+with its own band certificate.  The spec and the proof: make_prg_amd/from_msa/star_align.py, "Free end pairs"; tests/freepairs_ref.py
+states it in plain Python; kernels: k_align_pairs_endgap, k_align_pairs_endgap_banded, k_align_bounds_endgap (csrc/al_pairs.inc,
+csrc/al_pairs_band.inc, csrc/k_align.inc).
+
 Host side: leaves and sequences packed once, the profiles built for the whole batch in one launch, the pairs sorted by cell
 count (longest first) and launched in chunks that fit a workspace budget (a pair whose traceback alone exceeds the budget is an
 error), every pair's ops into one device buffer (pairs_on_device; from_msa --unaligned merges them there, csrc/k_star.inc);
@@ -226,6 +231,16 @@ def certified_widths(n, C, SB, m, S0):
     return np.minimum(w_minus, n + np.minimum(0, delta)), np.minimum(w_plus, C - np.maximum(0, delta))
 
 
+def certified_widths_endgap(n, C, SB, m, z, S0):
+    """(w*-, w*+) of the two-pass rule of "Free end pairs" (star_align.py) from pass 1's score S0 and mprg_align_bounds_endgap's
+    {SB', m', z}: the smallest w >= 0 with U(w) = SB' - m' max(0, max(0, Delta) + w + 1 - z) < S0, the same on both sides, clamped
+    as certified_widths clamps; with m' = 0 no band is certified below min(n, C)."""
+    up = np.maximum(0, C - n)
+    w = np.maximum(0, (SB - S0) // np.maximum(m, 1) + z - up)
+    w = np.where(S0 > SB, 0, np.where(m > 0, w, np.minimum(n, C)))      # (S0 > SB': no path scores that; U(0) <= SB' < S0)
+    return np.minimum(w, n + np.minimum(0, C - n)), np.minimum(w, C - up)
+
+
 def _codes(seq: str, what: str) -> np.ndarray:
     raw = np.frombuffer(seq.upper().encode(), np.uint8)
     raw = raw[raw != _GAP]
@@ -236,11 +251,13 @@ def _codes(seq: str, what: str) -> np.ndarray:
 
 
 def align_batch(backend, leaves: Sequence[np.ndarray], seqs: Sequence[Sequence[np.ndarray]],
-                budget_bytes: int = DEFAULT_BUDGET_BYTES, band=None, counters: Optional[dict] = None) -> List[List[Tuple[bytes, int]]]:
+                budget_bytes: int = DEFAULT_BUDGET_BYTES, band=None, counters: Optional[dict] = None,
+                free_ends: bool = False) -> List[List[Tuple[bytes, int]]]:
     """leaves: R x C uint8 cell-code matrices; seqs[k]: the gap-free code arrays to align against leaf k.
-    Returns, per leaf, per sequence, (ops as bytes over b"MID" in forward order, score).  band, counters: as pairs_on_device."""
+    Returns, per leaf, per sequence, (ops as bytes over b"MID" in forward order, score).  band, counters, free_ends: as
+    pairs_on_device."""
     out: List[List[Optional[Tuple[bytes, int]]]] = [[None] * len(s) for s in seqs]
-    dp = pairs_on_device(backend, leaves, seqs, budget_bytes, band, counters)
+    dp = pairs_on_device(backend, leaves, seqs, budget_bytes, band, counters, free_ends=free_ends)
     if dp is None:
         return out
     ops = backend.download(dp.d_ops, np.uint8, dp.ops_bytes)
@@ -271,7 +288,7 @@ class PreparedProfiles:
 
 def pairs_on_device(backend, leaves: Optional[Sequence[np.ndarray]], seqs: Sequence[Sequence[np.ndarray]],
                     budget_bytes: int = DEFAULT_BUDGET_BYTES, band=None, counters: Optional[dict] = None,
-                    prepared: Optional[PreparedProfiles] = None) -> Optional[DevicePairs]:
+                    prepared: Optional[PreparedProfiles] = None, free_ends: bool = False) -> Optional[DevicePairs]:
     """The pairs of align_batch on the device: the profiles in one launch, the pairs longest first in launches that fit the
     workspace budget, every pair's ops into one buffer that stays on the device.  None when there is no pair.
     band: None: the full DP.  True or a half-width w0: the spec's Band, two passes: the same ops, counts and scores from the
@@ -279,7 +296,10 @@ def pairs_on_device(backend, leaves: Optional[Sequence[np.ndarray]], seqs: Seque
     counters: a dict that then receives (added up) band_pairs, band_second_passes, band_full_pairs (pairs sent to the full DP),
     band_cells (DP cells computed, all passes and the full form) and band_full_cells (n C summed: what the full DP computes).
     prepared: the leaves' profiles are already on the device (PreparedProfiles; `leaves` is then not read and no profile launch is
-    made): the leave-one-out profiles of from_msa --unaligned --refine."""
+    made): the leave-one-out profiles of from_msa --unaligned --refine.
+    free_ends: the pairs as overlap alignments (star_align.py, "Free end pairs"): the _endgap form of the three entries and
+    certified_widths_endgap; nothing else in the launches, the sizing or the counters changes.  False: the calls, uploads and
+    downloads are what they are without it."""
     be = backend
     n_leaves = len(leaves) if prepared is None else len(prepared.shapes)
     if not n_leaves:
@@ -346,25 +366,27 @@ def pairs_on_device(backend, leaves: Optional[Sequence[np.ndarray]], seqs: Seque
                 raise ProfileAlignError(f"{call}: {STATUS.get(int(res[bad[0], 0]), int(res[bad[0], 0]))}")
             score[idx] = res[:, 1]
             count[idx] = res[:, 2]
+    full_call, band_call = ("mprg_align_pairs_endgap", "mprg_align_pairs_endgap_banded") if free_ends else ("mprg_align_pairs", "mprg_align_pairs_banded")
     if band is None:
-        launches("mprg_align_pairs", full_plan)
+        launches(full_call, full_plan)
         return DevicePairs(d_ops, ops_bytes, pl, pi, ops_off, count, score)
     # the spec's Band: pass 1 with w0, the certificate over the downloaded scores, pass 2 with the certified widths; the full DP
     # for the pairs whose band needs no less workspace than the full matrix
     w0 = BAND_W0 if band is True else int(band)
     if w0 < 0:
         raise ProfileAlignError("band: a negative half-width")
-    d_bounds = be.empty(16 * n_leaves)
-    be.call("mprg_align_bounds", be.ptr(d_prof), be.ptr(d_leaves), n_leaves, be.ptr(d_bounds), be.stream, work=float((6 * C).sum()))
-    bounds = be.download(d_bounds, np.int64, 2 * n_leaves).reshape(-1, 2)
-    SB, m = bounds[pl, 0], bounds[pl, 1]
+    n_bounds = 3 if free_ends else 2
+    d_bounds = be.empty(8 * n_bounds * n_leaves)
+    be.call("mprg_align_bounds_endgap" if free_ends else "mprg_align_bounds", be.ptr(d_prof), be.ptr(d_leaves), n_leaves, be.ptr(d_bounds),
+            be.stream, work=float((6 * C).sum()))
+    bounds = be.download(d_bounds, np.int64, n_bounds * n_leaves).reshape(-1, n_bounds)[pl]
 
     def pass1(first, dlo, dhi):
-        launches("mprg_align_pairs_banded", packed(first, band_workspace_words(pn, pc, dlo, dhi)), dlo, dhi)
-        return certified_widths(pn, pc, SB, m, score)
+        launches(band_call, packed(first, band_workspace_words(pn, pc, dlo, dhi)), dlo, dhi)
+        return (certified_widths_endgap if free_ends else certified_widths)(pn, pc, *bounds.T, score)
     second, rest, dlo, dhi, counts = band_plan(pn, pc, w0, pass1)
-    launches("mprg_align_pairs_banded", packed(second, band_workspace_words(pn, pc, dlo, dhi)), dlo, dhi)
-    launches("mprg_align_pairs", packed(rest, need))
+    launches(band_call, packed(second, band_workspace_words(pn, pc, dlo, dhi)), dlo, dhi)
+    launches(full_call, packed(rest, need))
     for key, v in zip(("band_pairs", "band_second_passes", "band_full_pairs", "band_cells", "band_full_cells"), counts):
         add_to(counters, key, int(v))
     return DevicePairs(d_ops, ops_bytes, pl, pi, ops_off, count, score)

@@ -50,6 +50,8 @@ pair_dist_loci_lower (by the locus's objective S) and s_total_kmer beside s_tota
 line then also gives position_gap_merges.
 `--free-end-gaps` (with --progressive): the merges as overlap alignments (`from_msa --unaligned --progressive --free-end-gaps`); the
 line then also gives free_end_gap_merges.
+`--free-end-pairs`: the pairs of the star pass and the realignments of --refine as overlap alignments (`from_msa --unaligned
+--free-end-pairs`), with or without --progressive; the line then also gives free_end_pair_alignments.
 `--fragments SHARE` (with --diverged): that share of each locus's records but the first is cut to a piece of 30-80 % of its length
 at either end or inside (utils/synthetic.py's fragment_locus, seeded); the truth keeps the cut residues out.
 `--truth`: the MSAs written are scored against the alignment that is true by construction (`compare_msa`'s counts,
@@ -120,6 +122,7 @@ if position_gaps and not progressive:
 free_end_gaps = "--free-end-gaps" in sys.argv
 if free_end_gaps and not progressive:
     sys.exit("--free-end-gaps needs --progressive")
+free_end_pairs = "--free-end-pairs" in sys.argv
 fragments = float(sys.argv[sys.argv.index("--fragments") + 1]) if "--fragments" in sys.argv else None
 if fragments is not None and not diverged:
     sys.exit("--fragments needs --diverged")
@@ -137,6 +140,8 @@ prog_kw = dict(progressive=True, **(dict(device_tree=True) if device_tree else {
                **(dict(seq_weights=True) if seq_weights else {}), **(dict(pair_distances=True) if pair_distances else {}),
                **(dict(position_gaps=True) if position_gaps else {}),
                **(dict(free_end_gaps=True) if free_end_gaps else {})) if progressive else {}
+if free_end_pairs:
+    prog_kw = dict(prog_kw, free_end_pairs=True)             # (not an option of progressive, but handed on with them to every run)
 
 
 def objectives(be, msas):
@@ -202,7 +207,7 @@ try:
     tree_refinement = []
     retreeing = []
     msas = sa.star_msas(be, recs, timings=timings, adjust_direction=flip is not None, orientation=orientation, band=band, refine=refine,
-                        refinement=refinement, **(dict(prog_kw, progression=progression) if progressive else {}),
+                        refinement=refinement, **(dict(prog_kw, progression=progression) if progressive else prog_kw),
                         **(dict(tree_refinement=tree_refinement) if refine_tree else {}), **(dict(retreeing=retreeing) if retree else {}),
                         **(dict(collapse=True) if collapse else {}))
     t_star = time.perf_counter() - t0
@@ -259,6 +264,8 @@ try:
         extra.update(position_gaps=True)
     if free_end_gaps:
         extra.update(free_end_gaps=True)
+    if free_end_pairs:
+        extra.update(free_end_pairs=True)
     if fragments is not None:
         extra.update(fragments=fragments)
     if truth:
