@@ -659,6 +659,20 @@ int mprg_align_pair_scores_banded(const int32_t *profile, const int64_t *leaves,
                                   int n_pairs, int32_t *workspace, long long workspace_words, uint32_t *table, long long table_words,
                                   int32_t *out, void *stream);
 
+/* `from_msa --unaligned --progressive --pair-distances --free-end-distances`: the scores of mprg_align_pairs_endgap /
+ * mprg_align_pairs_endgap_banded alone: overlap scores, row 0 and column 0 of the DP 0, a run of D ops in the last row and a run of
+ * I ops in the last column free (the spec: make_prg_amd/from_msa/star_align.py, "Free end distances").
+ * mprg_align_pair_scores_endgap: signature, pair table, workspace need, `out`, the table write and status codes of
+ *   mprg_align_pair_scores; with n = 0 the score is 0.
+ * mprg_align_pair_scores_endgap_banded: those of mprg_align_pair_scores_banded (the band must hold (0, 0) and (n, C) as there); the
+ *   certificate is that of mprg_align_bounds_endgap. */
+int mprg_align_pair_scores_endgap(const int32_t *profile, const int64_t *leaves, int n_leaves, const uint8_t *seqs, const int64_t *pairs,
+                                  int n_pairs, int32_t *workspace, long long workspace_words, uint32_t *table, long long table_words,
+                                  int32_t *out, void *stream);
+int mprg_align_pair_scores_endgap_banded(const int32_t *profile, const int64_t *leaves, int n_leaves, const uint8_t *seqs,
+                                         const int64_t *pairs, int n_pairs, int32_t *workspace, long long workspace_words, uint32_t *table,
+                                         long long table_words, int32_t *out, void *stream);
+
 /* `from_msa --unaligned`: centre-star MSAs of unaligned loci (the spec: make_prg_amd/from_msa/star_align.py).
  * Not MAFFT: no reference function is replaced.  The pairs are mprg_align_pairs' (the centre as a 1-row leaf).
  * codes: the loci's sequences as cell codes (ACGT-RYKMSWN -> 0..11, no gaps), codes_bytes long.  seqs: n_seqs x 2 int64

@@ -100,6 +100,10 @@ SIGNATURES = {
                                        ctypes.c_longlong, c_void_p, c_void_p]),
     "mprg_align_pair_scores_banded": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong,
                                               c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
+    "mprg_align_pair_scores_endgap": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong,
+                                              c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
+    "mprg_align_pair_scores_endgap_banded": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong,
+                                                     c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
     "mprg_star_centres": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, c_void_p]),
     "mprg_star_centres_canonical": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, c_void_p]),
     "mprg_star_strand": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, c_void_p, c_void_p,

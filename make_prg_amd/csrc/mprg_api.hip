@@ -675,6 +675,26 @@ int mprg_align_pair_scores_banded(const int32_t *profile, const int64_t *leaves,
   return check_launch("k_align_scores_banded");
 }
 
+// `from_msa --unaligned --progressive --pair-distances --free-end-distances`: the two entries above with free ends (star_align.py,
+// "Free end distances")
+int mprg_align_pair_scores_endgap(const int32_t *profile, const int64_t *leaves, int n_leaves, const uint8_t *seqs, const int64_t *pairs,
+                                  int n_pairs, int32_t *workspace, long long workspace_words, uint32_t *table, long long table_words,
+                                  int32_t *out, void *stream) {
+  if (n_pairs <= 0) return 0;
+  LAUNCH(k_align_scores_endgap, (n_pairs + AL_WAVES - 1) / AL_WAVES, AL_THREADS, stream, profile, leaves, n_leaves, seqs, pairs, n_pairs,
+         workspace, workspace_words, table, table_words, out);      // a wavefront per pair
+  return check_launch("k_align_scores_endgap");
+}
+
+int mprg_align_pair_scores_endgap_banded(const int32_t *profile, const int64_t *leaves, int n_leaves, const uint8_t *seqs,
+                                         const int64_t *pairs, int n_pairs, int32_t *workspace, long long workspace_words, uint32_t *table,
+                                         long long table_words, int32_t *out, void *stream) {
+  if (n_pairs <= 0) return 0;
+  LAUNCH(k_align_scores_endgap_banded, (n_pairs + AL_WAVES - 1) / AL_WAVES, AL_THREADS, stream, profile, leaves, n_leaves, seqs, pairs,
+         n_pairs, workspace, workspace_words, table, table_words, out);      // a wavefront per pair
+  return check_launch("k_align_scores_endgap_banded");
+}
+
 int mprg_star_centres(const uint8_t *codes, long long codes_bytes, const int64_t *seqs, long long n_seqs, const int64_t *loci,
                       int n_loci, int32_t *centre, void *stream) {
   if (n_loci <= 0) return 0;

@@ -33,7 +33,7 @@ and counts that often in every merge (Sequence weights below; kernel: csrc/k_pro
 
 With `--pair-distances` (and `--progressive`) the first guide tree is built from the scores of the pair DP over all pairs of a locus's
 leaves instead of from 6-mer counts (Pair distances below; kernels: csrc/k_align_scores.inc, C ABI: mprg_align_pair_scores /
-mprg_align_pair_scores_banded).
+mprg_align_pair_scores_banded; with free_end_distances the overlap scores, Free end distances below).
 
 With `--position-gaps` (and `--progressive`) a merge charges the opening of a gap run by the occupancy of the column the run starts
 at instead of -704 whatever the column (Position gaps below; kernels: csrc/pg_pairs.inc, csrc/pg_pairs_band.inc,
@@ -459,8 +459,8 @@ better.  Here the merge is an overlap (semi-global) alignment.
             runs, so Retree and Tree refinement accept by the same S; refine, which runs afterwards with charged ends (as it runs
             with the fixed open after position_gaps); the star pass; adjust_direction; the pair DPs of pair_distances; `update
             --aligner builtin`.  Not part of it: treating the terminal '-' cells inside a profile's rows as missing data in the
-            planes; free ends in the pair scores of pair_distances; any change of defaults.  The flag promises these boundaries,
-            not a higher S.
+            planes; any change of defaults.  The pair scores of pair_distances keep their charged ends under this flag; they are
+            free under free_end_distances ("Free end distances" below).  The flag promises these boundaries, not a higher S.
   Band.     With band the same bytes.  The bound of "Progressive, band" does not carry over: a path that leaves the band can now
             take both of its forced runs for free, a leading D run in row 0 and a trailing I run in column C.  With B_j as there,
                 B'_j = max(B_j, 0),   SB' = sum_j B'_j,   LY'(k) = the sum of the k smallest B'_j (k clamped to C).
@@ -498,7 +498,8 @@ that DP is an overlap alignment too.
             mprg_align_profile_pairs_endgap with X the sequence as a one-row side: then s(i, j) = P[j][x] and Ic = -640.
   Which alignments.  The Pairs of the star pass, also of the loci a progressive run leaves to it (with collapse: the
             representatives' pairs), and every realignment of Refinement, on a star or a progressive MSA.
-  Not changed: the score-only DPs of adjust_direction; pair_distances; `update --aligner builtin`; the merges (free_end_gaps'
+  Not changed: the score-only DPs of adjust_direction; pair_distances (its pair scores get this boundary under free_end_distances,
+            "Free end distances" below, not under this flag); `update --aligner builtin`; the merges (free_end_gaps'
             business); Centre; the Merge rule (insertions at boundaries 0 and C are left-justified as always); the objective S and
             the acceptance rule, limits and reports of Refinement; the planes of a profile (terminal '-' cells stay gaps there);
             any default.
@@ -528,6 +529,44 @@ that DP is an overlap alignment too.
             form of the three entries and certified_widths_endgap; nothing else in the launches, the sizing or the counters
             changes.  timings receives free_end_pair_alignments: the pairs run with free ends, over the star pass and all
             refine rounds.
+
+Free end distances (only with progressive, pair_distances and free_end_distances; integers only; tests/freedist_ref.py states it in
+plain Python; kernels: csrc/al_scores.inc, csrc/al_scores_band.inc, included from csrc/k_align_scores.inc; C ABI:
+mprg_align_pair_scores_endgap / mprg_align_pair_scores_endgap_banded).  Free end gaps and Free end pairs made the alignments overlap
+alignments; the pair scores of Pair distances still charged end gaps.  With partial records that score does not measure distance: an
+equal ACGT pair scores 1 280, a residue against a gap -640, a run -704 to open, so a fragment that is an exact copy of a share f of a
+record of length L scores 1 280 f L - 640 (1 - f) L - 704 against it: below 0 for f < 1/3, hence s'' = 0 and D'' = 65 536, as far from
+its own source as a random sequence; at f = 1/2 an exact copy still sits at D'' near 33 000.  UPGMA then joins the fragments last, or
+to each other by the tie rule, and free_end_gaps cannot do its work, which needs the fragment beside its relatives.  Here the score
+is the overlap score.
+  Score.    For leaves a < b, score(a, b) is the score of "Free end pairs"' DP of sequence a against sequence b as a one-row leaf:
+            profile_align.py's DP with four boundary changes: row 0 = 0, column 0 = 0, D ops free in row n, I ops free in column C.
+            Everything else is unchanged: the cell, the int32 arithmetic, the tie order, the refusal at n + C >= 10^6.  The value
+            at (n, C) is the overlap optimum.
+  Four facts (tested): score(a, b) = score(b, a) (the costs are the same on either side and the four changes are mirrored by the
+            exchange of rows and columns); every score is a multiple of 64; 0 <= score <= 1 280 min(acgt_a, acgt_b): the path of
+            free D ops along row 0 and free I ops down column C scores 0, and only an equal ACGT pair scores above 0; score >= the
+            charged score of "Pair distances", because every path costs no more here.
+  Tables.   s'' = score / 64 (score >= 0: the max of "Pair distances" changes nothing); nw'' and D'' exactly as in "Pair distances".
+            Hence 0 <= s'' <= min(nw''), and the tree kernels, prog_distance_matrix, prog_tree and mprg_prog_leaf_weights take the
+            tables unchanged.
+  Consequence (tested).  An ACGT-only record that is an exact substring of another has s'' = nw'' of the shorter, so D'' = 0.
+  Which loci, the cap, "limit", the reports: "Pair distances"' rules, unchanged.
+  Nothing else changes: the merges, Y and X, the row order, the objective S, the acceptance rules of Retree, Tree refinement and
+            Refinement; adjust_direction's DPs; `update --aligner builtin`; any default.  seq_weights takes its heights from these
+            D'', as it does from D'' without the flag; retree replaces them with D' for a rebuilt tree as before.  The flag is
+            independent of free_end_gaps and free_end_pairs: any combination is allowed.
+  Band.     With band the same scores.  The bound is "Free end pairs, Band" verbatim with the one-row leaf as the profile: {SB', m',
+            z} from mprg_align_bounds_endgap, w* from profile_align.certified_widths_endgap; band_plan, BAND_W0 and the two-pass rule
+            are unchanged.  For an ACGT leaf m' = 1 280 and z = 0, so w* = floor((1 280 C - S0) / 1 280) - max(0, Delta): every
+            mismatch and every gap column of pass 1's path costs about one column of width, where the charged bound paid about
+            two thirds of one; so more pairs take a second pass (the counts are in DESIGN.md §3b).
+  The flag promises these distances, not a higher S and not a higher recovery.
+  Host side: _pair_scores_launch(free_ends=True) calls the _endgap form of the two score entries in pass 1, in pass 2 and for the full
+            form, and with band mprg_align_bounds_endgap (three int64 a leaf) and certified_widths_endgap; nothing else in the
+            sizing, the order or the launches changes.  _PairTables and prog_pair_tables carry the switch.  timings receives
+            free_end_distance_pairs: the pairs scored with free ends.  With the flag off every call, upload and download is what
+            it was.
 
 Progressive, host side: per chunk the distances in launches whose m x m tables fit budget_bytes (loci of three or more leaves), D
 and the tree per locus in NumPy / Python integers (prog_tree: a float64 quotient only shortlists, the choice is exact).  A node's
@@ -751,6 +790,9 @@ class Options(NamedTuple):
     progressive run leaves to it) and every realignment of refine as overlap alignments.  timings also receives
     free_end_pair_alignments (the pairs run with free ends, over the star pass and all refine rounds).  False: nothing launches,
     uploads or downloads differently.
+    free_end_distances: only with progressive and pair_distances (else a ValueError): the spec's Free end distances: the pair
+    scores of pair_distances are overlap scores.  timings also receives free_end_distance_pairs (the pairs scored with free ends).
+    False: nothing launches, uploads or downloads differently.
     The fields hold them as the stages read them: band is None, True or pass 1's half-width; refine_tree and retree are 0 when off;
     limits (large_loci, max_records) is None or (max_leaves, max_records); pair_dist (pair_distances, its cap) None or the cap."""
     budget_bytes: int = pa.DEFAULT_BUDGET_BYTES
@@ -770,11 +812,12 @@ class Options(NamedTuple):
     position_gaps: bool = False
     free_end_gaps: bool = False
     free_end_pairs: bool = False
+    free_end_distances: bool = False
 
     def star(self) -> "Options":
         """The settings of loci that go to the star pass: none of the options of progressive (free_end_pairs is not one: kept)."""
         return self._replace(progressive=False, device_tree=False, refine_tree=0, limits=None, retree=0, seq_weights=False, pair_dist=None,
-                             position_gaps=False, free_end_gaps=False)
+                             position_gaps=False, free_end_gaps=False, free_end_distances=False)
 
     def merge(self, counters: Optional[dict]) -> "_Merge":
         """How the merges of a stage run under these settings, their counters into `counters`."""
@@ -811,7 +854,7 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
               max_records: Optional[int] = None, retree: Optional[int] = None, retreeing: Optional[list] = None,
               seq_weights: bool = False, pair_distances: bool = False, pair_distancing: Optional[list] = None,
               pair_dist_max_leaves: int = PAIR_DIST_MAX_LEAVES, position_gaps: bool = False,
-              free_end_gaps: bool = False, free_end_pairs: bool = False) -> List[MSA]:
+              free_end_gaps: bool = False, free_end_pairs: bool = False, free_end_distances: bool = False) -> List[MSA]:
     """loci: per locus its records as (title, sequence).  Returns the loci's centre-star MSAs (ids: the titles' first words,
     descriptions: the titles).  names: the loci's names for error messages (default: their indices).  timings: a dict that
     receives the wall seconds of the stages (orient, centre, pairs, merge: each ends at a download, so includes its kernels).
@@ -820,6 +863,8 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
                     ("position_gaps", position_gaps), ("free_end_gaps", free_end_gaps)):
         if on and not progressive:
             raise ValueError(f"{key}: only with progressive")
+    if free_end_distances and not (progressive and pair_distances):
+        raise ValueError("free_end_distances: only with progressive and pair_distances")
     if large_loci and not (progressive and collapse):
         raise ValueError("large_loci: only with progressive and collapse")
     if max_records is not None and not (large_loci and 0 <= int(max_records) <= PROG_MAX_RECORDS):
@@ -843,7 +888,7 @@ def star_msas(backend, loci: Sequence[Sequence[Tuple[str, str]]], names: Optiona
                    int(refine_tree or 0), int(tree_refine_max_leaves),
                    (max_leaves, PROG_MAX_RECORDS if max_records is None else int(max_records)) if large_loci else None, int(retree or 0),
                    bool(seq_weights), int(pair_dist_max_leaves) if pair_distances else None, bool(position_gaps), bool(free_end_gaps),
-                   bool(free_end_pairs))
+                   bool(free_end_pairs), bool(free_end_distances))
     reports = Reports(orientation=orientation, refinement=refinement, progression=progression, tree_refinement=tree_refinement,
                       retreeing=retreeing, pair_distancing=pair_distancing)
     if progressive:
@@ -1254,7 +1299,8 @@ def _acgt(chunk: Chunk) -> np.ndarray:
     return np.array([int((c < 4).sum()) for cs in chunk.codes for c in cs], np.int64)
 
 
-def _pair_scores_launch(be, chunk: Chunk, d_seqs, grp, band=None, counters=None, acgt=None, budget_bytes=pa.DEFAULT_BUDGET_BYTES):
+def _pair_scores_launch(be, chunk: Chunk, d_seqs, grp, band=None, counters=None, acgt=None, budget_bytes=pa.DEFAULT_BUDGET_BYTES,
+                        free_ends=False):
     """The spec's Pair distances over the loci `grp` of a chunk: what _distances_launch returns, the tables s'' and nw'' in its layout,
     so _prog_shared, _prog_trees and _prog_weights take either source.  One mprg_align_profiles launch over the group's leaves as
     1-row texts, with band one mprg_align_bounds launch, then the pairs a < b of every locus (sequence a against leaf b), longest
@@ -1263,7 +1309,10 @@ def _pair_scores_launch(be, chunk: Chunk, d_seqs, grp, band=None, counters=None,
     overwriting the pair's entry.  {status, score} per pair and, with band, the bounds are all that comes back.  acgt: per record
     of the chunk's tables its ACGT cells (default: counted from chunk.codes); nw'' = 20 acgt is uploaded.  counters receives
     pair_dist_pairs, pair_dist_cells and with band pair_dist_second_passes, pair_dist_full_pairs.  The status words returned are
-    a single zero: every pair's status has been checked here."""
+    a single zero: every pair's status has been checked here.
+    free_ends: the spec's Free end distances: the _endgap form of the two score entries, with band mprg_align_bounds_endgap (three
+    int64 a leaf) and certified_widths_endgap; nothing else in the sizing, the order or the launches changes.  counters then also
+    receives free_end_distance_pairs."""
     lens, first = chunk.lens, chunk.first
     m = chunk.counts[grp]
     toff = exclusive_sum(m * m)
@@ -1320,44 +1369,50 @@ def _pair_scores_launch(be, chunk: Chunk, d_seqs, grp, band=None, counters=None,
         pending.clear()
     need = (2 * (pc + 1) + 63) // 64 * 64
     w0 = None if band is None or band is False else pa.BAND_W0 if band is True else int(band)
+    full_call, band_call = (("mprg_align_pair_scores_endgap", "mprg_align_pair_scores_endgap_banded") if free_ends else
+                            ("mprg_align_pair_scores", "mprg_align_pair_scores_banded"))
     if w0 is None:
-        launches("mprg_align_pair_scores", np.argsort(-((pn + 1) * pc), kind="stable"), need)
+        launches(full_call, np.argsort(-((pn + 1) * pc), kind="stable"), need)
         collect()
         cells = int((pn * pc).sum())
     else:
         if w0 < 0:
             raise StarAlignError("band: a negative half-width")
-        d_bounds = be.empty(16 * len(lrec))
-        be.call("mprg_align_bounds", be.ptr(d_prof), be.ptr(d_leaves), len(lrec), be.ptr(d_bounds), be.stream, work=float((6 * C).sum()))
-        bounds = be.download(d_bounds, np.int64, 2 * len(lrec)).reshape(-1, 2)
-        SB, mn = bounds[pl, 0], bounds[pl, 1]
+        n_bounds = 3 if free_ends else 2
+        d_bounds = be.empty(8 * n_bounds * len(lrec))
+        be.call("mprg_align_bounds_endgap" if free_ends else "mprg_align_bounds", be.ptr(d_prof), be.ptr(d_leaves), len(lrec), be.ptr(d_bounds),
+                be.stream, work=float((6 * C).sum()))
+        bounds = be.download(d_bounds, np.int64, n_bounds * len(lrec)).reshape(-1, n_bounds)[pl]
 
         def band_need(dlo, dhi):
             return (2 * (dhi - dlo + 1) + 63) // 64 * 64
 
         def pass1(firstp, dlo, dhi):
-            launches("mprg_align_pair_scores_banded", firstp, band_need(dlo, dhi), dlo, dhi)
+            launches(band_call, firstp, band_need(dlo, dhi), dlo, dhi)
             collect()
-            return pa.certified_widths(pn, pc, SB, mn, score)
+            return (pa.certified_widths_endgap if free_ends else pa.certified_widths)(pn, pc, *bounds.T, score)
         second, rest, dlo, dhi, counts = pa.band_plan(pn, pc, w0, pass1)
-        launches("mprg_align_pair_scores_banded", second, band_need(dlo, dhi), dlo, dhi)
-        launches("mprg_align_pair_scores", rest, need)
+        launches(band_call, second, band_need(dlo, dhi), dlo, dhi)
+        launches(full_call, rest, need)
         collect()
         cells = int(counts[3])
         add_to(counters, "pair_dist_second_passes", int(counts[1]))
         add_to(counters, "pair_dist_full_pairs", int(counts[2]))
     add_to(counters, "pair_dist_pairs", n_pairs)
     add_to(counters, "pair_dist_cells", cells)
+    if free_ends:
+        add_to(counters, "free_end_distance_pairs", n_pairs)
     return m, toff, words, d_shared, d_nw, d_status, 1
 
 
 class _PairTables:
     """The spec's Pair distances as a source of tables for _prog_shared, _prog_trees and _prog_weights: called like
     _distances_launch.  keep: the tables _prog_shared downloads are kept per locus, and a group all of whose loci are kept is
-    uploaded, not launched again (the host's tree with seq_weights: a locus's pair scores are computed once per run)."""
+    uploaded, not launched again (the host's tree with seq_weights: a locus's pair scores are computed once per run).  free_ends: the
+    spec's Free end distances."""
 
-    def __init__(self, band, counters, acgt, budget_bytes, keep=False):
-        self.band, self.counters, self.acgt, self.budget_bytes = band, counters, acgt, budget_bytes
+    def __init__(self, band, counters, acgt, budget_bytes, keep=False, free_ends=False):
+        self.band, self.counters, self.acgt, self.budget_bytes, self.free_ends = band, counters, acgt, budget_bytes, free_ends
         self.cache, self.spent = ({} if keep else None), 0.0
 
     def __call__(self, be, chunk: Chunk, d_seqs, grp):
@@ -1367,19 +1422,21 @@ class _PairTables:
             flat = np.concatenate([self.cache[l] for l in grp.tolist()]).astype(np.uint32)
             got = (m, exclusive_sum(m * m), int((m * m).sum()), be.upload(flat), be.upload(PAIR_DIST_MATCH * self.acgt), be.zeros(4), 1)
         else:
-            got = _pair_scores_launch(be, chunk, d_seqs, grp, self.band, self.counters, self.acgt, self.budget_bytes)
+            got = _pair_scores_launch(be, chunk, d_seqs, grp, self.band, self.counters, self.acgt, self.budget_bytes,
+                                      self.free_ends)
         self.spent += time.perf_counter() - t0
         return got
 
 
 def prog_pair_tables(backend, codes: Sequence[Sequence[np.ndarray]], band=None, budget_bytes: int = pa.DEFAULT_BUDGET_BYTES,
-                     counters: Optional[dict] = None):
+                     counters: Optional[dict] = None, free_ends: bool = False):
     """The spec's Pair distances over the loci (per locus its gap-free code arrays; an empty one is no leaf): per locus (s'', nw''):
     s'' an (m, m) int64 array whose part above the diagonal holds max(score(a, b), 0) / 64 of the records a < b, nw'' = 20 acgt per
-    record (0 for an empty one).  band: None, True or pass 1's half-width: the same tables over certified bands."""
+    record (0 for an empty one).  band: None, True or pass 1's half-width: the same tables over certified bands.  free_ends: the spec's Free end
+    distances: score is the overlap score."""
     chunk = _pack(backend, codes)
     got = _prog_shared(backend, chunk, np.arange(len(codes)), budget_bytes,
-                       _PairTables(band, counters, _acgt(chunk), budget_bytes))
+                       _PairTables(band, counters, _acgt(chunk), budget_bytes, free_ends=free_ends))
     return [got[l] for l in range(len(codes))]
 
 
@@ -1957,8 +2014,8 @@ def _progressive(be, chunk: Chunk, opts: Options, laps: _Laps, reports: Reports,
     device_tree: the trees by mprg_prog_tree (_prog_trees) instead of prog_tree; pair_dist: their tables from the pair scores;
     seq_weights: q per leaf from the trees, after the plan, as the rows' weights in every merge; retree, then refine_tree, on the
     roots' texts before they are written out (progression then reports the trees that built the texts that are written);
-    position_gaps and free_end_gaps in every merge of these three stages (the pair DPs of pair_dist keep the fixed open and their
-    charged ends)."""
+    position_gaps and free_end_gaps in every merge of these three stages (the pair DPs of pair_dist keep the fixed open; their
+    ends are free with free_end_distances alone)."""
     laps.lap()
     budget_bytes, band, device_tree, seq_weights, pair_dist = opts.budget_bytes, opts.band, opts.device_tree, opts.seq_weights, opts.pair_dist
     lens, first, counts = chunk.lens, chunk.first, chunk.counts
@@ -1986,7 +2043,8 @@ def _progressive(be, chunk: Chunk, opts: Options, laps: _Laps, reports: Reports,
     if pair_dist is not None:
         how = _pair_dist_how(chunk, n_leaves, int(pair_dist))
         by_pairs = np.array([how[l] == "pairs" for l in sel.tolist()], bool)
-        pair_tables = _PairTables(band, laps.timings, acgt, budget_bytes, keep=seq_weights and not device_tree)
+        pair_tables = _PairTables(band, laps.timings, acgt, budget_bytes, keep=seq_weights and not device_tree,
+                                  free_ends=opts.free_end_distances)
         parts = [(sel[~by_pairs], None), (sel[by_pairs], pair_tables)]
     lw = _LeafWeights(be, chunk) if seq_weights and device_tree and len(sel) else None
     if device_tree:

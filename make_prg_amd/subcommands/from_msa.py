@@ -158,6 +158,14 @@ def register_parser(subparsers):
                         "deletion of hundreds of columns.  --progressive --free-end-gaps --refine wants it: without it --refine "
                         "realigns every row with charged ends.  The centre, the merges, the objective and --adjust-direction are "
                         "unchanged; --band and --collapse-identical give the same bytes.  Off by default")
+    p.add_argument("--free-end-distances", dest="free_end_distances", action="store_true", default=False,
+                   help="(this implementation) with --unaligned --progressive --pair-distances: the pair scores the first guide tree "
+                        "is built from are overlap (semi-global) scores: end gaps cost nothing in the score-only sweep, as in "
+                        "--free-end-pairs' DP (star_align.py, Free end distances; csrc/al_scores.inc).  For loci with partial "
+                        "records: with charged ends a fragment that is an exact copy of less than a third of a record is as far from "
+                        "it as a random sequence; with free ends its distance is 0 and the tree puts it beside its relatives.  "
+                        "Everything after the distances is unchanged; independent of --free-end-gaps and --free-end-pairs; --band "
+                        "and --device-tree give the same bytes.  Off by default")
     p.set_defaults(func=run, check=check_options)
     return p
 
@@ -205,6 +213,11 @@ def check_options(args, parser):
         parser.error("--free-end-gaps needs --progressive")
     if getattr(args, "free_end_pairs", False) and not args.unaligned:
         parser.error("--free-end-pairs needs --unaligned")
+    if getattr(args, "free_end_distances", False):
+        if not getattr(args, "progressive", False):
+            parser.error("--free-end-distances needs --progressive")
+        if not getattr(args, "pair_distances", False):
+            parser.error("--free-end-distances needs --pair-distances")
     if getattr(args, "refine", None) is not None:
         if not args.unaligned:
             parser.error("--refine needs --unaligned")
@@ -704,7 +717,8 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
              ("refine", "refine", "count"), ("progressive", "progressive", "flag"), ("device_tree", "device_tree", "flag"),
              ("large_loci", "large_loci", "flag"), ("refine_tree", "refine_tree", "count"), ("retree", "retree", "count"),
              ("seq_weights", "seq_weights", "flag"), ("pair_distances", "pair_distances", "flag"), ("position_gaps", "position_gaps", "flag"),
-             ("free_end_gaps", "free_end_gaps", "flag"), ("free_end_pairs", "free_end_pairs", "flag"))
+             ("free_end_gaps", "free_end_gaps", "flag"), ("free_end_pairs", "free_end_pairs", "flag"),
+             ("free_end_distances", "free_end_distances", "flag"))
     lists = dict(adjust_direction="orientation", refine="refinement", progressive="progression", refine_tree="tree_refinement")
     on = {key: bool(getattr(options, attr, False)) if kind == "flag" else int(getattr(options, attr, None) or 0) for attr, key, kind in table}
     kw = {key: value for key, value in on.items() if value}
@@ -744,6 +758,8 @@ def align_unaligned_inputs(options, backend, tmp_dir: list) -> List[Path]:
         logger.info(f"rank {rank}: --free-end-gaps: {counters.get('free_end_gap_merges', 0)} merges with free end gaps")
     if on["free_end_pairs"]:
         logger.info(f"rank {rank}: --free-end-pairs: {counters.get('free_end_pair_alignments', 0)} pair alignments with free ends")
+    if on["free_end_distances"]:
+        logger.info(f"rank {rank}: --free-end-distances: {counters.get('free_end_distance_pairs', 0)} pair scores with free ends")
     if on["pair_distances"]:
         logger.info(f"rank {rank}: --pair-distances: {counters.get('pair_dist_loci', 0)} loci, {counters.get('pair_dist_pairs', 0)} pairs, "
                     f"{counters.get('pair_dist_cells', 0)} DP cells, {counters.get('pair_dist_above_cap', 0)} above the cap, "

@@ -52,6 +52,8 @@ line then also gives position_gap_merges.
 line then also gives free_end_gap_merges.
 `--free-end-pairs`: the pairs of the star pass and the realignments of --refine as overlap alignments (`from_msa --unaligned
 --free-end-pairs`), with or without --progressive; the line then also gives free_end_pair_alignments.
+`--free-end-distances` (with --progressive --pair-distances): the pair scores as overlap scores (`from_msa --unaligned --progressive
+--pair-distances --free-end-distances`); the line then also gives free_end_distance_pairs.
 `--fragments SHARE` (with --diverged): that share of each locus's records but the first is cut to a piece of 30-80 % of its length
 at either end or inside (utils/synthetic.py's fragment_locus, seeded); the truth keeps the cut residues out.
 `--truth`: the MSAs written are scored against the alignment that is true by construction (`compare_msa`'s counts,
@@ -123,6 +125,9 @@ free_end_gaps = "--free-end-gaps" in sys.argv
 if free_end_gaps and not progressive:
     sys.exit("--free-end-gaps needs --progressive")
 free_end_pairs = "--free-end-pairs" in sys.argv
+free_end_distances = "--free-end-distances" in sys.argv
+if free_end_distances and not (progressive and pair_distances):
+    sys.exit("--free-end-distances needs --progressive and --pair-distances")
 fragments = float(sys.argv[sys.argv.index("--fragments") + 1]) if "--fragments" in sys.argv else None
 if fragments is not None and not diverged:
     sys.exit("--fragments needs --diverged")
@@ -139,7 +144,8 @@ prog_kw = dict(progressive=True, **(dict(device_tree=True) if device_tree else {
                **(dict(refine_tree=refine_tree) if refine_tree else {}), **(dict(retree=retree) if retree else {}),
                **(dict(seq_weights=True) if seq_weights else {}), **(dict(pair_distances=True) if pair_distances else {}),
                **(dict(position_gaps=True) if position_gaps else {}),
-               **(dict(free_end_gaps=True) if free_end_gaps else {})) if progressive else {}
+               **(dict(free_end_gaps=True) if free_end_gaps else {}),
+               **(dict(free_end_distances=True) if free_end_distances else {})) if progressive else {}
 if free_end_pairs:
     prog_kw = dict(prog_kw, free_end_pairs=True)             # (not an option of progressive, but handed on with them to every run)
 
@@ -254,7 +260,7 @@ try:
         extra.update(seq_weights=True, seq_weight_loci_changed=sum(1 for a, b in zip(msas, plain) if sa.msa_fasta(a) != sa.msa_fasta(b)),
                      s_total_unweighted=objective_total(be, plain))
     if pair_distances:
-        plain = sa.star_msas(be, recs, adjust_direction=flip is not None, band=band, refine=refine, **dict(prog_kw, pair_distances=False),
+        plain = sa.star_msas(be, recs, adjust_direction=flip is not None, band=band, refine=refine, **dict(prog_kw, pair_distances=False, free_end_distances=False),
                              **(dict(collapse=True) if collapse else {}))
         s_on, s_off = objectives(be, msas), objectives(be, plain)
         extra.update(pair_distances=True, pair_dist_loci_changed=sum(1 for a, b in zip(msas, plain) if sa.msa_fasta(a) != sa.msa_fasta(b)),
@@ -266,6 +272,8 @@ try:
         extra.update(free_end_gaps=True)
     if free_end_pairs:
         extra.update(free_end_pairs=True)
+    if free_end_distances:
+        extra.update(free_end_distances=True)
     if fragments is not None:
         extra.update(fragments=fragments)
     if truth:
